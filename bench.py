@@ -1,6 +1,6 @@
 """Headline benchmark: ODE-integrate+update samples/s (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N>1: launched by torch.distributed.run, one rank per GPU, RCCL)
 
 A "step" is one ``update_parameters``-equivalent pass of the hot path over one
@@ -13,11 +13,20 @@ default (every rank runs its own 4096-row shard of a 4096*N global batch; the
 headline ``value``), and the same line carries ``strong`` — the metric's literal
 split, ONE 4096-row global batch sharded over the N ranks — measured right after.
 ``--global-batch G`` makes the strong split the headline instead.
+
+A plain run sets up, warms up, times the K steps and prints the JSON line
+(``ms_per_step``: one timed step).  ``--full`` adds everything else the line can
+carry: the pipelined replay, the roofline (event-timed pass, HBM figures), the
+NODE odeint sub-metric, the CPU baseline and, for N > 1, the other scaling split
+and dopri5 step control.  ``--dump-outputs DIR`` writes what the last timed step
+computed to DIR/<name>.npy; the inputs are seeded, so two builds compare output
+for output.
 """
 import argparse
 import io
 import json
 import os
+import random
 import sys
 import time
 
@@ -225,6 +234,29 @@ def pmc_update_traffic(env_name, solver, B, adjoint=False):
     return None
 
 
+def dump_outputs(out_dir, agent, ret):
+    """What the timed region's last update handed its caller, as ``out_dir/<name>.npy`` (float32 / float64, about 2 MB
+    at hidden 256): the six returned floats, every arena's parameters after the update (and the Polyak targets), and the
+    device scalars (losses, temperatures, multipliers; the two augmented-Lagrangian coefficients kept as doubles)."""
+    from nlbac_amd.sac_cbf_clf import _layout as SC
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {"returned_floats": np.asarray(ret, dtype=np.float64)}
+    for attr, name in (("ar_c", "critic_lyapunov"), ("ar_a", "actor"), ("ar_b", "backup_actor"), ("ar_n", "node")):
+        ar = getattr(agent, attr, None)
+        if ar is not None:
+            arrays[name + "_params"] = ar.theta.detach().cpu().numpy().astype(np.float32)
+            if ar.target is not None:
+                arrays[name + "_target_params"] = ar.target.detach().cpu().numpy().astype(np.float32)
+    sc = agent._scalars()
+    arrays["scalars"] = np.concatenate([sc[:SC.SC_RHO_F64], sc[SC.SC_BRHO_F64 + 2:]]).astype(np.float32)
+    arrays["augmented_terms"] = sc[SC.SC_RHO_F64:SC.SC_BRHO_F64 + 2].view(np.float64).copy()
+    assert sum(v.nbytes for v in arrays.values()) <= 64 << 20
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    log("outputs of the last timed step written to %s (%s)" % (out_dir, ", ".join(sorted(arrays))))
+
+
 def log(msg):
     print("[bench %.1fs] %s" % (time.perf_counter() - _T0, msg), file=sys.stderr, flush=True)
 
@@ -338,11 +370,21 @@ def main():
     ap.add_argument("--global-batch", type=int, default=0,
                     help="strong scaling: ONE global batch of this many rows sharded over the ranks (default 0: weak "
                          "scaling, --batch rows per rank)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline: pipelined replay, event-timed roofline pass, HBM figures, "
+                         "NODE odeint sub-metric, CPU baseline; N > 1: the other scaling split and step control.  "
+                         "Without it the process runs exactly warmup + steps updates")
     ap.add_argument("--lean", action="store_true",
-                    help="warm-up + timed region only (no pipelined replay, event-timed pass, sub-metric, CPU baseline): "
-                         "the process runs exactly warmup + steps updates — what the counter passes profile")
+                    help="warm-up + timed region only, even with --full (the default without --full): the process runs "
+                         "exactly warmup + steps updates — what the counter passes profile")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last step computed (the six returned floats, the "
+                         "updated parameters, targets and scalars) to DIR/<name>.npy")
     a = ap.parse_args()
-    if a.lean:
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    full = a.full and not a.lean
+    if not full:
         a.profile_steps, a.no_cpu_baseline = 0, True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -382,11 +424,17 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t)
 
-    def measure(B, global_B, steps, warmup, extras, strong=False, dp_step_control=None):
+    def measure(B, global_B, steps, warmup, extras, strong=False, dp_step_control=None, dump=None):
         """One agent at ``B`` rows per rank (losses normalised by ``global_B``): warm-up, the timed region bracketed by
-        barrier + synchronize, max over ranks.  ``extras``: also the pipelined replay / event-timed pass / sub-metric."""
+        barrier + synchronize, max over ranks.  ``extras``: also the pipelined replay / event-timed pass / sub-metric.
+        ``dump``: a directory that receives the timed region's outputs (dump_outputs) before anything else runs."""
         args = Args(global_B)                                         # global batch in the loss normalisation
         args.gamma_b = GAMMA_B[a.env]
+        # every generator seeded before the agent exists, as the driver does (train.py): the critic and Lyapunov nets are
+        # initialised before the agent seeds its own, and torch's default generator starts from a per-process seed
+        random.seed(args.seed)
+        np.random.seed(args.seed)
+        torch.manual_seed(args.seed)
         agent = SAC_CBF_CLF(env.obs_dim, env.action_space, env, args)
         agent.solver = a.solver
         agent.adjoint = a.adjoint
@@ -424,10 +472,11 @@ def main():
             step(i)
         fence()
         drop_prefetch()
-        snap = io.BytesIO()            # agent + replay-draw state at the start of the timed region (replayed below)
-        agent.save_checkpoint(snap)
-        draws0 = replay._draws
-        fence()
+        if extras:
+            snap = io.BytesIO()        # agent + replay-draw state at the start of the timed region (replayed below)
+            agent.save_checkpoint(snap)
+            draws0 = replay._draws
+            fence()
         stats0 = dict(agent.node_solver.stats)
         t0 = time.perf_counter()
         marks = []
@@ -444,6 +493,8 @@ def main():
         res = dict(agent=agent, B=B, global_B=global_B, elapsed=elapsed, value=global_B * steps / elapsed,
                    ms=1e3 * elapsed / steps, ret=[float(x) for x in ret], stats=stats,
                    fit_rows_per_rank=fit_local, step=step, base=warmup + steps)
+        if dump and rank == 0:
+            dump_outputs(dump, agent, ret)
         if not extras:
             return res
         # ---- secondary figure: the SAME updates again (state and replay draws rewound to the start of the timed
@@ -480,14 +531,14 @@ def main():
     else:
         B, GB = a.batch, a.batch * world
     log("setup; warm-up + timed region: %d steps, %d rows per rank, global batch %d" % (a.steps, B, GB))
-    main_run = measure(B, GB, a.steps, a.warmup, extras=not a.lean, strong=strong_first)
+    main_run = measure(B, GB, a.steps, a.warmup, extras=full, strong=strong_first, dump=a.dump_outputs)
     agent, value, elapsed, step, base = (main_run[k] for k in ("agent", "value", "elapsed", "step", "base"))
     log("timed region done: %.3f ms/step, %.0f samples/s" % (main_run["ms"], value))
     pipelined = main_run.get("pipelined")
 
     # ---- N > 1: the other split of the same metric, measured right after (its own agent)
     other = None
-    if world > 1 and not a.lean:
+    if world > 1 and full:
         if strong_first:
             o = measure(a.batch, a.batch * world, a.steps, a.warmup, extras=False)
             kind = "weak"
@@ -505,7 +556,7 @@ def main():
     # inside a solve; a different computation within solver tolerance, see README).  Whoever reads a scaling curve off
     # these lines has both.
     other_ctl = None
-    if world > 1 and not a.lean and a.solver == "dopri5":
+    if world > 1 and full and a.solver == "dopri5":
         alt = "global" if a.dp_step_control == "shard" else "shard"
         o = measure(B, GB, a.steps, a.warmup, extras=False, strong=strong_first, dp_step_control=alt)
         other_ctl = {"dp_step_control": alt, "value": o["value"], "unit": "samples/s", "ms_per_step": o["ms"],
@@ -580,7 +631,7 @@ def main():
         for i in range(a.profile_steps):
             step(base + i)
     fence()
-    if rank == 0:
+    if rank == 0 and full:
         alg = algorithmic_bytes_per_update(agent, B)
         cnt = pmc_update_traffic(a.env, a.solver, B, a.adjoint)
         sec = main_run["ms"] * 1e-3
@@ -600,7 +651,7 @@ def main():
     # ---- sub-metric: the NODE odeint alone, forward + backward to the controls, on the rollout
     #      shape of the update (one problem per controller, B rows each)
     ode_sub = None
-    if rank == 0 and world == 1 and not a.lean:
+    if rank == 0 and world == 1 and full:
         ode_sub = node_odeint_submetric(agent, env, B, a.solver)
 
     cpu = None

@@ -3,7 +3,7 @@
 #   bash tools/ab_bench.sh "<bench args>" base <variant> <variant> ...     (base = the product library)
 # prints ms/update and the event-timed per-entry-point averages of each; full lines under gpurun_out/ab/
 cd "${GRAFT_REPO_ROOT:-.}"
-ARGS=$1; shift
+ARGS="--full $1"; shift
 mkdir -p gpurun_out/ab
 LIBDIR=$(echo neural-*-nlbac_amd/lib)
 for v in "$@"; do

@@ -4,12 +4,12 @@
 O=gpurun_out/r4/cadj
 mkdir -p $O
 for solver in rk4 dopri5; do
-  python bench.py --env SimulatedCars --batch 8192 --solver $solver --steps 60 --no-cpu-baseline > $O/cars_${solver}_direct.json 2> $O/cars_${solver}_direct.err &&
-  python bench.py --env SimulatedCars --batch 8192 --solver $solver --steps 60 --no-cpu-baseline --adjoint > $O/cars_${solver}_adjoint.json 2> $O/cars_${solver}_adjoint.err &&
-  NLBAC_CONCAT_ADJ_RR=0 python bench.py --env SimulatedCars --batch 8192 --solver $solver --steps 60 --no-cpu-baseline --adjoint > $O/cars_${solver}_adjoint_staged.json 2> $O/cars_${solver}_adjoint_staged.err || exit 1
+  python bench.py --full --env SimulatedCars --batch 8192 --solver $solver --steps 60 --no-cpu-baseline > $O/cars_${solver}_direct.json 2> $O/cars_${solver}_direct.err &&
+  python bench.py --full --env SimulatedCars --batch 8192 --solver $solver --steps 60 --no-cpu-baseline --adjoint > $O/cars_${solver}_adjoint.json 2> $O/cars_${solver}_adjoint.err &&
+  NLBAC_CONCAT_ADJ_RR=0 python bench.py --full --env SimulatedCars --batch 8192 --solver $solver --steps 60 --no-cpu-baseline --adjoint > $O/cars_${solver}_adjoint_staged.json 2> $O/cars_${solver}_adjoint_staged.err || exit 1
 done
-python bench.py --env QuadrotorLike --batch 32768 --steps 40 --no-cpu-baseline --adjoint > $O/quad_adjoint.json 2> $O/quad_adjoint.err &&
-NLBAC_CONCAT_ADJ_RR=0 python bench.py --env QuadrotorLike --batch 32768 --steps 40 --no-cpu-baseline --adjoint > $O/quad_adjoint_staged.json 2> $O/quad_adjoint_staged.err
+python bench.py --full --env QuadrotorLike --batch 32768 --steps 40 --no-cpu-baseline --adjoint > $O/quad_adjoint.json 2> $O/quad_adjoint.err &&
+NLBAC_CONCAT_ADJ_RR=0 python bench.py --full --env QuadrotorLike --batch 32768 --steps 40 --no-cpu-baseline --adjoint > $O/quad_adjoint_staged.json 2> $O/quad_adjoint_staged.err
 for f in $O/*.json; do python - "$f" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -4,6 +4,7 @@
 set -e
 cd "${GRAFT_REPO_ROOT:-.}"
 TAG=$1; shift
+set -- --full "$@"      # (the profiled process runs the extra passes too: pipelined replay, event-timed pass)
 export TMPDIR=/tmp
 D=gpurun_out/pmc_${TAG}_mfma
 mkdir -p $D

@@ -477,9 +477,14 @@ int nlbac_rk_stage_bwd(const float *dYup, const float *dXf, const float *dXg, in
  * K_s = f + g u, and optionally out = y0 + h sum c_out[j] K_j and err = h sum c_err[j] K_j.
  * K / Y / G are [n_stages_total][n][.] stage-major; stages < stage_begin are read from K (FSAL, f0).
  * acts_* ([layer][n_stages_total*n][hid], layer stride *_ls) may be NULL when no backward follows.
- * acts_bits != 0: the acts_* buffers receive bit-packed ReLU masks instead — uint32 words
+ * acts_bits == 1: the acts_* buffers receive bit-packed ReLU masks instead — uint32 words
  * [layer][n_stages_total*n][ceil(hid/32)] (bit c of word t = unit 32 t + c is active), layer stride in words: all a
- * backward without weight gradients needs, at 1/32 of the HBM traffic. */
+ * backward without weight gradients needs, at 1/32 of the HBM traffic.
+ * acts_bits == 2 (nlbac_node_rk_mask_words(f, g, .) == 4 only: the register-resident kernels): rows AND words — the
+ * activation rows as with 0 (same arithmetic, same bits), and each net's mask words in the register-resident format,
+ * [layer][n_stages_total*n][4] uint32, directly behind its rows at acts_* + (n_layers - 1) * acts_*_ls.  The backward
+ * of the same step (acts_bits 2) gates on the words and still writes dz / dG: what a fit with weight gradients needs
+ * (nlbac_mlp_bwd_weights reads the rows), without re-reading the rows for the gates. */
 /* Device-driven dopri5 step chain (optional, NULL = one self-contained launch).  A solve's accepted steps live in
  * STEP SLOTS — identical buffer layouts `slot_floats` floats apart; every K / Y / G / acts / err / dK / dG / dz /
  * dy0 / dYup pointer a launch is given is slot 0's.  ctl (the NLBAC_DOPRI_CTL control blocks): a problem whose `done`
@@ -589,7 +594,7 @@ int nlbac_node_rk_bwd(const nlbac_mlp *f, const nlbac_mlp *g, const float *u, co
                       int rows_per_problem, int n_stages_total, int st_lo, int st_hi, int dx_stage0,
                       const float *beta, const float *h_host, const double *h_dev, int h_dev_stride,
                       const float *acts_f, long acts_f_ls, const float *acts_g, long acts_g_ls,
-                      int acts_bits /* as written by nlbac_node_rk_fwd; excludes dz_f/dz_g/dG */,
+                      int acts_bits /* as written by nlbac_node_rk_fwd; 1 excludes dz_f/dz_g/dG, 2 does not */,
                       float *dz_f, float *dz_g, float *dG, float *dK, const float *dYup, float *dy0,
                       int dy0_in, float *du, int du_acc, const nlbac_rk_chain *chain, int back_idx,
                       nlbac_stream_t s);

@@ -570,7 +570,8 @@ extern "C" int nlbac_node_rk_bwd(const nlbac_mlp* f, const nlbac_mlp* g, const f
                                  float* dy0, int dy0_in, float* du, int du_acc, const nlbac_rk_chain* chain,
                                  int back_idx, nlbac_stream_t s) {
     NLBAC_REQUIRE(f && g && u && G && acts_f && acts_g && dK, "nlbac_node_rk_bwd: null pointer");
-    NLBAC_REQUIRE(!(acts_bits && dz_f), "nlbac_node_rk_bwd: weight gradients need the activations, not bit masks");
+    NLBAC_REQUIRE(acts_bits >= 0 && acts_bits <= 2, "nlbac_node_rk_bwd: acts_bits is 0, 1 or 2");
+    NLBAC_REQUIRE(!(acts_bits == 1 && dz_f), "nlbac_node_rk_bwd: weight gradients need the activations, not bit masks");
     NLBAC_REQUIRE(P >= 1 && P <= 8 && rows_per_problem >= 1, "nlbac_node_rk_bwd: bad problem sizes");
     NLBAC_REQUIRE(n_stages_total >= 1 && n_stages_total <= RK_MAX_STAGES && st_lo >= 0 && st_lo < st_hi &&
                       st_hi <= n_stages_total, "nlbac_node_rk_bwd: bad stage range");
@@ -627,6 +628,7 @@ extern "C" int nlbac_node_rk_bwd(const nlbac_mlp* f, const nlbac_mlp* g, const f
         const int rr = nlbac_node_rr_bwd_launch(L, (hipStream_t)s);
         if (rr <= 0) return rr;
     }
+    NLBAC_REQUIRE(acts_bits != 2, "nlbac_node_rk_bwd: acts_bits 2 (rows + words) needs the register-resident kernels");
     NLBAC_REQUIRE(!L.ip_on, "nlbac_node_rk_bwd: interp_bwd needs the register-resident kernels (nlbac_rk_interp_ok)");
     int w = ((f->hid > g->hid ? f->hid : g->hid) + 31) & ~31;
     L.ld = w + 4;
@@ -670,6 +672,7 @@ static int rk_fwd_fill(NodeRkLaunch& L, const nlbac_mlp* f, const nlbac_mlp* g, 
                       g->out_dim <= RK_MAX_GOUT, "nlbac_node_rk_fwd: f/g shapes are not a control-affine field");
     NLBAC_REQUIRE(f->hid % 4 == 0 && g->hid % 4 == 0 && f->hid <= 256 && g->hid <= 256, "nlbac_node_rk_fwd: bad hid");
     NLBAC_REQUIRE(h_dev || h_host, "nlbac_node_rk_fwd: no step size");
+    NLBAC_REQUIRE(acts_bits >= 0 && acts_bits <= 2, "nlbac_node_rk_fwd: acts_bits is 0, 1 or 2");
     NLBAC_REQUIRE(n_out <= n_stages_total && n_err <= n_stages_total, "nlbac_node_rk_fwd: bad coefficient counts");
     memset(&L, 0, sizeof(L));
     L.net[0] = *f; L.net[1] = *g;
@@ -747,6 +750,7 @@ extern "C" int nlbac_node_rk_fwd(const nlbac_mlp* f, const nlbac_mlp* g, const f
         const int rr = nlbac_node_rr_fwd_launch(L, (hipStream_t)s);
         if (rr <= 0) return rr;
     }
+    NLBAC_REQUIRE(acts_bits != 2, "nlbac_node_rk_fwd: acts_bits 2 (rows + words) needs the register-resident kernels");
     NLBAC_REQUIRE(!L.ip_out, "nlbac_node_rk_fwd: interp_out needs the register-resident kernels (nlbac_rk_interp_ok)");
     // LDS tiles hold pad8(hid) columns (the next layer's K extent), row stride = 4 mod 8 dwords: two workgroups fit per CU
     int w = ((f->hid > g->hid ? f->hid : g->hid) + 7) & ~7;

@@ -53,8 +53,13 @@ extern "C" int nlbac_debug_bwd_stamps(long long* out) {
 // tile takes over the upper groups of output blocks of f_net's LAST hid x hid layer: the f_net wave hands its layer-2
 // activations over through LDS (behind a flag only the two waves touch), both compute their blocks and their part of
 // f_net's output layer, and the two partial outputs meet in the stage's k = f + g u step.
+// BITS: what the backward gets of each layer — 0 the activation rows, 1 the ReLU mask words instead, 2 both (the NODE
+// fit: its backward gates on the words, the weight gradients read the rows; the words sit behind the rows, see
+// nlbac_node_rk_fwd's acts_bits).
 template <int NB, int R, int BITS, int SPLIT>
 __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L) {
+    static_assert(BITS != 2 || SPLIT == 0, "rows + words: the fit's forward is the unsplit one (same sums as mode 0)");
+    constexpr bool WORDS = BITS != 0, ROWS = BITS != 1;
     using S = RRShape<NB, R>;
     constexpr int KS = S::KS, HID = S::HID;
     constexpr int TB = NB - 2;                 // first block of a layer's last group, the "tail": its accumulators are
@@ -95,6 +100,10 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L) {
     for (int l = 0; l < RR_MAX_W; ++l) boff[l] = net.b_off[l];
     float* const acts = L.acts[grp] ? L.acts[grp] + w.soff : nullptr;
     const long acts_ls = L.acts_ls[grp];
+    // the mask words: in place of the rows (BITS 1, layer stride acts_ls), or behind the net's nw layers of rows (BITS 2,
+    // [layer][S_total * n][4])
+    unsigned* const words = !acts ? nullptr : reinterpret_cast<unsigned*>(BITS == 2 ? acts + (long)nw * acts_ls : acts);
+    const long words_ls = (BITS == 2) ? (long)L.S_total * n * 4 : acts_ls;
     const int stage_end = L.stage_end, S_last = L.S_total - 1;
     // the initial-step probe with its norm fused into this launch (norm_mode 1): nothing it would leave in memory — the
     // probe point, its derivative, g there — is read by anyone (the norm comes from LDS, the step's stage 1 overwrites
@@ -219,7 +228,7 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L) {
         // loads' in-order vmcnt queue: issued one by one between the fragment loads, each made the MFMAs behind it wait
         // for its own trip to HBM; as a burst the trips overlap and the stream stalls once per layer.
         auto save_layer = [&](int l, const float (&H)[KS]) __attribute__((always_inline)) {
-            if (BITS || !acts || !row_ok) return;
+            if (!ROWS || !acts || !row_ok) return;
             float* rowp = acts + (long)l * acts_ls + srow * HID;
 #pragma unroll
             for (int jo = 0; jo < NB; ++jo) {
@@ -230,14 +239,14 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L) {
             }
         };
         auto save_word = [&](int l, unsigned word) __attribute__((always_inline)) {
-            if (BITS && acts && row_ok) reinterpret_cast<unsigned*>(acts + (long)l * acts_ls)[srow * 4 + q] = word;
+            if (WORDS && words && row_ok) words[(long)l * words_ls + srow * 4 + q] = word;
         };
         // layer 0's value ks (no bias: folded into the product), finished just before layer 1's k-step ks reads it
         auto pre_l0 = [&](int ks) __attribute__((always_inline)) {
             const int jo = (ks < 4 * (NB - 1)) ? (ks >> 2) : NB - 1, r = ks - 4 * jo;
             const float h = rr_relu(acc0[jo][r]);
             Ha[ks] = h;
-            if (BITS) rr_mask_push(wd, h);
+            if (WORDS) rr_mask_push(wd, h);
             if (ks == KS - 1) save_word(0, wd);
         };
         // the tail of hid x hid layer lp (blocks TB, TB+1 of `acc`), finished inside the product that follows it: value t
@@ -247,7 +256,7 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L) {
             const int jo = TB + (t >> 2), r = t & 3;
             const float h = rr_relu(acc[jo][r]);
             H[4 * TB + t] = h;
-            if (BITS) rr_mask_push(wd, h);
+            if (WORDS) rr_mask_push(wd, h);
             if (t == NT - 1) save_word(lp, wd);
         };
 
@@ -306,7 +315,7 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L) {
                      [&](int jo, int r) __attribute__((always_inline)) {
                          const float h = rr_relu(acc[jo][r]);
                          Hout[4 * jo + r] = h;
-                         if (BITS) rr_mask_push(wd, h);
+                         if (WORDS) rr_mask_push(wd, h);
                      },
                      [&]() __attribute__((always_inline)) {
                          if (l + 1 < nw) prefetch_bias(l + 1);
@@ -375,7 +384,7 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L) {
                 auto fin3 = [&](int jo, int r) __attribute__((always_inline)) {
                     const float h = rr_relu(acc[jo][r]);
                     Hb[4 * jo + r] = h;
-                    if (BITS) rr_mask_push(wp, h);
+                    if (WORDS) rr_mask_push(wp, h);
                 };
                 partF.run(acc, bv, Ha, rs, voff, curF3, [&](int) __attribute__((always_inline)) {}, fin3);
                 RSTAMP(sb + 4)
@@ -399,7 +408,7 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L) {
                 auto fin3 = [&](int jo, int r) __attribute__((always_inline)) {
                     const float h = rr_relu(acc[jo][r]);
                     Ha[4 * jo + r] = h;
-                    if (BITS) rr_mask_push(wp, h);
+                    if (WORDS) rr_mask_push(wp, h);
                 };
                 partG.run(acc, bv, Hb, rsF, voff, curF3, [&](int) __attribute__((always_inline)) {}, fin3);
                 const f32x4 o = PG::block(wof, Ha, [&](int ks) __attribute__((always_inline)) {
@@ -504,6 +513,8 @@ __global__ __launch_bounds__(256) void node_rr_fwd_begin_kernel(const NodeRkLaun
 // (dz_3 comes over through LDS behind a flag, the blocks go back the same way), the f_net wave the upper groups.
 template <int NB, int R, int BITS, int SPLIT>
 __global__ __launch_bounds__(256) void node_rr_bwd_kernel(const NodeRkBwdLaunch L) {
+    constexpr bool WORDS = BITS != 0;          // the gates come from the mask words (1, 2) or from the activation rows (0)
+    constexpr bool DZ = BITS != 1;             // dz rows are stored when asked for (0; 2: the fit, words behind the rows)
     using S = RRShape<NB, R>;
     constexpr int KS = S::KS, HID = S::HID, TB = NB - 2, NT = KS - 4 * TB;
     constexpr int MB = rr_split_m<S>();        // (SPLIT) f_net's first product: MFMAs [0, MB) go to the g_net wave
@@ -539,6 +550,9 @@ __global__ __launch_bounds__(256) void node_rr_bwd_kernel(const NodeRkBwdLaunch 
     const float* const acts = L.acts[grp] + w.soff;
     float* const dz = keep_dz ? L.dz[grp] + w.soff : nullptr;
     const long acts_ls = L.acts_ls[grp];
+    // (WORDS) where the forward left the words: in place of the rows (1), or behind the net's nw layers of rows (2)
+    const unsigned* const words = reinterpret_cast<const unsigned*>(BITS == 2 ? acts + (long)nw * acts_ls : acts);
+    const long words_ls = (BITS == 2) ? (long)L.S_total * n * 4 : acts_ls;
     const int dx_stage0 = L.dx_stage0;
 
     // ---- weight stream: backward fragments of layers nw-1 .. 1, then nw-1 again (next stage)
@@ -655,8 +669,8 @@ __global__ __launch_bounds__(256) void node_rr_bwd_kernel(const NodeRkBwdLaunch 
         unsigned mw = 0u, mwt = 0u;
         f32x4 avA[NB], avB[NB], avt[2];       // (activation mode) two sets: a product's masks are requested one product ahead
         auto fetch_masks = [&](int l, f32x4 (&av)[NB]) __attribute__((always_inline)) {
-            if (BITS) {        // (rows past the end contribute nothing: their word is cleared once)
-                mw = reinterpret_cast<const unsigned*>(acts + (long)l * acts_ls)[srow * 4 + q];
+            if (WORDS) {       // (rows past the end contribute nothing: their word is cleared once)
+                mw = words[(long)l * words_ls + srow * 4 + q];
                 mw = row_ok ? mw : 0u;
             }
             else {
@@ -668,7 +682,7 @@ __global__ __launch_bounds__(256) void node_rr_bwd_kernel(const NodeRkBwdLaunch 
         // (activation mode, weight gradients wanted) a finished dz leaves in one burst inside the product that consumes it,
         // like the forward's activations (see there)
         auto save_dz = [&](int l, const float (&Z)[KS]) __attribute__((always_inline)) {
-            if (BITS || !dz || !row_ok) return;
+            if (!DZ || !dz || !row_ok) return;
             float* rowp = dz + (long)l * acts_ls + ((long)st * n + grow) * HID;
 #pragma unroll
             for (int jo = 0; jo < NB; ++jo) {
@@ -681,20 +695,20 @@ __global__ __launch_bounds__(256) void node_rr_bwd_kernel(const NodeRkBwdLaunch 
         // the top product's value ks (mask mode: finished just before the next product's k-step ks reads it)
         auto pre_top = [&](int ks) __attribute__((always_inline)) {
             const int jo = (ks < 4 * (NB - 1)) ? (ks >> 2) : NB - 1, r = ks - 4 * jo;
-            if (BITS) Za[ks] = rr_mask_gate<KS>(mwt, ks, acct[jo][r]);
+            if (WORDS) Za[ks] = rr_mask_gate<KS>(mwt, ks, acct[jo][r]);
             else Za[ks] = (row_ok && avA[jo][r] > 0.f) ? acct[jo][r] : 0.f;
         };
         // the tail (blocks TB, TB+1 of `acc`) of the product that produced dz of layer lp, finished inside the next one
         auto pre_tail = [&](float (&Z)[KS], int t) __attribute__((always_inline)) {
             if (t >= NT) return;
             const int jo = TB + (t >> 2), r = t & 3;
-            if (BITS) Z[4 * TB + t] = rr_mask_gate<KS>(mwt, 4 * TB + t, acc[jo][r]);
+            if (WORDS) Z[4 * TB + t] = rr_mask_gate<KS>(mwt, 4 * TB + t, acc[jo][r]);
             else Z[4 * TB + t] = (row_ok && avt[jo - TB][r] > 0.f) ? acc[jo][r] : 0.f;
         };
 
         // ---- top product: dz_top = mask_top * (W_out^T dy); the first chain product's masks are requested with its own
         fetch_masks(nw - 1, avA);
-        if (!BITS) fetch_masks(nw - 2, avB);
+        if (!WORDS) fetch_masks(nw - 2, avB);
         {
             float at[4][NB];
 #pragma unroll
@@ -721,7 +735,7 @@ __global__ __launch_bounds__(256) void node_rr_bwd_kernel(const NodeRkBwdLaunch 
         constexpr bool defer_top = false;
         mwt = mw;
 #else
-        constexpr bool defer_top = BITS != 0;
+        constexpr bool defer_top = WORDS;
 #endif
         if (!defer_top) {       // (activation mode keeps one set of mask registers: the top product is finished at once)
 #pragma unroll
@@ -734,7 +748,7 @@ __global__ __launch_bounds__(256) void node_rr_bwd_kernel(const NodeRkBwdLaunch 
             constexpr int p = decltype(pc)::value;
             const int lo = nw - 1 - p;                            // the layer whose dz this product yields
             mwt = mw;
-            if (BITS) fetch_masks(lo, avC);
+            if (WORDS) fetch_masks(lo, avC);
             __builtin_amdgcn_sched_barrier(0);
             const int cur = wbase + lo * S::LAYER_BYTES;              // fragments of layer lo + 1 sit at index lo
             const int nxt = (lo >= 1) ? cur - S::LAYER_BYTES : wbase + first_l * S::LAYER_BYTES;
@@ -744,12 +758,12 @@ __global__ __launch_bounds__(256) void node_rr_bwd_kernel(const NodeRkBwdLaunch 
                          else pre_tail(Zin, ks);
                      },
                      [&](int jo, int r) __attribute__((always_inline)) {
-                         if (BITS) Zout[4 * jo + r] = rr_mask_gate<KS>(mw, 4 * jo + r, acc[jo][r]);
+                         if (WORDS) Zout[4 * jo + r] = rr_mask_gate<KS>(mw, 4 * jo + r, acc[jo][r]);
                          else Zout[4 * jo + r] = (row_ok && avC[jo][r] > 0.f) ? acc[jo][r] : 0.f;
                      },
                      [&]() __attribute__((always_inline)) {
                          save_dz(lo + 1, Zin);                        // (Zin is complete: its tail was finished in group 0)
-                         if (!BITS && lo >= 1) fetch_masks(lo - 1, avN);
+                         if (!WORDS && lo >= 1) fetch_masks(lo - 1, avN);
                      });
             avt[0] = avC[TB]; avt[1] = avC[TB + 1];               // (this product's own tail is finished in the next one)
         };
@@ -790,14 +804,14 @@ __global__ __launch_bounds__(256) void node_rr_bwd_kernel(const NodeRkBwdLaunch 
                 __hip_atomic_store(sFlag + half, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 PF partF;
                 partF.prime(rs, voff, curB3);
-                if (BITS) fetch_masks(2, avB);                // (activation mode: layer 2's rows are in avB already)
+                if (WORDS) fetch_masks(2, avB);                // (activation mode: layer 2's rows are in avB already)
                 partF.run(acc, zero, Za, rs, voff, curB3, [&](int) __attribute__((always_inline)) {},
                           [&](int jo, int r) __attribute__((always_inline)) {
-                              if (BITS) Zb[4 * jo + r] = rr_mask_gate<KS>(mw, 4 * jo + r, acc[jo][r]);
+                              if (WORDS) Zb[4 * jo + r] = rr_mask_gate<KS>(mw, 4 * jo + r, acc[jo][r]);
                               else Zb[4 * jo + r] = (row_ok && avB[jo][r] > 0.f) ? acc[jo][r] : 0.f;
                           });
                 save_dz(3, Za);
-                if (!BITS) fetch_masks(1, avA);
+                if (!WORDS) fetch_masks(1, avA);
                 avt[0] = avB[TB]; avt[1] = avB[TB + 1];
                 // the lower blocks, from the g_net wave
                 while (__hip_atomic_load(sFlag + 2 + half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != key) __builtin_amdgcn_s_sleep(1);
@@ -813,8 +827,10 @@ __global__ __launch_bounds__(256) void node_rr_bwd_kernel(const NodeRkBwdLaunch 
                 // the lower groups of blocks of f_net's dz_2 for the same rows, before this wave's own chain
                 unsigned mwF = 0u;
                 f32x4 avF[PG::J1];
-                if (BITS) {
-                    mwF = reinterpret_cast<const unsigned*>(actsF + 2 * L.acts_ls[0])[srow * 4 + q];
+                if (WORDS) {
+                    const unsigned* const wordsF = reinterpret_cast<const unsigned*>(
+                        BITS == 2 ? actsF + (long)(netF.n_layers - 1) * L.acts_ls[0] : actsF);
+                    mwF = wordsF[2 * (BITS == 2 ? (long)L.S_total * n * 4 : L.acts_ls[0]) + srow * 4 + q];
                     mwF = row_ok ? mwF : 0u;
                 } else {
                     const float* arow = actsF + 2 * L.acts_ls[0] + srow * HID;
@@ -836,7 +852,7 @@ __global__ __launch_bounds__(256) void node_rr_bwd_kernel(const NodeRkBwdLaunch 
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         float v;
-                        if (BITS) v = rr_mask_gate<KS>(mwF, 4 * jo + r, acc[jo][r]);
+                        if (WORDS) v = rr_mask_gate<KS>(mwF, 4 * jo + r, acc[jo][r]);
                         else v = (row_ok && avF[jo][r] > 0.f) ? acc[jo][r] : 0.f;
                         sX2[(half * 16 + 4 * jo + r) * 64 + lane] = v;
                     }
@@ -937,10 +953,14 @@ int nlbac_node_rr_fwd_launch(NodeRkLaunch& L, hipStream_t s) {
                                          {node_rr_fwd_kernel<8, 4, 0, 1>, node_rr_fwd_kernel<8, 4, 1, 1>}}};
     const size_t lds = (size_t)(RkFwdTile::floats() + NLBAC_MLP_TILE * 8 + 2 * 3 * 8 * 64 +
                                 2 * 32 * 64 + NLBAC_MLP_TILE * RK_MAX_NS + 2 * 2 * 64 + 4) * sizeof(float);
+    // rows + words (acts_bits 2, the NODE fit): the unsplit forward, whose sums are those of the rows-only one
+    static const KernelF kfw[3] = {node_rr_fwd_kernel<4, 4, 2, 0>, node_rr_fwd_kernel<7, 1, 2, 0>, node_rr_fwd_kernel<8, 4, 2, 0>};
     const dim3 grid(nlbac_ceil_div(L.n, NLBAC_MLP_TILE));
+    const int shape = rr_shape_index(L.net[0].hid);
     // (the forward is split in mask mode only: with activation rows kept — the NODE fit, 32768 rows, two workgroups per
     //  CU — the two waves' store bursts and the hand-over cost more than the balance gains: 140 against 124 us per launch)
-    hipLaunchKernelGGL(kf[(rr_split() && L.acts_bits) ? 1 : 0][rr_shape_index(L.net[0].hid)][L.acts_bits ? 1 : 0], grid, dim3(256), lds, s, L);
+    const KernelF k = (L.acts_bits == 2) ? kfw[shape] : kf[(rr_split() && L.acts_bits) ? 1 : 0][shape][L.acts_bits ? 1 : 0];
+    hipLaunchKernelGGL(k, grid, dim3(256), lds, s, L);
     NLBAC_CHECK_LAUNCH("nlbac_node_rk_fwd(rr)");
     return 0;
 }
@@ -968,9 +988,14 @@ int nlbac_node_rr_bwd_launch(NodeRkBwdLaunch& L, hipStream_t s) {
                                         {{node_rr_bwd_kernel<4, 4, 0, 1>, node_rr_bwd_kernel<4, 4, 1, 1>},
                                          {node_rr_bwd_kernel<7, 1, 0, 1>, node_rr_bwd_kernel<7, 1, 1, 1>},
                                          {node_rr_bwd_kernel<8, 4, 0, 1>, node_rr_bwd_kernel<8, 4, 1, 1>}}};
+    // rows + words (acts_bits 2, the NODE fit): gates from the words, dz rows stored as in activation mode
+    static const KernelB kbw[2][3] = {{node_rr_bwd_kernel<4, 4, 2, 0>, node_rr_bwd_kernel<7, 1, 2, 0>, node_rr_bwd_kernel<8, 4, 2, 0>},
+                                      {node_rr_bwd_kernel<4, 4, 2, 1>, node_rr_bwd_kernel<7, 1, 2, 1>, node_rr_bwd_kernel<8, 4, 2, 1>}};
     const size_t lds = (size_t)(RkBwdTile::floats() + 2 * 4 * 8 * 64 + 2 * 32 * 64 + 2 * 16 * 64 + 4) * sizeof(float);
     const dim3 grid(nlbac_ceil_div(L.n, NLBAC_MLP_TILE));
-    hipLaunchKernelGGL(kb[rr_split() ? 1 : 0][rr_shape_index(L.net[0].hid)][L.acts_bits ? 1 : 0], grid, dim3(256), lds, s, L);
+    const int split = rr_split() ? 1 : 0, shape = rr_shape_index(L.net[0].hid);
+    const KernelB k = (L.acts_bits == 2) ? kbw[split][shape] : kb[split][shape][L.acts_bits ? 1 : 0];
+    hipLaunchKernelGGL(k, grid, dim3(256), lds, s, L);
     NLBAC_CHECK_LAUNCH("nlbac_node_rk_bwd(rr)");
     return 0;
 }

@@ -136,8 +136,19 @@ class _StepWS:
             self.acts_g = zi(g.n_layers - 1, S * n, self.wg)
         else:
             self.wf, self.wg = f.hid, g.hid
+        # rows + words (acts_bits 2, the NODE fit on the register-resident kernels): the forward also leaves the ReLU
+        # mask words, which the backward gates on; the weight gradients read the rows.  Each net's words
+        # [layer][S*n][4] sit directly behind its rows — where nlbac_node_rk_fwd / _bwd look for them
+        self.words = not self.bits and solver._fit_words_on()
+        self.acts_bits = 1 if self.bits else (2 if self.words else 0)
+        if not self.bits:       # (hid % 4 == 0: the rows fill their carve, the words start where they end)
+            mw = lambda net: self._store.zeros(net.n_layers - 1, S * n, 4, dtype=torch.int32) if self.words else None
             self.acts_f = z(f.n_layers - 1, S * n, f.hid)
+            self.mw_f = mw(f)
             self.acts_g = z(g.n_layers - 1, S * n, g.hid)
+            self.mw_g = mw(g)
+        if self.words:
+            self.ADOPT = _StepWS.ADOPT + ("mw_f", "mw_g")
         self.y1 = z(n, ns)
         self.err = z(n, ns)
         self._bwd = None
@@ -225,7 +236,7 @@ class AffineNodeSolver:
         used buckets are kept).  ``generation`` counts every event that frees or re-lays-out device buffers — captured
         hipGraphs bake their addresses in and are dropped by their owners when it moves."""
         pools = self.__dict__.setdefault("_pools", {})
-        key = (self._bucket(n), S, self.fused, self.keep_acts)
+        key = (self._bucket(n), S, self.fused, self.keep_acts, self._fit_words_on())
         pool = pools.get(key)
         dropped = False
         if pool is not None and pool.n_slots < min_slots:
@@ -257,6 +268,24 @@ class AffineNodeSolver:
 
     MAX_POOL_BYTES = 128 * 2 ** 30
 
+    def _fit_words_on(self):
+        """A solve whose backward wants weight gradients (the NODE fit: ``keep_acts``) keeps the activation rows AND the
+        ReLU mask words (acts_bits 2) where the register-resident kernels serve both nets: the backward gates on the
+        words instead of re-reading the rows, which only the weight gradients need.  ``fit_words = False``
+        (NLBAC_FIT_WORDS=0): rows only, the backward gates on them — the cross-check."""
+        if not (self.fused and self.keep_acts):
+            return False
+        on = self.__dict__.get("fit_words")
+        if on is None:
+            on = self.fit_words = os.environ.get("NLBAC_FIT_WORDS", "1") != "0"
+        if not on:
+            return False
+        ok = self.__dict__.get("_words_ok")
+        if ok is None:
+            lib, f, g = _lib.load(), C.byref(self.f.desc), C.byref(self.g.desc)
+            ok = self._words_ok = lib.nlbac_node_rk_mask_words(f, g, 0) == 4 and lib.nlbac_node_rk_mask_words(f, g, 1) == 4
+        return ok
+
     def _step_ws(self, n, S, idx):
         pool = self._pool(n, S)
         had = (n, idx) in pool.views
@@ -284,6 +313,7 @@ class AffineNodeSolver:
                     self._children[p] = type(self)(self.node, self.device)
                 k = self._children[p]
                 k.comm, k.fused, k.keep_acts = self.comm, self.fused, self.keep_acts
+                k.fit_words = self.__dict__.get("fit_words")
                 # the per-problem solvers run one after the other inside this solver's solve: they share its read-back
                 # stream and pinned blocks (a pinned allocation costs milliseconds)
                 self._ctl_io(1)
@@ -383,7 +413,7 @@ class AffineNodeSolver:
                   fptr(*h_host) if h_host is not None else None, h_dev, _lib.DOPRI_CTL if h_dev else 0,
                   ws.K.data_ptr(), ws.Y.data_ptr(), ws.gout.data_ptr(),
                   ws.acts_f.data_ptr() if save_acts else None, ws.S * n * ws.wf,
-                  ws.acts_g.data_ptr() if save_acts else None, ws.S * n * ws.wg, 1 if ws.bits else 0,
+                  ws.acts_g.data_ptr() if save_acts else None, ws.S * n * ws.wg, ws.acts_bits if save_acts else int(ws.bits),
                   out.data_ptr() if out is not None else None, err.data_ptr() if err is not None else None,
                   C.byref(chain) if chain is not None else None, C.byref(im) if im is not None else None, stream_ptr())
         self.nfe += st1 - st0
@@ -396,7 +426,7 @@ class AffineNodeSolver:
         _lib.call("nlbac_node_rk_bwd", C.byref(f.desc), C.byref(g.desc), u.data_ptr(), ws.gout.data_ptr(), P, rpp,
                   S, 0 if first_eval else 1, S, 1 if need_dy0 else 0, beta_arr, h_host, h_dev, h_stride,
                   ws.acts_f.data_ptr(), S * ws.n * ws.wf, ws.acts_g.data_ptr(), S * ws.n * ws.wg,
-                  1 if ws.bits else 0, ws.dz_f.data_ptr() if need_params else None,
+                  ws.acts_bits, ws.dz_f.data_ptr() if need_params else None,
                   ws.dz_g.data_ptr() if need_params else None, ws.dG.data_ptr() if need_params else None,
                   ws.dK.data_ptr(), top_up.data_ptr() if top_up is not None else None, ws.dy0.data_ptr(), 1,
                   du.data_ptr() if du is not None else None, 0 if last else 1,
@@ -1103,6 +1133,7 @@ class AffineNodeSolver:
                 self._children[p] = type(self)(self.node, self.device)
             k = self._children[p]
             k.comm, k.fused, k.keep_acts = self.comm, self.fused, self.keep_acts
+            k.fit_words = self.__dict__.get("fit_words")
             self._ctl_io(1)
             k._side, k._ev_ctl, k._ctl_pin = self._side, self._ev_ctl, self._ctl_pin
             k.before_wait = self.__dict__.get("before_wait")
@@ -1607,6 +1638,9 @@ class ConcatNodeSolver(AffineNodeSolver):
 
     def _interp_nets(self):
         return C.byref(self.net.desc), None
+
+    def _fit_words_on(self):
+        return False
 
     def _begin_persistent(self, ws0, ch, y0, u, P, rpp):
         return False

@@ -787,53 +787,6 @@ extern "C" int nlbac_node_rk_fwd(const nlbac_mlp* f, const nlbac_mlp* g, const f
     return 0;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// The three launches that open a dopri5 solve on the device-driven chain as ONE persistent launch (node_rr_kernels.hip:
-// node_rr_fwd_begin_kernel).  What the host would pass to the three nlbac_node_rk_fwd calls is derived here:
-//   A  stage 0 of the step (with the in-map), norm mode 0 -> Hairer's first guess C_H0;
-//   B  the probe f(y0 + h0 f0): tableau [[1]], step size C_H0, no masks kept, norm mode 1 -> the initial step C_H;
-//   C  the first attempted step, stages 1..6 with step size C_H, error estimate, interpolation at t_end (chain->interp_*);
-//      its norm + controller stay the separate slot-aware launch (nlbac_dopri_norm_control), as for every attempt.
-// chain: the attempt's description (ctl = ctl_w = the control blocks, partials / tickets for the fused norms of A and B).
-// gen: P uint32, zero before the first use; target: any value > 0 that no earlier launch on these words used + 2.
-// ---------------------------------------------------------------------------------------------------------------------
-extern "C" int nlbac_node_rk_fwd_begin_ok(const nlbac_mlp* f, const nlbac_mlp* g, int P, int rows_per_problem) {
-    if (!f || !g || !nlbac_node_rr_eligible(f, g)) return 0;
-    // every workgroup of the launch must be resident at once: one 32-row tile per CU
-    return ((P == 1 || rows_per_problem % NLBAC_MLP_TILE == 0) && (long)P * rows_per_problem <= 256L * NLBAC_MLP_TILE) ? 1 : 0;
-}
-
-extern "C" int nlbac_node_rk_fwd_begin(const nlbac_mlp* f, const nlbac_mlp* g, float* y0, const float* u, int P,
-                                       int rows_per_problem, const float* beta /* dopri5: [7][7] */, const float* c_err,
-                                       int n_err, float* K, float* Y, float* G, float* acts_f, long acts_f_ls,
-                                       float* acts_g, long acts_g_ls, float* err, const nlbac_rk_chain* chain,
-                                       const nlbac_in_map* in_map, unsigned* gen, unsigned target, nlbac_stream_t s) {
-    const char* who = "nlbac_node_rk_fwd_begin";
-    NLBAC_REQUIRE(chain && chain->ctl && chain->ctl_w == chain->ctl && chain->partials && chain->tickets && gen && target >= 1u &&
-                      target < 0xFFFFFFF0u && err && c_err && acts_f && acts_g,
-                  "%s: needs the control blocks, partials, tickets, the error buffer, mask buffers and the generation words", who);
-    NLBAC_REQUIRE(nlbac_node_rk_fwd_begin_ok(f, g, P, rows_per_problem), "%s: not available for these nets / sizes (nlbac_node_rk_fwd_begin_ok)", who);
-    double* ctl = chain->ctl_w;
-    nlbac_rk_chain ca = *chain, cb = *chain, cc = *chain;
-    ca.ctl = nullptr; ca.norm_mode = 0; ca.interp_out = nullptr; ca.interp_bwd = 0;
-    cb.ctl = nullptr; cb.norm_mode = 1; cb.interp_out = nullptr; cb.interp_bwd = 0;
-    cc.norm_mode = -1;
-    static const float probe_beta[4] = {0.f, 0.f, 1.f, 0.f};      // [[0, 0], [1, 0]]
-    NodeRkLaunch LA, LB, LC;
-    if (rk_fwd_fill(LA, f, g, y0, u, P, rows_per_problem, 0, 1, 7, beta, nullptr, 0, nullptr, 0, nullptr, ctl + C_H,
-                    NLBAC_DOPRI_CTL, K, Y, G, acts_f, acts_f_ls, acts_g, acts_g_ls, 1, nullptr, nullptr, &ca, in_map)) return -1;
-    if (rk_fwd_fill(LB, f, g, y0, u, P, rows_per_problem, 1, 2, 2, probe_beta, nullptr, 0, nullptr, 0, nullptr, ctl + C_H0,
-                    NLBAC_DOPRI_CTL, K, Y, G, nullptr, acts_f_ls, nullptr, acts_g_ls, 1, nullptr, nullptr, &cb, nullptr)) return -1;
-    if (rk_fwd_fill(LC, f, g, y0, u, P, rows_per_problem, 1, 7, 7, beta, nullptr, 0, c_err, n_err, nullptr, ctl + C_H,
-                    NLBAC_DOPRI_CTL, K, Y, G, acts_f, acts_f_ls, acts_g, acts_g_ls, 1, nullptr, err, &cc, nullptr)) return -1;
-    LA.pers_gen = gen; LA.pers_target = target;      LA.coh = 0;
-    LB.pers_gen = gen; LB.pers_target = target + 1u; LB.coh = 1;
-    LC.pers_gen = nullptr;                           LC.coh = 1;
-    const int rr = nlbac_node_rr_fwd_begin_launch(LA, LB, LC, (hipStream_t)s);
-    NLBAC_REQUIRE(rr == 0, "%s: the register-resident kernels do not take this launch", who);
-    return 0;
-}
-
 bool nlbac_concat_rr_eligible(const nlbac_mlp* net);      // (concat_rr_kernels.hip)
 extern "C" int nlbac_rk_interp_ok(const nlbac_mlp* f, const nlbac_mlp* g) {
     if (!f) return 0;

@@ -485,24 +485,6 @@ __global__ __launch_bounds__(256) void node_rr_fwd_kernel(const NodeRkLaunch L) 
     node_rr_fwd_body<NB, R, BITS, SPLIT>(L);
 }
 
-// The three launches that open a dopri5 solve — f0 = field(y0) with Hairer's first guess, the probe f(y0 + h0 f0) with
-// the initial step size, the first attempted step (stages 1..6) — as ONE launch (nlbac_node_rk_fwd_begin): the same code
-// three times, a per-problem wait in between (rk_fwd_grid_wait: the workgroup that ran the phase's controller releases
-// the others).  What it was meant to save is two launches' dispatch, prologue and cold weights (f0 + probe cost 44 us in
-// the update for two stage evaluations of 8.7 us) — measured, it saves nothing: 108 us against 105 (the cost of the
-// one-stage launches is their norm's election, and the waits here are the same elections).  Kept behind
-// NLBAC_NODE_PERSIST=1, tested against the three launches (bit-identical).  Needs every workgroup of the launch resident
-// at once: <= 8192 rows.
-template <int NB, int R, int SPLIT>
-__global__ __launch_bounds__(256) void node_rr_fwd_begin_kernel(const NodeRkLaunch LA, const NodeRkLaunch LB, const NodeRkLaunch LC) {
-    const int row0 = blockIdx.x * NLBAC_MLP_TILE;
-    node_rr_fwd_body<NB, R, 1, SPLIT>(LA);
-    if (!rk_fwd_grid_wait(LA, row0)) return;
-    node_rr_fwd_body<NB, R, 1, SPLIT>(LB);
-    if (!rk_fwd_grid_wait(LB, row0)) return;
-    node_rr_fwd_body<NB, R, 1, SPLIT>(LC);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // Backward of the same step, same wave roles.  Per stage (descending): the output layer's gradient enters as the B
 // operand of one transposed block product, then dz_{l-1} = mask_{l-1} * (W_l^T dz_l) down the chain in registers (the
@@ -962,20 +944,6 @@ int nlbac_node_rr_fwd_launch(NodeRkLaunch& L, hipStream_t s) {
     const KernelF k = (L.acts_bits == 2) ? kfw[shape] : kf[(rr_split() && L.acts_bits) ? 1 : 0][shape][L.acts_bits ? 1 : 0];
     hipLaunchKernelGGL(k, grid, dim3(256), lds, s, L);
     NLBAC_CHECK_LAUNCH("nlbac_node_rk_fwd(rr)");
-    return 0;
-}
-
-// 0 = launched, 1 = not these nets' launch
-int nlbac_node_rr_fwd_begin_launch(NodeRkLaunch& LA, NodeRkLaunch& LB, NodeRkLaunch& LC, hipStream_t s) {
-    if (!nlbac_node_rr_eligible(&LA.net[0], &LA.net[1]) || !LA.acts_bits) return 1;
-    using Kernel3 = void (*)(const NodeRkLaunch, const NodeRkLaunch, const NodeRkLaunch);
-    static const Kernel3 k3[2][3] = {{node_rr_fwd_begin_kernel<4, 4, 0>, node_rr_fwd_begin_kernel<7, 1, 0>, node_rr_fwd_begin_kernel<8, 4, 0>},
-                                     {node_rr_fwd_begin_kernel<4, 4, 1>, node_rr_fwd_begin_kernel<7, 1, 1>, node_rr_fwd_begin_kernel<8, 4, 1>}};
-    const size_t lds = (size_t)(RkFwdTile::floats() + NLBAC_MLP_TILE * 8 + 2 * 3 * 8 * 64 +
-                                2 * 32 * 64 + NLBAC_MLP_TILE * RK_MAX_NS + 2 * 2 * 64 + 4) * sizeof(float);
-    const dim3 grid(nlbac_ceil_div(LA.n, NLBAC_MLP_TILE));
-    hipLaunchKernelGGL(k3[rr_split() ? 1 : 0][rr_shape_index(LA.net[0].hid)], grid, dim3(256), lds, s, LA, LB, LC);
-    NLBAC_CHECK_LAUNCH("nlbac_node_rk_fwd_begin(rr)");
     return 0;
 }
 

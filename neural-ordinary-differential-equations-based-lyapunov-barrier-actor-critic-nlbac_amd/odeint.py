@@ -45,12 +45,9 @@ TABLEAU = {
 }
 
 
-# How small results reach the host (the dopri5 control block here, the update's scalars block in sac_cbf_clf.py):
-# "kernel" — the producing kernel writes pinned host memory itself; "side" — an async copy on a side stream behind an event.
-HOST_COPY = os.environ.get("NLBAC_HOST_COPY", "kernel")
-# How the host learns that a controller launch has left its decision in the pinned control block: by polling the block's
-# stamp (a sequence lock the launch writes, nlbac_rk_chain::ctl_seq) or ("0") by an event behind the launch.
-CTL_POLL = os.environ.get("NLBAC_CTL_POLL", "1") != "0"
+# How the host learns the dopri5 controller's decision: where the controller launch writes the pinned control block
+# itself, by polling the block's stamp (a sequence lock the launch writes, nlbac_rk_chain::ctl_seq); where it cannot
+# (data parallelism, the host-driven steps of ragged row counts), by a copy on a side stream behind an event (_ctl_post).
 _SEQ = [0]
 NORM_DEFER_ATTEMPT = os.environ.get("NLBAC_NORM_DEFER_ATTEMPT", "1") != "0"
 
@@ -541,9 +538,9 @@ class AffineNodeSolver:
         self.ctx["ctl_pending"] = P
 
     def _seq_next(self, first_of_solve=False):
-        """Stamp for the next controller launch that writes the host's copy (``CTL_POLL``); ctx["ctl_seq"] = (stamp of the
-        solve's first such launch, stamp of its latest).  None when the block is read behind an event."""
-        if not CTL_POLL or torch.cuda.is_current_stream_capturing() or HOST_COPY == "side":
+        """Stamp for the next controller launch that writes the host's copy; ctx["ctl_seq"] = (stamp of the solve's first
+        such launch, stamp of its latest).  None when the block is read behind an event."""
+        if torch.cuda.is_current_stream_capturing():
             self.ctx["ctl_seq"] = None
             return 0.0
         _SEQ[0] += 1                 # (one counter per process: solvers share pinned blocks, see _solve_split)
@@ -775,9 +772,7 @@ class AffineNodeSolver:
         c.ctl_w, c.hslots = ctl.data_ptr(), hs.data_ptr()
         c.alog, c.alog_cap = self._buf("alog", P, self.ALOG_CAP, 3, dtype=torch.float64).data_ptr(), self.ALOG_CAP
         # the controller leaves the host's copy of the control block in pinned memory itself (see _ctl_posted)
-        # ... unless host_copy == "side": a kernel that writes host memory holds the stream until the write has crossed PCIe
-        # (~5 us before the next launch may start); a copy on the side stream does not
-        c.ctl_host = None if (torch.cuda.is_current_stream_capturing() or HOST_COPY == "side") else self._ctl_io(P)[1].data_ptr()
+        c.ctl_host = None if torch.cuda.is_current_stream_capturing() else self._ctl_io(P)[1].data_ptr()
         # Where the norm + controller run.  Fused into the RK launch's epilogue (last workgroup of a problem) for the two
         # one-stage launches of the initial-step selection: same GPU time as a launch of their own (26.7 us against
         # 18 + 9), one launch less each.  NOT for an attempted step: the epilogue's device-scope atomics queue behind the
@@ -831,11 +826,6 @@ class AffineNodeSolver:
                 ch[2].interp_kind, ch[2].interp_l, ch[2].interp_p = om.kind, om.l, om.p
         ctx["chain"] = dict(pool=pool, ws0=ws0, ch=ch[2], attempts=0, y0=y0, ip=ip, ip_om=om is not None)
         k = max(1, int(self.__dict__.get("_chain_len", 1)))
-        if self._begin_persistent(ws0, ch, y0, u, P, rpp):
-            # f0, the probe and the first attempted step were ONE launch (nlbac_node_rk_fwd_begin); the attempt's norm +
-            # controller and any further attempts follow as usual
-            self._chain_attempts(k, first_rk_done=True)
-            return
         if self._norm_defer_ok(ch):
             # The norms of f0 and of the probe without their elections (nlbac_rk_chain::norm_defer / norm_pre): each
             # launch leaves its tiles' partial sums, the NEXT launch's workgroups sum them and run the controller
@@ -873,59 +863,18 @@ class AffineNodeSolver:
             ok = self._interp_ok = bool(_lib.load().nlbac_rk_interp_ok(*self._interp_nets()))
         return bool(ok and self.fused)
 
-    def _begin_persistent(self, ws0, ch, y0, u, P, rpp):
-        """f0 + first guess, probe + initial step and the first attempted step as ONE persistent launch
-        (nlbac_node_rk_fwd_begin) where the kernels and the sizes allow it: single GPU (the first two norms are fused:
-        no all-reduce in between), mask words (rollouts), every workgroup resident at once (<= 8192 rows).
-        OFF unless ``persistent = True`` / NLBAC_NODE_PERSIST=1: measured on MI355X it does not win — 108 us against
-        23.6 + 20.7 + 60.9 = 105 us for the three launches at 8192 rows (profiles/r04: what the one-stage launches cost
-        beyond their stage is not dispatch but the norm's election — partial sums, ticket, the controller, the release —
-        ~10 us of serial round trips each, and the persistent launch has the same two)."""
-        if not (self.fused and (self.comm is None or self.comm.world == 1) and ws0.bits and not self.adjoint):
-            return False
-        on = self.__dict__.get("persistent")
-        if on is None:
-            on = os.environ.get("NLBAC_NODE_PERSIST", "0") == "1"
-        if not on:
-            return False
-        key = (P, rpp)
-        ok = self.__dict__.setdefault("_pers_ok", {}).get(key)
-        if ok is None:
-            ok = self._pers_ok[key] = bool(_lib.load().nlbac_node_rk_fwd_begin_ok(C.byref(self.f.desc), C.byref(self.g.desc), P, rpp))
-        if not ok or ch[0].norm_mode != 0 or ch[1].norm_mode != 1:       # (the first two norms must be the fused ones)
-            return False
-        n = P * rpp
-        im = None
-        if self.ctx.pop("in_map_pending", None):
-            m, im = self._in_map, _lib.InMap()
-            im.kind, im.obs, im.obs_ld, im.l = m["kind"], m["obs"].data_ptr(), m["obs_ld"], m["l"]
-            im.ps = m["ps"].data_ptr() if m["ps"] is not None else None
-        c = _lib.RkChain.from_buffer_copy(ch[2])
-        c.partials, c.tickets = ch[0].partials, ch[0].tickets       # (the fused norms of the first two phases)
-        gen = self._buf("pers_gen", 8, dtype=torch.int32)
-        self._pers_id = self.__dict__.get("_pers_id", 0) + 1
-        beta, S = self._beta("dopri5")
-        cerr = self._coef("err")
-        _lib.call("nlbac_node_rk_fwd_begin", C.byref(self.f.desc), C.byref(self.g.desc), y0.data_ptr(), u.data_ptr(), P, rpp,
-                  beta, cerr, len(cerr), ws0.K.data_ptr(), ws0.Y.data_ptr(), ws0.gout.data_ptr(),
-                  ws0.acts_f.data_ptr(), ws0.S * n * ws0.wf, ws0.acts_g.data_ptr(), ws0.S * n * ws0.wg, ws0.err.data_ptr(),
-                  C.byref(c), C.byref(im) if im is not None else None, gen.data_ptr(), 2 * self._pers_id, stream_ptr())
-        self.nfe += 8
-        return True
-
-    def _chain_attempts(self, k, first_rk_done=False):
+    def _chain_attempts(self, k):
         ctx = self.ctx
         st = ctx["chain"]
         P, rpp, u = ctx["P"], ctx["rpp"], ctx["u"]
         ws0, pool, ch = st["ws0"], st["pool"], st["ch"]
         cp = self._ctl(P).data_ptr()
-        for i in range(k):
-            if not (first_rk_done and i == 0):
-                self._rk_fused(ws0, st["y0"], u, P, rpp, "dopri5", 1, 7, h_dev=cp, c_err=self._coef("err"), err=ws0.err,
-                               chain=st.pop("ch_first", None) or ch)
+        for _ in range(k):
+            self._rk_fused(ws0, st["y0"], u, P, rpp, "dopri5", 1, 7, h_dev=cp, c_err=self._coef("err"), err=ws0.err,
+                           chain=st.pop("ch_first", None) or ch)
             self._chain_control(ws0, pool, ch, st["y0"], u, 2, P, rpp)
         st["attempts"] += k
-        if (self.comm is not None and self.comm.world > 1) or HOST_COPY == "side" or (ch.norm_mode == 2 and not ch.norm_defer):
+        if (self.comm is not None and self.comm.world > 1) or (ch.norm_mode == 2 and not ch.norm_defer):
             self._ctl_post(P)        # (the all-reduced controller is nlbac_dopri_control: it leaves no host copy; nor does
                                      #  the RK launch's own epilogue, FUSED_NORM_MODES with 2)
         else:
@@ -1304,7 +1253,7 @@ class AffineNodeSolver:
         # (an attempt's controller leaves the host's copy of the control block in pinned memory itself: no copy launch
         #  between the decision and the host; see _ctl_posted)
         host, seq = None, 0.0
-        if mode == 2 and not torch.cuda.is_current_stream_capturing() and HOST_COPY != "side":
+        if mode == 2 and not torch.cuda.is_current_stream_capturing():
             host = self._ctl_io(P)[1].data_ptr()
             seq = self._seq_next()
         ctx["adj_ctl_host"] = host is not None
@@ -1640,9 +1589,6 @@ class ConcatNodeSolver(AffineNodeSolver):
         return C.byref(self.net.desc), None
 
     def _fit_words_on(self):
-        return False
-
-    def _begin_persistent(self, ws0, ch, y0, u, P, rpp):
         return False
 
     # -- continuous adjoint (odeint_adjoint) of the single-net field ---------------------------------------------

@@ -30,7 +30,6 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..odeint import HOST_COPY
 from ..arena import Arena, bwd_weights, io_array, mlp_array, pack, skinny_partials_ws, stream_ptr
 from . import _layout as SC
 from .model import BarrierNetwork, GaussianPolicy, LyaNetwork, QNetwork
@@ -1148,21 +1147,8 @@ class SAC_CBF_CLF(object):
                        [sc + 4 * (SC.SC_ALPHA + g.first + k) for k in range(cnt)]) if tune else None
             last = g is P.act_groups[-1][0]
             mir = self.__dict__.get("_mirror") if last else None
-            side = mir is not None and HOST_COPY == "side"
-            self._adam(a, self.lr, a.n_slabs, before_step=alpha_grads, alpha=refresh, mirror=mir[1] if (mir and not side) else None)
-            if side:
-                # the scalars block reaches the host by a copy on a side stream: a kernel that writes host memory holds
-                # the launch stream until the write has crossed PCIe (~5 us before the prefetched launches could start)
-                st = self.__dict__.get("_sc_side")
-                if st is None:
-                    st = self._sc_side = (torch.cuda.Stream(device=self.device), torch.cuda.Event())
-                st[1].record()
-                st[0].wait_event(st[1])
-                with torch.cuda.stream(st[0]):
-                    mir[1].copy_(self.sc, non_blocking=True)
-                    self._sc_ev[mir[0]].record()
-                self._mirror_done = mir[0]
-            elif mir:
+            self._adam(a, self.lr, a.n_slabs, before_step=alpha_grads, alpha=refresh, mirror=mir[1] if mir else None)
+            if mir:
                 self._mirror_done = mir[0]
                 self._sc_ev[mir[0]].record()     # (here, not in _returns: what _prefetch_next queues is not waited for)
         self._prefetch_next(ws, ws.updates_now)

@@ -29,13 +29,15 @@ def header_functions():
     return sorted(set(re.findall(r"\b(nlbac_[a-z0-9_]+)\s*\(", txt)))
 
 
-def test_library_exports_every_declared_symbol(lib):
+def test_library_exports_every_declared_symbol_and_its_abi_version(lib):
     names = header_functions()
     assert len(names) >= 30
     for n in names:
         assert hasattr(lib, n), "libnlbac_hip.so does not export %s" % n
     assert set(names) == set(_lib.EXPORTS), set(names) ^ set(_lib.EXPORTS)
-    assert lib.nlbac_abi_version() == _lib.ABI_VERSION == 16
+    txt = open(os.path.join(ROOT, "include", "nlbac_hip.h")).read()
+    header_abi = int(re.search(r"#define NLBAC_ABI_VERSION (\d+)", txt).group(1))
+    assert lib.nlbac_abi_version() == _lib.ABI_VERSION == header_abi == 17
 
 
 def test_ctypes_structs_match_header_sizes(lib):

@@ -580,6 +580,27 @@ int nlbac_node_rk_bwd(const nlbac_mlp *f, const nlbac_mlp *g, const float *u, co
                       float *dz_f, float *dz_g, float *dG, float *dK, const float *dYup, float *dy0,
                       int dy0_in, float *du, int du_acc, const nlbac_rk_chain *chain, int back_idx,
                       nlbac_stream_t s);
+/* One-launch fixed-grid rollout of the control-affine NODE (euler: n_stages 1, rk4: 4, with that method's beta
+ * [n_stages][n_stages] and c_out [n_stages]): H intervals of step h, interval k integrating from out[k-1] (x0 for k = 0)
+ * with actions u[k] — what H nlbac_node_rk_fwd launches compute, bit for bit, in one launch (no inter-workgroup
+ * synchronisation).  Only where nlbac_node_rk_traj_ok(f, g) is 1 (the register-resident kernels' shapes), else 0.
+ * x0 [n][n_s], u [H][n][n_u], out [H][n][n_s] (the states after each interval).  Step-major buffers of H*n_stages
+ * stages, stage (k, st) at index k*n_stages + st: K, Y [H*n_stages][n][n_s], G [H*n_stages][n][n_s*n_u]; acts_* (or
+ * NULL with acts_bits 0: nothing kept) as nlbac_node_rk_fwd lays them out for n_stages_total = H*n_stages. */
+int nlbac_node_rk_traj_ok(const nlbac_mlp *f, const nlbac_mlp *g);
+int nlbac_node_rk_traj_fwd(const nlbac_mlp *f, const nlbac_mlp *g, const float *x0, const float *u, int n, int H,
+                           int n_stages, const float *beta, const float *c_out, float h, float *out, float *K, float *Y,
+                           float *G, float *acts_f, long acts_f_ls, float *acts_g, long acts_g_ls, int acts_bits,
+                           nlbac_stream_t s);
+/* Its backward, intervals H-1 .. 0 in one launch: dout [H+1][n][n_s] = dL/d(x0, out[0..H-1]) -> dx0 [n][n_s] and
+ * du [H][n][n_u]; the gradient w.r.t. an interval's initial state is carried to the interval before it in the launch,
+ * added to dout in the order of the chained one-step backward (nlbac_rk_stage_bwd + nlbac_node_rk_bwd).  dK, dG, dz_f,
+ * dz_g (together, or all NULL; not with acts_bits 1): every stage's dL/dK, d g(x) and pre-activation grads, step-major
+ * as in the forward — the rows nlbac_mlp_bwd_weights takes as one batch of H*n_stages*n. */
+int nlbac_node_rk_traj_bwd(const nlbac_mlp *f, const nlbac_mlp *g, const float *u, int n, int H, int n_stages,
+                           const float *beta, const float *c_out, float h, const float *G, const float *acts_f,
+                           long acts_f_ls, const float *acts_g, long acts_g_ls, int acts_bits, const float *dout,
+                           float *dx0, float *du, float *dK, float *dG, float *dz_f, float *dz_g, nlbac_stream_t s);
 /* The same one-launch RK step for the single-net NODE dx/dt = net([x | c]) with carried inputs c = (u, t)
  * (SimulatedCars, C/sac_cbf_clf/model.py:179-205; odeint call sites C/sac_cbf_clf/sac_cbf_clf.py:437,458,581,603,
  * C/model.py:245): n_s = net->out_dim state columns, n_c = net->in_dim - n_s carried columns (c: (rows, n_c)),

@@ -81,6 +81,11 @@ struct NodeRkBwdLaunch {
 int nlbac_node_rr_fwd_launch(NodeRkLaunch& L, hipStream_t s);
 int nlbac_node_rr_bwd_launch(NodeRkBwdLaunch& L, hipStream_t s);
 bool nlbac_node_rr_eligible(const nlbac_mlp* f, const nlbac_mlp* g);
+// what the trajectory kernels (node_traj_kernels.hip) select by, as the one-step launchers do: the kernels are on
+// (NLBAC_NODE_RR), the width's template shape (0, 1, 2 for 64, 100, 128; -1 none), the f_net / g_net wave balance
+bool nlbac_node_rr_enabled();
+int nlbac_node_rr_shape(int hid);
+bool nlbac_node_rr_split();
 
 // ---------------------------------------------------------------------------------------------------------------
 // forward: the small per-tile arrays in LDS
@@ -671,5 +676,109 @@ __device__ __forceinline__ void rk_bwd_outputs(const NodeRkBwdLaunch& L, const R
         for (int idx = tid; idx < NLBAC_MLP_TILE * nu; idx += NTHR) {
             const int m = idx / nu, c = idx - m * nu, row = row0 + m;
             if (row < n) L.du[(long)row * nu + c] = T.sDU[m * RK_MAX_NU + c];
+        }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// one-launch fixed-grid trajectories (node_traj_kernels.hip): H intervals of euler / rk4 with a new action per interval,
+// every row on its own — a tile walks the intervals one after the other, no workgroup waits for another
+// ---------------------------------------------------------------------------------------------------------------
+struct NodeRkTrajBwd {
+    int H;
+    const float* dout;                // [H+1][n][n_s] dL/d(rollout output)
+    float* dx0;                       // [n][n_s]
+    float c_out[RK_MAX_STAGES]; int n_out;
+};
+
+// forward, behind interval k's last stage: out[k] = y0 + h sum_j c_j K_j (rk_fwd_outputs_and_control's arithmetic) to
+// global and, as interval k+1's y0, to sY0; interval k+1's actions to sU.  One (row, component) per thread; ends with a
+// barrier (every thread must call it).
+template <int NTHR>
+__device__ __forceinline__ void rk_traj_advance(const NodeRkLaunch& L, const RkFwdTile& T, int row0, int k, int H, int tid) {
+    static_assert(NTHR >= NLBAC_MLP_TILE * RK_MAX_NS, "one (row, component) per thread");
+    const int n = L.n, ns = L.n_s, nu = L.n_u;
+    const bool more = k + 1 < H;
+    float vu = 0.f;
+    if (more && tid < NLBAC_MLP_TILE * RK_MAX_NU) {
+        const int m = tid >> 2, c = tid & 3;
+        vu = L.u[(long)(k + 1) * n * nu + (long)min(row0 + m, n - 1) * nu + min(c, nu - 1)];
+    }
+    if (tid < NLBAC_MLP_TILE * RK_MAX_NS) {
+        const int m = tid >> 3, r = tid & 7, row = row0 + m;
+        if (r < ns && row < n) {
+            const float h = T.sH[m];
+            float a = T.sY0[m * RK_MAX_NS + r];
+            for (int j = 0; j < L.n_out; ++j)
+                if (L.c_out[j] != 0.f) a = a + T.sK[(j * NLBAC_MLP_TILE + m) * RK_MAX_NS + r] * (L.c_out[j] * h);
+            L.out[(long)k * n * ns + (long)row * ns + r] = a;
+            T.sY0[m * RK_MAX_NS + r] = a;
+        }
+    }
+    if (more && tid < NLBAC_MLP_TILE * RK_MAX_NU) {
+        const int m = tid >> 2, c = tid & 3;
+        T.sU[tid] = (row0 + m < n && c < nu) ? vu : 0.f;
+    }
+    __syncthreads();
+}
+
+// backward, before interval k's stages (kk = H-1-k intervals done): u_k -> sU, du = 0, and from
+// d = dout[k+1] (+ the dy0 of interval k+1, in sDY0 when kk > 0): dy0 = 0 + d, dK_j = 0 + (c_j h) d — what
+// nlbac_rk_stage_bwd leaves for the one-step backward (same arithmetic).  No barrier inside.
+template <int NTHR>
+__device__ __forceinline__ void rk_traj_bwd_begin(const NodeRkBwdLaunch& L, const NodeRkTrajBwd& X, const RkBwdTile& T,
+                                                  int row0, int k, int kk, int tid) {
+    static_assert(NTHR >= NLBAC_MLP_TILE * RK_MAX_NS, "one (row, component) per thread");
+    const int n = L.n, ns = L.n_s, nu = L.n_u;
+    float vu = 0.f, vd = 0.f;
+    const float vh = L.h_val[0];          // (one problem: one step size for every row)
+    if (tid < NLBAC_MLP_TILE * RK_MAX_NU) {
+        const int m = tid >> 2, c = tid & 3;
+        vu = L.u[(long)k * n * nu + (long)min(row0 + m, n - 1) * nu + min(c, nu - 1)];
+    }
+    if (tid < NLBAC_MLP_TILE * RK_MAX_NS) {
+        const int m = tid >> 3, c = tid & 7;
+        vd = X.dout[(long)(k + 1) * n * ns + (long)min(row0 + m, n - 1) * ns + min(c, ns - 1)];
+    }
+    if (tid < NLBAC_MLP_TILE * RK_MAX_NU) {
+        const int m = tid >> 2, c = tid & 3;
+        const bool ok = row0 + m < n && c < nu;
+        T.sU[tid] = ok ? vu : 0.f;
+        T.sDU[tid] = 0.f;
+    }
+    if (tid < NLBAC_MLP_TILE) T.sH[tid] = vh;
+    if (tid < NLBAC_MLP_TILE * RK_MAX_NS) {
+        const int m = tid >> 3, c = tid & 7;
+        const bool ok = row0 + m < n && c < ns;
+        float d = vd;
+        if (kk > 0) d = d + T.sDY0[tid];
+        T.sDY0[tid] = ok ? 0.f + d : 0.f;
+        for (int j = 0; j < RK_MAX_STAGES; ++j) {
+            float v = 0.f;
+            if (j < X.n_out && X.c_out[j] != 0.f) v = 0.f + (X.c_out[j] * vh) * d;
+            if (j < L.S_total) T.sDK[j * NLBAC_MLP_TILE * RK_MAX_NS + tid] = ok ? v : 0.f;
+        }
+    }
+}
+
+// backward, behind interval k's stages: du_k (and dK when the weight gradients want it) to global; the dy0 stays in sDY0
+// for interval k-1, after interval 0 dx0 = dout[0] + dy0.  No barrier inside.
+template <int NTHR>
+__device__ __forceinline__ void rk_traj_bwd_end(const NodeRkBwdLaunch& L, const NodeRkTrajBwd& X, const RkBwdWhere& w,
+                                                const RkBwdTile& T, int row0, int k, int tid) {
+    const int n = L.n, ns = L.n_s, nu = L.n_u;
+    if (w.gdK)
+        for (int idx = tid; idx < L.st_hi * NLBAC_MLP_TILE * ns; idx += NTHR) {
+            const int j = idx / (NLBAC_MLP_TILE * ns), rem = idx - j * NLBAC_MLP_TILE * ns;
+            const int m = rem / ns, c = rem - m * ns, row = row0 + m;
+            if (row < n) w.gdK[((long)j * n + row) * ns + c] = T.sDK[(j * NLBAC_MLP_TILE + m) * RK_MAX_NS + c];
+        }
+    for (int idx = tid; idx < NLBAC_MLP_TILE * nu; idx += NTHR) {
+        const int m = idx / nu, c = idx - m * nu, row = row0 + m;
+        if (row < n) L.du[(long)k * n * nu + (long)row * nu + c] = T.sDU[m * RK_MAX_NU + c];
+    }
+    if (k == 0)
+        for (int idx = tid; idx < NLBAC_MLP_TILE * ns; idx += NTHR) {
+            const int m = idx / ns, c = idx - m * ns, row = row0 + m;
+            if (row < n) X.dx0[(long)row * ns + c] = X.dout[(long)row * ns + c] + T.sDY0[m * RK_MAX_NS + c];
         }
 }

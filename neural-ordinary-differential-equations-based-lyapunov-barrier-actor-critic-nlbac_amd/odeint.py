@@ -1904,7 +1904,8 @@ def odeint(func, y0, t, *, method="dopri5", atol=1e-7, rtol=1e-5, **options):
     carried control columns passed through, differentiable w.r.t. ``y0`` and ``func.parameters()``.  ``method`` is
     ``'euler'`` / ``'rk4'`` (one step over the interval, torchdiffeq's fixed-grid semantics) or ``'dopri5'``.
     The packed MFMA copies of the weights are refreshed first, so a ``torch.optim`` step on ``func.parameters()``
-    between calls is picked up."""
+    between calls is picked up.  For several intervals ahead with a new control each, differentiated as a whole, use
+    ``nlbac_amd.rollout.rollout``."""
     return _odeint(func, y0, t, method, atol, rtol, False, options)
 
 

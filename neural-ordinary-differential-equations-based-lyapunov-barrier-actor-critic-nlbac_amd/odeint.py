@@ -15,8 +15,11 @@ actions on the same states).  Every stage costs one batched f_net/g_net
 launch (``nlbac_mlp_fwd``) plus two per-row algebra kernels; the step-size
 controller runs on the device and the host reads one 128-byte control block
 per attempted step.
+
+This module holds the solvers' forward drivers, the discrete backward and the weight-gradient accumulation.  Beside it:
+``ode_workspace`` (step slots and scratch buffers), ``ode_ctl`` (how the host reads the control block),
+``ode_adjoint`` (the continuous adjoint), ``ode_consts`` (tableaus and environment switches).
 """
-import os
 import ctypes as C
 
 import torch
@@ -24,178 +27,58 @@ import torch
 from . import _lib
 from ._lib import fptr
 from .arena import bwd_weights, io_array, mlp_array, stream_ptr
-
-DP_BETA = [
-    [1 / 5],
-    [3 / 40, 9 / 40],
-    [44 / 45, -56 / 15, 32 / 9],
-    [19372 / 6561, -25360 / 2187, 64448 / 6561, -212 / 729],
-    [9017 / 3168, -355 / 33, 46732 / 5247, 49 / 176, -5103 / 18656],
-    [35 / 384, 0, 500 / 1113, 125 / 192, -2187 / 6784, 11 / 84],
-]
-DP_C_ERR = [35 / 384 - 1951 / 21600, 0, 500 / 1113 - 22642 / 50085, 125 / 192 - 451 / 720,
-            -2187 / 6784 - -12231 / 42400, 11 / 84 - 649 / 6300, -1. / 60.]
-
-TABLEAU = {
-    "euler": dict(beta=[], c_sol=[1.0]),
-    "rk4": dict(beta=[[1 / 3], [-1 / 3, 1.0], [1.0, -1.0, 1.0]], c_sol=[1 / 8, 3 / 8, 3 / 8, 1 / 8]),
-    "dopri5": dict(beta=DP_BETA, c_sol=None),
-    # the initial-step probe of dopri5: f(y0 + h0 f0) as "stage 1" of a two-stage table (f0 = stage 0 is in place)
-    "probe": dict(beta=[[1.0]], c_sol=None),
-}
+from .ode_adjoint import AffineAdjoint, ConcatAdjoint
+from .ode_consts import DP_BETA, DP_C_ERR, NORM_DEFER_ATTEMPT, TABLEAU, env_switch
+from .ode_ctl import ControlBlockReader
+from .ode_workspace import SolverWorkspaces, _ConcatStepWS, _StepWS
 
 
-# How the host learns the dopri5 controller's decision: where the controller launch writes the pinned control block
-# itself, by polling the block's stamp (a sequence lock the launch writes, nlbac_rk_chain::ctl_seq); where it cannot
-# (data parallelism, the host-driven steps of ragged row counts), by a copy on a side stream behind an event (_ctl_post).
-_SEQ = [0]
-NORM_DEFER_ATTEMPT = os.environ.get("NLBAC_NORM_DEFER_ATTEMPT", "1") != "0"
-
-class _Carver:
-    """Hands out the buffers of ONE step slot: consecutive 16-byte-aligned pieces of a flat float32 slice.  Every slot
-    of a pool is carved by the same sequence of requests, so a buffer sits at the same offset in every slot — which is
-    what lets the device-driven dopri5 chain address "the same buffer, k slots further" by pointer arithmetic
-    (``nlbac_rk_chain.slot_floats``).  ``flat is None``: dry run, only counts."""
-
-    def __init__(self, flat, device):
-        self.flat, self.device, self.k = flat, device, 0
-
-    def zeros(self, *shape, dtype=torch.float32):
-        numel = 1
-        for d in shape:
-            numel *= d
-        take = (numel + 3) & ~3
-        off, self.k = self.k, self.k + take
-        if self.flat is None:
-            return torch.empty(0, dtype=dtype)
-        assert self.k <= self.flat.numel(), "step slot too small"
-        t = self.flat[off:off + numel]
-        if dtype != torch.float32:
-            t = t.view(dtype)
-        return t.view(*shape)
-
-
-class _SlotPool:
-    """Step slots of one capacity bucket: chunks of ``slots_per_chunk`` slots, each chunk ONE allocation
-    [slots][slot_floats].  The device-driven chain works inside chunk 0 (contiguous, ``n_slots`` = its size); the
-    host-driven path just asks for the next slot and may spill into further chunks."""
-
-    def __init__(self, solver, cap, S, n_slots, dry_only=False):
-        self.solver, self.cap, self.S, self.n_slots = solver, cap, S, n_slots
-        dry = _Carver(None, solver.device)
-        solver.STEP_WS(solver, cap, S, dry).bwd(solver)
-        self.slot_floats = (dry.k + 63) & ~63
-        if dry_only:
-            return
-        self.chunks = [torch.zeros(n_slots, self.slot_floats, dtype=torch.float32, device=solver.device)]
-        self.views = {}                  # (n, idx) -> step workspace
-
-    def ws(self, n, idx):
-        assert n <= self.cap
-        w = self.views.get((n, idx))
-        if w is None:
-            c, i = divmod(idx, self.n_slots)
-            while c >= len(self.chunks):
-                self.chunks.append(torch.zeros(self.n_slots, self.slot_floats, dtype=torch.float32,
-                                               device=self.solver.device))
-            for k in [k for k in self.views if k[0] != n]:      # views laid out for another row count go
-                del self.views[k]
-            w = self.views[(n, idx)] = self.solver.STEP_WS(self.solver, n, self.S, _Carver(self.chunks[c][i], self.solver.device))
-            w.slot, w.pool = idx, self
-        return w
-
-
-class _StepWS:
-    """Device buffers of one RK step for n rows (stage-major)."""
-    # what a per-problem solver takes over from a joint first attempt: (buffer, leading blocks per row range)
-    ADOPT = ("K", "Y", "gout", "err", "acts_f", "acts_g")
-
-    def __init__(self, solver, n, S, store):
-        dev, ns, nu = solver.device, solver.n_s, solver.n_u
-        f, g = solver.f, solver.g
-        self.n, self.S = n, S
-        self._store = store
-        z = self._store.zeros
-        self.K = z(S, n, ns)
-        self.Y = z(S, n, ns)
-        self.fout = z(n, ns)
-        self.gout = z(S, n, ns * nu)
-        # a rollout that is only differentiated w.r.t. its inputs keeps bit-packed ReLU masks (one uint32 per 32
-        # hidden units) instead of the activations: 1/32 of the HBM traffic of the fused step kernels
-        self.bits = bool(solver.fused and not solver.keep_acts)
-        if self.bits:
-            zi = lambda *s: self._store.zeros(*s, dtype=torch.int32)
-            # words per row and layer: one per 32 hidden units, or (register-resident kernels) one per lane quarter
-            lib = _lib.load()
-            self.wf = lib.nlbac_node_rk_mask_words(C.byref(f.desc), C.byref(g.desc), 0)
-            self.wg = lib.nlbac_node_rk_mask_words(C.byref(f.desc), C.byref(g.desc), 1)
-            self.acts_f = zi(f.n_layers - 1, S * n, self.wf)
-            self.acts_g = zi(g.n_layers - 1, S * n, self.wg)
-        else:
-            self.wf, self.wg = f.hid, g.hid
-        # rows + words (acts_bits 2, the NODE fit on the register-resident kernels): the forward also leaves the ReLU
-        # mask words, which the backward gates on; the weight gradients read the rows.  Each net's words
-        # [layer][S*n][4] sit directly behind its rows — where nlbac_node_rk_fwd / _bwd look for them
-        self.words = not self.bits and solver._fit_words_on()
-        self.acts_bits = 1 if self.bits else (2 if self.words else 0)
-        if not self.bits:       # (hid % 4 == 0: the rows fill their carve, the words start where they end)
-            mw = lambda net: self._store.zeros(net.n_layers - 1, S * n, 4, dtype=torch.int32) if self.words else None
-            self.acts_f = z(f.n_layers - 1, S * n, f.hid)
-            self.mw_f = mw(f)
-            self.acts_g = z(g.n_layers - 1, S * n, g.hid)
-            self.mw_g = mw(g)
-        if self.words:
-            self.ADOPT = _StepWS.ADOPT + ("mw_f", "mw_g")
-        self.y1 = z(n, ns)
-        self.err = z(n, ns)
-        self._bwd = None
-        self.io_fwd, self.io_bwd = {}, {}
-
-    def bwd(self, solver):
-        if self._bwd is None:
-            dev, ns, nu, n, S = solver.device, solver.n_s, solver.n_u, self.n, self.S
-            f, g = solver.f, solver.g
-            z = self._store.zeros
-            self.dK = z(S, n, ns)
-            keep = solver.keep_acts or not solver.fused      # weight gradients / the stage-by-stage path need dz
-            self.dG = z(S, n, ns * nu) if keep else None
-            self.dz_f = z(f.n_layers - 1, S * n, f.hid) if keep else None
-            self.dz_g = z(g.n_layers - 1, S * n, g.hid) if keep else None
-            self.dXf = z(n, f.in_dim)
-            self.dXg = z(n, g.in_dim)
-            self.dy0 = z(n, ns)
-            self.dy1 = z(n, ns)
-            self._bwd = True
-        return self
-
-
-class AffineNodeSolver:
-    """odeint for ``dx/dt = f(x) + g(x) u`` with u constant over the step."""
+class AffineNodeSolver(SolverWorkspaces, AffineAdjoint):
+    """odeint for ``dx/dt = f(x) + g(x) u`` with u constant over the step.  Step slots and scratch buffers:
+    ``ode_workspace.SolverWorkspaces``; the continuous adjoint: ``ode_adjoint.AffineAdjoint``."""
     STEP_WS = _StepWS
 
     def __init__(self, node, device):
         self.node, self.f, self.g = node, node.f, node.g
         self.n_s, self.n_u = node.n_s, node.n_u
-        self.device = torch.device(device)
-        self._ws = {}          # (n, S, idx) -> _StepWS
-        self._scratch = {}
-        self.nfe = 0
-        self._net_arr = None
-        self._coefs = {}
         # one nlbac_node_rk_fwd / _bwd launch per RK step instead of 3 launches per stage — when the fused backward's
         # LDS carve fits (4 tiles + both nets' first / last layers: up to 232-wide nets); wider ones run stage by stage
         self.fused = self._fused_fits(node.f, node.g)
+        self._init_state(device)
+
+    def _init_state(self, device):
+        """Everything a solver keeps besides its field (both solver kinds).  Nothing here touches the device or the
+        library: streams, pinned blocks and capability probes come at first use."""
+        self.device = torch.device(device)
+        self._init_workspaces()
+        self._init_adjoint()
+        self.ctx = None        # the state of the current solve (a dict, see ``forward_begin``)
+        self.nfe = 0
+        self._net_arr = None
+        self._coefs = {}
         self.keep_acts = True  # False: backward never asks for weight gradients -> ReLU bit masks suffice
-        self._children = {}    # per-problem solvers for batches whose problems diverge (dopri5)
+        self._children = {}    # per-problem solvers for batches whose problems diverge (dopri5), see ``_child``
         self.stats = dict(solves=0, single_step=0, multi_attempt=0, split=0)
+        self.ctl = ControlBlockReader(self.device, self.stats)      # how the host reads dopri5's accept decisions
+        self.before_wait = None   # the owner's hook, run before the host blocks on an accept decision (``_ctl_read``)
         self.comm = None       # nlbac_amd.parallel.DataParallel: global dopri5 error norms
         # > 1: every problem of a solve is cut into this many contiguous row groups, each an adaptive solve of its own
         # (own error norm, step sizes and accept decisions) — what a sample-sharded run with per-shard step control
         # (SAC_CBF_CLF.enable_data_parallel(step_control="shard")) computes on that many ranks, on one device
         self.row_groups = 1
         self.adjoint = False   # True: ``backward`` is the continuous adjoint (odeint_adjoint); the forward keeps nothing
-        self.generation = 0    # bumped whenever device buffers are freed or re-laid-out (owners of hipGraphs watch it)
         self.device_loop = True   # dopri5 attempts as a device-driven chain (no host decision per attempt)
+        self._chain_len = 1    # attempts the last chain solve needed = launches enqueued before the host first looks
+        self._in_map, self._in_map_armed = None, False      # ``set_in_map``
+        self._out_map = None                                # ``set_out_map``
+        # A/B switches (ode_consts): the environment's value unless assigned before the first solve
+        self.norm_defer = env_switch("norm_defer")
+        self.norm_defer_attempt = NORM_DEFER_ATTEMPT
+        self.interp_fold = env_switch("interp_fold")
+        self.fit_words = env_switch("fit_words")
+        # what the library says about the nets' kernels, asked once at first use
+        self._words_ok = None      # nlbac_node_rk_mask_words == 4 for both nets (``_fit_words_on``)
+        self._interp_ok = None     # nlbac_rk_interp_ok (``_rr_kernels``)
 
     @staticmethod
     def _fused_fits(f, g):
@@ -205,66 +88,6 @@ class AffineNodeSolver:
         lds = 4 * (4 * 32 * ld + 8 * 32 * 8 + 32 * (4 + 1 + 8 + 4 + 2 * 8 + 2 * 16) + sw)      # nlbac_node_rk_bwd's carve
         return lds <= 160 * 1024 - 64
 
-    # -- workspace -----------------------------------------------------------
-    MAX_SIZES = 2      # distinct row counts whose buffers are kept (the NODE fit's batch grows with the replay)
-
-    def _touch(self, n):
-        """Start of a solve on n rows: make n the current size and drop the scratch of the least recently used sizes
-        beyond ``MAX_SIZES`` — a training run feeds the NODE fit min(replay size, 32768) rows, a new count at every fit
-        while the replay fills.  (Step slots live in per-capacity pools, see ``_pool``.)"""
-        order = self.__dict__.setdefault("_n_order", [])
-        if n in order:
-            order.remove(n)
-        order.append(n)
-        while len(order) > self.MAX_SIZES:
-            old = order.pop(0)
-            self._scratch.pop(old, None)
-            self.generation += 1
-        self._cur_n = n
-
-    @staticmethod
-    def _bucket(n):
-        return n if n <= 4096 else -(-n // 4096) * 4096
-
-    DEFAULT_SLOTS = 4      # step slots of a pool's first chunk = steps the device-driven chain can accept without a restart
-
-    def _pool(self, n, S, min_slots=1):
-        """The slot pool serving n rows / S stages (one per capacity bucket and solver mode; the two most recently
-        used buckets are kept).  ``generation`` counts every event that frees or re-lays-out device buffers — captured
-        hipGraphs bake their addresses in and are dropped by their owners when it moves."""
-        pools = self.__dict__.setdefault("_pools", {})
-        key = (self._bucket(n), S, self.fused, self.keep_acts, self._fit_words_on())
-        pool = pools.get(key)
-        dropped = False
-        if pool is not None and pool.n_slots < min_slots:
-            del pools[key]
-            pool, dropped = None, True
-        if pool is None:
-            buckets = list(dict.fromkeys(k[0] for k in pools))              # in order of first use
-            if key[0] not in buckets and len(buckets) >= self.MAX_SIZES:
-                for k in [k for k in pools if k[0] == buckets[0]]:         # the oldest bucket goes, whole
-                    del pools[k]
-                dropped = True
-            if dropped:
-                self.generation += 1
-                # pools are GB-sized and each regrowth asks for a new size: hand the freed blocks back to the driver,
-                # or the caching allocator keeps every size it has ever seen (279 GiB reserved for 39 GiB in use in a
-                # long dopri5 training run before this)
-                if not torch.cuda.is_current_stream_capturing():
-                    torch.cuda.empty_cache()
-            n_slots = max(min_slots, self.DEFAULT_SLOTS if S == 7 else 1)
-            pool = _SlotPool(self, key[0], S, n_slots, dry_only=True)
-            if pool.slot_floats * 4 * n_slots > self.MAX_POOL_BYTES:
-                raise _lib.NlbacError(
-                    "dopri5: %d accepted steps of %d rows need %.0f GiB of step slots (limit %.0f GiB): the field has "
-                    "become stiff for back-propagation through the steps — use the adjoint (agent.adjoint = True / "
-                    "odeint_adjoint), whose memory does not grow with the step count"
-                    % (n_slots, key[0], pool.slot_floats * 4 * n_slots / 2 ** 30, self.MAX_POOL_BYTES / 2 ** 30))
-            pool = pools[key] = _SlotPool(self, key[0], S, n_slots)
-        return pool
-
-    MAX_POOL_BYTES = 128 * 2 ** 30
-
     def _fit_words_on(self):
         """A solve whose backward wants weight gradients (the NODE fit: ``keep_acts``) keeps the activation rows AND the
         ReLU mask words (acts_bits 2) where the register-resident kernels serve both nets: the backward gates on the
@@ -272,24 +95,13 @@ class AffineNodeSolver:
         (NLBAC_FIT_WORDS=0): rows only, the backward gates on them — the cross-check."""
         if not (self.fused and self.keep_acts):
             return False
-        on = self.__dict__.get("fit_words")
-        if on is None:
-            on = self.fit_words = os.environ.get("NLBAC_FIT_WORDS", "1") != "0"
-        if not on:
+        if not self.fit_words:
             return False
-        ok = self.__dict__.get("_words_ok")
+        ok = self._words_ok
         if ok is None:
             lib, f, g = _lib.load(), C.byref(self.f.desc), C.byref(self.g.desc)
             ok = self._words_ok = lib.nlbac_node_rk_mask_words(f, g, 0) == 4 and lib.nlbac_node_rk_mask_words(f, g, 1) == 4
         return ok
-
-    def _step_ws(self, n, S, idx):
-        pool = self._pool(n, S)
-        had = (n, idx) in pool.views
-        ws = pool.ws(n, idx)
-        if not had and any(k[0] != n for k in pool.views):
-            self.generation += 1
-        return ws
 
     def reserve(self, n, P, method, steps=2):
         """Allocate the buffers of a solve on n rows / P problems ahead of time (the slot pool and, for a host-driven
@@ -303,36 +115,24 @@ class AffineNodeSolver:
             return
         for idx in range(steps):
             self._step_ws(n, 7, idx).bwd(self)
-        self._ctl_io(P)
+        self.ctl.io(P)
         if P > 1 and not self._chain_ok(P, n // P):
             for p in range(P):
-                if p not in self._children:
-                    self._children[p] = type(self)(self.node, self.device)
-                k = self._children[p]
-                k.comm, k.fused, k.keep_acts = self.comm, self.fused, self.keep_acts
-                k.fit_words = self.__dict__.get("fit_words")
-                # the per-problem solvers run one after the other inside this solver's solve: they share its read-back
-                # stream and pinned blocks (a pinned allocation costs milliseconds)
-                self._ctl_io(1)
-                k._side, k._ev_ctl, k._ctl_pin = self._side, self._ev_ctl, self._ctl_pin
-                k.before_wait = self.__dict__.get("before_wait")
-                k.reserve(n // P, 1, method, steps)
+                self._child(p).reserve(n // P, 1, method, steps)
 
-    def _out_buf(self, n, fallback=None):
-        """Where the solve's result goes: the caller's tensor (``out_into``, when it has the solve's shape — the next
-        launches read it there, no copy) or a solver-owned buffer."""
-        t = self.__dict__.get("out_into")
-        if t is not None and tuple(t.shape) == (n, self.n_s) and t.is_contiguous():
-            return t
-        return fallback if fallback is not None else self._buf("dopri_out", n, self.n_s)
-
-    def _buf(self, name, *shape, dtype=torch.float32):
-        """Named scratch buffer of the current solve size (dropped with that size's workspaces, see ``_touch``)."""
-        pool = self._scratch.setdefault(self.__dict__.get("_cur_n", 0), {})
-        key = (name, shape, dtype)
-        if key not in pool:
-            pool[key] = torch.zeros(*shape, dtype=dtype, device=self.device)
-        return pool[key]
+    def _child(self, p):
+        """The per-problem solver of problem ``p`` (``reserve``, ``_solve_split``), with everything it takes from this
+        solver — and nothing else: ``norm_defer``, ``interp_fold`` and ``row_groups`` stay at a child's own defaults
+        (a child solves one problem on the host-driven path, which uses none of them)."""
+        k = self._children.get(p)
+        if k is None:
+            k = self._children[p] = type(self)(self.node, self.device)
+        k.comm, k.fused, k.keep_acts, k.fit_words = self.comm, self.fused, self.keep_acts, self.fit_words
+        # the per-problem solvers run one after the other inside this solver's solve: they read through its read-back
+        # stream and pinned blocks (a pinned allocation costs milliseconds)
+        k.ctl = self.ctl
+        k.before_wait = self.before_wait
+        return k
 
     # -- one field evaluation k = f(x) + g(x) u -----------------------------------
     def _nets(self):
@@ -363,7 +163,7 @@ class AffineNodeSolver:
 
     def _probe_eval(self, ytmp, u, n, ktmp, gtmp):
         """field evaluation outside the step workspaces (dopri5 initial-step probe), nothing saved"""
-        pool = self._scratch.setdefault(self.__dict__.get("_cur_n", 0), {})
+        pool = self._scratch.setdefault(self._cur_n, {})
         tio = pool.get(("tmp_io", n))
         if tio is None:
             tio = pool[("tmp_io", n)] = self._eval_io(ytmp, gtmp)
@@ -452,7 +252,8 @@ class AffineNodeSolver:
         self.stats["solves"] += 1
         self.ctx = dict(method=method, P=P, rpp=rpp, n=n, u=u, y0=y0, steps=[], t_end=float(dt), atol=atol,
                         rtol=rtol)
-        if self.__dict__.pop("_in_map_armed", False):
+        if self._in_map_armed:
+            self._in_map_armed = False
             self.ctx["in_map_pending"] = True          # (consumed by the solve's first launch, _rk_fused)
         if method in ("euler", "rk4"):
             tab = TABLEAU[method]
@@ -510,95 +311,15 @@ class AffineNodeSolver:
     def _ctl(self, P):
         return self._buf("ctl", P, _lib.DOPRI_CTL, dtype=torch.float64)
 
-    def _ctl_post(self, P, src=None):
-        """After an attempted step: send the control block to pinned host memory on a side stream, so that the
-        host can read the accept decision as soon as the controller has run — without draining the launch
-        stream, on which the caller may have queued independent work behind the attempt (the agent queues its
-        whole critic phase there).  Not inside a hipGraph capture (the replay path reads with ``_ctl(P).cpu()``)."""
-        if torch.cuda.is_current_stream_capturing():
-            return
-        side, pin = self._ctl_io(P)
-        self.ctx["ctl_seq"] = None        # (a copy, read behind its event: nothing to poll)
-        ev_a, ev_b = self._ev_ctl
-        ev_a.record()
-        side.wait_event(ev_a)
-        with torch.cuda.stream(side):
-            pin.copy_(self._ctl(P) if src is None else src, non_blocking=True)
-            ev_b.record()
-        self.ctx["ctl_pending"] = P
-
-    def _ctl_posted(self, P):
-        """Device-driven chain: the controller launches have written the host's copy themselves (``ctl_host``); mark the
-        point on the launch stream behind which it is complete."""
-        if torch.cuda.is_current_stream_capturing():
-            return
-        self._ctl_io(P)
-        if self.ctx.get("ctl_seq") is None:
-            self._ev_ctl[1].record()     # (stamped blocks are polled: no event, no marker on the launch stream)
-        self.ctx["ctl_pending"] = P
-
-    def _seq_next(self, first_of_solve=False):
-        """Stamp for the next controller launch that writes the host's copy; ctx["ctl_seq"] = (stamp of the solve's first
-        such launch, stamp of its latest).  None when the block is read behind an event."""
-        if torch.cuda.is_current_stream_capturing():
-            self.ctx["ctl_seq"] = None
-            return 0.0
-        _SEQ[0] += 1                 # (one counter per process: solvers share pinned blocks, see _solve_split)
-        rng = self.ctx.get("ctl_seq")
-        self.ctx["ctl_seq"] = (_SEQ[0] if (first_of_solve or rng is None) else rng[0], _SEQ[0])
-        return float(_SEQ[0])
-
-    def _ctl_poll(self, P, first, last, patience=0.05):
-        """Wait for the stamped control blocks of the launch with stamp ``last``: a problem's block is complete when it
-        carries that stamp — or an earlier one of the same solve with the done flag (launches skip finished problems).
-        Sequence-lock read: stamp, block, stamp.  After ``patience`` seconds of spinning the launch stream is drained
-        (everything queued has then run) and the block must be there."""
-        import time
-        arr = self._ctl_pin[P].numpy()          # (the same memory)
-        t0 = drained = None
-        n = 0
-        stamps = arr[:, 15]
-        while True:
-            s1 = stamps.tolist()                       # (stamp, block, stamp: the sequence lock's read side)
-            if all(x == last or first <= x < last for x in s1):
-                c = arr.copy()
-                if all(c[p, 15] == s1[p] and (s1[p] == last or c[p, 4] > 0) for p in range(P)):
-                    return torch.from_numpy(c)
-            n += 1
-            if n & 63 == 0:
-                now = time.perf_counter()
-                if t0 is None:
-                    t0 = now
-                elif drained:
-                    raise _lib.NlbacError("control block %r never reached stamp %d (solve from %d)" % (s1, last, first))
-                elif now - t0 > patience:
-                    torch.cuda.current_stream().synchronize()
-                    drained = True
-                    self.stats["poll_drained"] = self.stats.get("poll_drained", 0) + 1
-
-    def _ctl_io(self, P):
-        """(side stream, pinned block for P problems) of the control-block read-back, created on first use."""
-        if self.__dict__.get("_side") is None:
-            self._side = torch.cuda.Stream(device=self.device)
-            self._ev_ctl = (torch.cuda.Event(), torch.cuda.Event())
-            self._ctl_pin = {}
-        pin = self._ctl_pin.get(P)
-        if pin is None:
-            pin = self._ctl_pin[P] = torch.zeros(P, _lib.DOPRI_CTL, dtype=torch.float64).pin_memory()
-        return self._side, pin
+    def _ctl_post(self, P):
+        self.ctl.post(self.ctx, P, self._ctl(P))
 
     def _ctl_read(self, P):
-        """Host copy of the control block of the last attempted step."""
-        if self.ctx.pop("ctl_pending", None) == P:
-            hook = self.__dict__.get("before_wait")
-            if hook is not None:
-                hook()                   # (the owner queues independent work behind the attempt before the host blocks)
-            rng = self.ctx.get("ctl_seq")
-            if rng is not None:
-                return self._ctl_poll(P, *rng)
-            self._ev_ctl[1].synchronize()
-            return self._ctl_pin[P].clone()
-        return self._ctl(P).cpu()
+        """Host copy of the control block of the last attempted step (``ode_ctl``; inside a replayed hipGraph nothing
+        was posted: the device block is read)."""
+        c = self.ctl.read(self.ctx, P, self.before_wait)
+        return c if c is not None else self._ctl(P).cpu()
+
 
     def _norm_control(self, a, b, y0, y1, u, mode, P, rpp, slot_ctl=None, slot_floats=0, chain=None):
         """Scaled RMS norm(s) of mode 0/1/2 (include/nlbac_hip.h) over each problem's rows, then the step-size
@@ -727,7 +448,7 @@ class AffineNodeSolver:
         return bool(self.ctx.get("out_mapped"))
 
     def _out_map_fwd(self, n):
-        m = self.__dict__.get("_out_map")
+        m = self._out_map
         if m is None or m["p"].shape[0] != n or self.adjoint:
             return None
         om = _lib.OutMap()
@@ -735,7 +456,7 @@ class AffineNodeSolver:
         return om
 
     def _out_map_bwd(self, n):
-        m = self.__dict__.get("_out_map")
+        m = self._out_map
         if m is None or m["dp"] is None or not self.ctx.get("out_mapped"):
             return None
         om = _lib.OutMap()
@@ -747,15 +468,18 @@ class AffineNodeSolver:
     def _interp_nets(self):
         return C.byref(self.f.desc), C.byref(self.g.desc)
 
+    def _rr_kernels(self):
+        """The register-resident kernels serve the nets (nlbac_rk_interp_ok)."""
+        ok = self._interp_ok
+        if ok is None:
+            ok = self._interp_ok = bool(_lib.load().nlbac_rk_interp_ok(*self._interp_nets()))
+        return ok
+
     def _interp_fold(self):
         """The interpolation at t_end is evaluated by the attempt launches themselves and its backward by the last step's
         backward launch (nlbac_rk_chain::interp_*; the register-resident kernels): no nlbac_dopri_interp_fwd / _bwd
         launches.  ``interp_fold = False`` (NLBAC_INTERP_FOLD=0) keeps the two launches — the cross-check."""
-        on = self._interp_fold_on()
-        ok = self.__dict__.get("_interp_ok")
-        if ok is None:
-            ok = self._interp_ok = bool(_lib.load().nlbac_rk_interp_ok(*self._interp_nets()))
-        return on and ok and self.fused
+        return bool(self.interp_fold and self._rr_kernels() and self.fused)
 
     def _chain_ok(self, P, rpp):
         return bool(self.device_loop and self.fused and (P == 1 or rpp % _lib.MLP_TILE == 0))
@@ -771,8 +495,8 @@ class AffineNodeSolver:
         c.rtol, c.atol, c.t_end = ctx["rtol"], ctx["atol"], ctx["t_end"]
         c.ctl_w, c.hslots = ctl.data_ptr(), hs.data_ptr()
         c.alog, c.alog_cap = self._buf("alog", P, self.ALOG_CAP, 3, dtype=torch.float64).data_ptr(), self.ALOG_CAP
-        # the controller leaves the host's copy of the control block in pinned memory itself (see _ctl_posted)
-        c.ctl_host = None if torch.cuda.is_current_stream_capturing() else self._ctl_io(P)[1].data_ptr()
+        # the controller leaves the host's copy of the control block in pinned memory itself (see ControlBlockReader.posted)
+        c.ctl_host = None if torch.cuda.is_current_stream_capturing() else self.ctl.io(P)[1].data_ptr()
         # Where the norm + controller run.  Fused into the RK launch's epilogue (last workgroup of a problem) for the two
         # one-stage launches of the initial-step selection: same GPU time as a launch of their own (26.7 us against
         # 18 + 9), one launch less each.  NOT for an attempted step: the epilogue's device-scope atomics queue behind the
@@ -794,7 +518,7 @@ class AffineNodeSolver:
         if chain.norm_mode >= 0:
             # an attempt whose RK launch left its tiles' partial sums (norm_defer): one small workgroup per problem
             if chain.ctl_host:
-                chain.ctl_seq = self._seq_next()
+                chain.ctl_seq = self.ctl.next_stamp(self.ctx)
             _lib.call("nlbac_dopri_control_tiles", C.byref(chain), self.n_s, self.n_u, rpp, P, stream_ptr())
             return
         ctl = self._ctl(P)
@@ -804,14 +528,14 @@ class AffineNodeSolver:
             self._norm_control(ws0.K[1], ws0.K[0], y0, None, None, 1, P, rpp)
         else:
             if chain.ctl_host and not (self.comm is not None and self.comm.world > 1):
-                chain.ctl_seq = self._seq_next()
+                chain.ctl_seq = self.ctl.next_stamp(self.ctx)
             self._norm_control(ws0.err, None, y0, ws0.Y[6], None, 2, P, rpp, slot_ctl=ctl.data_ptr(),
                                slot_floats=pool.slot_floats, chain=chain)
 
     def _dopri_begin_chain(self, y0, u, P, rpp, min_slots=1):
         n, S = P * rpp, 7
         ctx = self.ctx
-        ctx["ctl_seq"] = None         # (stamps of this solve's controller launches start here: _seq_next)
+        self.ctl.begin(ctx)           # (stamps of this solve's controller launches start here)
         pool = self._pool(n, S, min_slots)
         ws0 = pool.ws(n, 0)
         ctl = self._ctl(P)
@@ -825,7 +549,7 @@ class AffineNodeSolver:
             if om is not None:
                 ch[2].interp_kind, ch[2].interp_l, ch[2].interp_p = om.kind, om.l, om.p
         ctx["chain"] = dict(pool=pool, ws0=ws0, ch=ch[2], attempts=0, y0=y0, ip=ip, ip_om=om is not None)
-        k = max(1, int(self.__dict__.get("_chain_len", 1)))
+        k = max(1, int(self._chain_len))
         if self._norm_defer_ok(ch):
             # The norms of f0 and of the probe without their elections (nlbac_rk_chain::norm_defer / norm_pre): each
             # launch leaves its tiles' partial sums, the NEXT launch's workgroups sum them and run the controller
@@ -834,7 +558,7 @@ class AffineNodeSolver:
             part0, part1 = self._buf("cpart", P, nblk, 2).data_ptr(), self._buf("cpart1", P, nblk, 2).data_ptr()
             ch[0].norm_defer, ch[0].partials = 1, part0
             ch[1].norm_pre, ch[1].partials_pre, ch[1].norm_defer, ch[1].partials = 1, part0, 1, part1
-            if self.__dict__.get("norm_defer_attempt", NORM_DEFER_ATTEMPT):
+            if self.norm_defer_attempt:
                 # ... and the attempts': the RK launch leaves the error norm's tile partials, the controller launch is one
                 # 64-thread workgroup per problem (nlbac_dopri_control_tiles) instead of a pass over the error rows
                 ch[2].norm_mode, ch[2].norm_defer = 2, 1
@@ -853,15 +577,9 @@ class AffineNodeSolver:
         """The election-free form of the two fused norms that open a dopri5 solve: where those norms are fused at all (one
         GPU) and the register-resident kernels serve the nets.  ``norm_defer = False`` (NLBAC_NORM_DEFER=0): the fused
         norms with their elections — the cross-check."""
-        on = self.__dict__.get("norm_defer")
-        if on is None:
-            on = self.norm_defer = os.environ.get("NLBAC_NORM_DEFER", "1") != "0"
-        if not on or ch[0].norm_mode != 0 or ch[1].norm_mode != 1 or self._interp_nets()[1] is None:
+        if not self.norm_defer or ch[0].norm_mode != 0 or ch[1].norm_mode != 1 or self._interp_nets()[1] is None:
             return False
-        ok = self.__dict__.get("_interp_ok")
-        if ok is None:
-            ok = self._interp_ok = bool(_lib.load().nlbac_rk_interp_ok(*self._interp_nets()))
-        return bool(ok and self.fused)
+        return bool(self._rr_kernels() and self.fused)
 
     def _chain_attempts(self, k):
         ctx = self.ctx
@@ -878,7 +596,7 @@ class AffineNodeSolver:
             self._ctl_post(P)        # (the all-reduced controller is nlbac_dopri_control: it leaves no host copy; nor does
                                      #  the RK launch's own epilogue, FUSED_NORM_MODES with 2)
         else:
-            self._ctl_posted(P)
+            self.ctl.posted(self.ctx, P)
 
     def _dopri_finish_chain(self, assume_done=False):
         ctx = self.ctx
@@ -1078,14 +796,7 @@ class AffineNodeSolver:
         out = self._out_buf(n)
         kids, info = [], []
         for p in range(P):
-            if p not in self._children:
-                self._children[p] = type(self)(self.node, self.device)
-            k = self._children[p]
-            k.comm, k.fused, k.keep_acts = self.comm, self.fused, self.keep_acts
-            k.fit_words = self.__dict__.get("fit_words")
-            self._ctl_io(1)
-            k._side, k._ev_ctl, k._ctl_pin = self._side, self._ev_ctl, self._ctl_pin
-            k.before_wait = self.__dict__.get("before_wait")
+            k = self._child(p)
             rows = slice(p * rpp, (p + 1) * rpp)
             if p == 0:
                 key = "adopted" if st["attempt"] == 0 else "adopted_late"
@@ -1181,249 +892,6 @@ class AffineNodeSolver:
         dy0 = steps[0]["ws"].dy0 if need_dy0 else None
         return du, dy0
 
-    # -- continuous adjoint (odeint_adjoint) ---------------------------------------------------------
-    # torchdiffeq 0.2.3 OdeintAdjointMethod.backward restated on the device: the augmented state z = [y | a_x | a_u]
-    # (+ the parameter adjoint, a quadrature) is integrated from t1 back to t0 with the forward's method and
-    # tolerances and the mixed default adjoint norm; one nlbac_node_adj_step launch per RK step re-computes the nets on
-    # every stage input and back-propagates a_x through them, so nothing of the forward solve is kept.  The dopri5
-    # attempts are a device-driven chain (kernels skip problems whose solve is done, an accepted step is handed over
-    # by nlbac_adj_commit); the host looks at the control block once per chain, not once per attempt.
-    ADJ_MAX_ATTEMPTS = 1000
-
-    def _adj_ws(self, n, S):
-        key = ("adj", n, S)
-        pool = self._scratch.setdefault(n, {})
-        w = pool.get(key)
-        if w is None:
-            W = 2 * self.n_s + self.n_u
-            z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=self.device)
-            w = pool[key] = dict(Z0=z(n, W), Z1=z(n, W), KZ=z(S, n, W), ERR=z(n, W), OUT=z(n, W), W=W)
-        return w
-
-    def _adj_interp_fold(self):
-        """The attempt launches of the adjoint solve write the interpolant of z at t_end themselves (no
-        nlbac_dopri_interp_fwd launch behind the solve) where the kernel that serves the nets does so."""
-        ok = self.__dict__.get("_adj_ip_ok")
-        if ok is None:
-            ok = self._adj_ip_ok = bool(_lib.load().nlbac_node_adj_interp_ok(C.byref(self.f.desc), C.byref(self.g.desc)))
-        return ok and self._interp_fold_on()
-
-    def _interp_fold_on(self):
-        on = self.__dict__.get("interp_fold")
-        if on is None:
-            on = self.interp_fold = os.environ.get("NLBAC_INTERP_FOLD", "1") != "0"
-        return on
-
-    def _adj_step(self, w, u, P, rpp, method, st0, st1, h_host=None, h_dev=None, ctl=None, c_out=None, c_err=None,
-                  keep=None, interp=False):
-        beta, S = self._beta(method)
-        f, g = self.f, self.g
-        k = keep or {}
-        dp = lambda t: t.data_ptr() if t is not None else None
-        _lib.call("nlbac_node_adj_step", C.byref(f.desc), C.byref(g.desc), u.data_ptr(), P, rpp, st0, st1, S, beta,
-                  c_out, len(c_out) if c_out is not None else 0, c_err, len(c_err) if c_err is not None else 0,
-                  fptr(*h_host) if h_host is not None else None, h_dev, _lib.DOPRI_CTL if h_dev else 0, ctl,
-                  w["Z0"].data_ptr(), w["KZ"].data_ptr(), w["Z1"].data_ptr() if c_out is not None else None,
-                  w["ERR"].data_ptr() if c_err is not None else None, dp(k.get("ZS")), dp(k.get("dG")),
-                  dp(k.get("acts_f")), k.get("ls_f", 0), dp(k.get("acts_g")), k.get("ls_g", 0), dp(k.get("dz_f")),
-                  dp(k.get("dz_g")), w["OUT"].data_ptr() if interp else None, self.ctx["t_end"], stream_ptr())
-        self.nfe += st1 - st0
-        if keep:
-            for st in range(st0, st1):
-                self._adj_stage_dw(self._adj_par_cur, st)
-
-    def _adj_norm_control(self, a, b, w, u, mode, P, rpp, ctl, pnorm=None):
-        ctx = self.ctx
-        ns, nu, s = self.n_s, self.n_u, stream_ptr()
-        nblk = (rpp + 255) // 256
-        part = self._buf("adj_part", P, nblk, 4)
-        dp = lambda t: t.data_ptr() if t is not None else None
-        if self.comm is not None and self.comm.world > 1:
-            _lib.call("nlbac_adj_norm_control", dp(a), dp(b), w["Z0"].data_ptr(), w["Z1"].data_ptr(), dp(u), mode,
-                      ctx["rtol"], ctx["atol"], ns, nu, rpp, P, ctx["t_end"], None, part.data_ptr(), None,
-                      ctl.data_ptr(), None, 0.0, s)
-            sums = self._buf("adj_psum", P, 1, 4)
-            for p in range(P):
-                _lib.call("nlbac_sum_partials", part[p].data_ptr(), nblk, 4, 1.0, sums[p].data_ptr(), s)
-            self.comm.all_reduce_(sums)
-            _lib.call("nlbac_adj_control", sums.data_ptr(), 1, mode, ns, nu, rpp * self.comm.world, P, ctx["t_end"],
-                      dp(pnorm), ctl.data_ptr(), s)
-            return
-        tickets = self._buf("adj_tickets", P, dtype=torch.int32)
-        # (an attempt's controller leaves the host's copy of the control block in pinned memory itself: no copy launch
-        #  between the decision and the host; see _ctl_posted)
-        host, seq = None, 0.0
-        if mode == 2 and not torch.cuda.is_current_stream_capturing():
-            host = self._ctl_io(P)[1].data_ptr()
-            seq = self._seq_next()
-        ctx["adj_ctl_host"] = host is not None
-        _lib.call("nlbac_adj_norm_control", dp(a), dp(b), w["Z0"].data_ptr(), w["Z1"].data_ptr(), dp(u), mode,
-                  ctx["rtol"], ctx["atol"], ns, nu, rpp, P, ctx["t_end"], dp(pnorm), part.data_ptr(),
-                  tickets.data_ptr(), ctl.data_ptr(), host, seq, s)
-
-    # -- parameter adjoint (a quadrature beside the per-row state; single-problem solves) -----------------
-    ADJ_SUB_SLABS = 40       # row slabs of one stage's weight-gradient GEMM (workgroups: layers x slabs x nets)
-
-    def _adj_params_begin(self, w, n, S):
-        ctx = self.ctx
-        assert ctx["P"] == 1, "parameter gradients are only taken on single-problem solves"
-        key = ("adj_par", n, S)
-        pool = self._scratch.setdefault(n, {})
-        par = pool.get(key)
-        if par is None:
-            f, g, ns, nu, dev = self.f, self.g, self.n_s, self.n_u, self.device
-            z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=dev)
-            arena = f.arena
-            NP = arena.n
-            keep = dict(ZS=z(S, n, w["W"]), dG=z(S, n, ns * nu), acts_f=z(f.n_layers - 1, S * n, f.hid),
-                        acts_g=z(g.n_layers - 1, S * n, g.hid), dz_f=z(f.n_layers - 1, S * n, f.hid),
-                        dz_g=z(g.n_layers - 1, S * n, g.hid), ls_f=S * n * f.hid, ls_g=S * n * g.hid)
-            segs = [(arena.offset_of[id(p)], p.numel()) for p in self.node.parameters()]
-            par = pool[key] = dict(
-                keep=keep, NP=NP, K=z(S, NP), th0=z(NP), th1=z(NP), out=z(NP), slabs=z(self.ADJ_SUB_SLABS, NP),
-                seg_off=torch.tensor([o for o, _ in segs], dtype=torch.int32, device=dev),
-                seg_len=torch.tensor([l for _, l in segs], dtype=torch.int32, device=dev), n_seg=len(segs),
-                pseg=z(2 * len(segs)), ticket=z(1, dtype=torch.int32), pnorm=z(2), io={}, n=n, S=S, w=w)
-        _lib.call("nlbac_fill", par["th0"].data_ptr(), 0.0, par["NP"], stream_ptr())
-        par["grad"] = None
-        return par
-
-    def _adj_stage_dw(self, par, st):
-        """K_theta[st] = sum over the rows of stage ``st`` of (dF/dtheta)^T a_x: nlbac_mlp_bwd_weights on what the
-        step kernel kept of that stage (row slabs), then the slab sum."""
-        k, n, S, w = par["keep"], par["n"], par["S"], par["w"]
-        W, ns, nu = w["W"], self.n_s, self.n_u
-        io = par["io"].get(st)
-        if io is None:
-            io = par["io"][st] = io_array(2)
-            ZS = k["ZS"][st]
-            for i, (net, acts, dz) in enumerate(((self.f, k["acts_f"], k["dz_f"]), (self.g, k["acts_g"], k["dz_g"]))):
-                io[i].x0, io[i].x0_dim, io[i].x0_ld = ZS.data_ptr(), ns, W
-                io[i].acts, io[i].dz = acts[:, st * n:].data_ptr(), dz[:, st * n:].data_ptr()
-                io[i].acts_ls = S * n * net.hid
-                io[i].grad = par["slabs"].data_ptr()
-            io[0].dy, io[0].dy_ld = ZS.data_ptr() + 4 * ns, W              # cotangent of f_net's output: a_x
-            io[1].dy, io[1].dy_ld = k["dG"][st].data_ptr(), ns * nu        # of g_net's: a_x u^T
-        bwd_weights(self._nets(), io, 2, n, self.ADJ_SUB_SLABS, par["NP"], self.device)
-        _lib.call("nlbac_reduce_slabs", par["K"][st].data_ptr(), par["slabs"].data_ptr(), self.ADJ_SUB_SLABS,
-                  par["NP"], par["NP"], stream_ptr())
-        if self.comm is not None and self.comm.world > 1:
-            # sample-sharded solve: the parameter adjoint is a sum over ALL rows, and its norm takes part in the step
-            # control — every rank must form it from the same (global) stage derivative, or the ranks' accept / done
-            # decisions part ways and their collectives no longer pair up
-            self.comm.all_reduce_(par["K"][st])
-
-    def _adj_params_norm(self, par, mode, cp, h_host=None, c_sol=None):
-        ctx = self.ctx
-        _lib.call("nlbac_adj_param_norm", mode, par["th0"].data_ptr(), par["K"].data_ptr(), par["NP"], par["S"],
-                  c_sol if c_sol is not None else self._coef("sol"), self._coef("err") if c_sol is None else fptr(*([0.0] * par["S"])),
-                  fptr(h_host) if h_host is not None else None, cp if h_host is None else None,
-                  par["seg_off"].data_ptr(), par["seg_len"].data_ptr(), par["n_seg"], ctx["rtol"], ctx["atol"],
-                  cp if (mode == 2 and h_host is None) else None, par["th1"].data_ptr(), par["pseg"].data_ptr(),
-                  par["ticket"].data_ptr(), par["pnorm"].data_ptr(), stream_ptr())
-        return par["pnorm"]
-
-    def _adj_params_commit(self, par, cp):
-        NP = par["NP"]
-        _lib.call("nlbac_adj_commit", cp, NP // 4, NP // 4, 4, par["th0"].data_ptr(), par["th1"].data_ptr(),
-                  par["K"][0].data_ptr(), par["K"][6].data_ptr(), stream_ptr())
-
-    def _adj_params_finish(self, par, cp):
-        NP = par["NP"]
-        _lib.call("nlbac_dopri_interp_fwd", par["th0"].data_ptr(), par["th1"].data_ptr(), par["K"].data_ptr(), None,
-                  None, cp, 1, NP // 4, 4, par["out"].data_ptr(), 0, None, stream_ptr())
-        par["grad"] = par["out"]
-        self.ctx["adj_par"] = par
-
-    def _adj_params_fixed(self, par, w, c_sol, h):
-        """fixed grid: theta_bar(t0) = h sum_j c_sol[j] K_theta[j]"""
-        self._adj_params_norm(par, 2, None, h_host=h, c_sol=fptr(*c_sol))
-        par["grad"] = par["th1"]
-        self.ctx["adj_par"] = par
-
-    def backward_adjoint(self, dout, need_du=True, need_params=False, need_dy0=False):
-        """dL/du, dL/dy0 (and, with ``need_params``, the parameter adjoint for ``accumulate_param_grads``) from
-        dL/dy(t1) = ``dout`` by solving the adjoint system backwards from the forward's y(t1)."""
-        ctx = self.ctx
-        P, rpp, n, u, method = ctx["P"], ctx["rpp"], ctx["n"], ctx["u"], ctx["method"]
-        ns, nu, s = self.n_s, self.n_u, stream_ptr()
-        assert dout.shape == (n, ns) and dout.is_contiguous()
-        self._cur_n = n
-        S = 7 if method == "dopri5" else len(TABLEAU[method]["c_sol"])
-        w = self._adj_ws(n, S)
-        par = self._adj_par_cur = self._adj_params_begin(w, n, S) if need_params else None
-        _lib.call("nlbac_adj_pack", ctx["out"].data_ptr(), dout.data_ptr(), ns, nu, n, w["Z0"].data_ptr(), s)
-        if method in ("euler", "rk4"):
-            tab = TABLEAU[method]
-            h = [ctx["t_end"]] * P
-            self._adj_step(w, u, P, rpp, method, 0, S, h_host=h, c_out=fptr(*tab["c_sol"]),
-                           keep=par and par["keep"])
-            if par:
-                self._adj_params_fixed(par, w, tab["c_sol"], h[0])
-            res = w["Z1"]
-            ctx["adjoint_info"] = None
-        else:
-            res = self._adj_dopri(w, u, P, rpp, par)
-        du = self._buf("du", n, nu) if need_du else None
-        dy0 = self._buf("dy0_adj", n, ns) if need_dy0 else None
-        if du is not None or dy0 is not None:
-            _lib.call("nlbac_adj_unpack", res.data_ptr(), ns, nu, n, dy0.data_ptr() if dy0 is not None else None,
-                      du.data_ptr() if du is not None else None, s)
-        return du, dy0
-
-    def _adj_dopri(self, w, u, P, rpp, par):
-        ctx = self.ctx
-        n, S, s = ctx["n"], 7, stream_ptr()
-        ctl = self._buf("adj_ctl", P, _lib.DOPRI_CTL, dtype=torch.float64)
-        cp = ctl.data_ptr()
-        KZ = w["KZ"]
-        keep = par and par["keep"]
-        ctx["ctl_seq"] = None         # (the adjoint solve's own range of stamps: _seq_next)
-        # f0 = G(z(t1)) and Hairer's initial step
-        self._adj_step(w, u, P, rpp, "dopri5", 0, 1, h_host=[0.0] * P, keep=keep)
-        pn = self._adj_params_norm(par, 0, cp) if par else None
-        self._adj_norm_control(KZ[0], None, w, u, 0, P, rpp, ctl, pn)
-        self._adj_step(w, u, P, rpp, "probe", 1, 2, h_dev=cp + 8 * 6, keep=keep)             # C_H0
-        pn = self._adj_params_norm(par, 1, cp) if par else None
-        self._adj_norm_control(KZ[1], KZ[0], w, None, 1, P, rpp, ctl, pn)
-        c_sol, c_err = self._coef("sol"), self._coef("err")
-        chain = max(1, int(self.__dict__.get("_adj_chain", 1)))
-        attempts = 0
-        ip = self._adj_interp_fold()
-        while True:
-            for i in range(chain):
-                if attempts:
-                    # accepted and not finished: z0 <- z1, first stage <- last stage (FSAL); decided on the device
-                    _lib.call("nlbac_adj_commit", cp, rpp, n, w["W"], w["Z0"].data_ptr(), w["Z1"].data_ptr(),
-                              KZ[0].data_ptr(), KZ[6].data_ptr(), s)
-                    if par:
-                        self._adj_params_commit(par, cp)
-                self._adj_step(w, u, P, rpp, "dopri5", 1, S, h_dev=cp, ctl=cp, c_out=c_sol, c_err=c_err, keep=keep, interp=ip)
-                pn = self._adj_params_norm(par, 2, cp) if par else None
-                self._adj_norm_control(w["ERR"], None, w, None, 2, P, rpp, ctl, pn)
-                attempts += 1
-            if ctx.get("adj_ctl_host"):
-                self._ctl_posted(P)
-            else:
-                self._ctl_post(P, ctl)
-            c = self._ctl_read(P) if ctx.get("ctl_pending") == P else ctl.cpu()
-            if all(bool(c[p, 4] > 0) for p in range(P)):
-                break
-            if attempts >= self.ADJ_MAX_ATTEMPTS:
-                raise _lib.NlbacError("odeint_adjoint (dopri5): max_num_steps exceeded")
-            chain = 2
-        used = int(max(float(c[p, 10]) for p in range(P)))       # C_NSTEPS: attempts of the slowest problem
-        self._adj_chain = max(1, used)
-        ctx["adjoint_info"] = [[(float(c[p, 11]), float(c[p, 2]), int(c[p, 10])) for p in range(P)]]
-        # the interpolant of the last accepted step at t0 (steps are not clipped), all columns of z at once: written by
-        # the attempt that finished each problem (interp), or by a launch of its own
-        if not ip:
-            _lib.call("nlbac_dopri_interp_fwd", w["Z0"].data_ptr(), w["Z1"].data_ptr(), KZ.data_ptr(), None, None, cp, P,
-                      rpp, w["W"], w["OUT"].data_ptr(), 0, None, s)
-        if par:
-            self._adj_params_finish(par, cp)
-        return w["OUT"]
-
     def _stage_backward(self, ws, st, need_dx, need_params, du, up, coef, h_host, h_dev, h_stride):
         """Un-fused backward of one stage of the control-affine field: affine_bwd -> mlp_bwd_data[f,g] ->
         rk_stage_bwd (kept as the cross-check of nlbac_node_rk_bwd)."""
@@ -1510,51 +978,8 @@ class AffineNodeSolver:
 # Non-affine field  dx/dt = net([x, c])  with carried inputs c = (u, t, ...) constant over the step
 # (SimulatedCars: C/sac_cbf_clf/model.py:179-205).  Same RK machinery, stage by stage on nlbac_mlp_*.
 # ---------------------------------------------------------------------------
-class _ConcatStepWS:
-    ADOPT = ("K", "Y", "err", "acts")
 
-    def __init__(self, solver, n, S, store):
-        dev, ns, nc = solver.device, solver.n_s, solver.n_u
-        net = solver.net
-        self.n, self.S = n, S
-        self._store = store
-        z = self._store.zeros
-        self.K = z(S, n, ns)
-        self.Y = z(S, n, ns)
-        # a rollout that is only differentiated w.r.t. its inputs keeps ReLU mask words instead of the activations, where
-        # the fused kernels can (the register-resident ones: nlbac_concat_rk_mask_words)
-        words = _lib.load().nlbac_concat_rk_mask_words(C.byref(net.desc)) if (solver.fused and not solver.keep_acts) else 0
-        self.bits = words > 0
-        if self.bits:
-            self.wa = words
-            self.acts = self._store.zeros(net.n_layers - 1, S * n, words, dtype=torch.int32)
-        else:
-            self.wa = net.hid
-            self.acts = z(net.n_layers - 1, S * n, net.hid)
-        self.y1 = z(n, ns)
-        self.err = z(n, ns)
-        self.io_fwd, self.io_bwd = {}, {}
-        self._bwd = None
-        # a normalised field keeps the normalised net inputs of every stage for the first layer's weight gradient
-        self.Xn = z(S, n, net.in_dim) if solver.norm is not None else None
-
-    def bwd(self, solver):
-        if self._bwd is None:
-            dev, ns, nc, n, S = solver.device, solver.n_s, solver.n_u, self.n, self.S
-            net = solver.net
-            z = self._store.zeros
-            self.dK = z(S, n, ns)
-            self.dz = z(net.n_layers - 1, S * n, net.hid)
-            self.dX = z(n, net.in_dim)
-            self.dy0 = z(n, ns)
-            self.dy1 = z(n, ns)
-            self.c_rep = z(S * n, nc)      # carried inputs repeated per stage (first-layer weight gradients)
-            self.dyn = z(S, n, ns) if solver.norm is not None else None      # d/d(net output) = dK * out_std
-            self._bwd = True
-        return self
-
-
-class ConcatNodeSolver(AffineNodeSolver):
+class ConcatNodeSolver(ConcatAdjoint, AffineNodeSolver):
     """``u`` here is the (n, n_carry) block of carried inputs; ``backward`` returns its gradient."""
     STEP_WS = _ConcatStepWS
 
@@ -1562,19 +987,9 @@ class ConcatNodeSolver(AffineNodeSolver):
         self.node, self.net = node, node.net_handle
         self.f = self.g = self.net            # (base-class bookkeeping only)
         self.n_s, self.n_u = node.n_s, node.n_carry
-        self.device = torch.device(device)
-        self._ws, self._scratch = {}, {}
-        self.nfe = 0
-        self._net_arr, self._coefs, self._children = None, {}, {}
         # one nlbac_concat_rk_fwd / _bwd launch per RK step (nets of <= 128 hidden units; wider ones run stage by stage)
         self.fused = self.net.hid <= 128
-        self.keep_acts = True
-        self.stats = dict(solves=0, single_step=0, multi_attempt=0, split=0)
-        self.comm = None
-        self.row_groups = 1
-        self.adjoint = False
-        self.generation = 0
-        self.device_loop = True
+        self._init_state(device)
         # input normalisation / output de-normalisation lives inside the fused step kernels only
         self.norm = node.norm_device() if getattr(node, "normalized", False) else None
         if self.norm is not None and not self.fused:
@@ -1590,132 +1005,6 @@ class ConcatNodeSolver(AffineNodeSolver):
 
     def _fit_words_on(self):
         return False
-
-    # -- continuous adjoint (odeint_adjoint) of the single-net field ---------------------------------------------
-    # The base class drives the solve (initial step, attempts, mixed norm, commit, interpolation, parameter-adjoint
-    # quadrature); what differs is one RK step of the augmented system z = [y | a_y | a_c] and the stage derivative of
-    # the parameter adjoint: stage by stage on the MLP entry points (nlbac_concat_adj_in -> nlbac_mlp_fwd ->
-    # nlbac_mlp_bwd_data -> nlbac_concat_adj_out), the RK combinations by nlbac_rk_combine on the w-wide rows.
-    def _adj_scratch(self, n, S):
-        net, ns, nc = self.net, self.n_s, self.n_u
-        return dict(ZS=self._buf("cadj_ZS", n, 2 * ns + nc), Xin=self._buf("cadj_Xin", n, net.in_dim),
-                    Ay=self._buf("cadj_Ay", n, ns), f=self._buf("cadj_f", n, ns), dX=self._buf("cadj_dX", n, net.in_dim),
-                    acts=self._buf("cadj_acts", net.n_layers - 1, n, net.hid))
-
-    def _adj_fused(self):
-        """One nlbac_concat_adj_step launch per attempted step (the reference's depth at widths 64 / 100 / 128);
-        ``adj_fused = False`` keeps the stage-by-stage launches (other shapes; the cross-check)."""
-        f = self.__dict__.get("adj_fused")
-        if f is None:
-            f = self.adj_fused = bool(_lib.load().nlbac_concat_adj_step_ok(C.byref(self.net.desc)))
-        return f
-
-    def _adj_interp_fold(self):
-        return self._adj_fused() and self._interp_fold_on()
-
-    def _adj_step(self, w, u, P, rpp, method, st0, st1, h_host=None, h_dev=None, ctl=None, c_out=None, c_err=None,
-                  keep=None, interp=False):
-        """(Stage by stage: problems whose solve is done are recomputed to the same values — their control block, z0
-        and first stage no longer change — instead of being skipped; the fused launch leaves their rows alone.)"""
-        if self._adj_fused():
-            beta, S = self._beta(method)
-            k = keep or {}
-            dp = lambda t: t.data_ptr() if t is not None else None
-            _lib.call("nlbac_concat_adj_step", C.byref(self.net.desc), u.data_ptr(), P, rpp, st0, st1, S, beta,
-                      c_out, len(c_out) if c_out is not None else 0, c_err, len(c_err) if c_err is not None else 0,
-                      fptr(*h_host) if h_host is not None else None, h_dev, _lib.DOPRI_CTL if h_dev else 0, ctl,
-                      w["Z0"].data_ptr(), w["KZ"].data_ptr(), w["Z1"].data_ptr() if c_out is not None else None,
-                      w["ERR"].data_ptr() if c_err is not None else None,
-                      self.norm.data_ptr() if self.norm is not None else None, dp(k.get("Xin")), dp(k.get("Ay")),
-                      dp(k.get("acts")), k.get("ls", 0), dp(k.get("dz")), w["OUT"].data_ptr() if interp else None,
-                      self.ctx["t_end"], stream_ptr())
-            self.nfe += st1 - st0
-            if keep:
-                for st in range(st0, st1):
-                    self._adj_stage_dw(self._adj_par_cur, st)
-            return
-        n, W, ns, nc, net, s = P * rpp, w["W"], self.n_s, self.n_u, self.net, stream_ptr()
-        rows = TABLEAU[method]["beta"]
-        S = len(rows) + 1
-        sc = self._adj_scratch(n, S)
-        hh = fptr(*h_host) if h_host is not None else None
-        stride = _lib.DOPRI_CTL if h_dev else 0
-        norm = self.norm.data_ptr() if self.norm is not None else None
-        KZ = w["KZ"]
-        for st in range(st0, st1):
-            if st == 0:
-                ZS = w["Z0"]
-            else:
-                ZS = sc["ZS"]
-                _lib.call("nlbac_rk_combine", w["Z0"].data_ptr(), KZ.data_ptr(), st, fptr(*rows[st - 1]), hh, h_dev, stride,
-                          P, rpp, W, ZS.data_ptr(), s)
-            if keep:      # the parameter adjoint's quadrature reads every stage's net inputs / cotangents / activations
-                Xin, Ay = keep["Xin"][st], keep["Ay"][st]
-                acts, dz, ls = keep["acts"][:, st * n:], keep["dz"][:, st * n:], keep["ls"]
-            else:
-                Xin, Ay, acts, dz, ls = sc["Xin"], sc["Ay"], sc["acts"], None, n * net.hid
-            _lib.call("nlbac_concat_adj_in", ZS.data_ptr(), W, u.data_ptr(), ns, nc, norm, n, Xin.data_ptr(), Ay.data_ptr(), s)
-            io = io_array(1)
-            io[0].x0, io[0].x0_dim, io[0].x0_ld = Xin.data_ptr(), net.in_dim, net.in_dim
-            io[0].y, io[0].y_ld = sc["f"].data_ptr(), ns
-            io[0].acts, io[0].acts_ls = acts.data_ptr(), ls
-            _lib.call("nlbac_mlp_fwd", self._nets(), io, 1, n, s)
-            io[0].dy, io[0].dy_ld = Ay.data_ptr(), ns
-            io[0].dx, io[0].dx_ld = sc["dX"].data_ptr(), net.in_dim
-            if dz is not None:
-                io[0].dz = dz.data_ptr()
-            _lib.call("nlbac_mlp_bwd_data", self._nets(), io, 1, n, s)
-            _lib.call("nlbac_concat_adj_out", sc["f"].data_ptr(), sc["dX"].data_ptr(), ns, nc, norm, n, W, KZ[st].data_ptr(), s)
-            if keep:
-                self._adj_stage_dw(self._adj_par_cur, st)
-        if c_out is not None:
-            _lib.call("nlbac_rk_combine", w["Z0"].data_ptr(), KZ.data_ptr(), len(c_out), c_out, hh, h_dev, stride, P, rpp, W,
-                      w["Z1"].data_ptr(), s)
-        if c_err is not None:
-            _lib.call("nlbac_rk_combine", None, KZ.data_ptr(), len(c_err), c_err, hh, h_dev, stride, P, rpp, W,
-                      w["ERR"].data_ptr(), s)
-        self.nfe += st1 - st0
-
-    def _adj_params_begin(self, w, n, S):
-        ctx = self.ctx
-        assert ctx["P"] == 1, "parameter gradients are only taken on single-problem solves"
-        key = ("adj_par", n, S)
-        pool = self._scratch.setdefault(n, {})
-        par = pool.get(key)
-        if par is None:
-            net, ns, dev = self.net, self.n_s, self.device
-            z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=dev)
-            arena = net.arena
-            NP = arena.n
-            keep = dict(Xin=z(S, n, net.in_dim), Ay=z(S, n, ns), acts=z(net.n_layers - 1, S * n, net.hid),
-                        dz=z(net.n_layers - 1, S * n, net.hid), ls=S * n * net.hid)
-            segs = [(arena.offset_of[id(p)], p.numel()) for p in self.node.parameters()]
-            par = pool[key] = dict(
-                keep=keep, NP=NP, K=z(S, NP), th0=z(NP), th1=z(NP), out=z(NP), slabs=z(self.ADJ_SUB_SLABS, NP),
-                seg_off=torch.tensor([o for o, _ in segs], dtype=torch.int32, device=dev),
-                seg_len=torch.tensor([l for _, l in segs], dtype=torch.int32, device=dev), n_seg=len(segs),
-                pseg=z(2 * len(segs)), ticket=z(1, dtype=torch.int32), pnorm=z(2), io={}, n=n, S=S, w=w)
-        _lib.call("nlbac_fill", par["th0"].data_ptr(), 0.0, par["NP"], stream_ptr())
-        par["grad"] = None
-        return par
-
-    def _adj_stage_dw(self, par, st):
-        """K_theta[st] = sum over the rows of stage ``st`` of (d net / d theta)^T (a_y out_sig) at the stage's
-        (normalised) inputs: nlbac_mlp_bwd_weights on what the step kept of that stage, then the slab sum."""
-        k, n, S, net = par["keep"], par["n"], par["S"], self.net
-        io = par["io"].get(st)
-        if io is None:
-            io = par["io"][st] = io_array(1)
-            io[0].x0, io[0].x0_dim, io[0].x0_ld = k["Xin"][st].data_ptr(), net.in_dim, net.in_dim
-            io[0].dy, io[0].dy_ld = k["Ay"][st].data_ptr(), self.n_s
-            io[0].acts, io[0].dz = k["acts"][:, st * n:].data_ptr(), k["dz"][:, st * n:].data_ptr()
-            io[0].acts_ls = S * n * net.hid
-            io[0].grad = par["slabs"].data_ptr()
-        bwd_weights(self._nets(), io, 1, n, self.ADJ_SUB_SLABS, par["NP"], self.device)
-        _lib.call("nlbac_reduce_slabs", par["K"][st].data_ptr(), par["slabs"].data_ptr(), self.ADJ_SUB_SLABS,
-                  par["NP"], par["NP"], stream_ptr())
-        if self.comm is not None and self.comm.world > 1:
-            self.comm.all_reduce_(par["K"][st])       # (see AffineNodeSolver._adj_stage_dw)
 
     def _rk_fused(self, ws, y0, u, P, rpp, method, st0, st1, h_host=None, h_dev=None, c_out=None, out=None,
                   c_err=None, err=None, save_acts=True, chain=None):
@@ -1835,13 +1124,13 @@ def _solver_of(func, adjoint=False):
         raise TypeError("nlbac_amd.odeint integrates this build's NeuralODEModel (its field runs as HIP kernels); "
                         "got %s" % type(func).__name__)
     key = "_odeint_solver_adj" if adjoint else "_odeint_solver"
-    sv = func.__dict__.get(key)
+    sv = getattr(func, key, None)
     if sv is None:
         handles = func.device_handles()
         sv = (AffineNodeSolver if func.affine else ConcatNodeSolver)(func, handles[0].arena.device)
         sv.keep_acts = True                  # parameter gradients need the pre-activation gradients of every stage
         sv.adjoint = bool(adjoint)
-        func.__dict__[key] = sv
+        setattr(func, key, sv)
     return sv
 
 

@@ -19,7 +19,8 @@ import torch
 from . import _lib
 from ._lib import fptr
 from .arena import bwd_weights, io_array, mlp_array, stream_ptr
-from .odeint import TABLEAU, AffineNodeSolver, ConcatNodeSolver
+from .ode_consts import TABLEAU, env_switch
+from .odeint import AffineNodeSolver, ConcatNodeSolver
 
 ONE_LAUNCH = os.environ.get("NLBAC_ROLLOUT_ONE_LAUNCH", "1") != "0"
 METHODS = ("euler", "rk4", "dopri5")
@@ -128,7 +129,7 @@ class _Traj:
         z = lambda *s, dtype=torch.float32: torch.empty(*s, dtype=dtype, device=device)
         self.K, self.Y, self.G = z(HS, n, self.ns), z(HS, n, self.ns), z(HS, n, self.ns * self.nu)
         self.rows = mode == "params"
-        words = mode == "inputs" or (self.rows and os.environ.get("NLBAC_FIT_WORDS", "1") != "0")
+        words = mode == "inputs" or (self.rows and env_switch("fit_words"))
         self.bits = 0 if mode == "none" else (1 if mode == "inputs" else (2 if words else 0))
         self.acts, self.ls = [None, None], [0, 0]
         if mode != "none":

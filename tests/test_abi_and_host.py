@@ -342,21 +342,21 @@ def test_pmc_summary_differences_two_run_lengths(tmp_path):
 
 
 def test_host_reader_of_the_stamped_control_block():
-    """``AffineNodeSolver._ctl_poll`` (host side of nlbac_rk_chain::ctl_seq, no GPU needed): a problem's block is complete
+    """``ControlBlockReader.poll`` (host side of nlbac_rk_chain::ctl_seq, no GPU needed): a problem's block is complete
     when it carries the stamp of the launch waited for — or an earlier stamp of the same solve with the done flag (launches
     skip finished problems); a block whose stamp is negative (a writer is in the middle of it), older than the solve or
     not yet there is waited for; torn reads (stamp changes under the copy) are retried."""
     import threading
     import time
-    from nlbac_amd.odeint import AffineNodeSolver
+    from nlbac_amd.ode_ctl import ControlBlockReader
 
     class Fake:
         stats = {}
-        _ctl_poll = AffineNodeSolver._ctl_poll
+        _ctl_poll = ControlBlockReader.poll
 
     f = Fake()
     pin = torch.zeros(2, _lib.DOPRI_CTL, dtype=torch.float64)
-    f._ctl_pin = {2: pin}
+    f.pin = {2: pin}
     arr = pin.numpy()
     # both problems carry the stamp waited for
     arr[:, 15] = 7.0

@@ -1,5 +1,5 @@
 #!/bin/bash
-# GPU box: the election-free opening norms (NLBAC_NORM_DEFER, odeint.py) against the fused norms with elections.
+# GPU box: the election-free opening norms (NLBAC_NORM_DEFER, ode_consts.py) against the fused norms with elections.
 cd "${GRAFT_REPO_ROOT:-.}"
 O=gpurun_out/defer; mkdir -p $O
 run() {   # name, defer, bench args

@@ -16,8 +16,10 @@ reference.  Differences that are visible to a caller:
 The environment-specific half of an update (row layout, NODE form, rollout, CBF / CLF terms, NODE fit) is a task
 object (``tasks.py``) chosen from ``env.dynamics_mode``; this file holds the shared SAC / Lyapunov machinery:
 ``_upd_part1`` (targets, critic step, actor forward, rollout start) and ``_upd_part2`` (constraints, actor backward,
-actor step), see DESIGN.md §3.  Host<->device traffic per update: the minibatch upload (or 8 bytes per row of
-indices), one 512-byte scalars read-back and, for dopri5, one 256-byte control block per attempted step.
+actor step), see DESIGN.md §3.  What they work on — the per-batch-size workspace, the launch descriptors, the captured
+hipGraphs — is ``update_plan.py``; how the returned floats reach the host, ``scalars_readback.py``.  Host<->device
+traffic per update: the minibatch upload (or 8 bytes per row of indices), one 512-byte scalars read-back and, for
+dopri5, one 256-byte control block per attempted step.
 """
 import collections
 import ctypes as C
@@ -30,10 +32,12 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..arena import Arena, bwd_weights, io_array, mlp_array, pack, skinny_partials_ws, stream_ptr
+from ..arena import Arena, bwd_weights, pack, stream_ptr
 from . import _layout as SC
 from .model import BarrierNetwork, GaussianPolicy, LyaNetwork, QNetwork
+from .scalars_readback import ScalarsReadback
 from .tasks import TASKS
+from .update_plan import GraphCache, Plan, _Layout, _Workspace
 from .utils import to_tensor
 
 DYNAMICS_MODE = {'Unicycle': {'n_s': 3, 'n_u': 2}, 'SimulatedCars': {'n_s': 10, 'n_u': 1},
@@ -46,69 +50,6 @@ class PoseLoss(nn.Module):
 
     def forward(self, predicted_state, true_state):
         return nn.functional.mse_loss(predicted_state, true_state)
-
-
-class _Layout:
-    """Column offsets of one minibatch row in HBM: the fields of ``ReplayMemory.sample``
-    (replay_memory.py:24-25) side by side, row stride padded to 16 bytes."""
-
-    def __init__(self, task):
-        self.obs_dim, self.act_dim, self.lya_dim = task.obs_dim, task.act_dim, task.lya_dim
-        c = 0
-        fields = [("obs", task.obs_dim), ("act", task.act_dim), ("rew", 1), ("con", 1), ("lya", task.lya_dim),
-                  ("nlya", task.lya_dim), ("nobs", task.obs_dim), ("mask", 1), ("t", 1), ("nt", 1)]
-        if task.has_signal:          # learned-barrier copies store a barrier signal after the constraint
-            fields.insert(4, ("sig", 1))
-        self.sig = None
-        for name, w in fields:
-            setattr(self, name, c)
-            c += w
-        self.width = c
-        self.LD = (c + 3) // 4 * 4
-
-
-class _Workspace:
-    """Per-batch-size device buffers (allocated once, reused every update); the task adds its own."""
-
-    def __init__(self, B, H, dev, lay, task):
-        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
-        A, Do = lay.act_dim, lay.obs_dim
-        NP, NX = task.n_pol, task.n_extra_critics      # controllers; critic-type nets beyond Q1, Q2, L
-        self.B = B
-        self.mb = z(B, lay.LD)                   # minibatch rows (see _Layout)
-        self.eps = z(task.n_eps, B, A)
-        # policy samples of one update live side by side: rows [0,B) pi(s'), then pi(s) (and pi_backup(s)), so that
-        # one forward launch and one sampling launch serve all of them
-        self.heads3, self.act3, self.logp3 = z((1 + NP) * B, 2 * A), z((1 + NP) * B, A), z((1 + NP) * B)
-        self.heads_n, self.na, self.nlogp = self.heads3[:B], self.act3[:B], self.logp3[:B]
-        self.q6 = z(6 + 2 * NX, B)               # q1t q2t lt q1 q2 lf [xt x]...
-        self.dq3 = z(3 + NX, B)
-        self.next_q, self.next_l = z(B), z(B)
-        self.acts_c = z(3 + NX, 2, B, H)         # Q1,Q2,L[,extras] saved activations
-        self.dz_c = z(3 + NX, 2, B, H)
-        self.nblk = (B + 255) // 256
-        self.part_td = z(self.nblk, 3)
-        self.n_tiles = (B + _lib.MLP_TILE_MIN - 1) // _lib.MLP_TILE_MIN
-        self.part_td32 = z(self.n_tiles, 4)            # per-tile sums of the fused dy heads (nlbac_dy_head; 16-row tiles at most)
-        # tickets of the heads' two-level elections: 1 + ceil(workgroups / 16) words each (TD head: <= 4 nets; actor head)
-        self.tickets_td = torch.zeros(2 + self.n_tiles * 4 // 16 + 1, dtype=torch.int32, device=dev)
-        self.tickets_q = torch.zeros(2 + self.n_tiles * NP // 16 + 1, dtype=torch.int32, device=dev)
-        self.sums_tiles = torch.zeros(4, dtype=torch.int32, device=dev)    # nlbac_dy_head::sums_tiles of the td / actor-q heads
-        self.sc_stage = z(SC.SC_SIZE)                                        # nlbac_dy_head::cb_stage
-        self.part_tdx = z(max(NX, 1), self.nblk)
-        self.heads2, self.pi2, self.logp2 = self.heads3[B:], self.act3[B:], self.logp3[B:]
-        self.acts_p = z(NP, 2, B, H)
-        self.dz_p = z(NP, 2, B, H)
-        self.plan = None
-        self.graphs, self.warm = {}, 0
-        self.qpi = z(2, NP * B)
-        self.acts_q = z(2 * NP, 2, B, H)
-        self.dq_pi = z(2, NP * B)
-        self.part_q = z(NP, self.nblk, 2)
-        self.part_q32 = z(NP, self.n_tiles, 2)
-        self.dxq = z(2, NP * B, Do + A)
-        self.dheads2 = z(NP * B, 2 * A)
-        task.alloc(self)
 
 
 class SAC_CBF_CLF(object):
@@ -249,7 +190,9 @@ class SAC_CBF_CLF(object):
         self._ws = {}
         self._noise = None
         self._fit_ws = {}
-        self._fill = collections.deque()
+        self._fill = collections.deque()      # pieces of part 1 not yet queued (see _upd_part1)
+        self._fill_first = True               # the next solver wait is the first of its update
+        self._readback = ScalarsReadback(self.sc)
         for sv in self.task.solvers:          # independent launches go in just before a solver waits for a decision
             sv.before_wait = self._fill_one
         self.use_graphs = False  # replay the update as hipGraphs (single GPU; see update_on_device)
@@ -257,6 +200,7 @@ class SAC_CBF_CLF(object):
         # nlbac_dy_head, nlbac_in_map / nlbac_out_map, results written to pinned memory by the kernels): False (or
         # NLBAC_FOLD=0) runs every step as the launch of its own it was — same numbers, for A/B runs and the tests
         self.fold_launches = os.environ.get("NLBAC_FOLD", "1") != "0"
+        self.sums_defer = os.environ.get("NLBAC_SUMS_DEFER", "1") != "0"      # (see _sums_defer)
         self.adjoint = bool(getattr(args, "adjoint", False))
         self.dp = None          # nlbac_amd.parallel.DataParallel when sharded over GPUs
         self._xb = {}
@@ -336,7 +280,7 @@ class SAC_CBF_CLF(object):
         if self.world == 1:
             if before_step is not None:
                 before_step(a.grad.data_ptr())
-            # mirror: (pinned host block) the step's last workgroup writes the scalars block to (see _returns)
+            # mirror: (pinned host block) the step's last workgroup writes the scalars block to (scalars_readback.py)
             _lib.call("nlbac_adam_fused", a.theta.data_ptr(), a.m.data_ptr(), a.v.data_ptr(), a.grad.data_ptr(),
                       n_slabs, a.n, a.n, a.state.data_ptr(), lr, target, tau, scat.data_ptr(), scat_t, a.scatter_slots,
                       n_al, al_off, al_dst, self.sc.data_ptr() if mirror is not None else None,
@@ -367,21 +311,9 @@ class SAC_CBF_CLF(object):
         backup sample)], each (B, n_u)."""
         self._noise = [torch.as_tensor(e, dtype=torch.float32) for e in eps_list]
 
-    def _sc_pins(self):
-        pin = self.__dict__.get("_sc_pin")
-        if pin is None:
-            pin = self._sc_pin = [torch.zeros(SC.SC_SIZE, dtype=torch.float32).pin_memory() for _ in range(3)]
-            self._sc_ev = [torch.cuda.Event() for _ in range(3)]
-            self._sc_lag = None
-        return pin
-
     def _scalars(self):
-        """Host copy of the device scalars (one 512-byte read through a pinned buffer; waits for the launch stream)."""
-        pin = self._sc_pins()
-        pin[0].copy_(self.sc, non_blocking=True)
-        self._sc_ev[0].record()
-        self._sc_ev[0].synchronize()
-        return pin[0].numpy().copy()
+        """Host copy of the device scalars (waits for the launch stream)."""
+        return self._readback.read()
 
     @property
     def alpha(self):
@@ -519,7 +451,7 @@ class SAC_CBF_CLF(object):
             while len(self._fit_ws) >= 2:       # the fit batch grows with the replay: keep the two latest sizes only
                 self._fit_ws.pop(next(iter(self._fit_ws)))      # (its graphs go with it)
             w = task.fit_ws(N)
-            w.update(graphs={}, warm=0)
+            w.update(graphs=GraphCache(task.solvers), warm=0)
             self._fit_ws[N] = w
         w = self._fit_ws[N]
         w["u"].copy_(action)
@@ -531,12 +463,11 @@ class SAC_CBF_CLF(object):
             self._fit_part2(w, N, task.fit_solver.forward_finish())
             return
         g = w["graphs"]
-        self._replay(self._graph(g, ("p1",) + key, part1))
+        g.replay(("p1",) + key, part1)
         if self.solver == "dopri5" and not task.fit_solver.first_step_done():
             self._fit_part2(w, N, task.fit_solver.forward_finish())      # rare: finish this one eagerly
             return
-        self._replay(self._graph(g, ("p2",) + key,
-                                 lambda: self._fit_part2(w, N, task.fit_solver.forward_finish(assume_single_step=True))))
+        g.replay(("p2",) + key, lambda: self._fit_part2(w, N, task.fit_solver.forward_finish(assume_single_step=True)))
 
     def _fit_part2(self, w, N, pred):
         s = stream_ptr()
@@ -554,174 +485,11 @@ class SAC_CBF_CLF(object):
             self.ar_n, max(1, min(self.n_fit_slabs, self.ar_n.n_slabs // min(n_steps, self.ar_n.n_slabs))))
         self._adam(self.ar_n, 1e-3, used, extra=self.sc[SC.SC_NODE_LOSS:SC.SC_NODE_LOSS + 1])
 
-    def _capture(self, fn):
-        """Record the launches of ``fn`` into a hipGraph (all kernel arguments are static device pointers /
-        constants; per-update scalars live in device memory).  The graph bakes in the addresses of the solvers'
-        buffers and belongs to the solves it recorded: the entry keeps the solvers' ``generation`` (any freed or
-        re-laid-out buffer invalidates it) and their solve contexts (restored before a replay, so that what the host
-        does around the replay — reading the control block, finishing a solve eagerly — talks about THIS graph's
-        solve and not about whichever batch size ran last)."""
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            fn()
-        svs = self.task.solvers
-        return types.SimpleNamespace(graph=g, gens=tuple(sv.generation for sv in svs),
-                                     ctxs=[(sv, sv.__dict__.get("ctx"), sv.__dict__.get("_cur_n")) for sv in svs])
-
-    def _graph(self, cache, key, fn):
-        """The captured graph for ``key``, re-captured if the solvers' buffers have moved since."""
-        e = cache.get(key)
-        if e is not None and e.gens != tuple(sv.generation for sv in self.task.solvers):
-            e = None
-        if e is None:
-            e = cache[key] = self._capture(fn)
-        return e
-
-    def _replay(self, e):
-        for sv, ctx, n in e.ctxs:
-            if ctx is not None:
-                sv.ctx, sv._cur_n = ctx, n
-        e.graph.replay()
-
     # -- the update proper --------------------------------------------------------
     def _plan(self, ws, NP=None):
-        """ctypes launch descriptors of one workspace: every pointer is static (arenas, workspace tensors),
-        so they are built once (per number of controllers updated: Pvtol trains its backup every 20th update);
-        an update is then a plain sequence of C calls."""
+        """The launch descriptors of ``ws`` for an update of ``NP`` controllers (update_plan.Plan), built once."""
         NP = NP or self.task.n_pol
-        if ws.plan is None:
-            ws.plan = {}
-        if NP in ws.plan:
-            return ws.plan[NP]
-        B, lay = ws.B, self.lay
-        mb = ws.mb.data_ptr()
-        LD, Do, Da, Dl = lay.LD, lay.obs_dim, lay.act_dim, lay.lya_dim
-        col = lambda c: mb + 4 * c
-        lc, lnc = self.task.lya_train_cols(lay)       # inputs the Lyapunov critic is regressed on
-        p_obs, p_act, p_cen, p_ncen, p_nobs = col(lay.obs), col(lay.act), col(lc), col(lnc), col(lay.nobs)
-
-        def x(io, i, p0, d0, ld0, p1=None, d1=0, ld1=0):
-            io[i].x0, io[i].x0_dim, io[i].x0_ld = p0, d0, ld0
-            if p1 is not None:
-                io[i].x1, io[i].x1_dim, io[i].x1_ld = p1, d1, ld1
-        P = types.SimpleNamespace()
-        P.p_obs, P.p_rew, P.p_con, P.p_mask, P.LD = p_obs, col(lay.rew), col(lay.con), col(lay.mask), LD
-        q1, q2, l, pi = self.h_q1, self.h_q2, self.h_l, self.h_p
-        P.NP, NX = NP, len(self.h_extra)
-        # A: pi(s')
-        P.n_pol, P.io_pol_next = mlp_array([pi.desc]), io_array(1)
-        x(P.io_pol_next, 0, p_nobs, Do, LD)
-        P.io_pol_next[0].y, P.io_pol_next[0].y_ld = ws.heads_n.data_ptr(), 2 * Da
-        # A: targets + critic / Lyapunov forward (6 nets)
-        descs = [q1.desc_target, q2.desc_target, l.desc_target, q1.desc, q2.desc, l.desc]
-        for h in self.h_extra:
-            descs += [h.desc_target, h.desc]
-        P.n_six, P.n_six_count = mlp_array(descs), len(descs)
-        io = P.io_six = io_array(len(descs))
-        for i in range(len(descs)):
-            io[i].y, io[i].y_ld = ws.q6[i].data_ptr(), 1
-        for k in range(NX):            # extra critic-type nets on (s', a') [target] and (s, a)
-            x(io, 6 + 2 * k, p_nobs, Do, LD, ws.na.data_ptr(), Da, Da)
-            x(io, 7 + 2 * k, p_obs, Do, LD, p_act, Da, LD)
-            io[7 + 2 * k].acts = ws.acts_c[3 + k].data_ptr()
-        for i in (0, 1):
-            x(io, i, p_nobs, Do, LD, ws.na.data_ptr(), Da, Da)
-        x(io, 2, p_ncen, Dl, LD)
-        for i in (3, 4):
-            x(io, i, p_obs, Do, LD, p_act, Da, LD)
-            io[i].acts = ws.acts_c[i - 3].data_ptr()
-        x(io, 5, p_cen, Dl, LD)
-        io[5].acts = ws.acts_c[2].data_ptr()
-        # B: critic / Lyapunov backward
-        P.n_crit = mlp_array([h.desc for h in self.h_crit])
-        io = P.io_crit = io_array(3 + NX)
-        for i in range(3 + NX):
-            io[i].dy, io[i].dy_ld = ws.dq3[i].data_ptr(), 1
-            io[i].acts, io[i].dz = ws.acts_c[i].data_ptr(), ws.dz_c[i].data_ptr()
-            io[i].grad = self.ar_c.grad.data_ptr()
-        for i in [0, 1] + list(range(3, 3 + NX)):
-            x(io, i, p_obs, Do, LD, p_act, Da, LD)
-        x(io, 2, p_cen, Dl, LD)
-        # (its data backward leaves the skinny-gradient partial sums for the weight backward: one launch less)
-        P.sk_crit = skinny_partials_ws(P.n_crit, (io,), 3 + NX, B, self.device)
-        # C: both actors (forward and backward share one descriptor)
-        def act_io(io, j, i):            # entry j of an io array describes controller i
-            x(io, j, p_obs, Do, LD)
-            io[j].y, io[j].y_ld = ws.heads2[i * B:].data_ptr(), 2 * Da
-            io[j].acts, io[j].dz = ws.acts_p[i].data_ptr(), ws.dz_p[i].data_ptr()
-            io[j].dy, io[j].dy_ld = ws.dheads2[i * B:].data_ptr(), 2 * Da
-            io[j].grad = self.pol_arena[i].grad.data_ptr()
-        P.n_act = mlp_array([h.desc for h in self.h_pols[:NP]])
-        io = P.io_act = io_array(NP)
-        for i in range(NP):
-            act_io(io, i, i)
-        P.n_pol3 = mlp_array([pi.desc] + [h.desc for h in self.h_pols[:NP]])     # pi(s') + the actors on s
-        io3 = P.io_pol3 = io_array(1 + NP)
-        x(io3, 0, p_nobs, Do, LD)
-        io3[0].y, io3[0].y_ld = ws.heads_n.data_ptr(), 2 * Da
-        for i in range(NP):
-            act_io(io3, 1 + i, i)
-        P.act_groups = []                # per Adam group: the nets whose weight gradients land in its arena
-        for g in self.actor_groups:
-            cnt = min(g.count, NP - g.first)
-            if cnt <= 0:
-                continue
-            gio = io_array(cnt)
-            for j in range(cnt):
-                act_io(gio, j, g.first + j)
-            nets_g = mlp_array([h.desc for h in self.h_pols[g.first:g.first + cnt]])
-            # the actors' data backward (P.io_act) leaves this group's skinny-gradient partials for its weight backward
-            io_act_g = [P.io_act[g.first + j] for j in range(cnt)]       # (views into the array, not copies)
-            sk = skinny_partials_ws(nets_g, (gio, io_act_g), cnt, B, self.device)
-            P.act_groups.append((g, cnt, nets_g, gio, sk))
-        # C: Q(s, pi) for primary / backup + V(current Lyapunov input)
-        extra = self.task.extra_value_nets()
-        P.n_q5 = mlp_array([q1.desc, q2.desc] * NP + [l.desc] + [h.desc for h in extra])
-        P.n_q5_count = 2 * NP + 1 + len(extra)
-        io = P.io_q5 = io_array(P.n_q5_count)
-        for i in range(2 * NP):
-            half = i // 2                                      # 0 primary, 1 backup
-            x(io, i, p_obs, Do, LD, ws.pi2[half * B:].data_ptr(), Da, Da)
-            io[i].y, io[i].y_ld = ws.qpi[i % 2, half * B:].data_ptr(), 1
-            io[i].acts = ws.acts_q[i].data_ptr()
-            io[i].dy, io[i].dy_ld = ws.dq_pi[i % 2, half * B:].data_ptr(), 1
-            io[i].dx, io[i].dx_ld = ws.dxq[i % 2, half * B:].data_ptr(), Do + Da
-            io[i].dx_first = Do                                # (only dQ / da is consumed)
-        self.task.value_now_io(ws, io, 2 * NP)
-        self.task.extra_value_io(ws, io, 2 * NP + 1)
-        self.task.plan(ws, P)
-        self._masks_for_dx_only_nets(ws, P)
-        ws.plan[NP] = P
-        return P
-
-    def _masks_for_dx_only_nets(self, ws, P):
-        """Where the register-resident MLP kernels serve the heads, every forward that saves something for a backward
-        also leaves ReLU mask words (``nlbac_mlp_io::masks``, 64 B per row) and every data backward gates with them
-        instead of loading the activation rows (24 float4 per lane at the head of each tile's critical path).  Nets that
-        are only differentiated w.r.t. their inputs (Q(s, pi), V(p(x')), the barrier on predicted states: dx wanted, no
-        dz / weight gradients) then keep nothing else — their activation buffer is dropped from the descriptors: the
-        forward's 2 KB-per-row store burst goes.  Works on the finished launch descriptors: an activation buffer that no
-        descriptor pairs with a dz buffer is such a net's."""
-        if not self.fold_launches or not _lib.load().nlbac_mlp_masks_ok(mlp_array([h.desc for h in self.h_crit + self.h_pols]),
-                                                                       len(self.h_crit) + len(self.h_pols)):
-            return
-        arrays = [v for v in P.__dict__.values() if isinstance(v, C.Array) and getattr(v, "_type_", None) is _lib.MlpIO]
-        arrays += [g[3] for g in P.act_groups]
-        rows = set()
-        for arr in arrays:
-            for e in arr:
-                if e.acts and (e.dz or e.grad or e.skinny_ws):
-                    rows.add(e.acts)
-        bufs = ws.__dict__.setdefault("_mask_bufs", {})
-        for arr in arrays:
-            for e in arr:
-                if e.acts:
-                    if e.acts not in bufs:
-                        bufs[e.acts] = torch.zeros(2, ws.B, 8, dtype=torch.int32, device=self.device)
-                    e.masks = bufs[e.acts].data_ptr()
-                    if e.acts not in rows:
-                        e.acts = None
+        return ws.plan.get(NP) or ws.plan.setdefault(NP, Plan(self, ws, NP))
 
     def auglag_fused(self, ws, n_cbf, lam_upd):
         """The (fused, ticket, sc) tail of a ``*_constraints_fwd`` call: on one GPU the launch's last workgroup runs the
@@ -747,17 +515,13 @@ class SAC_CBF_CLF(object):
             ws.p_part_q, ws.n_part_q = ws.part_q.data_ptr(), ws.nblk
             return
         ncol = n_cbf + 1 + (n_cbf if NP == 2 else 0)
-        p_part_c, n_part = ws.part_c.data_ptr(), ws.nblk
-        ws.p_part_q, ws.n_part_q = ws.part_q.data_ptr(), ws.nblk
-        if self.world > 1:
-            xs = self._exchange_buf("sums", 64)
-            call("nlbac_sum_partials", ws.part_c.data_ptr(), ws.nblk, ncol, 1.0, xs.data_ptr(), s)
-            for pp in range(NP):
-                call("nlbac_sum_partials", ws.part_q[pp].data_ptr(), ws.nblk, 2, 1.0, xs.data_ptr() + 4 * (32 + 2 * pp), s)
-            self.dp.all_reduce_(xs)
-            p_part_c, n_part = xs.data_ptr(), 1
-            ws.p_part_q, ws.n_part_q = xs.data_ptr() + 4 * 32, 1
-        call("nlbac_auglag", p_part_c, n_part, n_cbf, 1, float(self.batch_size), lam_upd, ws.blam_upd,
+        xs = self._exchange_buf("sums", 64)
+        call("nlbac_sum_partials", ws.part_c.data_ptr(), ws.nblk, ncol, 1.0, xs.data_ptr(), s)
+        for pp in range(NP):
+            call("nlbac_sum_partials", ws.part_q[pp].data_ptr(), ws.nblk, 2, 1.0, xs.data_ptr() + 4 * (32 + 2 * pp), s)
+        self.dp.all_reduce_(xs)
+        ws.p_part_q, ws.n_part_q = xs.data_ptr() + 4 * 32, 1
+        call("nlbac_auglag", xs.data_ptr(), 1, n_cbf, 1, float(self.batch_size), lam_upd, ws.blam_upd,
              self.task.ratio_mode, self.task.backup_mode if NP == 2 else 0, 0.01, self.task.lam_hi,
              self.sc.data_ptr(), s)
 
@@ -773,8 +537,7 @@ class SAC_CBF_CLF(object):
         back with the first launches, ~30 us of idle GPU otherwise — is covered by ~30 us of queued work.  The draw sees
         the replay as of the end of this update: a driver that pushes transitions between two updates and wants them
         eligible at once does not pass ``prefetch``."""
-        pre = ws.__dict__.get("_prefetched")
-        ws._prefetched = None
+        pre, ws._prefetched = ws._prefetched, None
         if prefetch is not None:
             eps_ready = True
             if pre is None or pre[0] != updates:
@@ -797,18 +560,7 @@ class SAC_CBF_CLF(object):
         ws.updates_now = updates
         assert ws._pre_now is None or ws._pre_now[1] == NP
         ws.blam_upd = self.task.backup_lam_due(updates, self.Lagrangian_multiplier_update_interval)
-        # where the update's last launch (the actors' optimiser step) leaves the scalars block for the host: straight
-        # in pinned memory, so that no copy launch sits between that step and the host's wait.  Not under hipGraph
-        # replay (the address would be baked in) or data parallelism (the step is not the last thing that happens).
-        self._mirror = None
-        if sync and self.world == 1 and not self._graphs_on() and self.fold_launches:
-            pin = self._sc_pins()
-            if sync == "lagged":
-                k = 1 + (self.__dict__.get("_sc_flip", 0) & 1)
-                self._sc_flip = k
-            else:
-                k = 0
-            self._mirror = (k, pin[k])
+        self._readback.choose_mirror(sync, self.world == 1 and not self._graphs_on() and self.fold_launches)
         if not self._graphs_on() or ws.warm < 1:
             ws.warm += 1
             self._upd_part1(ws, soft)
@@ -817,42 +569,14 @@ class SAC_CBF_CLF(object):
             # hipGraph replay: part 1 up to the dopri5 accept decision, one 256-byte read, part 2
             g = ws.graphs
             k1, k2 = ("p1", soft, self.solver, NP), ("p2", lam_upd, ws.blam_upd, self.solver, NP)
-            self._replay(self._graph(g, k1, lambda: self._upd_part1(ws, soft)))
+            g.replay(k1, lambda: self._upd_part1(ws, soft))
             if self.solver == "dopri5" and not self.task.first_step_done():
                 self._upd_part2(ws, lam_upd, False)          # rare: finish eagerly
             else:
-                self._replay(self._graph(g, k2, lambda: self._upd_part2(ws, lam_upd, True)))
-        return self._returns(sync)
-
-    def _returns(self, sync):
-        """The reference's 6 floats.  ``sync``: True — of this update (the host waits for it, as the reference's
-        ``.item()`` calls do); "lagged" — of the previous ``"lagged"`` call (None on the first), while this update's
-        are on their way to pinned memory: the launch stream never drains, for drivers that only log the values;
-        False — nothing."""
-        if not sync:
+                g.replay(k2, lambda: self._upd_part2(ws, lam_upd, True))
+        h = self._readback.returns(sync)      # (sync False, or the first "lagged" call: None)
+        if h is None:
             return None
-        mirrored = self.__dict__.get("_mirror_done")      # (buffer index the last optimiser step wrote to, or None)
-        self._mirror_done = None
-        if sync == "lagged":
-            if mirrored is not None:
-                k = mirrored
-            else:
-                self._sc_pins()
-                k = 1 + (self.__dict__.get("_sc_flip", 0) & 1)
-                self._sc_flip = k
-                self._sc_pin[k].copy_(self.sc, non_blocking=True)
-            prev, self._sc_lag = self._sc_lag, k
-            if mirrored is None:
-                self._sc_ev[k].record()
-            if prev is None:
-                return None
-            self._sc_ev[prev].synchronize()
-            h = self._sc_pin[prev].numpy().copy()
-        elif mirrored is not None:
-            self._sc_ev[mirrored].synchronize()
-            h = self._sc_pin[mirrored].numpy().copy()
-        else:
-            h = self._scalars()
         alpha_loss = float(h[SC.SC_ALOSS]) if self.automatic_entropy_tuning else 0.0
         return (float(h[SC.SC_QF1]), float(h[SC.SC_QF2]), float(h[SC.SC_LF]), float(h[SC.SC_PL1]),
                 alpha_loss, float(h[SC.SC_ALPHA]))
@@ -867,7 +591,7 @@ class SAC_CBF_CLF(object):
         LD = P.LD
 
         # ---- A. targets (no grad): pi(s'), Q_target(s', a'), L_target(c') ; critic / Lyapunov forward
-        if ws.__dict__.get("_pre_now") is None:       # (else: queued behind the previous update's last launch, see prefetch)
+        if ws._pre_now is None:       # (else: queued behind the previous update's last launch, see prefetch)
             self._policy_forward(ws, P, NP)
         # the rollout of the learned dynamics needs only pi(s) and the NODE: its first attempted step goes in here,
         # so that the critic phase below is queued behind it while the host waits for the accept decision
@@ -882,7 +606,7 @@ class SAC_CBF_CLF(object):
         # how many pieces the first wait pulls: a rollout of ONE adaptive solve gets them all at once (the host needs
         # ~100 us of queued work to read the decision and come back); chained solves (SimulatedCars 2, Pvtol 3) one per wait
         self._fill_first = self.task.rollout_waits == 1
-        if ws.__dict__.get("_pre_now") is not None and ws._pre_now[2]:
+        if ws._pre_now is not None and ws._pre_now[2]:
             self._fill.popleft()                # (targets + critic data backward: queued with the prefetch)
             # (the first wait still queues both remaining pieces: holding the Q(s, pi) forward back for the launch it
             #  could share with V(p(x')) left the stream dry for ~20 us while the host got from the accept decision to
@@ -898,7 +622,7 @@ class SAC_CBF_CLF(object):
         pol = self.policy
         p_scale, p_bias = pol.action_scale.data_ptr(), pol.action_bias.data_ptr()
         if self.fold_launches:      # (the samples are drawn by the policy launch itself: nlbac_gauss_head)
-            gh = P.__dict__.get("head_pol3")
+            gh = P.head_pol3
             if gh is None:
                 gh = P.head_pol3 = _lib.GaussHead()
                 gh.eps, gh.scale, gh.bias, gh.n_u = ws.eps.data_ptr(), p_scale, p_bias, A
@@ -911,10 +635,10 @@ class SAC_CBF_CLF(object):
 
     def _prefetch_next(self, ws, updates):
         """Behind this update's last launch: the next update's minibatch draw and first launches (update_on_device)."""
-        fn = ws.__dict__.get("_prefetch_fn")
+        fn = ws._prefetch_fn
         if fn is None or self._graphs_on() or self.world != 1 or self._noise is not None:
             return
-        if ws._sync and self.__dict__.get("_mirror") is None:
+        if ws._sync and self._readback.mirror is None:
             return      # (the returned floats would be copied BEHIND the queued launches, whose dy head rewrites the losses)
         fn()
         NP = self.task.n_pol_now(updates + 1)
@@ -948,7 +672,7 @@ class SAC_CBF_CLF(object):
         """Called by a solver just before it waits for an accept decision: queue the next piece(s) of part 1 behind the
         attempted step.  The first wait of an update gets two (the host needs ~100 us of queued work to read the
         decision and launch what follows without the stream running dry), later ones one each."""
-        k, self._fill_first = (2 if self.__dict__.get("_fill_first", True) else 1), False
+        k, self._fill_first = (2 if self._fill_first else 1), False
         while k and self._fill:
             self._fill.popleft()()
             k -= 1
@@ -965,7 +689,7 @@ class SAC_CBF_CLF(object):
         if one and len(self.h_extra) <= 1 and self.fold_launches:
             # single GPU, no extra critic: targets, dL/dq and the three losses are produced by the critics' data backward
             # itself (nlbac_dy_head kind 2) — no launch between the six-net forward and the backward
-            H = P.__dict__.get("head_td")
+            H = P.head_td
             if H is None:
                 H = P.head_td = _lib.DyHead()
                 H.kind, H.B_norm = 2, G
@@ -1018,7 +742,7 @@ class SAC_CBF_CLF(object):
             return               # (the branch terms and their sums come out of the Q(s, pi) data backward: _actor_q_head)
         fused = None
         if self.world == 1:      # policy_loss_1 / alpha losses / d log_alpha by the launch's last workgroup (nlbac_actor_scalars)
-            fused = P.__dict__.get("actor_scalars")
+            fused = P.actor_scalars
             if fused is None:
                 fused = P.actor_scalars = _lib.ActorScalarArgs()
                 fused.target_entropy, fused.sc = self.target_entropy, sc
@@ -1032,7 +756,7 @@ class SAC_CBF_CLF(object):
              C.byref(fused) if fused is not None else None, self._tickets.data_ptr() + 4 * 8 if fused is not None else None, s)
 
     def _actor_q_head(self, ws, P, NP, G):
-        H = P.__dict__.get("head_actor_q")
+        H = P.head_actor_q
         if H is None:
             sc = self.sc.data_ptr()
             H = P.head_actor_q = _lib.DyHead()
@@ -1056,10 +780,7 @@ class SAC_CBF_CLF(object):
         by an election at the end of their own launches (nlbac_dy_head::sums_defer / finish): single GPU with the launch
         folds (the heads exist and the actors' backward follows them in every update).  ``sums_defer = False``
         (NLBAC_SUMS_DEFER=0): the elections."""
-        on = self.__dict__.get("sums_defer")
-        if on is None:
-            on = self.sums_defer = os.environ.get("NLBAC_SUMS_DEFER", "1") != "0"
-        return bool(on and self.world == 1 and self.fold_launches)
+        return bool(self.sums_defer and self.world == 1 and self.fold_launches)
 
     def _upd_part2(self, ws, lam_upd, assume_single):
         """Constraints, augmented-Lagrangian scalars, the whole actor backward and the actor Adam step."""
@@ -1090,7 +811,7 @@ class SAC_CBF_CLF(object):
                  NP * B, B, ws.dxq[0].data_ptr() + 4 * Do, D, ws.dxq[1].data_ptr() + 4 * Do, D, du2.data_ptr(), du_ld,
                  sc + 4 * SC.SC_ALPHA, 1.0 / G, ws.dheads2.data_ptr(), 2 * A, s)
             call("nlbac_mlp_bwd_data", P.n_act, P.io_act, NP, B, s)
-        H = P.__dict__.get("head_gauss") if self.fold_launches else False
+        H = P.head_gauss if self.fold_launches else False
         if H is None:
             H = P.head_gauss = _lib.DyHead()
             H.kind, H.B_norm = 1, G
@@ -1102,7 +823,7 @@ class SAC_CBF_CLF(object):
             # the sums the td head and the actor-q head of this update left as tile partials (sums_defer): two workgroups
             # of this launch finish them — before the Adam step that reads d log_alpha and mirrors the losses
             J = 0
-            for src in (P.__dict__.get("head_td"), P.__dict__.get("head_actor_q")):
+            for src in (P.head_td, P.head_actor_q):
                 if src is None or not src.sums_defer:
                     continue
                 F = H.finish[J]
@@ -1116,7 +837,7 @@ class SAC_CBF_CLF(object):
         if H is not False:
             # (per call: the step's lambda-update flags change from update to update) the augmented-Lagrangian step a
             # constraint head deferred (tasks.py: cf_job) is committed by this launch
-            job = P.__dict__.get("cf_job")
+            job = P.cf_job
             F = H.finish[2]
             F.kind = 4 if job else 0
             if job:
@@ -1146,11 +867,10 @@ class SAC_CBF_CLF(object):
             refresh = ([g.la_off + k * g.la_stride for k in range(cnt)],
                        [sc + 4 * (SC.SC_ALPHA + g.first + k) for k in range(cnt)]) if tune else None
             last = g is P.act_groups[-1][0]
-            mir = self.__dict__.get("_mirror") if last else None
+            mir = self._readback.mirror if last else None
             self._adam(a, self.lr, a.n_slabs, before_step=alpha_grads, alpha=refresh, mirror=mir[1] if mir else None)
             if mir:
-                self._mirror_done = mir[0]
-                self._sc_ev[mir[0]].record()     # (here, not in _returns: what _prefetch_next queues is not waited for)
+                self._readback.mirrored(mir[0])
         self._prefetch_next(ws, ws.updates_now)
 
     # ------------------------------------------------------------ checkpoints

@@ -16,9 +16,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..arena import io_array, mlp_array, stream_ptr
+from ..arena import mlp_array, stream_ptr
 from ..odeint import AffineNodeSolver, ConcatNodeSolver
-from . import _layout as SC
 from .model import NeuralODEModel
 
 
@@ -39,6 +38,8 @@ class _Task:
 
     def __init__(self, agent, env, args):
         self.agent, self.env = agent, env
+        self._reserved = set()      # (solver, rows, problems, method) whose buffers ``reserve`` has pre-allocated
+        self._cf_ok = None          # nlbac_mlp_fwd_head_ok of the V(p(x')) launch, asked once (UnicycleTask)
 
     def z(self, *shape):
         return torch.zeros(*shape, dtype=torch.float32, device=self.agent.device)
@@ -49,9 +50,8 @@ class _Task:
             solver.interp_fold = False        # (NLBAC_FOLD=0: the interpolation launches too, as every other folded step)
             solver.norm_defer = False         # ... and the norms with their elections / as a launch over the error rows
         key = (id(solver), n, P, self.agent.solver)
-        seen = self.__dict__.setdefault("_reserved", set())
-        if key not in seen:
-            seen.add(key)
+        if key not in self._reserved:
+            self._reserved.add(key)
             solver.reserve(n, P, self.agent.solver)
 
     def policy_sample(self, ws, key, nets, io, n_nets, B, heads, eps, n_u, action, action_ld, logp):
@@ -65,10 +65,9 @@ class _Task:
             _lib.call("nlbac_gauss_sample_fwd", heads.data_ptr(), 2 * n_u, eps.data_ptr(), p_scale, p_bias, n_u, n_nets * B,
                       action.data_ptr(), action_ld, logp.data_ptr(), s)
             return
-        hs = ws.__dict__.setdefault("_gauss_heads", {})
-        gh = hs.get(key)
+        gh = ws._gauss_heads.get(key)
         if gh is None:
-            gh = hs[key] = _lib.GaussHead()
+            gh = ws._gauss_heads[key] = _lib.GaussHead()
             gh.eps, gh.scale, gh.bias, gh.n_u = eps.data_ptr(), p_scale, p_bias, n_u
             gh.action, gh.action_ld, gh.logp = action.data_ptr(), action_ld, logp.data_ptr()
         _lib.call("nlbac_mlp_fwd_gauss", nets, io, n_nets, B, C.byref(gh), s)
@@ -135,14 +134,15 @@ class UnicycleTask(_Task):
 
     def plan(self, ws, P):
         a, lay = self.agent, self.agent.lay
+        P.cf_head = P.head_actor_q_cb = None       # launch arguments built on first use (loss_and_backward)
         P.n_l = mlp_array([a.h_l.desc])
-        io = P.io_vn = io_array(1)                 # V(p(x')) forward + data backward
+        io = P.io_vn = P.io(1)                     # V(p(x')) forward + data backward
         io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.ps_next2.data_ptr(), 2, 2
         io[0].y, io[0].y_ld = ws.Vn.data_ptr(), 1
         io[0].acts = ws.acts_vn.data_ptr()
         io[0].dy, io[0].dy_ld = ws.dVn.data_ptr(), 1
         io[0].dx, io[0].dx_ld = ws.dps_v2.data_ptr(), 2
-        P.io_vc = io_array(1)                      # V(centre), value only
+        P.io_vc = P.io(1)                          # V(centre), value only
         P.io_vc[0].x0, P.io_vc[0].x0_dim, P.io_vc[0].x0_ld = ws.mb.data_ptr() + 4 * lay.lya, 2, lay.LD
         P.io_vc[0].y, P.io_vc[0].y_ld = ws.V.data_ptr(), 1
         # the data backward of V(p(x')) and of the Q(s, pi) nets do not depend on each other and are both due when the
@@ -150,7 +150,7 @@ class UnicycleTask(_Task):
         # 128-tile launch on 256 CUs followed by a second one
         n2 = 2 * P.NP
         P.n_q5v = mlp_array([a.h_q1.desc, a.h_q2.desc] * P.NP + [a.h_l.desc])
-        P.io_q5v = io_array(n2 + 1)
+        P.io_q5v = P.io(n2 + 1)
         for i in range(n2):
             C.memmove(C.byref(P.io_q5v, i * C.sizeof(_lib.MlpIO)), C.byref(P.io_q5, i * C.sizeof(_lib.MlpIO)), C.sizeof(_lib.MlpIO))
         C.memmove(C.byref(P.io_q5v, n2 * C.sizeof(_lib.MlpIO)), C.byref(P.io_vn, 0), C.sizeof(_lib.MlpIO))
@@ -158,7 +158,7 @@ class UnicycleTask(_Task):
         # rollout — when that piece is still pending at that point, both go out as one launch
         nq = P.n_q5_count
         P.n_q5f = mlp_array([a.h_q1.desc, a.h_q2.desc] * P.NP + [a.h_l.desc] * (nq - n2) + [a.h_l.desc])
-        P.io_q5f = io_array(nq + 1)
+        P.io_q5f = P.io(nq + 1)
         for i in range(nq):
             C.memmove(C.byref(P.io_q5f, i * C.sizeof(_lib.MlpIO)), C.byref(P.io_q5, i * C.sizeof(_lib.MlpIO)), C.sizeof(_lib.MlpIO))
         C.memmove(C.byref(P.io_q5f, nq * C.sizeof(_lib.MlpIO)), C.byref(P.io_vn, 0), C.sizeof(_lib.MlpIO))
@@ -212,7 +212,7 @@ class UnicycleTask(_Task):
             # the constraint terms, their column sums and the augmented-Lagrangian step are the epilogue of V(p(x'))'s
             # workgroups in this launch (nlbac_gauss_head::cf_kind 1): no nlbac_unicycle_constraints_fwd launch
             A = a.auglag_fused(ws, self.num_cbfs, lam_upd)[0]._obj
-            G = P.__dict__.get("cf_head")       # (built once per plan: ~40 ctypes field stores sit between the accept
+            G = P.cf_head                       # (built once per plan: ~40 ctypes field stores sit between the accept
             if G is None:                       #  decision and this launch; only the lambda-update flags change per update)
                 G = P.cf_head = _lib.GaussHead()
                 G.cf_kind, G.cf_net, G.cf_nh = 1, cnt - 1, self.num_cbfs
@@ -244,14 +244,14 @@ class UnicycleTask(_Task):
             # of both controllers from the CBF terms, dV_next from the CLF term) is the prologue of V's workgroups in that
             # launch (nlbac_dy_head::cb_kind 1): no nlbac_unicycle_constraints_bwd launch
             NP = ws.np_now
-            H = P.__dict__.get("head_actor_q_cb")
+            H = P.head_actor_q_cb
             if H is None:
                 H = P.head_actor_q_cb = _lib.DyHead.from_buffer_copy(a._actor_q_head(ws, P, NP, B * a.world))
                 H.cb_kind, H.cb_nh = 1, self.num_cbfs
                 H.cb_ps_next, H.cb_matr, H.cb_bmatr = ws.ps_next2.data_ptr(), ws.matr.data_ptr(), ws.bmatr.data_ptr()
                 H.cb_hazards, H.cb_sc, H.cb_dt, H.cb_batch = self.hazards.data_ptr(), sc, dt, float(a.batch_size)
                 H.cb_dps_next, H.cb_dV = ws.dps_next2.data_ptr(), ws.dVn.data_ptr()
-            job = P.__dict__.get("cf_job") if use_head else None
+            job = P.cf_job if use_head else None
             H.cb_defer = 1 if job else 0
             if job:
                 H.cb_partials, H.cb_tiles, H.cb_stage = job[0], job[1], job[4]
@@ -277,10 +277,9 @@ class UnicycleTask(_Task):
         a = self.agent
         if not (a.world == 1 and a.fold_launches and ws.np_now == 2 and self.num_cbfs == 7):
             return False
-        ok = self.__dict__.get("_cf_ok")
-        if ok is None:
-            ok = self._cf_ok = bool(_lib.load().nlbac_mlp_fwd_head_ok(nets, cnt))
-        return ok
+        if self._cf_ok is None:
+            self._cf_ok = bool(_lib.load().nlbac_mlp_fwd_head_ok(nets, cnt))
+        return self._cf_ok
 
     def first_step_done(self):
         return self.solver.first_step_done()
@@ -347,18 +346,18 @@ class UnicycleBarrierTask(UnicycleTask):
     def plan(self, ws, P):
         a = self.agent
         P.n_l = mlp_array([a.h_l.desc])
-        io = P.io_vn = io_array(1)                     # V(p(x')) forward + data backward
+        io = P.io_vn = P.io(1)                         # V(p(x')) forward + data backward
         io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.ps_next.data_ptr(), 2, 2
         io[0].y, io[0].y_ld = ws.Vn.data_ptr(), 1
         io[0].acts = ws.acts_vn.data_ptr()
         io[0].dy, io[0].dy_ld = ws.dVn.data_ptr(), 1
         io[0].dx, io[0].dx_ld = ws.dps_v.data_ptr(), 2
         P.n_pi = mlp_array([a.h_p.desc])
-        io = P.io_nx = io_array(1)                     # policy on the predicted next observation
+        io = P.io_nx = P.io(1)                         # policy on the predicted next observation
         io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.obs_pred.data_ptr(), 7, 7
         io[0].y, io[0].y_ld = ws.heads_nx.data_ptr(), 4
         P.n_bar = mlp_array([a.h_extra[0].desc])
-        io = P.io_bn = io_array(1)                     # B(obs', a') forward + data backward
+        io = P.io_bn = P.io(1)                         # B(obs', a') forward + data backward
         io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.obs_pred.data_ptr(), 7, 7
         io[0].x1, io[0].x1_dim, io[0].x1_ld = ws.pi_next.data_ptr(), 2, 2
         io[0].y, io[0].y_ld = ws.Bn.data_ptr(), 1
@@ -450,13 +449,13 @@ class CarsTask(_Task):
     def plan(self, ws, P):
         a, B = self.agent, ws.B
         P.n_l = mlp_array([a.h_l.desc])
-        io = P.io_v1 = io_array(1)                 # V(x_t+1[4:8]) forward + data backward
+        io = P.io_v1 = P.io(1)                     # V(x_t+1[4:8]) forward + data backward
         io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.x1_2.data_ptr() + 4 * 4, 4, 10
         io[0].y, io[0].y_ld = ws.V1.data_ptr(), 1
         io[0].acts = ws.acts_v1.data_ptr()
         io[0].dy, io[0].dy_ld = ws.dV1.data_ptr(), 1
         io[0].dx, io[0].dx_ld = ws.dlya.data_ptr(), 4
-        io = P.io_nx = io_array(2)                 # both policies on the predicted next observation
+        io = P.io_nx = P.io(2)                     # both policies on the predicted next observation
         for i in range(2):
             io[i].x0, io[i].x0_dim, io[i].x0_ld = ws.obs1_2[i * B:].data_ptr(), 10, 10
             io[i].y, io[i].y_ld = ws.heads_nx[i * B:].data_ptr(), 2
@@ -597,7 +596,7 @@ class PvtolTask(_Task):
     def plan(self, ws, P):
         a, B, NP = self.agent, ws.B, P.NP
         P.n_l = mlp_array([a.h_l.desc])
-        io = P.io_v1 = io_array(1)                 # V(obs(x_t+1)) forward + data backward
+        io = P.io_v1 = P.io(1)                     # V(obs(x_t+1)) forward + data backward
         io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.obs1.data_ptr(), 11, 11
         io[0].y, io[0].y_ld = ws.V1.data_ptr(), 1
         io[0].acts = ws.acts_v1.data_ptr()
@@ -606,7 +605,7 @@ class PvtolTask(_Task):
         P.n_pols = mlp_array([h.desc for h in a.h_pols[:NP]])
         P.io_nx = []
         for obs, heads in ((ws.obs1, ws.heads_n1), (ws.obs2, ws.heads_n2)):
-            io = io_array(NP)                      # each controller on its own rows of the predicted observation
+            io = P.io(NP)                          # each controller on its own rows of the predicted observation
             for i in range(NP):
                 io[i].x0, io[i].x0_dim, io[i].x0_ld = obs[i * B:].data_ptr(), 11, 11
                 io[i].y, io[i].y_ld = heads[i * B:].data_ptr(), 4
@@ -748,18 +747,18 @@ class PvtolBarrierTask(PvtolTask):
     def plan(self, ws, P):
         a = self.agent
         P.n_l = mlp_array([a.h_l.desc])
-        io = P.io_v1 = io_array(1)                     # V(obs(x')) forward + data backward
+        io = P.io_v1 = P.io(1)                         # V(obs(x')) forward + data backward
         io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.obs_pred.data_ptr(), 11, 11
         io[0].y, io[0].y_ld = ws.V1.data_ptr(), 1
         io[0].acts = ws.acts_v1.data_ptr()
         io[0].dy, io[0].dy_ld = ws.dV1.data_ptr(), 1
         io[0].dx, io[0].dx_ld = ws.dobs1.data_ptr(), 11
         P.n_pi = mlp_array([a.h_p.desc])
-        io = P.io_nx = io_array(1)                     # policy on the predicted next observation
+        io = P.io_nx = P.io(1)                         # policy on the predicted next observation
         io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.obs_pred.data_ptr(), 11, 11
         io[0].y, io[0].y_ld = ws.heads_nx.data_ptr(), 4
         P.n_bar = mlp_array([a.h_extra[0].desc])
-        io = P.io_bn = io_array(1)                     # B(obs', a') forward + data backward
+        io = P.io_bn = P.io(1)                         # B(obs', a') forward + data backward
         io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.obs_pred.data_ptr(), 11, 11
         io[0].x1, io[0].x1_dim, io[0].x1_ld = ws.pi_next.data_ptr(), 2, 2
         io[0].y, io[0].y_ld = ws.Bn.data_ptr(), 1
@@ -846,18 +845,18 @@ class QuadrotorBarrierTask(PvtolBarrierTask):
     def plan(self, ws, P):
         a = self.agent
         P.n_l = mlp_array([a.h_l.desc])
-        io = P.io_v1 = io_array(1)                     # V(obs') forward + data backward, d obs' lands in dx_next
+        io = P.io_v1 = P.io(1)                         # V(obs') forward + data backward, d obs' lands in dx_next
         io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.obs_pred.data_ptr(), 6, 6
         io[0].y, io[0].y_ld = ws.V1.data_ptr(), 1
         io[0].acts = ws.acts_v1.data_ptr()
         io[0].dy, io[0].dy_ld = ws.dV1.data_ptr(), 1
         io[0].dx, io[0].dx_ld = ws.dx_next.data_ptr(), 6
         P.n_pi = mlp_array([a.h_p.desc])
-        io = P.io_nx = io_array(1)                     # policy on the predicted next observation
+        io = P.io_nx = P.io(1)                         # policy on the predicted next observation
         io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.obs_pred.data_ptr(), 6, 6
         io[0].y, io[0].y_ld = ws.heads_nx.data_ptr(), 4
         P.n_bar = mlp_array([a.h_extra[0].desc])
-        io = P.io_bn = io_array(1)                     # B(obs', a') forward + data backward
+        io = P.io_bn = P.io(1)                         # B(obs', a') forward + data backward
         io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.obs_pred.data_ptr(), 6, 6
         io[0].x1, io[0].x1_dim, io[0].x1_ld = ws.pi_next.data_ptr(), 2, 2
         io[0].y, io[0].y_ld = ws.Bn.data_ptr(), 1

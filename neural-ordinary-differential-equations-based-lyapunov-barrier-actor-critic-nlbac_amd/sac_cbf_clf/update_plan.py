@@ -1,0 +1,263 @@
+"""What one update works on, built once per batch size: the minibatch row layout (``_Layout``), the device buffers
+and per-update host state (``_Workspace``), the ctypes launch descriptors (``Plan``) with the pass that trades saved
+activation rows for ReLU mask words (``keep_masks_drop_unpaired_acts``), and the captured hipGraphs (``GraphCache``).
+``SAC_CBF_CLF`` (sac_cbf_clf.py) and the tasks (tasks.py) fill and launch these; nothing here launches a kernel.
+"""
+import torch
+
+from .. import _lib
+from ..arena import io_array, mlp_array, skinny_partials_ws
+from . import _layout as SC
+
+
+class _Layout:
+    """Column offsets of one minibatch row in HBM: the fields of ``ReplayMemory.sample``
+    (replay_memory.py:24-25) side by side, row stride padded to 16 bytes."""
+
+    def __init__(self, task):
+        self.obs_dim, self.act_dim, self.lya_dim = task.obs_dim, task.act_dim, task.lya_dim
+        c = 0
+        fields = [("obs", task.obs_dim), ("act", task.act_dim), ("rew", 1), ("con", 1), ("lya", task.lya_dim),
+                  ("nlya", task.lya_dim), ("nobs", task.obs_dim), ("mask", 1), ("t", 1), ("nt", 1)]
+        if task.has_signal:          # learned-barrier copies store a barrier signal after the constraint
+            fields.insert(4, ("sig", 1))
+        self.sig = None
+        for name, w in fields:
+            setattr(self, name, c)
+            c += w
+        self.width = c
+        self.LD = (c + 3) // 4 * 4
+
+
+class _Workspace:
+    """Per-batch-size device buffers (allocated once, reused every update); the task adds its own."""
+
+    def __init__(self, B, H, dev, lay, task):
+        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+        A, Do = lay.act_dim, lay.obs_dim
+        NP, NX = task.n_pol, task.n_extra_critics      # controllers; critic-type nets beyond Q1, Q2, L
+        self.B = B
+        self.mb = z(B, lay.LD)                   # minibatch rows (see _Layout)
+        self.eps = z(task.n_eps, B, A)
+        # policy samples of one update live side by side: rows [0,B) pi(s'), then pi(s) (and pi_backup(s)), so that
+        # one forward launch and one sampling launch serve all of them
+        self.heads3, self.act3, self.logp3 = z((1 + NP) * B, 2 * A), z((1 + NP) * B, A), z((1 + NP) * B)
+        self.heads_n, self.na, self.nlogp = self.heads3[:B], self.act3[:B], self.logp3[:B]
+        self.q6 = z(6 + 2 * NX, B)               # q1t q2t lt q1 q2 lf [xt x]...
+        self.dq3 = z(3 + NX, B)
+        self.next_q, self.next_l = z(B), z(B)
+        self.acts_c = z(3 + NX, 2, B, H)         # Q1,Q2,L[,extras] saved activations
+        self.dz_c = z(3 + NX, 2, B, H)
+        self.nblk = (B + 255) // 256
+        self.part_td = z(self.nblk, 3)
+        self.n_tiles = (B + _lib.MLP_TILE_MIN - 1) // _lib.MLP_TILE_MIN
+        self.part_td32 = z(self.n_tiles, 4)            # per-tile sums of the fused dy heads (nlbac_dy_head; 16-row tiles at most)
+        # tickets of the heads' two-level elections: 1 + ceil(workgroups / 16) words each (TD head: <= 4 nets; actor head)
+        self.tickets_td = torch.zeros(2 + self.n_tiles * 4 // 16 + 1, dtype=torch.int32, device=dev)
+        self.tickets_q = torch.zeros(2 + self.n_tiles * NP // 16 + 1, dtype=torch.int32, device=dev)
+        self.sums_tiles = torch.zeros(4, dtype=torch.int32, device=dev)    # nlbac_dy_head::sums_tiles of the td / actor-q heads
+        self.sc_stage = z(SC.SC_SIZE)                                        # nlbac_dy_head::cb_stage
+        self.part_tdx = z(max(NX, 1), self.nblk)
+        self.heads2, self.pi2, self.logp2 = self.heads3[B:], self.act3[B:], self.logp3[B:]
+        self.acts_p = z(NP, 2, B, H)
+        self.dz_p = z(NP, 2, B, H)
+        self.plan = {}                           # controllers updated -> Plan (SAC_CBF_CLF._plan)
+        self.graphs, self.warm = GraphCache(task.solvers), 0
+        self.qpi = z(2, NP * B)
+        self.acts_q = z(2 * NP, 2, B, H)
+        self.dq_pi = z(2, NP * B)
+        self.part_q = z(NP, self.nblk, 2)
+        self.part_q32 = z(NP, self.n_tiles, 2)
+        self.dxq = z(2, NP * B, Do + A)
+        self.dheads2 = z(NP * B, 2 * A)
+        # --- host state of the update in flight (written by update_on_device and the pieces it runs) ---
+        self._prefetched = None      # (update index, NP, targets piece queued?) of a draw + launches already queued
+        self._pre_now = None         # ... the entry the current update consumed
+        self._prefetch_fn = None     # the caller's draw (update_on_device(prefetch=...))
+        self._sync = True            # the caller's ``sync``
+        self.np_now, self.updates_now, self.blam_upd = task.n_pol, 0, 0     # controllers updated, update index, backup lambda step due
+        self.q5_bwd_done = False     # the task ran the Q(s, pi) data backward inside one of its own launches
+        self.p_part_q, self.n_part_q = None, 0      # where the actor step reads the Q(s, pi) sums (data parallel: all-reduced)
+        self._auglag_args = None     # nlbac_auglag_args of the constraints launch (kept alive until the call is made)
+        self._mask_bufs = {}         # activation buffer address -> its ReLU mask words, shared by this workspace's plans
+        self._gauss_heads = {}       # key -> nlbac_gauss_head of a task's policy_sample launch
+        task.alloc(self)
+
+
+class GraphCache:
+    """Captured hipGraphs by key.  All kernel arguments of a recorded launch sequence are static device pointers /
+    constants (per-update scalars live in device memory).  A graph bakes in the addresses of the solvers' buffers and
+    belongs to the solves it recorded: its entry keeps the solvers' ``generation`` (any freed or re-laid-out buffer
+    invalidates it) and their solve contexts (restored before a replay, so that what the host does around the replay —
+    reading the control block, finishing a solve eagerly — talks about THIS graph's solve and not about whichever
+    batch size ran last)."""
+
+    def __init__(self, solvers):
+        self.solvers = solvers
+        self.entries = {}          # key -> (graph, solver generations, [(solver, ctx, row count)])
+
+    def __len__(self):
+        return len(self.entries)
+
+    def replay(self, key, fn):
+        """Replay the graph of ``key``; ``fn``'s launches are recorded first if there is none yet or the solvers'
+        buffers have moved since."""
+        gens = tuple(sv.generation for sv in self.solvers)
+        e = self.entries.get(key)
+        if e is None or e[1] != gens:
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                fn()
+            e = self.entries[key] = (g, tuple(sv.generation for sv in self.solvers),
+                                     [(sv, sv.ctx, sv._cur_n) for sv in self.solvers])
+        for sv, ctx, n in e[2]:
+            if ctx is not None:
+                sv.ctx, sv._cur_n = ctx, n
+        e[0].replay()
+
+
+def keep_masks_drop_unpaired_acts(io_arrays, bufs, alloc):
+    """Where the register-resident MLP kernels serve the heads, every forward that saves something for a backward
+    also leaves ReLU mask words (``nlbac_mlp_io::masks``, 64 B per row) and every data backward gates with them
+    instead of loading the activation rows (24 float4 per lane at the head of each tile's critical path).  Nets that
+    are only differentiated w.r.t. their inputs (Q(s, pi), V(p(x')), the barrier on predicted states: dx wanted, no
+    dz / weight gradients) then keep nothing else — their activation buffer is dropped from the descriptors: the
+    forward's 2 KB-per-row store burst goes.  Works on the finished launch descriptors of ALL of a plan's arrays: an
+    activation buffer that no descriptor pairs with a dz, grad or skinny_ws buffer is such a net's.  ``bufs``:
+    activation address -> mask buffer (anything with ``data_ptr()``), extended through ``alloc()``."""
+    rows = {e.acts for arr in io_arrays for e in arr if e.acts and (e.dz or e.grad or e.skinny_ws)}
+    for arr in io_arrays:
+        for e in arr:
+            if e.acts:
+                if e.acts not in bufs:
+                    bufs[e.acts] = alloc()
+                e.masks = bufs[e.acts].data_ptr()
+                if e.acts not in rows:
+                    e.acts = None
+
+
+class Plan:
+    """ctypes launch descriptors of one workspace: every pointer is static (arenas, workspace tensors), so they are
+    built once (per number of controllers updated: Pvtol trains its backup every 20th update); an update is then a
+    plain sequence of C calls.  Every ``nlbac_mlp_io`` array is made by ``io()``, which is how the mask pass finds
+    them all — wherever the plan keeps them.  The task's ``plan()`` adds its own fields as plain attributes."""
+
+    def __init__(self, agent, ws, NP):
+        self.io_arrays = []
+        # launch arguments that need the first update's state: built by the launch sites on first use
+        self.head_pol3 = self.head_td = self.head_actor_q = self.head_gauss = self.actor_scalars = None
+        # per update: the augmented-Lagrangian step a task's constraint head left for the update's last MLP launch
+        self.cf_job = None
+        B, lay, task = ws.B, agent.lay, agent.task
+        mb = ws.mb.data_ptr()
+        LD, Do, Da, Dl = lay.LD, lay.obs_dim, lay.act_dim, lay.lya_dim
+        col = lambda c: mb + 4 * c
+        lc, lnc = task.lya_train_cols(lay)       # inputs the Lyapunov critic is regressed on
+        p_obs, p_act, p_cen, p_ncen, p_nobs = col(lay.obs), col(lay.act), col(lc), col(lnc), col(lay.nobs)
+
+        def x(io, i, p0, d0, ld0, p1=None, d1=0, ld1=0):
+            io[i].x0, io[i].x0_dim, io[i].x0_ld = p0, d0, ld0
+            if p1 is not None:
+                io[i].x1, io[i].x1_dim, io[i].x1_ld = p1, d1, ld1
+        P = self
+        P.p_obs, P.p_rew, P.p_con, P.p_mask, P.LD = p_obs, col(lay.rew), col(lay.con), col(lay.mask), LD
+        q1, q2, l, pi = agent.h_q1, agent.h_q2, agent.h_l, agent.h_p
+        P.NP, NX = NP, len(agent.h_extra)
+        # A: pi(s')
+        P.n_pol, P.io_pol_next = mlp_array([pi.desc]), P.io(1)
+        x(P.io_pol_next, 0, p_nobs, Do, LD)
+        P.io_pol_next[0].y, P.io_pol_next[0].y_ld = ws.heads_n.data_ptr(), 2 * Da
+        # A: targets + critic / Lyapunov forward (6 nets)
+        descs = [q1.desc_target, q2.desc_target, l.desc_target, q1.desc, q2.desc, l.desc]
+        for h in agent.h_extra:
+            descs += [h.desc_target, h.desc]
+        P.n_six, P.n_six_count = mlp_array(descs), len(descs)
+        io = P.io_six = P.io(len(descs))
+        for i in range(len(descs)):
+            io[i].y, io[i].y_ld = ws.q6[i].data_ptr(), 1
+        for k in range(NX):            # extra critic-type nets on (s', a') [target] and (s, a)
+            x(io, 6 + 2 * k, p_nobs, Do, LD, ws.na.data_ptr(), Da, Da)
+            x(io, 7 + 2 * k, p_obs, Do, LD, p_act, Da, LD)
+            io[7 + 2 * k].acts = ws.acts_c[3 + k].data_ptr()
+        for i in (0, 1):
+            x(io, i, p_nobs, Do, LD, ws.na.data_ptr(), Da, Da)
+        x(io, 2, p_ncen, Dl, LD)
+        for i in (3, 4):
+            x(io, i, p_obs, Do, LD, p_act, Da, LD)
+            io[i].acts = ws.acts_c[i - 3].data_ptr()
+        x(io, 5, p_cen, Dl, LD)
+        io[5].acts = ws.acts_c[2].data_ptr()
+        # B: critic / Lyapunov backward
+        P.n_crit = mlp_array([h.desc for h in agent.h_crit])
+        io = P.io_crit = P.io(3 + NX)
+        for i in range(3 + NX):
+            io[i].dy, io[i].dy_ld = ws.dq3[i].data_ptr(), 1
+            io[i].acts, io[i].dz = ws.acts_c[i].data_ptr(), ws.dz_c[i].data_ptr()
+            io[i].grad = agent.ar_c.grad.data_ptr()
+        for i in [0, 1] + list(range(3, 3 + NX)):
+            x(io, i, p_obs, Do, LD, p_act, Da, LD)
+        x(io, 2, p_cen, Dl, LD)
+        # (its data backward leaves the skinny-gradient partial sums for the weight backward: one launch less)
+        P.sk_crit = skinny_partials_ws(P.n_crit, (io,), 3 + NX, B, agent.device)
+        # C: both actors (forward and backward share one descriptor)
+        def act_io(io, j, i):            # entry j of an io array describes controller i
+            x(io, j, p_obs, Do, LD)
+            io[j].y, io[j].y_ld = ws.heads2[i * B:].data_ptr(), 2 * Da
+            io[j].acts, io[j].dz = ws.acts_p[i].data_ptr(), ws.dz_p[i].data_ptr()
+            io[j].dy, io[j].dy_ld = ws.dheads2[i * B:].data_ptr(), 2 * Da
+            io[j].grad = agent.pol_arena[i].grad.data_ptr()
+        P.n_act = mlp_array([h.desc for h in agent.h_pols[:NP]])
+        io = P.io_act = P.io(NP)
+        for i in range(NP):
+            act_io(io, i, i)
+        P.n_pol3 = mlp_array([pi.desc] + [h.desc for h in agent.h_pols[:NP]])     # pi(s') + the actors on s
+        io3 = P.io_pol3 = P.io(1 + NP)
+        x(io3, 0, p_nobs, Do, LD)
+        io3[0].y, io3[0].y_ld = ws.heads_n.data_ptr(), 2 * Da
+        for i in range(NP):
+            act_io(io3, 1 + i, i)
+        P.act_groups = []                # per Adam group: the nets whose weight gradients land in its arena
+        for g in agent.actor_groups:
+            cnt = min(g.count, NP - g.first)
+            if cnt <= 0:
+                continue
+            gio = P.io(cnt)
+            for j in range(cnt):
+                act_io(gio, j, g.first + j)
+            nets_g = mlp_array([h.desc for h in agent.h_pols[g.first:g.first + cnt]])
+            # the actors' data backward (P.io_act) leaves this group's skinny-gradient partials for its weight backward
+            io_act_g = [P.io_act[g.first + j] for j in range(cnt)]       # (views into the array, not copies)
+            sk = skinny_partials_ws(nets_g, (gio, io_act_g), cnt, B, agent.device)
+            P.act_groups.append((g, cnt, nets_g, gio, sk))
+        # C: Q(s, pi) for primary / backup + V(current Lyapunov input)
+        extra = task.extra_value_nets()
+        P.n_q5 = mlp_array([q1.desc, q2.desc] * NP + [l.desc] + [h.desc for h in extra])
+        P.n_q5_count = 2 * NP + 1 + len(extra)
+        io = P.io_q5 = P.io(P.n_q5_count)
+        for i in range(2 * NP):
+            half = i // 2                                      # 0 primary, 1 backup
+            x(io, i, p_obs, Do, LD, ws.pi2[half * B:].data_ptr(), Da, Da)
+            io[i].y, io[i].y_ld = ws.qpi[i % 2, half * B:].data_ptr(), 1
+            io[i].acts = ws.acts_q[i].data_ptr()
+            io[i].dy, io[i].dy_ld = ws.dq_pi[i % 2, half * B:].data_ptr(), 1
+            io[i].dx, io[i].dx_ld = ws.dxq[i % 2, half * B:].data_ptr(), Do + Da
+            io[i].dx_first = Do                                # (only dQ / da is consumed)
+        task.value_now_io(ws, io, 2 * NP)
+        task.extra_value_io(ws, io, 2 * NP + 1)
+        task.plan(ws, P)
+        # mask words wherever the register-resident kernels serve the heads' launches (see the pass above).  The mask
+        # buffer is sized for what those kernels take: two hidden layers of at most 256 units (8 words per row and layer)
+        # (every net a descriptor of a plan names is one of these: Q1, Q2, L and the barrier net are ``h_crit`` — a task's
+        #  ``a.h_l`` / ``a.h_extra[0]`` are its members —, the controllers ``h_pols``)
+        nets = agent.h_crit + agent.h_pols
+        if agent.fold_launches and _lib.load().nlbac_mlp_masks_ok(mlp_array([h.desc for h in nets]), len(nets)):
+            assert all(h.n_layers == 3 and h.hid <= 256 for h in nets), "mask words: (2, B, 8) per net"
+            keep_masks_drop_unpaired_acts(P.io_arrays, ws._mask_bufs,
+                                          lambda: torch.zeros(2, B, 8, dtype=torch.int32, device=agent.device))
+
+    def io(self, n):
+        """A zeroed ``nlbac_mlp_io[n]`` that belongs to this plan."""
+        arr = io_array(n)
+        self.io_arrays.append(arr)
+        return arr

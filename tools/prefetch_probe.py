@@ -25,7 +25,7 @@ def run(prefetch, n=45, B=4096):
     for i in range(n):
         if prefetch:
             if i % 10 == 0:
-                if ws.__dict__.get("_prefetched") is None:
+                if ws._prefetched is None:
                     agent.update_prefetch(ws, i, draw)
                 agent.fit_node_rows(replay.sample_rows(Bn.NODE_FIT_ROWS, out=fit_rows))
             out.append(agent.update_on_device(ws, i, prefetch=draw))

@@ -601,6 +601,30 @@ int nlbac_node_rk_traj_bwd(const nlbac_mlp *f, const nlbac_mlp *g, const float *
                            const float *beta, const float *c_out, float h, const float *G, const float *acts_f,
                            long acts_f_ls, const float *acts_g, long acts_g_ls, int acts_bits, const float *dout,
                            float *dx0, float *du, float *dK, float *dG, float *dz_f, float *dz_g, nlbac_stream_t s);
+/* One-launch fixed-grid rollout of the single-net NODE dx/dt = net([x | c]) (euler: n_stages 1, rk4: 4, with that
+ * method's beta [n_stages][n_stages] and c_out [n_stages]): H intervals of step h, interval k integrating from out[k-1]
+ * (x0 for k = 0) with the carried columns c[k] — what H nlbac_concat_rk_fwd launches compute, bit for bit, in one launch
+ * (a wave carries its 16 rows through all H*n_stages stages: no inter-workgroup synchronisation).
+ * nlbac_concat_rk_traj_ok(net) is 1 exactly where nlbac_concat_rk_fwd runs on its register-resident kernels (four
+ * layers, hidden width 64 / 100 / 128, in_dim <= 15 with 1..4 carried columns), else 0: use the chained launches there.
+ * x0 [n][n_s], c [H][n][n_c], out [H][n][n_s] (the states after each interval); norm as in nlbac_concat_rk_fwd (or
+ * NULL).  What is kept, stage (k, st) at index k*n_stages + st of H*n_stages stages: acts NULL — nothing; acts_bits 1 —
+ * the three layers' ReLU mask words [layer][H*n_stages*n][4] uint32 (acts_ls = H*n_stages*n*4) and nothing else;
+ * acts_bits 0 — activation rows [layer][H*n_stages*n][hid] (acts_ls = H*n_stages*n*hid) and, in Xin
+ * [H*n_stages*n][in_dim] (or NULL), the rows layer 0 saw: [Y_st | c_k], normalised when norm is given. */
+int nlbac_concat_rk_traj_ok(const nlbac_mlp *net);
+int nlbac_concat_rk_traj_fwd(const nlbac_mlp *net, const float *x0, const float *c, int n, int H, int n_stages,
+                             const float *beta, const float *c_out, float h, float *out, float *Xin, float *acts,
+                             long acts_ls, int acts_bits, const float *norm, nlbac_stream_t s);
+/* Its backward, intervals H-1 .. 0 in one launch: dout [H+1][n][n_s] = dL/d(x0, out[0..H-1]) -> dx0 [n][n_s] and
+ * dc [H][n][n_c]; the gradient w.r.t. an interval's initial state is carried to the interval before it in the launch,
+ * added to dout in the order of the chained one-step backward (nlbac_rk_stage_bwd + nlbac_concat_rk_bwd).  dK and dz
+ * (together, or both NULL; not with acts_bits 1): every stage's gradient w.r.t. the net's own output — dL/dK, times
+ * out_sig under norm — as rows [H*n_stages*n][n_s], and the pre-activation grads [layer][H*n_stages*n][hid]: with Xin
+ * and acts the rows nlbac_mlp_bwd_weights takes as one batch of H*n_stages*n. */
+int nlbac_concat_rk_traj_bwd(const nlbac_mlp *net, int n, int H, int n_stages, const float *beta, const float *c_out,
+                             float h, const float *acts, long acts_ls, int acts_bits, const float *norm,
+                             const float *dout, float *dx0, float *dc, float *dK, float *dz, nlbac_stream_t s);
 /* The same one-launch RK step for the single-net NODE dx/dt = net([x | c]) with carried inputs c = (u, t)
  * (SimulatedCars, C/sac_cbf_clf/model.py:179-205; odeint call sites C/sac_cbf_clf/sac_cbf_clf.py:437,458,581,603,
  * C/model.py:245): n_s = net->out_dim state columns, n_c = net->in_dim - n_s carried columns (c: (rows, n_c)),

@@ -1,0 +1,135 @@
+// One-launch fixed-grid rollout of the single-net NODE  dx/dt = net([x | c])  (SimulatedCars, the Quadrotor-like task's
+// normalised form):  H intervals of euler / rk4 (3/8 rule) with new carried columns per interval, forward and backward,
+// on the register-resident layer chains.
+//
+// In the one-step kernels a wave owns its 16 rows for the whole launch and the stage loop has no barrier, so a
+// fixed-grid horizon is the same wave carrying the same rows through H x S stages: no grid-wide wait, no atomics, and
+// no barrier inside the interval loop either (the interval's result is written, and kept in LDS as the next interval's
+// y0, by the wave that owns the rows).  What the one-step launches pay H times is paid once per tile: the weight
+// stream's prime, layer 0's LDS fragments, the output layer's registers, the normaliser's constants.  Each interval is
+// the one-step kernel's step through the same code (concat_rr_body.h with TRAJ), so the results are those of H
+// one-step launches bit for bit.  dopri5 is not served: its step-size control is batch-wide (an RMS norm over all
+// rows), which would need grid-wide waits.
+//
+// Reference: the chained odeint calls of C/sac_cbf_clf/sac_cbf_clf.py:437-458 (odeint(model, [x_k | u_k | t_k],
+// [0, dt])[-1], one interval per call).
+#undef RR_TIMING          // (the ablation stamps belong to the one-step kernels)
+#include "concat_rr_body.h"
+
+struct ConcatRkTrajFwdLaunch {
+    ConcatRkLaunch L;
+    int H;
+};
+
+struct ConcatRkTrajBwdLaunch {
+    ConcatRkBwdLaunch L;
+    ConcatRkTrajBwd X;
+};
+
+template <int NB, int R, int BITS, int NW>
+__global__ __launch_bounds__(64 * NW) void concat_traj_fwd_kernel(const ConcatRkTrajFwdLaunch A) {
+    concat_rr_fwd_body<NB, R, BITS, NW, true>(A.L, A.H);
+}
+
+// (the mask-word instances of the two narrower shapes keep the one-step kernels' three waves per SIMD: the interval
+// loop's bookkeeping would otherwise push the allocator a few registers past 168)
+template <int NB, int R, int BITS, int NW>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((BITS == 1 && NB < 8) ? 3 : 2)))
+void concat_traj_bwd_kernel(const ConcatRkTrajBwdLaunch A) {
+    concat_rr_bwd_body<NB, R, BITS, NW, true>(A.L, &A.X);
+}
+
+extern "C" int nlbac_concat_rk_traj_ok(const nlbac_mlp* net) {
+    return (net && nlbac_concat_rr_eligible(net) && net->in_dim > net->out_dim && net->in_dim - net->out_dim <= CK_NC) ? 1 : 0;
+}
+
+static int ctraj_check(const nlbac_mlp* net, int n, int H, int n_stages, const float* beta, const float* c_out, float h,
+                       int acts_bits, const char* who) {
+    NLBAC_REQUIRE(net && beta && c_out, "%s: null pointer", who);
+    NLBAC_REQUIRE(nlbac_concat_rk_traj_ok(net), "%s: this net does not run on the trajectory kernels (nlbac_concat_rk_traj_ok)", who);
+    NLBAC_REQUIRE(n >= 1 && H >= 1 && (long)H * n_stages * n < (1L << 31), "%s: bad rows / intervals", who);
+    NLBAC_REQUIRE(n_stages >= 1 && n_stages <= CK_MAX_STAGES, "%s: bad stage count", who);
+    NLBAC_REQUIRE(h > 0.f, "%s: the step must be positive", who);
+    NLBAC_REQUIRE(acts_bits == 0 || acts_bits == 1, "%s: acts_bits is 0 or 1", who);
+    return 0;
+}
+
+extern "C" int nlbac_concat_rk_traj_fwd(const nlbac_mlp* net, const float* x0, const float* c, int n, int H,
+                                        int n_stages, const float* beta, const float* c_out, float h, float* out,
+                                        float* Xin, float* acts, long acts_ls, int acts_bits, const float* norm,
+                                        nlbac_stream_t s) {
+    if (ctraj_check(net, n, H, n_stages, beta, c_out, h, acts_bits, "nlbac_concat_rk_traj_fwd")) return -1;
+    NLBAC_REQUIRE(x0 && c && out, "nlbac_concat_rk_traj_fwd: null pointer");
+    NLBAC_REQUIRE(acts || acts_bits == 0, "nlbac_concat_rk_traj_fwd: acts_bits without acts");
+    NLBAC_REQUIRE(!Xin || (acts && acts_bits == 0), "nlbac_concat_rk_traj_fwd: Xin goes with the activation rows");
+    ConcatRkTrajFwdLaunch A;
+    memset(&A, 0, sizeof(A));
+    ConcatRkLaunch& L = A.L;
+    L.net = *net;
+    L.y0 = x0; L.c = c;
+    L.n = n; L.rpp = n; L.n_s = net->out_dim; L.n_c = net->in_dim - net->out_dim;
+    L.stage_begin = 0; L.stage_end = n_stages; L.S_total = n_stages;
+    for (int i = 0; i < n_stages; ++i) {
+        for (int j = 0; j < n_stages; ++j) L.beta[i][j] = beta[i * n_stages + j];
+        L.c_out[i] = c_out[i];
+    }
+    L.n_out = n_stages;
+    L.h_val[0] = h;
+    L.acts = acts; L.acts_ls = acts_ls; L.acts_bits = acts_bits;
+    L.out = out;
+    L.norm = norm; L.Xn = Xin;
+    L.norm_mode = -1;
+    A.H = H;
+    using KernelF = void (*)(const ConcatRkTrajFwdLaunch);
+    // the one-step launcher's choice of instance (nlbac_concat_rr_fwd_launch), so that the sums are the same
+    static const KernelF kf[2][3][2] = {{{concat_traj_fwd_kernel<4, 4, 0, 2>, concat_traj_fwd_kernel<4, 4, 1, 2>},
+                                         {concat_traj_fwd_kernel<7, 1, 0, 2>, concat_traj_fwd_kernel<7, 1, 1, 2>},
+                                         {concat_traj_fwd_kernel<8, 4, 0, 2>, concat_traj_fwd_kernel<8, 4, 1, 2>}},
+                                        {{concat_traj_fwd_kernel<4, 4, 0, 4>, concat_traj_fwd_kernel<4, 4, 1, 4>},
+                                         {concat_traj_fwd_kernel<7, 1, 0, 4>, concat_traj_fwd_kernel<7, 1, 1, 4>},
+                                         {concat_traj_fwd_kernel<8, 4, 0, 4>, concat_traj_fwd_kernel<8, 4, 1, 4>}}};
+    const int nw = crr_waves(n, n), tile = 16 * nw;
+    hipLaunchKernelGGL(kf[nw == 4][crr_shape_index(net->hid)][acts_bits ? 1 : 0], dim3(nlbac_ceil_div(n, tile)),
+                       dim3(64 * nw), crr_fwd_lds(tile), (hipStream_t)s, A);
+    NLBAC_CHECK_LAUNCH("nlbac_concat_rk_traj_fwd");
+    return 0;
+}
+
+extern "C" int nlbac_concat_rk_traj_bwd(const nlbac_mlp* net, int n, int H, int n_stages, const float* beta,
+                                        const float* c_out, float h, const float* acts, long acts_ls, int acts_bits,
+                                        const float* norm, const float* dout, float* dx0, float* dc, float* dK,
+                                        float* dz, nlbac_stream_t s) {
+    if (ctraj_check(net, n, H, n_stages, beta, c_out, h, acts_bits, "nlbac_concat_rk_traj_bwd")) return -1;
+    NLBAC_REQUIRE(!(acts_bits == 1 && dz), "nlbac_concat_rk_traj_bwd: weight gradients need the activation rows, not mask words");
+    NLBAC_REQUIRE(acts && dout && dx0 && dc, "nlbac_concat_rk_traj_bwd: null pointer");
+    NLBAC_REQUIRE((dz == nullptr) == (dK == nullptr), "nlbac_concat_rk_traj_bwd: dz and dK go together");
+    ConcatRkTrajBwdLaunch A;
+    memset(&A, 0, sizeof(A));
+    ConcatRkBwdLaunch& L = A.L;
+    L.net = *net;
+    L.acts = acts; L.acts_ls = acts_ls; L.acts_bits = acts_bits;
+    L.dz = dz; L.dyn = dK;
+    L.dc = dc;
+    L.n = n; L.rpp = n; L.n_s = net->out_dim; L.n_c = net->in_dim - net->out_dim;
+    L.S_total = n_stages; L.st_lo = 0; L.st_hi = n_stages; L.dx_stage0 = 1;
+    for (int i = 0; i < n_stages; ++i)
+        for (int j = 0; j < n_stages; ++j) L.beta[i][j] = beta[i * n_stages + j];
+    L.h_val[0] = h;
+    L.norm = norm;
+    A.X.H = H; A.X.dout = dout; A.X.dx0 = dx0;
+    for (int j = 0; j < n_stages; ++j) A.X.c_out[j] = c_out[j];
+    A.X.n_out = n_stages;
+    using KernelB = void (*)(const ConcatRkTrajBwdLaunch);
+    // the one-step launcher's choice of instance (nlbac_concat_rr_bwd_launch)
+    static const KernelB kb[2][3][2] = {{{concat_traj_bwd_kernel<4, 4, 0, 2>, concat_traj_bwd_kernel<4, 4, 1, 2>},
+                                         {concat_traj_bwd_kernel<7, 1, 0, 2>, concat_traj_bwd_kernel<7, 1, 1, 2>},
+                                         {concat_traj_bwd_kernel<8, 4, 0, 2>, concat_traj_bwd_kernel<8, 4, 1, 2>}},
+                                        {{concat_traj_bwd_kernel<4, 4, 0, 4>, concat_traj_bwd_kernel<4, 4, 1, 4>},
+                                         {concat_traj_bwd_kernel<7, 1, 0, 4>, concat_traj_bwd_kernel<7, 1, 1, 4>},
+                                         {concat_traj_bwd_kernel<8, 4, 0, 4>, concat_traj_bwd_kernel<8, 4, 1, 4>}}};
+    const int nw = crr_waves(n, n), tile = 16 * nw;
+    hipLaunchKernelGGL(kb[nw == 4][crr_shape_index(net->hid)][acts_bits ? 1 : 0], dim3(nlbac_ceil_div(n, tile)),
+                       dim3(64 * nw), crr_bwd_lds(tile), (hipStream_t)s, A);
+    NLBAC_CHECK_LAUNCH("nlbac_concat_rk_traj_bwd");
+    return 0;
+}

@@ -1057,6 +1057,7 @@ class ConcatNodeSolver(ConcatAdjoint, AffineNodeSolver):
         io = ws.io_fwd.get(st)
         if io is None:
             io = ws.io_fwd[st] = self._eval_io(ws.Y[st], ws.K[st], u, ws.acts[:, st * n:], S * n * self.net.hid)
+        io[0].x1 = u.data_ptr()      # (the cached descriptor outlives a solve; the carried inputs are the caller's tensor)
         self._eval(ws.Y[st], u, n, ws.K[st], None, io)
 
     def _stage_backward(self, ws, st, need_dx, need_params, du, up, coef, h_host, h_dev, h_stride):

@@ -3,11 +3,12 @@ the chain of one-interval solves the reference builds its constraints from (C/sa
 P/sac_cbf_clf/sac_cbf_clf.py:459-534: ``odeint(model, [x_k | u_k (| t_k)], [0, dt])[-1]`` per interval).
 
 Two paths, same results:
-  * one launch (the control-affine NODE at the register-resident kernels' shapes, euler / rk4): the whole horizon is
-    one ``nlbac_node_rk_traj_fwd`` launch, its backward one ``nlbac_node_rk_traj_bwd`` launch (+ the weight-gradient
-    launch over all H * stages * rows when parameter gradients are wanted);
-  * chained (dopri5, the single-net NODE, other widths): H single-interval solves on the existing solvers, one solver
-    per interval, cached on the model apart from ``odeint``'s and the agent's.
+  * one launch (either NODE form at its register-resident kernels' shapes, euler / rk4): the whole horizon is one
+    ``nlbac_node_rk_traj_fwd`` launch (control-affine NODE) or one ``nlbac_concat_rk_traj_fwd`` launch (single-net
+    NODE, normalised or not), its backward one ``nlbac_node_rk_traj_bwd`` / ``nlbac_concat_rk_traj_bwd`` launch (+ the
+    weight-gradient launch over all H * stages * rows when parameter gradients are wanted);
+  * chained (dopri5, nets wider than 128, shapes the register-resident kernels refuse): H single-interval solves on
+    the existing solvers, one solver per interval, cached on the model apart from ``odeint``'s and the agent's.
 ``ONE_LAUNCH = False`` (env ``NLBAC_ROLLOUT_ONE_LAUNCH=0``) runs the chained path everywhere: the A/B baseline.
 """
 import ctypes as C
@@ -85,8 +86,10 @@ def rollout(func, x0, controls, dt, *, method="rk4", atol=1e-7, rtol=1e-5):
 
 
 def _one_launch_ok(func, method):
-    if not (ONE_LAUNCH and func.affine and method in ("euler", "rk4")):
+    if not (ONE_LAUNCH and method in ("euler", "rk4")):
         return False
+    if not func.affine:
+        return _lib.load().nlbac_concat_rk_traj_ok(C.byref(func.device_handles()[0].desc)) == 1
     f, g = func.device_handles()
     return _lib.load().nlbac_node_rk_traj_ok(C.byref(f.desc), C.byref(g.desc)) == 1
 
@@ -145,6 +148,32 @@ class _Traj:
         return self.acts[i].data_ptr() if self.acts[i] is not None else None
 
 
+class _ConcatTraj:
+    """Device buffers of one one-launch rollout of the single-net NODE, step-major [k][stage][row] over H * S stages:
+    nothing without gradients, the three layers' mask words for input gradients, activation rows and the stage-input
+    rows layer 0 saw ([Y_st | c_k], normalised when the net is) for parameter gradients."""
+
+    def __init__(self, func, n, H, method, mode, device):
+        self.net = func.device_handles()[0]
+        self.ns, self.nc = func.n_s, func.n_carry
+        self.S, self.beta, self.c_out = _tableau(method)
+        self.n, self.H = n, H
+        self.norm = func.norm_device() if getattr(func, "normalized", False) else None
+        HS, nw = H * self.S, self.net.n_layers - 1
+        self.bits = 1 if mode == "inputs" else 0
+        self.acts, self.ls, self.Xin = None, 0, None
+        if mode == "inputs":
+            self.acts, self.ls = torch.empty(nw * HS * n * 4, dtype=torch.int32, device=device), HS * n * 4
+        elif mode == "params":
+            self.acts = torch.empty(nw, HS * n, self.net.hid, dtype=torch.float32, device=device)
+            self.ls = HS * n * self.net.hid
+            self.Xin = torch.empty(HS * n, self.net.in_dim, dtype=torch.float32, device=device)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
 class _RolloutFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, func, method, dt, atol, rtol, mode, x0, controls, *params):
@@ -154,6 +183,13 @@ class _RolloutFunction(torch.autograd.Function):
         out = torch.empty(H + 1, n, ns, dtype=torch.float32, device=x0.device)
         out[0].copy_(x0)
         ctx.func, ctx.mode, ctx.n_params = func, mode, len(params)
+        if _one_launch_ok(func, method) and not func.affine:
+            tj = _ConcatTraj(func, n, H, method, mode, x0.device)
+            _lib.call("nlbac_concat_rk_traj_fwd", C.byref(tj.net.desc), x0.data_ptr(), u.data_ptr(), n, H, tj.S, tj.beta,
+                      tj.c_out, dt, out[1].data_ptr(), _ptr(tj.Xin), _ptr(tj.acts), tj.ls, tj.bits, _ptr(tj.norm),
+                      stream_ptr())
+            ctx.path = ("ctraj", tj, dt) if mode != "none" else None
+            return out
         if _one_launch_ok(func, method):
             tj = _Traj(func, n, H, method, mode, x0.device)
             _lib.call("nlbac_node_rk_traj_fwd", C.byref(tj.f.desc), C.byref(tj.g.desc), x0.data_ptr(), u.data_ptr(), n,
@@ -177,7 +213,9 @@ class _RolloutFunction(torch.autograd.Function):
         assert path is not None, "rollout: nothing was kept for a backward (the forward ran without gradients)"
         dout = dout.float().contiguous()
         need_p = ctx.mode == "params" and any(ctx.needs_input_grad[8:])
-        if path[0] == "traj":
+        if path[0] == "ctraj":
+            dx0, du, flat = _concat_traj_backward(func, path[1], path[2], dout, need_p)
+        elif path[0] == "traj":
             dx0, du, flat = _traj_backward(func, path[1], path[2], path[3], dout, need_p)
         else:
             dx0, du, flat = _chain_backward(func, path[1], path[2], dout, need_p)
@@ -243,5 +281,29 @@ def _traj_backward(func, tj, u, dt, dout, need_p):
             io[i].dz = dz.data_ptr()
             io[i].grad = arena.grad.data_ptr()
         bwd_weights(mlp_array([tj.f.desc, tj.g.desc]), io, 2, HS * n, arena.n_slabs, arena.n, dev)
+        flat = _reduce(arena, arena.n_slabs)
+    return dx0, du, flat
+
+
+def _concat_traj_backward(func, tj, dt, dout, need_p):
+    n, H, S, HS = tj.n, tj.H, tj.S, tj.H * tj.S
+    dev = dout.device
+    z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    dx0, du = z(n, tj.ns), z(H, n, tj.nc)
+    dK = dz = None
+    if need_p:
+        dK, dz = z(HS * n, tj.ns), z(tj.net.n_layers - 1, HS * n, tj.net.hid)
+    _lib.call("nlbac_concat_rk_traj_bwd", C.byref(tj.net.desc), n, H, S, tj.beta, tj.c_out, dt, tj.acts.data_ptr(), tj.ls,
+              tj.bits, _ptr(tj.norm), dout.data_ptr(), dx0.data_ptr(), du.data_ptr(), _ptr(dK), _ptr(dz), stream_ptr())
+    flat = None
+    if need_p:      # every stage of every interval as ONE batch of H * S * n rows: layer 0's input is the kept Xin row
+        arena = tj.net.arena
+        io = io_array(1)
+        io[0].x0, io[0].x0_dim, io[0].x0_ld = tj.Xin.data_ptr(), tj.net.in_dim, tj.net.in_dim
+        io[0].dy, io[0].dy_ld = dK.data_ptr(), tj.ns
+        io[0].acts, io[0].acts_ls = tj.acts.data_ptr(), tj.ls
+        io[0].dz = dz.data_ptr()
+        io[0].grad = arena.grad.data_ptr()
+        bwd_weights(mlp_array([tj.net.desc]), io, 1, HS * n, arena.n_slabs, arena.n, dev)
         flat = _reduce(arena, arena.n_slabs)
     return dx0, du, flat

@@ -1,9 +1,11 @@
 """One-launch trajectory kernels against the chained one-interval solves (``nlbac_amd.rollout.ONE_LAUNCH`` on / off),
-in one process, alternating rounds, timed with device events.  Unicycle NODE (f_net 5 / g_net 4 layers of 100),
-rows x H x method x {forward only, forward + backward w.r.t. x0 / controls, + parameter gradients}.  The two paths'
-outputs are asserted equal before a time is printed.
+in one process, alternating rounds, timed with device events.  ``--kind unicycle`` (default): the control-affine
+Unicycle NODE (f_net 5 / g_net 4 layers of 100); ``cars``: the single-net ``NeuralODEModel(12, 10)`` of SimulatedCars;
+``quadrotor``: the normalised 8 -> 6 single-net NODE.  rows x H x method x {forward only, forward + backward w.r.t.
+x0 / controls, + parameter gradients}.  The two paths' outputs are asserted equal before a time is printed; the
+single-net kinds also print each path's round-to-round spread (max - min over the rounds).
 
-    python tools/microbench_rollout.py [--rounds 5] [--reps 10]
+    python tools/microbench_rollout.py [--kind unicycle|cars|quadrotor] [--rounds 5] [--reps 10]
 """
 import argparse
 import os
@@ -17,7 +19,6 @@ from nlbac_amd import _lib  # noqa: E402
 from nlbac_amd import rollout as R  # noqa: E402
 from nlbac_amd.sac_cbf_clf.model import NeuralODEModel  # noqa: E402
 
-FLOP_PER_ROW_STAGE = 2 * 51506       # Unicycle NODE: 2 x (f_net + g_net MACs) per row and stage
 PEAK = 157.3e12                      # fp32 MFMA peak of the MI355X
 
 
@@ -32,26 +33,47 @@ def run(m, x0, c, method, mode, w):
     return out, (x.grad, u.grad)
 
 
+def build(kind):
+    """The model of a kind, its state / control widths."""
+    if kind == "unicycle":
+        return NeuralODEModel(3, 3, 6), 3, 2
+    if kind == "cars":
+        return NeuralODEModel(12, 10), 10, 2
+    g = torch.Generator().manual_seed(2)
+    r = lambda n, lo, hi: torch.rand(n, generator=g) * (hi - lo) + lo
+    norm = (r(8, -0.5, 0.5), r(8, 0.5, 2.0), r(6, -0.5, 0.5), r(6, 0.5, 2.0))
+    return NeuralODEModel(8, 6, normalizer=tuple(v.numpy() for v in norm)), 6, 2
+
+
+def flop_per_row_stage(m):
+    """2 x MACs of the field's nets per row and stage, from their layer sizes."""
+    return 2 * sum(l.in_features * l.out_features for l in m.modules() if isinstance(l, torch.nn.Linear))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--kind", choices=("unicycle", "cars", "quadrotor"), default="unicycle")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=10)
     a = ap.parse_args()
     torch.manual_seed(0)
-    m = NeuralODEModel(3, 3, 6)
+    m, ns, nc = build(a.kind)
+    flop = flop_per_row_stage(m)
+    spread = a.kind != "unicycle"
     calls = []
     real = _lib.call
     _lib.call = lambda name, *args: (calls.append(name), real(name, *args))[1]
     print("%-6s %6s %3s %-7s | %10s %10s %7s | %7s %7s | %9s %6s" % (
-        "method", "rows", "H", "mode", "one us", "chain us", "ratio", "l_one", "l_chain", "fwd TF/s", "%peak"))
+        "method", "rows", "H", "mode", "one us", "chain us", "ratio", "l_one", "l_chain", "fwd TF/s", "%peak")
+          + (" | %8s %8s" % ("sp_one", "sp_chain") if spread else ""))
     for method in ("euler", "rk4"):
         S = 1 if method == "euler" else 4
         for B in (8192, 32768):
             for H in (1, 4, 16):
                 g = torch.Generator(device="cuda").manual_seed(1)
-                x0 = torch.rand(B, 3, device="cuda", generator=g) * 2 - 1
-                c = torch.rand(H, B, 2, device="cuda", generator=g) * 2 - 1
-                w = torch.randn(H + 1, B, 3, device="cuda", generator=g)
+                x0 = torch.rand(B, ns, device="cuda", generator=g) * 2 - 1
+                c = torch.rand(H, B, nc, device="cuda", generator=g) * 2 - 1
+                w = torch.randn(H + 1, B, ns, device="cuda", generator=g)
                 for mode in ("fwd", "inputs", "params"):
                     for p in m.parameters():
                         p.requires_grad_(mode == "params")
@@ -80,10 +102,11 @@ def main():
                             e1.synchronize()
                             t[on].append(e0.elapsed_time(e1) * 1e3 / a.reps)
                     one, chain = min(t[True]), min(t[False])
-                    tf = FLOP_PER_ROW_STAGE * B * S * H / (one * 1e-6) if mode == "fwd" else float("nan")
+                    tf = flop * B * S * H / (one * 1e-6) if mode == "fwd" else float("nan")
                     print("%-6s %6d %3d %-7s | %10.1f %10.1f %7.3f | %7d %7d | %9.1f %6.1f" % (
                         method, B, H, mode, one, chain, chain / one, launches[True], launches[False], tf / 1e12,
-                        100 * tf / PEAK), flush=True)
+                        100 * tf / PEAK)
+                          + (" | %8.1f %8.1f" % (max(t[True]) - one, max(t[False]) - chain) if spread else ""), flush=True)
     R.ONE_LAUNCH = True
 
 

@@ -651,8 +651,18 @@ int nlbac_concat_rk_bwd(const nlbac_mlp *net, int P, int rows_per_problem, int n
                         float *dK, const float *dYup,
                         float *dy0, int dy0_in, float *dc, int dc_acc, const float *norm, float *dyn,
                         const struct nlbac_rk_chain *chain, int back_idx, nlbac_stream_t s);
-/* dopri5 step control on the device.  ctl: per problem NLBAC_DOPRI_CTL doubles
- * {h, t, ratio, accept, done, x, h0, d0, d1, d2, n_steps, h_used}.
+/* dopri5 step control on the device.  ctl: per problem NLBAC_DOPRI_CTL doubles, in this order (csrc/ode_control.h,
+ * C_*; the host binding names them CTL_*):
+ *    0 h        the step size the next attempt tries       8 d1       || f0 / scale ||
+ *    1 t        the abscissa reached by accepted steps     9 d2       || (f1 - f0) / scale || / h0
+ *    2 ratio    the last attempt's error ratio            10 n_steps  attempts so far
+ *    3 accept   the last attempt was accepted             11 h_used   the step size the last attempt tried
+ *    4 done     the solve has reached t_end (or stopped)  12 n_acc    accepted steps so far = the step slot in use
+ *    5 x        (t_end - t) / h of the finishing step     13 ovf      out of step slots (set together with done)
+ *    6 h0       the initial step's first guess            14          unused
+ *    7 d0       || y0 / scale ||                          15 seq      the stamp of the launch that wrote the block:
+ *                                                                     HOST copy only (nlbac_rk_chain::ctl_host /
+ *                                                                     ctl_seq), unused in the device block
  * norm partials [P][ceil(rows/256)][2]; mode 0: (y0/scale, f0/scale) with a=f0;
  * mode 1: (f1-f0)/scale with a=f1,b=f0; mode 2: err/tol with a=err. */
 #define NLBAC_DOPRI_CTL 16

@@ -9,7 +9,7 @@ import torch
 from . import _lib
 from ._lib import fptr
 from .arena import bwd_weights, io_array, stream_ptr
-from .ode_consts import TABLEAU
+from .ode_consts import CTL_DONE, CTL_H0, CTL_HUSED, CTL_NSTEPS, CTL_RATIO, TABLEAU, ctl_field_ptr
 
 
 class AffineAdjoint:
@@ -219,7 +219,7 @@ class AffineAdjoint:
         self._adj_step(w, u, P, rpp, "dopri5", 0, 1, h_host=[0.0] * P, keep=keep)
         pn = self._adj_params_norm(par, 0, cp) if par else None
         self._adj_norm_control(KZ[0], None, w, u, 0, P, rpp, ctl, pn)
-        self._adj_step(w, u, P, rpp, "probe", 1, 2, h_dev=cp + 8 * 6, keep=keep)             # C_H0
+        self._adj_step(w, u, P, rpp, "probe", 1, 2, h_dev=ctl_field_ptr(cp, CTL_H0), keep=keep)
         pn = self._adj_params_norm(par, 1, cp) if par else None
         self._adj_norm_control(KZ[1], KZ[0], w, None, 1, P, rpp, ctl, pn)
         c_sol, c_err = self._coef("sol"), self._coef("err")
@@ -245,14 +245,15 @@ class AffineAdjoint:
             c = self.ctl.read(ctx, P, self.before_wait)
             if c is None:             # (inside a hipGraph capture nothing is posted)
                 c = ctl.cpu()
-            if all(bool(c[p, 4] > 0) for p in range(P)):
+            if all(bool(c[p, CTL_DONE] > 0) for p in range(P)):
                 break
             if attempts >= self.ADJ_MAX_ATTEMPTS:
                 raise _lib.NlbacError("odeint_adjoint (dopri5): max_num_steps exceeded")
             chain = 2
-        used = int(max(float(c[p, 10]) for p in range(P)))       # C_NSTEPS: attempts of the slowest problem
+        used = int(max(float(c[p, CTL_NSTEPS]) for p in range(P)))       # attempts of the slowest problem
         self._adj_chain = max(1, used)
-        ctx["adjoint_info"] = [[(float(c[p, 11]), float(c[p, 2]), int(c[p, 10])) for p in range(P)]]
+        ctx["adjoint_info"] = [[(float(c[p, CTL_HUSED]), float(c[p, CTL_RATIO]), int(c[p, CTL_NSTEPS]))
+                                for p in range(P)]]
         # the interpolant of the last accepted step at t0 (steps are not clipped), all columns of z at once: written by
         # the attempt that finished each problem (interp), or by a launch of its own
         if not ip:

@@ -13,6 +13,7 @@ import time
 import torch
 
 from . import _lib
+from .ode_consts import CTL_DONE, CTL_SEQ
 
 
 class ControlBlockReader:
@@ -88,12 +89,12 @@ class ControlBlockReader:
         arr = self.pin[P].numpy()          # (the same memory)
         t0 = drained = None
         n = 0
-        stamps = arr[:, 15]
+        stamps = arr[:, CTL_SEQ]
         while True:
             s1 = stamps.tolist()                       # (stamp, block, stamp: the sequence lock's read side)
             if all(x == last or first <= x < last for x in s1):
                 c = arr.copy()
-                if all(c[p, 15] == s1[p] and (s1[p] == last or c[p, 4] > 0) for p in range(P)):
+                if all(c[p, CTL_SEQ] == s1[p] and (s1[p] == last or c[p, CTL_DONE] > 0) for p in range(P)):
                     return torch.from_numpy(c)
             n += 1
             if n & 63 == 0:

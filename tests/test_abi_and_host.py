@@ -386,3 +386,23 @@ def test_host_reader_of_the_stamped_control_block():
     t.join()
     assert time.perf_counter() - t0 >= 0.02
     assert c[1, 15] == 7.0 and c[1, 0] == 0.125 and c[1, 4] == 0.0
+
+
+def test_host_names_of_the_control_block_fields_match_the_kernels_enum():
+    """``ode_consts.CTL_*`` (what the host indexes the dopri5 control block with) against the ``C_*`` enumerators of
+    csrc/ode_control.h (what the kernels index it with): the same names with the same values, every one inside the
+    block, and the block as long as the public header says."""
+    from nlbac_amd import ode_consts
+    csrc = os.path.join(os.path.dirname(_lib.__file__), "csrc")
+    txt = open(os.path.join(csrc, "ode_control.h")).read()
+    kernel = {}
+    for block in re.findall(r"enum\s*\{(.*?)\}", txt, flags=re.S):
+        kernel.update({name: int(v) for name, v in re.findall(r"C_(\w+)\s*=\s*(\d+)", block)})
+    host = {k[len("CTL_"):]: v for k, v in vars(ode_consts).items() if k.startswith("CTL_")}
+    assert len(kernel) == 15 and kernel == host, (kernel, host)
+    assert all(type(v) is int for v in host.values())          # (plain ints: read on the host's critical path)
+    assert len(set(host.values())) == len(host)
+    assert all(v < _lib.DOPRI_CTL for v in kernel.values())
+    header = open(os.path.join(ROOT, "include", "nlbac_hip.h")).read()
+    assert _lib.DOPRI_CTL == int(re.search(r"#define NLBAC_DOPRI_CTL (\d+)", header).group(1))
+    assert ode_consts.ctl_field_ptr(4096, ode_consts.CTL_H0) == 4096 + 8 * kernel["H0"]

@@ -3,6 +3,7 @@ import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import nlbac_amd
+from nlbac_amd.ode_consts import CTL_H
 from nlbac_amd.odeint import AffineNodeSolver
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 from test_agent_parity_gpu import make_agent
@@ -16,7 +17,7 @@ sol = AffineNodeSolver(node, "cuda")
 sol.ctx = {}
 ws = sol._step_ws(n, 7, 0)
 ctl = sol._ctl(2)
-ctl[:, 0] = 0.02
+ctl[:, CTL_H] = 0.02
 
 
 def run(save_acts, st0=1, st1=7):
@@ -41,7 +42,7 @@ sol_m.keep_acts = False
 sol_m.ctx = {}
 ws_m = sol_m._step_ws(n, 7, 0)
 ctl_m = sol_m._ctl(2)
-ctl_m[:, 0] = 0.02
+ctl_m[:, CTL_H] = 0.02
 
 
 def run_m(st0=1, st1=7):

@@ -7,6 +7,7 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
 import nlbac_amd
 from nlbac_amd import _lib
+from nlbac_amd.ode_consts import CTL_H0, ctl_field_ptr
 from nlbac_amd.odeint import AffineNodeSolver
 from test_agent_parity_gpu import make_agent
 agent, env = make_agent(128, 256, 0, "dopri5")
@@ -29,7 +30,7 @@ for mode in (0, 1):
     ch_f = sol._chain(ws0, pool, 2, n // 2, mode, read_ctl=False)
     ch_n = sol._chain(ws0, pool, 2, n // 2, mode, read_ctl=False); ch_n.norm_mode = -1
     name, s0, s1 = (("dopri5", 0, 1) if mode == 0 else ("probe", 1, 2))
-    hd = cp if mode == 0 else cp + 8 * 6
+    hd = cp if mode == 0 else ctl_field_ptr(cp, CTL_H0)
     a = timeit(lambda: sol._rk_fused(ws0, y0, u, 2, n // 2, name, s0, s1, h_dev=hd, save_acts=(mode == 0), chain=ch_f))
     b = timeit(lambda: sol._rk_fused(ws0, y0, u, 2, n // 2, name, s0, s1, h_dev=hd, save_acts=(mode == 0), chain=ch_n))
     c = timeit(lambda: (sol._rk_fused(ws0, y0, u, 2, n // 2, name, s0, s1, h_dev=hd, save_acts=(mode == 0), chain=ch_n), sol._chain_control(ws0, pool, ch_n, y0, u, mode, 2, n // 2)))

@@ -4,6 +4,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import numpy as np, torch
 import nlbac_amd
+from nlbac_amd.ode_consts import CTL_H
 from nlbac_amd.odeint import AffineNodeSolver
 from test_agent_parity_gpu import make_agent
 
@@ -15,7 +16,7 @@ sol = AffineNodeSolver(agent.neural_ode_model, "cuda")
 sol.keep_acts = False
 ws = sol._step_ws(n, 7, 0)
 ctl = sol._ctl(2)
-ctl[:, 0] = 0.02
+ctl[:, CTL_H] = 0.02
 FWD = not os.environ.get("PHASE_BWD_ONLY")       # (-DEXP_TIMING_BWD build: the forward runs normally, only the backward stamps)
 stamps = torch.zeros(4096, dtype=torch.int64, device="cuda")
 err = stamps.view(torch.float32)

@@ -23,11 +23,12 @@ stamps = torch.zeros(2048, dtype=torch.int64, device="cuda")
 sol._rk_fused(ws, y0, u, 2, B, "rk4", 0, 4, h_host=[0.02, 0.02], err=stamps.view(torch.float32))
 torch.cuda.synchronize()
 t = stamps.cpu().numpy()
+stage_at = lambda st: 2 + 8 * st        # the first stamp of a stage
 for half in (0, 1):
     s = t[half * 256:half * 256 + 64]
     print("wave %d: prime..constants+tile rows %d" % (half, s[1] - s[0]))
     for st in range(4):
-        b = 2 + 8 * st
+        b = stage_at(st)
         print("  stage %d: input %5d  L0 %5d  L1 %5d  L2 %5d  out+stores %5d | stage %6d" %
               (st, s[b + 1] - s[b], s[b + 2] - s[b + 1], s[b + 3] - s[b + 2], s[b + 4] - s[b + 3], s[b + 5] - s[b + 4], s[b + 5] - s[b]))
     print("  after the last stage (barrier) %d; first stamp -> last %d" % (s[2 + 32] - s[2 + 24 + 5], s[2 + 32] - s[0]))
@@ -57,10 +58,10 @@ od._lib.call = orig
 t = stamps.cpu().numpy()
 for half in (0, 1):
     s = t[half * 256:half * 256 + 64]
-    first = 2 + 8 * 3
+    first = stage_at(3)
     print("backward, wave %d: prologue %d" % (half, s[first] - s[0]))
     for st in (3, 2, 1, 0):
-        b = 2 + 8 * st
+        b = stage_at(st)
         print("  stage %d: dy + top %5d  prod 1 %5d  prod 2 %5d  dX %5d  stage algebra %5d | stage %6d" %
               (st, s[b + 1] - s[b], s[b + 2] - s[b + 1], s[b + 3] - s[b + 2], s[b + 4] - s[b + 3], s[b + 5] - s[b + 4], s[b + 5] - s[b]))
     print("  first stamp -> end of the stage loop %d" % (s[1] - s[0]))

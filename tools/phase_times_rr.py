@@ -6,6 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import numpy as np, torch
 import nlbac_amd
+from nlbac_amd.ode_consts import CTL_H
 from nlbac_amd.odeint import AffineNodeSolver, fptr
 from test_agent_parity_gpu import make_agent
 
@@ -19,7 +20,7 @@ sol.keep_acts = not bits
 sol.ctx = {}
 ws = sol._step_ws(n, 7, 0)
 ctl = sol._ctl(2)
-ctl[:, 0] = 0.02
+ctl[:, CTL_H] = 0.02
 stamps = torch.zeros(4096, dtype=torch.int64, device="cuda")
 err = stamps.view(torch.float32)
 for st0, st1 in ((1, 7), (0, 1)):

@@ -625,6 +625,34 @@ int nlbac_concat_rk_traj_fwd(const nlbac_mlp *net, const float *x0, const float 
 int nlbac_concat_rk_traj_bwd(const nlbac_mlp *net, int n, int H, int n_stages, const float *beta, const float *c_out,
                              float h, const float *acts, long acts_ls, int acts_bits, const float *norm,
                              const float *dout, float *dx0, float *dc, float *dK, float *dz, nlbac_stream_t s);
+/* The solution of the control-affine NODE on a whole time grid t_0 < t_1 < .. < t_H, torchdiffeq's fixed-grid rule (one
+ * euler / rk4 step per grid interval): nlbac_node_rk_traj_fwd / _bwd with two differences.  (1) A step size per
+ * interval: hs [H] is a DEVICE array (hs[k] = t_{k+1} - t_k, read by the kernel at the top of interval k) and hs_host
+ * [H] the same values in host memory, from which the launcher checks that every step is positive and finite.  (2) One
+ * set of actions u [n][n_u] for all intervals, and du [n][n_u] their gradient summed over the intervals — inside the
+ * launch, by the tile that owns the rows, in the order k = H-1 .. 0 (total = du_{H-1}; total = total + du_k: the fp32
+ * adds a chain of one-interval backwards does), no atomics.  Everything else — out, the step-major K / Y / G / acts_* /
+ * dK / dG / dz_* buffers, dout [H+1][n][n_s], dx0, acts_bits, where nlbac_node_rk_traj_ok is 1 — as in the _traj_
+ * functions; interval k's results are those of nlbac_node_rk_fwd / _bwd with h = hs[k], bit for bit. */
+int nlbac_node_rk_grid_fwd(const nlbac_mlp *f, const nlbac_mlp *g, const float *x0, const float *u, int n, int H,
+                           int n_stages, const float *beta, const float *c_out, const float *hs, const float *hs_host,
+                           float *out, float *K, float *Y, float *G, float *acts_f, long acts_f_ls, float *acts_g,
+                           long acts_g_ls, int acts_bits, nlbac_stream_t s);
+int nlbac_node_rk_grid_bwd(const nlbac_mlp *f, const nlbac_mlp *g, const float *u, int n, int H, int n_stages,
+                           const float *beta, const float *c_out, const float *hs, const float *hs_host,
+                           const float *G, const float *acts_f, long acts_f_ls, const float *acts_g, long acts_g_ls,
+                           int acts_bits, const float *dout, float *dx0, float *du, float *dK, float *dG, float *dz_f,
+                           float *dz_g, nlbac_stream_t s);
+/* The same for the single-net NODE: nlbac_concat_rk_traj_fwd / _bwd with hs / hs_host [H] in place of h, one set of
+ * carried columns c [n][n_c] for all intervals and dc [n][n_c] summed over the intervals (same order, formed by the
+ * wave that owns the rows).  Where nlbac_concat_rk_traj_ok is 1. */
+int nlbac_concat_rk_grid_fwd(const nlbac_mlp *net, const float *x0, const float *c, int n, int H, int n_stages,
+                             const float *beta, const float *c_out, const float *hs, const float *hs_host, float *out,
+                             float *Xin, float *acts, long acts_ls, int acts_bits, const float *norm, nlbac_stream_t s);
+int nlbac_concat_rk_grid_bwd(const nlbac_mlp *net, int n, int H, int n_stages, const float *beta, const float *c_out,
+                             const float *hs, const float *hs_host, const float *acts, long acts_ls, int acts_bits,
+                             const float *norm, const float *dout, float *dx0, float *dc, float *dK, float *dz,
+                             nlbac_stream_t s);
 /* The same one-launch RK step for the single-net NODE dx/dt = net([x | c]) with carried inputs c = (u, t)
  * (SimulatedCars, C/sac_cbf_clf/model.py:179-205; odeint call sites C/sac_cbf_clf/sac_cbf_clf.py:437,458,581,603,
  * C/model.py:245): n_s = net->out_dim state columns, n_c = net->in_dim - n_s carried columns (c: (rows, n_c)),

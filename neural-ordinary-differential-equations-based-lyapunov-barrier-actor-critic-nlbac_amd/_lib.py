@@ -212,6 +212,14 @@ _PROTOS = {
     "nlbac_concat_rk_traj_fwd": [C.POINTER(Mlp), _P, _P, _I, _I, _I, c_float_p, c_float_p, _F, _P, _P, _P, _L, _I, _P, _P],
     "nlbac_concat_rk_traj_bwd": [C.POINTER(Mlp), _I, _I, _I, c_float_p, c_float_p, _F, _P, _L, _I, _P, _P, _P, _P, _P, _P,
                                  _P],
+    "nlbac_node_rk_grid_fwd": [C.POINTER(Mlp), C.POINTER(Mlp), _P, _P, _I, _I, _I, c_float_p, c_float_p, _P, c_float_p, _P,
+                               _P, _P, _P, _P, _L, _P, _L, _I, _P],
+    "nlbac_node_rk_grid_bwd": [C.POINTER(Mlp), C.POINTER(Mlp), _P, _I, _I, _I, c_float_p, c_float_p, _P, c_float_p, _P, _P,
+                               _L, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "nlbac_concat_rk_grid_fwd": [C.POINTER(Mlp), _P, _P, _I, _I, _I, c_float_p, c_float_p, _P, c_float_p, _P, _P, _P, _L,
+                                 _I, _P, _P],
+    "nlbac_concat_rk_grid_bwd": [C.POINTER(Mlp), _I, _I, _I, c_float_p, c_float_p, _P, c_float_p, _P, _L, _I, _P, _P, _P,
+                                 _P, _P, _P, _P],
     "nlbac_concat_rk_fwd": [C.POINTER(Mlp), _P, _P, _I, _I, _I, _I, _I, c_float_p, c_float_p, _I, c_float_p, _I, c_float_p,
                             _P, _I, _P, _P, _P, _L, _I, _P, _P, _P, _P, C.POINTER(RkChain), _P],
     "nlbac_concat_rk_mask_words": [C.POINTER(Mlp)],

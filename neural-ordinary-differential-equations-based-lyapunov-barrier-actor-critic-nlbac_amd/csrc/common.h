@@ -28,6 +28,15 @@ extern thread_local char nlbac_err_buf[512];
 
 static inline int nlbac_ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
+// The step sizes of a time-grid launch (nlbac_node_rk_grid_* / nlbac_concat_rk_grid_*): hs [H] on the device is what the
+// kernel reads, hs_host [H] in host memory beside it is what the launcher checks.
+static inline int nlbac_grid_steps_check(const float* hs, const float* hs_host, int H, const char* who) {
+    NLBAC_REQUIRE(hs && hs_host, "%s: null pointer", who);
+    for (int k = 0; k < H; ++k)
+        NLBAC_REQUIRE(hs_host[k] > 0.f && hs_host[k] <= 3.0e38f, "%s: every interval's step must be positive and finite", who);
+    return 0;
+}
+
 // Block-wide deterministic sum of NV values per thread (256-thread blocks):
 // wave shuffle tree, then a fixed-order combine of the 4 wave results.
 template <int NV>

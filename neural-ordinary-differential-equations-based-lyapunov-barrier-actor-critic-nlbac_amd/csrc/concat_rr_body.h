@@ -36,8 +36,12 @@ __device__ __forceinline__ float crr_step_output(const ConcatRkLaunch& L, const 
 // un-normalised net too; K and Y rows are not written), its result to L.out + k n n_s and, as interval k+1's y0, to
 // sY0 — by the wave that owns the rows, so that no barrier enters the interval loop.  The dopri5 machinery (control
 // block, slots, FSAL, interpolant, norms, tickets) is compiled out.  TRAJ = false (H = 1): the one-step kernel.
-template <int NB, int R, int BITS, int NW, bool TRAJ = false>
-__device__ __forceinline__ void concat_rr_fwd_body(const ConcatRkLaunch& L, const int H = 1) {
+// GRID (with TRAJ; nlbac_concat_rk_grid_fwd: the solution on a time grid): interval k's step size is hs[k] (device
+// array), written to sH by the wave that owns the rows at the top of the interval, and the carried columns L.c [n][n_c]
+// are the same for every interval (sC is filled once).
+template <int NB, int R, int BITS, int NW, bool TRAJ = false, bool GRID = false>
+__device__ __forceinline__ void concat_rr_fwd_body(const ConcatRkLaunch& L, const int H = 1, const float* hs = nullptr) {
+    static_assert(TRAJ || !GRID, "a time grid is a trajectory");
     constexpr int TILE = 16 * NW, NTHR = 64 * NW;
     (void)NTHR;
     using S = RRShape<NB, R>;
@@ -209,10 +213,11 @@ __device__ __forceinline__ void concat_rr_fwd_body(const ConcatRkLaunch& L, cons
     // behind the previous interval's store burst — not between two fragment loads of a layer (vmcnt is in order); they
     // reach sC behind the interval's last stage
     float cnext = 0.f;
-    if constexpr (TRAJ) {
+    if constexpr (TRAJ && !GRID) {
         const int mm = 16 * half + (lane >> 2), c = lane & 3, row = row0 + mm;
         cnext = L.c[(long)min(k + 1, H - 1) * n * nc + (long)min(row, n - 1) * nc + min(c, max(nc - 1, 0))];
     }
+    if constexpr (GRID) { if (lane < 16) sH[16 * half + lane] = hs[k]; }      // (the wave's own rows: no barrier)
     const long kS = TRAJ ? (long)k * L.S_total : 0;      // interval k's first stage in the [k][stage][row] layout
     for (int st = L.stage_begin; st < stage_end; ++st) {
         const int sb = 2 + 8 * (st - L.stage_begin);
@@ -386,8 +391,10 @@ __device__ __forceinline__ void concat_rr_fwd_body(const ConcatRkLaunch& L, cons
             L.out[(long)k * n * ns + (long)row * ns + r] = a;
             sY0[mm * CK_LD + r] = a;
         }
-        const int mm = 16 * half + (lane >> 2), c = lane & 3;
-        sC[mm * CK_NC + c] = (row0 + mm < n && c < nc) ? cnext : 0.f;
+        if constexpr (!GRID) {
+            const int mm = 16 * half + (lane >> 2), c = lane & 3;
+            sC[mm * CK_NC + c] = (row0 + mm < n && c < nc) ? cnext : 0.f;
+        }
     }
     }
     if constexpr (TRAJ) return;
@@ -525,8 +532,14 @@ struct ConcatRkTrajBwd {
 // the net's own output (dK, times out_sig for a normalised net) goes to L.dyn as rows [k S + st][row][n_s].
 // X.dx0 = X.dout[0] + the dy0 of interval 0.  All of it on the wave's own 16 rows: no barrier in the interval loop.
 // The device-driven chain and the interpolant's backward are compiled out.  TRAJ = false (X null): the one-step kernel.
-template <int NB, int R, int BITS, int NW, bool TRAJ = false>
-__device__ __forceinline__ void concat_rr_bwd_body(const ConcatRkBwdLaunch& L, const ConcatRkTrajBwd* X = nullptr) {
+// GRID (with TRAJ; nlbac_concat_rk_grid_bwd): step size hs[k] per interval, and L.dc [n][n_c] is the sum of the
+// intervals' gradients w.r.t. the (one set of) carried columns, formed by the wave that owns the rows in the order
+// k = H-1 .. 0 — total = dc_{H-1}; total = total + dc_k, the fp32 adds the chained path does between its launches —
+// in sDYup, which only the interpolant's backward uses otherwise.
+template <int NB, int R, int BITS, int NW, bool TRAJ = false, bool GRID = false>
+__device__ __forceinline__ void concat_rr_bwd_body(const ConcatRkBwdLaunch& L, const ConcatRkTrajBwd* X = nullptr,
+                                                   const float* hs = nullptr) {
+    static_assert(TRAJ || !GRID, "a time grid is a trajectory");
     constexpr int TILE = 16 * NW;
     using S = RRShape<NB, R>;
     constexpr int KS = S::KS, HID = S::HID, TB = NB - 2, NT = KS - 4 * TB;
@@ -719,6 +732,7 @@ __device__ __forceinline__ void concat_rr_bwd_body(const ConcatRkBwdLaunch& L, c
     const int k = H - 1 - kk, kS = TRAJ ? k * L.S_total : 0;      // interval k's first stage in the [k][stage][row] layout
     if constexpr (TRAJ) {       // d = dout[k+1] (+ interval k+1's dy0): dy0 = 0 + d, dK_j = 0 + (c_out[j] h) d; dc = 0
         request_dout(k + 1);
+        if constexpr (GRID) { if (lane < 16) sH[16 * half + lane] = hs[k]; }
 #pragma unroll
         for (int it = 0; it < NITD; ++it) {
             const int idx = lane + 64 * it, mm = 16 * half + idx / CK_NS, c = idx % CK_NS;
@@ -883,7 +897,14 @@ __device__ __forceinline__ void concat_rr_bwd_body(const ConcatRkBwdLaunch& L, c
     if constexpr (TRAJ) {      // ---- interval k's gradient w.r.t. its carried columns, this wave's rows
         for (int idx = lane; idx < 16 * nc; idx += 64) {
             const int mm = 16 * half + idx / nc, c = idx % nc, row = row0 + mm;
-            if (row < n) L.dc[(long)k * n * nc + (long)row * nc + c] = sDC[mm * CK_NC + c];
+            if constexpr (GRID) {
+                float a = sDC[mm * CK_NC + c];
+                if (kk > 0) a = sDYup[mm * CK_NC + c] + a;
+                sDYup[mm * CK_NC + c] = a;
+                if (k == 0 && row < n) L.dc[(long)row * nc + c] = a;
+            } else {
+                if (row < n) L.dc[(long)k * n * nc + (long)row * nc + c] = sDC[mm * CK_NC + c];
+            }
         }
     }
     }

@@ -13,6 +13,10 @@
 //
 // Reference: the chained odeint calls of C/sac_cbf_clf/sac_cbf_clf.py:437-458 (odeint(model, [x_k | u_k | t_k],
 // [0, dt])[-1], one interval per call).
+//
+// nlbac_concat_rk_grid_*: the solution on a whole time grid, torchdiffeq's fixed-grid rule (one RK step per grid
+// interval): the same kernels with a step size per interval and one set of carried columns for all of them (GRID in
+// concat_rr_body.h), the carried columns' gradient summed over the intervals inside the launch.
 #undef RR_TIMING          // (the ablation stamps belong to the one-step kernels)
 #include "concat_rr_body.h"
 
@@ -25,6 +29,30 @@ struct ConcatRkTrajBwdLaunch {
     ConcatRkBwdLaunch L;
     ConcatRkTrajBwd X;
 };
+
+struct ConcatRkGridFwdLaunch {
+    ConcatRkLaunch L;
+    int H;
+    const float* hs;                  // [H] the intervals' step sizes (device)
+};
+
+struct ConcatRkGridBwdLaunch {
+    ConcatRkBwdLaunch L;
+    ConcatRkTrajBwd X;
+    const float* hs;
+};
+
+template <int NB, int R, int BITS, int NW>
+__global__ __launch_bounds__(64 * NW) void concat_grid_fwd_kernel(const ConcatRkGridFwdLaunch A) {
+    concat_rr_fwd_body<NB, R, BITS, NW, true, true>(A.L, A.H, A.hs);
+}
+
+// (waves per SIMD as concat_traj_bwd_kernel below)
+template <int NB, int R, int BITS, int NW>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((BITS == 1 && NB < 8) ? 3 : 2)))
+void concat_grid_bwd_kernel(const ConcatRkGridBwdLaunch A) {
+    concat_rr_bwd_body<NB, R, BITS, NW, true, true>(A.L, &A.X, A.hs);
+}
 
 template <int NB, int R, int BITS, int NW>
 __global__ __launch_bounds__(64 * NW) void concat_traj_fwd_kernel(const ConcatRkTrajFwdLaunch A) {
@@ -54,17 +82,13 @@ static int ctraj_check(const nlbac_mlp* net, int n, int H, int n_stages, const f
     return 0;
 }
 
-extern "C" int nlbac_concat_rk_traj_fwd(const nlbac_mlp* net, const float* x0, const float* c, int n, int H,
-                                        int n_stages, const float* beta, const float* c_out, float h, float* out,
-                                        float* Xin, float* acts, long acts_ls, int acts_bits, const float* norm,
-                                        nlbac_stream_t s) {
-    if (ctraj_check(net, n, H, n_stages, beta, c_out, h, acts_bits, "nlbac_concat_rk_traj_fwd")) return -1;
-    NLBAC_REQUIRE(x0 && c && out, "nlbac_concat_rk_traj_fwd: null pointer");
-    NLBAC_REQUIRE(acts || acts_bits == 0, "nlbac_concat_rk_traj_fwd: acts_bits without acts");
-    NLBAC_REQUIRE(!Xin || (acts && acts_bits == 0), "nlbac_concat_rk_traj_fwd: Xin goes with the activation rows");
-    ConcatRkTrajFwdLaunch A;
-    memset(&A, 0, sizeof(A));
-    ConcatRkLaunch& L = A.L;
+// what the scalar-step launch and the time-grid launch share: the descriptor of the interval's one-step launch
+static int ctraj_fwd_fill(ConcatRkLaunch& L, const nlbac_mlp* net, const float* x0, const float* c, int n, int n_stages,
+                          const float* beta, const float* c_out, float h, float* out, float* Xin, float* acts,
+                          long acts_ls, int acts_bits, const float* norm, const char* who) {
+    NLBAC_REQUIRE(x0 && c && out, "%s: null pointer", who);
+    NLBAC_REQUIRE(acts || acts_bits == 0, "%s: acts_bits without acts", who);
+    NLBAC_REQUIRE(!Xin || (acts && acts_bits == 0), "%s: Xin goes with the activation rows", who);
     L.net = *net;
     L.y0 = x0; L.c = c;
     L.n = n; L.rpp = n; L.n_s = net->out_dim; L.n_c = net->in_dim - net->out_dim;
@@ -79,15 +103,30 @@ extern "C" int nlbac_concat_rk_traj_fwd(const nlbac_mlp* net, const float* x0, c
     L.out = out;
     L.norm = norm; L.Xn = Xin;
     L.norm_mode = -1;
+    return 0;
+}
+
+// the one-step launchers' choice of instance (nlbac_concat_rr_fwd_launch / _bwd_launch), so that the sums are the same
+#define CONCAT_TRAJ_TABLE(KERN, KernelT, tab)                                                                           \
+    static const KernelT tab[2][3][2] = {{{KERN<4, 4, 0, 2>, KERN<4, 4, 1, 2>},                                         \
+                                          {KERN<7, 1, 0, 2>, KERN<7, 1, 1, 2>},                                         \
+                                          {KERN<8, 4, 0, 2>, KERN<8, 4, 1, 2>}},                                        \
+                                         {{KERN<4, 4, 0, 4>, KERN<4, 4, 1, 4>},                                         \
+                                          {KERN<7, 1, 0, 4>, KERN<7, 1, 1, 4>},                                         \
+                                          {KERN<8, 4, 0, 4>, KERN<8, 4, 1, 4>}}}
+
+extern "C" int nlbac_concat_rk_traj_fwd(const nlbac_mlp* net, const float* x0, const float* c, int n, int H,
+                                        int n_stages, const float* beta, const float* c_out, float h, float* out,
+                                        float* Xin, float* acts, long acts_ls, int acts_bits, const float* norm,
+                                        nlbac_stream_t s) {
+    if (ctraj_check(net, n, H, n_stages, beta, c_out, h, acts_bits, "nlbac_concat_rk_traj_fwd")) return -1;
+    ConcatRkTrajFwdLaunch A;
+    memset(&A, 0, sizeof(A));
+    if (ctraj_fwd_fill(A.L, net, x0, c, n, n_stages, beta, c_out, h, out, Xin, acts, acts_ls, acts_bits, norm,
+                       "nlbac_concat_rk_traj_fwd")) return -1;
     A.H = H;
     using KernelF = void (*)(const ConcatRkTrajFwdLaunch);
-    // the one-step launcher's choice of instance (nlbac_concat_rr_fwd_launch), so that the sums are the same
-    static const KernelF kf[2][3][2] = {{{concat_traj_fwd_kernel<4, 4, 0, 2>, concat_traj_fwd_kernel<4, 4, 1, 2>},
-                                         {concat_traj_fwd_kernel<7, 1, 0, 2>, concat_traj_fwd_kernel<7, 1, 1, 2>},
-                                         {concat_traj_fwd_kernel<8, 4, 0, 2>, concat_traj_fwd_kernel<8, 4, 1, 2>}},
-                                        {{concat_traj_fwd_kernel<4, 4, 0, 4>, concat_traj_fwd_kernel<4, 4, 1, 4>},
-                                         {concat_traj_fwd_kernel<7, 1, 0, 4>, concat_traj_fwd_kernel<7, 1, 1, 4>},
-                                         {concat_traj_fwd_kernel<8, 4, 0, 4>, concat_traj_fwd_kernel<8, 4, 1, 4>}}};
+    CONCAT_TRAJ_TABLE(concat_traj_fwd_kernel, KernelF, kf);
     const int nw = crr_waves(n, n), tile = 16 * nw;
     hipLaunchKernelGGL(kf[nw == 4][crr_shape_index(net->hid)][acts_bits ? 1 : 0], dim3(nlbac_ceil_div(n, tile)),
                        dim3(64 * nw), crr_fwd_lds(tile), (hipStream_t)s, A);
@@ -95,17 +134,13 @@ extern "C" int nlbac_concat_rk_traj_fwd(const nlbac_mlp* net, const float* x0, c
     return 0;
 }
 
-extern "C" int nlbac_concat_rk_traj_bwd(const nlbac_mlp* net, int n, int H, int n_stages, const float* beta,
-                                        const float* c_out, float h, const float* acts, long acts_ls, int acts_bits,
-                                        const float* norm, const float* dout, float* dx0, float* dc, float* dK,
-                                        float* dz, nlbac_stream_t s) {
-    if (ctraj_check(net, n, H, n_stages, beta, c_out, h, acts_bits, "nlbac_concat_rk_traj_bwd")) return -1;
-    NLBAC_REQUIRE(!(acts_bits == 1 && dz), "nlbac_concat_rk_traj_bwd: weight gradients need the activation rows, not mask words");
-    NLBAC_REQUIRE(acts && dout && dx0 && dc, "nlbac_concat_rk_traj_bwd: null pointer");
-    NLBAC_REQUIRE((dz == nullptr) == (dK == nullptr), "nlbac_concat_rk_traj_bwd: dz and dK go together");
-    ConcatRkTrajBwdLaunch A;
-    memset(&A, 0, sizeof(A));
-    ConcatRkBwdLaunch& L = A.L;
+static int ctraj_bwd_fill(ConcatRkBwdLaunch& L, ConcatRkTrajBwd& X, const nlbac_mlp* net, int n, int H, int n_stages,
+                          const float* beta, const float* c_out, float h, const float* acts, long acts_ls, int acts_bits,
+                          const float* norm, const float* dout, float* dx0, float* dc, float* dK, float* dz,
+                          const char* who) {
+    NLBAC_REQUIRE(!(acts_bits == 1 && dz), "%s: weight gradients need the activation rows, not mask words", who);
+    NLBAC_REQUIRE(acts && dout && dx0 && dc, "%s: null pointer", who);
+    NLBAC_REQUIRE((dz == nullptr) == (dK == nullptr), "%s: dz and dK go together", who);
     L.net = *net;
     L.acts = acts; L.acts_ls = acts_ls; L.acts_bits = acts_bits;
     L.dz = dz; L.dyn = dK;
@@ -116,20 +151,69 @@ extern "C" int nlbac_concat_rk_traj_bwd(const nlbac_mlp* net, int n, int H, int 
         for (int j = 0; j < n_stages; ++j) L.beta[i][j] = beta[i * n_stages + j];
     L.h_val[0] = h;
     L.norm = norm;
-    A.X.H = H; A.X.dout = dout; A.X.dx0 = dx0;
-    for (int j = 0; j < n_stages; ++j) A.X.c_out[j] = c_out[j];
-    A.X.n_out = n_stages;
+    X.H = H; X.dout = dout; X.dx0 = dx0;
+    for (int j = 0; j < n_stages; ++j) X.c_out[j] = c_out[j];
+    X.n_out = n_stages;
+    return 0;
+}
+
+extern "C" int nlbac_concat_rk_traj_bwd(const nlbac_mlp* net, int n, int H, int n_stages, const float* beta,
+                                        const float* c_out, float h, const float* acts, long acts_ls, int acts_bits,
+                                        const float* norm, const float* dout, float* dx0, float* dc, float* dK,
+                                        float* dz, nlbac_stream_t s) {
+    if (ctraj_check(net, n, H, n_stages, beta, c_out, h, acts_bits, "nlbac_concat_rk_traj_bwd")) return -1;
+    ConcatRkTrajBwdLaunch A;
+    memset(&A, 0, sizeof(A));
+    if (ctraj_bwd_fill(A.L, A.X, net, n, H, n_stages, beta, c_out, h, acts, acts_ls, acts_bits, norm, dout, dx0, dc, dK,
+                       dz, "nlbac_concat_rk_traj_bwd")) return -1;
     using KernelB = void (*)(const ConcatRkTrajBwdLaunch);
-    // the one-step launcher's choice of instance (nlbac_concat_rr_bwd_launch)
-    static const KernelB kb[2][3][2] = {{{concat_traj_bwd_kernel<4, 4, 0, 2>, concat_traj_bwd_kernel<4, 4, 1, 2>},
-                                         {concat_traj_bwd_kernel<7, 1, 0, 2>, concat_traj_bwd_kernel<7, 1, 1, 2>},
-                                         {concat_traj_bwd_kernel<8, 4, 0, 2>, concat_traj_bwd_kernel<8, 4, 1, 2>}},
-                                        {{concat_traj_bwd_kernel<4, 4, 0, 4>, concat_traj_bwd_kernel<4, 4, 1, 4>},
-                                         {concat_traj_bwd_kernel<7, 1, 0, 4>, concat_traj_bwd_kernel<7, 1, 1, 4>},
-                                         {concat_traj_bwd_kernel<8, 4, 0, 4>, concat_traj_bwd_kernel<8, 4, 1, 4>}}};
+    CONCAT_TRAJ_TABLE(concat_traj_bwd_kernel, KernelB, kb);
     const int nw = crr_waves(n, n), tile = 16 * nw;
     hipLaunchKernelGGL(kb[nw == 4][crr_shape_index(net->hid)][acts_bits ? 1 : 0], dim3(nlbac_ceil_div(n, tile)),
                        dim3(64 * nw), crr_bwd_lds(tile), (hipStream_t)s, A);
     NLBAC_CHECK_LAUNCH("nlbac_concat_rk_traj_bwd");
+    return 0;
+}
+
+// ---- the solution on a time grid: a step size per interval (hs [H] on the device for the kernel, hs_host [H] beside it
+//      for the launcher's checks, nlbac_grid_steps_check), one set of carried columns c [n][n_c], dc [n][n_c] summed over
+//      the intervals
+extern "C" int nlbac_concat_rk_grid_fwd(const nlbac_mlp* net, const float* x0, const float* c, int n, int H,
+                                        int n_stages, const float* beta, const float* c_out, const float* hs,
+                                        const float* hs_host, float* out, float* Xin, float* acts, long acts_ls,
+                                        int acts_bits, const float* norm, nlbac_stream_t s) {
+    if (ctraj_check(net, n, H, n_stages, beta, c_out, 1.f, acts_bits, "nlbac_concat_rk_grid_fwd")) return -1;
+    if (nlbac_grid_steps_check(hs, hs_host, H, "nlbac_concat_rk_grid_fwd")) return -1;
+    ConcatRkGridFwdLaunch A;
+    memset(&A, 0, sizeof(A));
+    if (ctraj_fwd_fill(A.L, net, x0, c, n, n_stages, beta, c_out, hs_host[0], out, Xin, acts, acts_ls, acts_bits, norm,
+                       "nlbac_concat_rk_grid_fwd")) return -1;
+    A.H = H; A.hs = hs;
+    using KernelF = void (*)(const ConcatRkGridFwdLaunch);
+    CONCAT_TRAJ_TABLE(concat_grid_fwd_kernel, KernelF, kf);
+    const int nw = crr_waves(n, n), tile = 16 * nw;
+    hipLaunchKernelGGL(kf[nw == 4][crr_shape_index(net->hid)][acts_bits ? 1 : 0], dim3(nlbac_ceil_div(n, tile)),
+                       dim3(64 * nw), crr_fwd_lds(tile), (hipStream_t)s, A);
+    NLBAC_CHECK_LAUNCH("nlbac_concat_rk_grid_fwd");
+    return 0;
+}
+
+extern "C" int nlbac_concat_rk_grid_bwd(const nlbac_mlp* net, int n, int H, int n_stages, const float* beta,
+                                        const float* c_out, const float* hs, const float* hs_host, const float* acts,
+                                        long acts_ls, int acts_bits, const float* norm, const float* dout, float* dx0,
+                                        float* dc, float* dK, float* dz, nlbac_stream_t s) {
+    if (ctraj_check(net, n, H, n_stages, beta, c_out, 1.f, acts_bits, "nlbac_concat_rk_grid_bwd")) return -1;
+    if (nlbac_grid_steps_check(hs, hs_host, H, "nlbac_concat_rk_grid_bwd")) return -1;
+    ConcatRkGridBwdLaunch A;
+    memset(&A, 0, sizeof(A));
+    if (ctraj_bwd_fill(A.L, A.X, net, n, H, n_stages, beta, c_out, hs_host[H - 1], acts, acts_ls, acts_bits, norm, dout,
+                       dx0, dc, dK, dz, "nlbac_concat_rk_grid_bwd")) return -1;
+    A.hs = hs;
+    using KernelB = void (*)(const ConcatRkGridBwdLaunch);
+    CONCAT_TRAJ_TABLE(concat_grid_bwd_kernel, KernelB, kb);
+    const int nw = crr_waves(n, n), tile = 16 * nw;
+    hipLaunchKernelGGL(kb[nw == 4][crr_shape_index(net->hid)][acts_bits ? 1 : 0], dim3(nlbac_ceil_div(n, tile)),
+                       dim3(64 * nw), crr_bwd_lds(tile), (hipStream_t)s, A);
+    NLBAC_CHECK_LAUNCH("nlbac_concat_rk_grid_bwd");
     return 0;
 }

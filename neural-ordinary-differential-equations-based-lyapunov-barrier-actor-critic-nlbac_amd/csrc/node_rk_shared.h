@@ -682,6 +682,10 @@ __device__ __forceinline__ void rk_bwd_outputs(const NodeRkBwdLaunch& L, const R
 // ---------------------------------------------------------------------------------------------------------------
 // one-launch fixed-grid trajectories (node_traj_kernels.hip): H intervals of euler / rk4 with a new action per interval,
 // every row on its own — a tile walks the intervals one after the other, no workgroup waits for another
+// GRID (nlbac_node_rk_grid_*: the solution on a time grid): the intervals have a step size each (hs[k], written to sH
+// by the body at the top of interval k) and ONE set of actions u [n][n_u] for all of them; the backward sums the
+// intervals' du in the tile's LDS (sDYup, which only the interpolant's backward uses otherwise), k = H-1 .. 0:
+//     total = du_{H-1};  total = total + du_k  —  the fp32 adds the chained path does between its launches
 // ---------------------------------------------------------------------------------------------------------------
 struct NodeRkTrajBwd {
     int H;
@@ -693,11 +697,11 @@ struct NodeRkTrajBwd {
 // forward, behind interval k's last stage: out[k] = y0 + h sum_j c_j K_j (rk_fwd_outputs_and_control's arithmetic) to
 // global and, as interval k+1's y0, to sY0; interval k+1's actions to sU.  One (row, component) per thread; ends with a
 // barrier (every thread must call it).
-template <int NTHR>
+template <int NTHR, bool GRID = false>
 __device__ __forceinline__ void rk_traj_advance(const NodeRkLaunch& L, const RkFwdTile& T, int row0, int k, int H, int tid) {
     static_assert(NTHR >= NLBAC_MLP_TILE * RK_MAX_NS, "one (row, component) per thread");
     const int n = L.n, ns = L.n_s, nu = L.n_u;
-    const bool more = k + 1 < H;
+    const bool more = !GRID && k + 1 < H;      // (GRID: the actions in sU are every interval's)
     float vu = 0.f;
     if (more && tid < NLBAC_MLP_TILE * RK_MAX_NU) {
         const int m = tid >> 2, c = tid & 3;
@@ -724,16 +728,16 @@ __device__ __forceinline__ void rk_traj_advance(const NodeRkLaunch& L, const RkF
 // backward, before interval k's stages (kk = H-1-k intervals done): u_k -> sU, du = 0, and from
 // d = dout[k+1] (+ the dy0 of interval k+1, in sDY0 when kk > 0): dy0 = 0 + d, dK_j = 0 + (c_j h) d — what
 // nlbac_rk_stage_bwd leaves for the one-step backward (same arithmetic).  No barrier inside.
-template <int NTHR>
+template <int NTHR, bool GRID = false>
 __device__ __forceinline__ void rk_traj_bwd_begin(const NodeRkBwdLaunch& L, const NodeRkTrajBwd& X, const RkBwdTile& T,
-                                                  int row0, int k, int kk, int tid) {
+                                                  int row0, int k, int kk, int tid, const float* hs = nullptr) {
     static_assert(NTHR >= NLBAC_MLP_TILE * RK_MAX_NS, "one (row, component) per thread");
     const int n = L.n, ns = L.n_s, nu = L.n_u;
     float vu = 0.f, vd = 0.f;
-    const float vh = L.h_val[0];          // (one problem: one step size for every row)
+    const float vh = GRID ? hs[k] : L.h_val[0];          // (one problem: one step size for every row)
     if (tid < NLBAC_MLP_TILE * RK_MAX_NU) {
         const int m = tid >> 2, c = tid & 3;
-        vu = L.u[(long)k * n * nu + (long)min(row0 + m, n - 1) * nu + min(c, nu - 1)];
+        vu = L.u[(long)(GRID ? 0 : k) * n * nu + (long)min(row0 + m, n - 1) * nu + min(c, nu - 1)];
     }
     if (tid < NLBAC_MLP_TILE * RK_MAX_NS) {
         const int m = tid >> 3, c = tid & 7;
@@ -762,7 +766,7 @@ __device__ __forceinline__ void rk_traj_bwd_begin(const NodeRkBwdLaunch& L, cons
 
 // backward, behind interval k's stages: du_k (and dK when the weight gradients want it) to global; the dy0 stays in sDY0
 // for interval k-1, after interval 0 dx0 = dout[0] + dy0.  No barrier inside.
-template <int NTHR>
+template <int NTHR, bool GRID = false>
 __device__ __forceinline__ void rk_traj_bwd_end(const NodeRkBwdLaunch& L, const NodeRkTrajBwd& X, const RkBwdWhere& w,
                                                 const RkBwdTile& T, int row0, int k, int tid) {
     const int n = L.n, ns = L.n_s, nu = L.n_u;
@@ -774,7 +778,14 @@ __device__ __forceinline__ void rk_traj_bwd_end(const NodeRkBwdLaunch& L, const 
         }
     for (int idx = tid; idx < NLBAC_MLP_TILE * nu; idx += NTHR) {
         const int m = idx / nu, c = idx - m * nu, row = row0 + m;
-        if (row < n) L.du[(long)k * n * nu + (long)row * nu + c] = T.sDU[m * RK_MAX_NU + c];
+        if constexpr (GRID) {       // (the same thread holds (m, c) in every interval: no barrier between them)
+            float a = T.sDU[m * RK_MAX_NU + c];
+            if (k != X.H - 1) a = T.sDYup[m * RK_MAX_NU + c] + a;
+            T.sDYup[m * RK_MAX_NU + c] = a;
+            if (k == 0 && row < n) L.du[(long)row * nu + c] = a;
+        } else {
+            if (row < n) L.du[(long)k * n * nu + (long)row * nu + c] = T.sDU[m * RK_MAX_NU + c];
+        }
     }
     if (k == 0)
         for (int idx = tid; idx < NLBAC_MLP_TILE * ns; idx += NTHR) {

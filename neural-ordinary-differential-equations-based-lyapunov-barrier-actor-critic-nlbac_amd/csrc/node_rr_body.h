@@ -60,8 +60,11 @@ __device__ long long g_bwd_stamps[2 * 256];      // (defined in the one translat
 // TRAJ: H intervals of a fixed-grid rollout in one launch (node_traj_kernels.hip).  Interval k's step is the one-step
 // launch's with y0 = out[k-1] (kept in the tile's LDS, sY0) and u = L.u + k n n_u; its K / Y / G / rows / words sit at
 // stage index k S + st of H S stages, and out[k] = L.out + k n n_s.  TRAJ = false, H = 1: the one-step kernel.
-template <int NB, int R, int BITS, int SPLIT, bool TRAJ = false>
-__device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 1) {
+// GRID (with TRAJ; nlbac_node_rk_grid_fwd): interval k's step size is hs[k] (device array), put into sH at the top of
+// the interval, and the actions L.u [n][n_u] are the same for every interval (node_rk_shared.h).
+template <int NB, int R, int BITS, int SPLIT, bool TRAJ = false, bool GRID = false>
+__device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 1, const float* hs = nullptr) {
+    static_assert(TRAJ || !GRID, "a time grid is a trajectory");
     static_assert(BITS != 2 || SPLIT == 0, "rows + words: the fit's forward is the unsplit one (same sums as mode 0)");
     constexpr bool WORDS = BITS != 0, ROWS = BITS != 1;
     using S = RRShape<NB, R>;
@@ -198,6 +201,9 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
         w.gY = L.Y + (long)kS * n * ns;
         w.gG = L.G + (long)kS * n * gout;
     }
+    // (GRID) this interval's step size: behind the barrier that ended the interval before, in front of the one behind
+    // the first stage's input (which, at stage 0, uses no step size; nlbac_node_rk_grid_fwd requires stage_begin == 0)
+    if constexpr (GRID) { if (tid < NLBAC_MLP_TILE) T.sH[tid] = hs[k]; }
     for (int st = L.stage_begin; st < stage_end; ++st) {
         const int sb = 2 + 8 * (st - L.stage_begin);
         (void)sb;
@@ -485,7 +491,7 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
         __syncthreads();
         RSTAMP(sb + 7)
     }
-    if constexpr (TRAJ) rk_traj_advance<256>(L, T, row0, k, H, tid);
+    if constexpr (TRAJ) rk_traj_advance<256, GRID>(L, T, row0, k, H, tid);
     }
     if constexpr (TRAJ) return;
 #ifdef RR_TIMING
@@ -507,8 +513,12 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
 // formed from it as nlbac_rk_stage_bwd forms them from the step's output combination, u = L.u + k n n_u, du -> L.du +
 // k n n_u; rows / words / G / dK / dG / dz at stage index k S + st of H S stages.  X.dx0 = X.dout[0] + the dy0 of
 // interval 0.  TRAJ = false (X null): the one-step kernel.
-template <int NB, int R, int BITS, int SPLIT, bool TRAJ = false>
-__device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const NodeRkTrajBwd* X = nullptr) {
+// GRID (with TRAJ; nlbac_node_rk_grid_bwd): step size hs[k] per interval, one set of actions L.u [n][n_u], and L.du
+// [n][n_u] the sum of the intervals' du, formed in the tile's LDS in the order k = H-1 .. 0 (node_rk_shared.h).
+template <int NB, int R, int BITS, int SPLIT, bool TRAJ = false, bool GRID = false>
+__device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const NodeRkTrajBwd* X = nullptr,
+                                                 const float* hs = nullptr) {
+    static_assert(TRAJ || !GRID, "a time grid is a trajectory");
     constexpr bool WORDS = BITS != 0;          // the gates come from the mask words (1, 2) or from the activation rows (0)
     constexpr bool DZ = BITS != 1;             // dz rows are stored when asked for (0; 2: the fit, words behind the rows)
     using S = RRShape<NB, R>;
@@ -619,7 +629,7 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
         w.gG = L.G + (long)kS * n * gout;
         w.gdG = L.dG ? L.dG + (long)kS * n * gout : nullptr;
         w.gdK = L.dK ? L.dK + (long)kS * n * ns : nullptr;
-        rk_traj_bwd_begin<256>(L, *X, T, row0, k, kk, tid);
+        rk_traj_bwd_begin<256, GRID>(L, *X, T, row0, k, kk, tid, hs);
         __syncthreads();
     }
 #pragma unroll
@@ -908,7 +918,7 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
     __syncthreads();
     BWSTAMP(2 + 8 * 7)
     if constexpr (TRAJ) {
-        rk_traj_bwd_end<256>(L, *X, w, T, row0, k, tid);
+        rk_traj_bwd_end<256, GRID>(L, *X, w, T, row0, k, tid);
         __syncthreads();
     }
     }

@@ -696,7 +696,8 @@ def odeint(func, y0, t, *, method="dopri5", atol=1e-7, rtol=1e-5, **options):
     ``'euler'`` / ``'rk4'`` (one step over the interval, torchdiffeq's fixed-grid semantics) or ``'dopri5'``.
     The packed MFMA copies of the weights are refreshed first, so a ``torch.optim`` step on ``func.parameters()``
     between calls is picked up.  For several intervals ahead with a new control each, differentiated as a whole, use
-    ``nlbac_amd.rollout.rollout``."""
+    ``nlbac_amd.rollout.rollout``; for the solution at every point of a longer time grid (euler / rk4), use
+    ``nlbac_amd.ode_grid.odeint_grid``."""
     return _odeint(func, y0, t, method, atol, rtol, False, options)
 
 

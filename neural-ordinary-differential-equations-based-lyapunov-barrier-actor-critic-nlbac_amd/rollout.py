@@ -94,10 +94,11 @@ def _one_launch_ok(func, method):
     return _lib.load().nlbac_node_rk_traj_ok(C.byref(f.desc), C.byref(g.desc)) == 1
 
 
-def _chain_solvers(func, mode, H):
+def _chain_solvers(func, mode, H, key="_rollout_solvers"):
     """Solvers of the chained path, cached on the model (apart from ``odeint``'s and any agent task's): one per interval
-    when a backward follows (each keeps its interval's state), one for all intervals otherwise."""
-    cache = func.__dict__.setdefault("_rollout_solvers", {})
+    when a backward follows (each keeps its interval's state), one for all intervals otherwise.  ``key``: the cache's
+    name on the model (``ode_grid.odeint_grid`` keeps solvers of its own)."""
+    cache = func.__dict__.setdefault(key, {})
     lst = cache.setdefault(mode, [])
     need = 1 if mode == "none" else H
     if len(lst) < need:
@@ -257,18 +258,21 @@ def _chain_backward(func, svs, solve_ids, dout, need_p):
     return dout[0] + carry, du_all, flat
 
 
-def _traj_backward(func, tj, u, dt, dout, need_p):
+def _traj_backward(func, tj, u, dt, dout, need_p, hs=None):
+    """``hs`` (``ode_grid``): (device array, host array) of the intervals' step sizes in place of ``dt`` — the time-grid
+    launch, whose ``u`` (n, n_u) is every interval's and whose ``du`` (n, n_u) is summed over the intervals."""
     n, H, S, HS = tj.n, tj.H, tj.S, tj.H * tj.S
     dev = dout.device
     z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-    dx0, du = z(n, tj.ns), z(H, n, tj.nu)
+    dx0, du = z(n, tj.ns), (z(H, n, tj.nu) if hs is None else z(n, tj.nu))
+    name, step = ("nlbac_node_rk_traj_bwd", (dt,)) if hs is None else ("nlbac_node_rk_grid_bwd", (hs[0].data_ptr(), hs[1]))
     dK = dG = dz_f = dz_g = None
     if need_p:
         dK, dG = z(HS, n, tj.ns), z(HS, n, tj.ns * tj.nu)
         dz_f, dz_g = z(tj.f.n_layers - 1, HS * n, tj.f.hid), z(tj.g.n_layers - 1, HS * n, tj.g.hid)
     p = lambda t: t.data_ptr() if t is not None else None
-    _lib.call("nlbac_node_rk_traj_bwd", C.byref(tj.f.desc), C.byref(tj.g.desc), u.data_ptr(), n, H, S, tj.beta,
-              tj.c_out, dt, tj.G.data_ptr(), tj.ptr(0), tj.ls[0], tj.ptr(1), tj.ls[1], tj.bits, dout.data_ptr(),
+    _lib.call(name, C.byref(tj.f.desc), C.byref(tj.g.desc), u.data_ptr(), n, H, S, tj.beta,
+              tj.c_out, *step, tj.G.data_ptr(), tj.ptr(0), tj.ls[0], tj.ptr(1), tj.ls[1], tj.bits, dout.data_ptr(),
               dx0.data_ptr(), du.data_ptr(), p(dK), p(dG), p(dz_f), p(dz_g), stream_ptr())
     flat = None
     if need_p:      # every stage of every interval as ONE batch of H * S * n rows through the weight-gradient launch
@@ -285,15 +289,17 @@ def _traj_backward(func, tj, u, dt, dout, need_p):
     return dx0, du, flat
 
 
-def _concat_traj_backward(func, tj, dt, dout, need_p):
+def _concat_traj_backward(func, tj, dt, dout, need_p, hs=None):
+    """``hs``: as in ``_traj_backward`` (the carried columns' gradient (n, n_c) summed over the intervals)."""
     n, H, S, HS = tj.n, tj.H, tj.S, tj.H * tj.S
     dev = dout.device
     z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-    dx0, du = z(n, tj.ns), z(H, n, tj.nc)
+    dx0, du = z(n, tj.ns), (z(H, n, tj.nc) if hs is None else z(n, tj.nc))
+    name, step = ("nlbac_concat_rk_traj_bwd", (dt,)) if hs is None else ("nlbac_concat_rk_grid_bwd", (hs[0].data_ptr(), hs[1]))
     dK = dz = None
     if need_p:
         dK, dz = z(HS * n, tj.ns), z(tj.net.n_layers - 1, HS * n, tj.net.hid)
-    _lib.call("nlbac_concat_rk_traj_bwd", C.byref(tj.net.desc), n, H, S, tj.beta, tj.c_out, dt, tj.acts.data_ptr(), tj.ls,
+    _lib.call(name, C.byref(tj.net.desc), n, H, S, tj.beta, tj.c_out, *step, tj.acts.data_ptr(), tj.ls,
               tj.bits, _ptr(tj.norm), dout.data_ptr(), dx0.data_ptr(), du.data_ptr(), _ptr(dK), _ptr(dz), stream_ptr())
     flat = None
     if need_p:      # every stage of every interval as ONE batch of H * S * n rows: layer 0's input is the kept Xin row

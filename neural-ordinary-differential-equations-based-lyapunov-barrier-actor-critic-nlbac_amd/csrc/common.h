@@ -37,6 +37,17 @@ static inline int nlbac_grid_steps_check(const float* hs, const float* hs_host, 
     return 0;
 }
 
+// The tableau of such a launch, beta [n_stages][n_stages] row-major and c_out [n_stages], into a launch descriptor's arrays.
+template <int S>
+static inline void nlbac_tableau_copy(float (&beta_to)[S][S], float (&c_out_to)[S], int& n_out_to, int n_stages,
+                                      const float* beta, const float* c_out) {
+    for (int i = 0; i < n_stages; ++i) {
+        for (int j = 0; j < n_stages; ++j) beta_to[i][j] = beta[i * n_stages + j];
+        c_out_to[i] = c_out[i];
+    }
+    n_out_to = n_stages;
+}
+
 // Block-wide deterministic sum of NV values per thread (256-thread blocks):
 // wave shuffle tree, then a fixed-order combine of the 4 wave results.
 template <int NV>

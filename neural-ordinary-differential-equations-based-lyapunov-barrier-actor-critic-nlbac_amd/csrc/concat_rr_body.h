@@ -952,3 +952,23 @@ static inline size_t crr_fwd_lds(int tile) {
 static inline size_t crr_bwd_lds(int tile) {
     return (size_t)(CK_MAX_STAGES * tile * CK_LD + tile * (1 + CK_LD + CK_NC + 16 + CK_LD) + 4 * 8 * 64) * sizeof(float);
 }
+
+// the instances of one kernel template KERN<NB, R, BITS, NW>, [NW == 4][shape][BITS]
+template <typename Launch>
+struct ConcatRrTable {
+    void (*k[2][3][2])(const Launch);
+};
+
+#define CONCAT_RR_TABLE(KERN)                                                                                           \
+    {{{{KERN<4, 4, 0, 2>, KERN<4, 4, 1, 2>}, {KERN<7, 1, 0, 2>, KERN<7, 1, 1, 2>}, {KERN<8, 4, 0, 2>, KERN<8, 4, 1, 2>}},  \
+      {{KERN<4, 4, 0, 4>, KERN<4, 4, 1, 4>}, {KERN<7, 1, 0, 4>, KERN<7, 1, 1, 4>}, {KERN<8, 4, 0, 4>, KERN<8, 4, 1, 4>}}}}
+
+// launch the instance of `t` for a net `hid` wide and this acts_bits over n rows in problems of rpp rows; `lds` is
+// crr_fwd_lds or crr_bwd_lds
+template <typename Launch>
+static void crr_start(const ConcatRrTable<Launch>& t, const Launch& A, int hid, int n, int rpp, int acts_bits,
+                      size_t (*lds)(int), hipStream_t s) {
+    const int nw = crr_waves(n, rpp), tile = 16 * nw;
+    hipLaunchKernelGGL(t.k[nw == 4][crr_shape_index(hid)][acts_bits ? 1 : 0], dim3(nlbac_ceil_div(n, tile)),
+                       dim3(64 * nw), lds(tile), s, A);
+}

@@ -33,34 +33,19 @@ static bool crr_eligible(const nlbac_mlp& net) {
            net.rr_fwd_off >= 0 && net.rr_bwd_off >= 0 && net.in_dim <= CRR_MAX_IN && net.out_dim <= CK_NS;
 }
 
+// which instance, how many waves and how much LDS: concat_rr_body.h's host section, shared with the trajectory launchers
 int nlbac_concat_rr_fwd_launch(ConcatRkLaunch& L, hipStream_t s) {
     if (!crr_eligible(L.net)) return 1;
-    using KernelF = void (*)(const ConcatRkLaunch);
-    static const KernelF kf[2][3][2] = {{{concat_rr_fwd_kernel<4, 4, 0, 2>, concat_rr_fwd_kernel<4, 4, 1, 2>},
-                                         {concat_rr_fwd_kernel<7, 1, 0, 2>, concat_rr_fwd_kernel<7, 1, 1, 2>},
-                                         {concat_rr_fwd_kernel<8, 4, 0, 2>, concat_rr_fwd_kernel<8, 4, 1, 2>}},
-                                        {{concat_rr_fwd_kernel<4, 4, 0, 4>, concat_rr_fwd_kernel<4, 4, 1, 4>},
-                                         {concat_rr_fwd_kernel<7, 1, 0, 4>, concat_rr_fwd_kernel<7, 1, 1, 4>},
-                                         {concat_rr_fwd_kernel<8, 4, 0, 4>, concat_rr_fwd_kernel<8, 4, 1, 4>}}};
-    const int nw = crr_waves(L.n, L.rpp), tile = 16 * nw;
-    const size_t lds = crr_fwd_lds(tile);
-    hipLaunchKernelGGL(kf[nw == 4][crr_shape_index(L.net.hid)][L.acts_bits ? 1 : 0], dim3(nlbac_ceil_div(L.n, tile)), dim3(64 * nw), lds, s, L);
+    static const ConcatRrTable<ConcatRkLaunch> table = CONCAT_RR_TABLE(concat_rr_fwd_kernel);
+    crr_start(table, L, L.net.hid, L.n, L.rpp, L.acts_bits, crr_fwd_lds, s);
     NLBAC_CHECK_LAUNCH("nlbac_concat_rk_fwd(rr)");
     return 0;
 }
 
 int nlbac_concat_rr_bwd_launch(ConcatRkBwdLaunch& L, hipStream_t s) {
     if (!crr_eligible(L.net)) return 1;
-    using KernelB = void (*)(const ConcatRkBwdLaunch);
-    static const KernelB kb[2][3][2] = {{{concat_rr_bwd_kernel<4, 4, 0, 2>, concat_rr_bwd_kernel<4, 4, 1, 2>},
-                                         {concat_rr_bwd_kernel<7, 1, 0, 2>, concat_rr_bwd_kernel<7, 1, 1, 2>},
-                                         {concat_rr_bwd_kernel<8, 4, 0, 2>, concat_rr_bwd_kernel<8, 4, 1, 2>}},
-                                        {{concat_rr_bwd_kernel<4, 4, 0, 4>, concat_rr_bwd_kernel<4, 4, 1, 4>},
-                                         {concat_rr_bwd_kernel<7, 1, 0, 4>, concat_rr_bwd_kernel<7, 1, 1, 4>},
-                                         {concat_rr_bwd_kernel<8, 4, 0, 4>, concat_rr_bwd_kernel<8, 4, 1, 4>}}};
-    const int nw = crr_waves(L.n, L.rpp), tile = 16 * nw;
-    const size_t lds = crr_bwd_lds(tile);
-    hipLaunchKernelGGL(kb[nw == 4][crr_shape_index(L.net.hid)][L.acts_bits ? 1 : 0], dim3(nlbac_ceil_div(L.n, tile)), dim3(64 * nw), lds, s, L);
+    static const ConcatRrTable<ConcatRkBwdLaunch> table = CONCAT_RR_TABLE(concat_rr_bwd_kernel);
+    crr_start(table, L, L.net.hid, L.n, L.rpp, L.acts_bits, crr_bwd_lds, s);
     NLBAC_CHECK_LAUNCH("nlbac_concat_rk_bwd(rr)");
     return 0;
 }

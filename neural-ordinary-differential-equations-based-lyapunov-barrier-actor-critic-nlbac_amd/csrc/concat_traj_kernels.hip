@@ -82,10 +82,25 @@ static int ctraj_check(const nlbac_mlp* net, int n, int H, int n_stages, const f
     return 0;
 }
 
-// what the scalar-step launch and the time-grid launch share: the descriptor of the interval's one-step launch
-static int ctraj_fwd_fill(ConcatRkLaunch& L, const nlbac_mlp* net, const float* x0, const float* c, int n, int n_stages,
-                          const float* beta, const float* c_out, float h, float* out, float* Xin, float* acts,
-                          long acts_ls, int acts_bits, const float* norm, const char* who) {
+// a time-grid launch carries a step size per interval
+template <typename Launch>
+constexpr bool ctraj_on_grid = std::is_same<Launch, ConcatRkGridFwdLaunch>::value || std::is_same<Launch, ConcatRkGridBwdLaunch>::value;
+
+// The forward launch of `who` (an entry point below) over H intervals: the instances of its kernel template in `table`
+// (chosen as the one-step launcher chooses, concat_rr_body.h, so that the sums are the same), its step — h for every
+// interval, or (time grid) hs [H] on the device for the kernel with hs_host [H] beside it for the checks here — and
+// what the interval's one-step launch takes.
+template <typename Launch>
+static int ctraj_fwd(const ConcatRrTable<Launch>& table, const char* who, float h, const float* hs, const float* hs_host,
+                     const nlbac_mlp* net, const float* x0, const float* c, int n, int H, int n_stages, const float* beta,
+                     const float* c_out, float* out, float* Xin, float* acts, long acts_ls, int acts_bits,
+                     const float* norm, nlbac_stream_t s) {
+    constexpr bool grid = ctraj_on_grid<Launch>;
+    if (ctraj_check(net, n, H, n_stages, beta, c_out, grid ? 1.f : h, acts_bits, who)) return -1;
+    if (grid && nlbac_grid_steps_check(hs, hs_host, H, who)) return -1;
+    Launch A;
+    memset(&A, 0, sizeof(A));
+    ConcatRkLaunch& L = A.L;
     NLBAC_REQUIRE(x0 && c && out, "%s: null pointer", who);
     NLBAC_REQUIRE(acts || acts_bits == 0, "%s: acts_bits without acts", who);
     NLBAC_REQUIRE(!Xin || (acts && acts_bits == 0), "%s: Xin goes with the activation rows", who);
@@ -93,51 +108,31 @@ static int ctraj_fwd_fill(ConcatRkLaunch& L, const nlbac_mlp* net, const float* 
     L.y0 = x0; L.c = c;
     L.n = n; L.rpp = n; L.n_s = net->out_dim; L.n_c = net->in_dim - net->out_dim;
     L.stage_begin = 0; L.stage_end = n_stages; L.S_total = n_stages;
-    for (int i = 0; i < n_stages; ++i) {
-        for (int j = 0; j < n_stages; ++j) L.beta[i][j] = beta[i * n_stages + j];
-        L.c_out[i] = c_out[i];
-    }
-    L.n_out = n_stages;
-    L.h_val[0] = h;
+    nlbac_tableau_copy(L.beta, L.c_out, L.n_out, n_stages, beta, c_out);
+    L.h_val[0] = grid ? hs_host[0] : h;
     L.acts = acts; L.acts_ls = acts_ls; L.acts_bits = acts_bits;
     L.out = out;
     L.norm = norm; L.Xn = Xin;
     L.norm_mode = -1;
-    return 0;
-}
-
-// the one-step launchers' choice of instance (nlbac_concat_rr_fwd_launch / _bwd_launch), so that the sums are the same
-#define CONCAT_TRAJ_TABLE(KERN, KernelT, tab)                                                                           \
-    static const KernelT tab[2][3][2] = {{{KERN<4, 4, 0, 2>, KERN<4, 4, 1, 2>},                                         \
-                                          {KERN<7, 1, 0, 2>, KERN<7, 1, 1, 2>},                                         \
-                                          {KERN<8, 4, 0, 2>, KERN<8, 4, 1, 2>}},                                        \
-                                         {{KERN<4, 4, 0, 4>, KERN<4, 4, 1, 4>},                                         \
-                                          {KERN<7, 1, 0, 4>, KERN<7, 1, 1, 4>},                                         \
-                                          {KERN<8, 4, 0, 4>, KERN<8, 4, 1, 4>}}}
-
-extern "C" int nlbac_concat_rk_traj_fwd(const nlbac_mlp* net, const float* x0, const float* c, int n, int H,
-                                        int n_stages, const float* beta, const float* c_out, float h, float* out,
-                                        float* Xin, float* acts, long acts_ls, int acts_bits, const float* norm,
-                                        nlbac_stream_t s) {
-    if (ctraj_check(net, n, H, n_stages, beta, c_out, h, acts_bits, "nlbac_concat_rk_traj_fwd")) return -1;
-    ConcatRkTrajFwdLaunch A;
-    memset(&A, 0, sizeof(A));
-    if (ctraj_fwd_fill(A.L, net, x0, c, n, n_stages, beta, c_out, h, out, Xin, acts, acts_ls, acts_bits, norm,
-                       "nlbac_concat_rk_traj_fwd")) return -1;
     A.H = H;
-    using KernelF = void (*)(const ConcatRkTrajFwdLaunch);
-    CONCAT_TRAJ_TABLE(concat_traj_fwd_kernel, KernelF, kf);
-    const int nw = crr_waves(n, n), tile = 16 * nw;
-    hipLaunchKernelGGL(kf[nw == 4][crr_shape_index(net->hid)][acts_bits ? 1 : 0], dim3(nlbac_ceil_div(n, tile)),
-                       dim3(64 * nw), crr_fwd_lds(tile), (hipStream_t)s, A);
-    NLBAC_CHECK_LAUNCH("nlbac_concat_rk_traj_fwd");
+    if constexpr (grid) A.hs = hs;
+    crr_start(table, A, net->hid, n, n, acts_bits, crr_fwd_lds, (hipStream_t)s);
+    NLBAC_CHECK_LAUNCH(who);
     return 0;
 }
 
-static int ctraj_bwd_fill(ConcatRkBwdLaunch& L, ConcatRkTrajBwd& X, const nlbac_mlp* net, int n, int H, int n_stages,
-                          const float* beta, const float* c_out, float h, const float* acts, long acts_ls, int acts_bits,
-                          const float* norm, const float* dout, float* dx0, float* dc, float* dK, float* dz,
-                          const char* who) {
+// The backward launch of `who`: as ctraj_fwd.
+template <typename Launch>
+static int ctraj_bwd(const ConcatRrTable<Launch>& table, const char* who, float h, const float* hs, const float* hs_host,
+                     const nlbac_mlp* net, int n, int H, int n_stages, const float* beta, const float* c_out,
+                     const float* acts, long acts_ls, int acts_bits, const float* norm, const float* dout, float* dx0,
+                     float* dc, float* dK, float* dz, nlbac_stream_t s) {
+    constexpr bool grid = ctraj_on_grid<Launch>;
+    if (ctraj_check(net, n, H, n_stages, beta, c_out, grid ? 1.f : h, acts_bits, who)) return -1;
+    if (grid && nlbac_grid_steps_check(hs, hs_host, H, who)) return -1;
+    Launch A;
+    memset(&A, 0, sizeof(A));
+    ConcatRkBwdLaunch& L = A.L;
     NLBAC_REQUIRE(!(acts_bits == 1 && dz), "%s: weight gradients need the activation rows, not mask words", who);
     NLBAC_REQUIRE(acts && dout && dx0 && dc, "%s: null pointer", who);
     NLBAC_REQUIRE((dz == nullptr) == (dK == nullptr), "%s: dz and dK go together", who);
@@ -147,32 +142,32 @@ static int ctraj_bwd_fill(ConcatRkBwdLaunch& L, ConcatRkTrajBwd& X, const nlbac_
     L.dc = dc;
     L.n = n; L.rpp = n; L.n_s = net->out_dim; L.n_c = net->in_dim - net->out_dim;
     L.S_total = n_stages; L.st_lo = 0; L.st_hi = n_stages; L.dx_stage0 = 1;
-    for (int i = 0; i < n_stages; ++i)
-        for (int j = 0; j < n_stages; ++j) L.beta[i][j] = beta[i * n_stages + j];
-    L.h_val[0] = h;
+    nlbac_tableau_copy(L.beta, A.X.c_out, A.X.n_out, n_stages, beta, c_out);
+    L.h_val[0] = grid ? hs_host[H - 1] : h;
     L.norm = norm;
-    X.H = H; X.dout = dout; X.dx0 = dx0;
-    for (int j = 0; j < n_stages; ++j) X.c_out[j] = c_out[j];
-    X.n_out = n_stages;
+    A.X.H = H; A.X.dout = dout; A.X.dx0 = dx0;
+    if constexpr (grid) A.hs = hs;
+    crr_start(table, A, net->hid, n, n, acts_bits, crr_bwd_lds, (hipStream_t)s);
+    NLBAC_CHECK_LAUNCH(who);
     return 0;
+}
+
+extern "C" int nlbac_concat_rk_traj_fwd(const nlbac_mlp* net, const float* x0, const float* c, int n, int H,
+                                        int n_stages, const float* beta, const float* c_out, float h, float* out,
+                                        float* Xin, float* acts, long acts_ls, int acts_bits, const float* norm,
+                                        nlbac_stream_t s) {
+    static const ConcatRrTable<ConcatRkTrajFwdLaunch> table = CONCAT_RR_TABLE(concat_traj_fwd_kernel);
+    return ctraj_fwd(table, "nlbac_concat_rk_traj_fwd", h, nullptr, nullptr, net, x0, c, n, H, n_stages, beta, c_out, out,
+                     Xin, acts, acts_ls, acts_bits, norm, s);
 }
 
 extern "C" int nlbac_concat_rk_traj_bwd(const nlbac_mlp* net, int n, int H, int n_stages, const float* beta,
                                         const float* c_out, float h, const float* acts, long acts_ls, int acts_bits,
                                         const float* norm, const float* dout, float* dx0, float* dc, float* dK,
                                         float* dz, nlbac_stream_t s) {
-    if (ctraj_check(net, n, H, n_stages, beta, c_out, h, acts_bits, "nlbac_concat_rk_traj_bwd")) return -1;
-    ConcatRkTrajBwdLaunch A;
-    memset(&A, 0, sizeof(A));
-    if (ctraj_bwd_fill(A.L, A.X, net, n, H, n_stages, beta, c_out, h, acts, acts_ls, acts_bits, norm, dout, dx0, dc, dK,
-                       dz, "nlbac_concat_rk_traj_bwd")) return -1;
-    using KernelB = void (*)(const ConcatRkTrajBwdLaunch);
-    CONCAT_TRAJ_TABLE(concat_traj_bwd_kernel, KernelB, kb);
-    const int nw = crr_waves(n, n), tile = 16 * nw;
-    hipLaunchKernelGGL(kb[nw == 4][crr_shape_index(net->hid)][acts_bits ? 1 : 0], dim3(nlbac_ceil_div(n, tile)),
-                       dim3(64 * nw), crr_bwd_lds(tile), (hipStream_t)s, A);
-    NLBAC_CHECK_LAUNCH("nlbac_concat_rk_traj_bwd");
-    return 0;
+    static const ConcatRrTable<ConcatRkTrajBwdLaunch> table = CONCAT_RR_TABLE(concat_traj_bwd_kernel);
+    return ctraj_bwd(table, "nlbac_concat_rk_traj_bwd", h, nullptr, nullptr, net, n, H, n_stages, beta, c_out, acts,
+                     acts_ls, acts_bits, norm, dout, dx0, dc, dK, dz, s);
 }
 
 // ---- the solution on a time grid: a step size per interval (hs [H] on the device for the kernel, hs_host [H] beside it
@@ -182,38 +177,16 @@ extern "C" int nlbac_concat_rk_grid_fwd(const nlbac_mlp* net, const float* x0, c
                                         int n_stages, const float* beta, const float* c_out, const float* hs,
                                         const float* hs_host, float* out, float* Xin, float* acts, long acts_ls,
                                         int acts_bits, const float* norm, nlbac_stream_t s) {
-    if (ctraj_check(net, n, H, n_stages, beta, c_out, 1.f, acts_bits, "nlbac_concat_rk_grid_fwd")) return -1;
-    if (nlbac_grid_steps_check(hs, hs_host, H, "nlbac_concat_rk_grid_fwd")) return -1;
-    ConcatRkGridFwdLaunch A;
-    memset(&A, 0, sizeof(A));
-    if (ctraj_fwd_fill(A.L, net, x0, c, n, n_stages, beta, c_out, hs_host[0], out, Xin, acts, acts_ls, acts_bits, norm,
-                       "nlbac_concat_rk_grid_fwd")) return -1;
-    A.H = H; A.hs = hs;
-    using KernelF = void (*)(const ConcatRkGridFwdLaunch);
-    CONCAT_TRAJ_TABLE(concat_grid_fwd_kernel, KernelF, kf);
-    const int nw = crr_waves(n, n), tile = 16 * nw;
-    hipLaunchKernelGGL(kf[nw == 4][crr_shape_index(net->hid)][acts_bits ? 1 : 0], dim3(nlbac_ceil_div(n, tile)),
-                       dim3(64 * nw), crr_fwd_lds(tile), (hipStream_t)s, A);
-    NLBAC_CHECK_LAUNCH("nlbac_concat_rk_grid_fwd");
-    return 0;
+    static const ConcatRrTable<ConcatRkGridFwdLaunch> table = CONCAT_RR_TABLE(concat_grid_fwd_kernel);
+    return ctraj_fwd(table, "nlbac_concat_rk_grid_fwd", 0.f, hs, hs_host, net, x0, c, n, H, n_stages, beta, c_out, out,
+                     Xin, acts, acts_ls, acts_bits, norm, s);
 }
 
 extern "C" int nlbac_concat_rk_grid_bwd(const nlbac_mlp* net, int n, int H, int n_stages, const float* beta,
                                         const float* c_out, const float* hs, const float* hs_host, const float* acts,
                                         long acts_ls, int acts_bits, const float* norm, const float* dout, float* dx0,
                                         float* dc, float* dK, float* dz, nlbac_stream_t s) {
-    if (ctraj_check(net, n, H, n_stages, beta, c_out, 1.f, acts_bits, "nlbac_concat_rk_grid_bwd")) return -1;
-    if (nlbac_grid_steps_check(hs, hs_host, H, "nlbac_concat_rk_grid_bwd")) return -1;
-    ConcatRkGridBwdLaunch A;
-    memset(&A, 0, sizeof(A));
-    if (ctraj_bwd_fill(A.L, A.X, net, n, H, n_stages, beta, c_out, hs_host[H - 1], acts, acts_ls, acts_bits, norm, dout,
-                       dx0, dc, dK, dz, "nlbac_concat_rk_grid_bwd")) return -1;
-    A.hs = hs;
-    using KernelB = void (*)(const ConcatRkGridBwdLaunch);
-    CONCAT_TRAJ_TABLE(concat_grid_bwd_kernel, KernelB, kb);
-    const int nw = crr_waves(n, n), tile = 16 * nw;
-    hipLaunchKernelGGL(kb[nw == 4][crr_shape_index(net->hid)][acts_bits ? 1 : 0], dim3(nlbac_ceil_div(n, tile)),
-                       dim3(64 * nw), crr_bwd_lds(tile), (hipStream_t)s, A);
-    NLBAC_CHECK_LAUNCH("nlbac_concat_rk_grid_bwd");
-    return 0;
+    static const ConcatRrTable<ConcatRkGridBwdLaunch> table = CONCAT_RR_TABLE(concat_grid_bwd_kernel);
+    return ctraj_bwd(table, "nlbac_concat_rk_grid_bwd", 0.f, hs, hs_host, net, n, H, n_stages, beta, c_out, acts, acts_ls,
+                     acts_bits, norm, dout, dx0, dc, dK, dz, s);
 }

@@ -925,3 +925,48 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
     if constexpr (!TRAJ) rk_bwd_outputs<256>(L, w, T, row0, tid);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// host side: which instance of a kernel template serves a launch, and with how much LDS — one definition for the
+// one-step launchers (node_rr_kernels.hip) and the trajectory / time-grid launchers (node_traj_kernels.hip), whose
+// results are the one-step launches' bit for bit only while they pick the same instance.
+// ---------------------------------------------------------------------------------------------------------------------
+// the instances of one kernel template KERN<NB, R, BITS, SPLIT>: k [SPLIT][shape][BITS != 0], and those that keep
+// activation rows + mask words (acts_bits 2, the NODE fit) rows [SPLIT][shape].  The forward is never split with rows:
+// its rows + words instances are the unsplit ones, whose sums are those of the rows-only forward
+template <typename Launch>
+struct NodeRrTable {
+    using Kernel = void (*)(const Launch);
+    Kernel k[2][3][2];
+    Kernel rows[2][3];
+};
+
+#define NODE_RR_SHAPES(KERN, BITS, SPLIT) {KERN<4, 4, BITS, SPLIT>, KERN<7, 1, BITS, SPLIT>, KERN<8, 4, BITS, SPLIT>}
+#define NODE_RR_K(KERN)                                                                                                 \
+    {{{KERN<4, 4, 0, 0>, KERN<4, 4, 1, 0>}, {KERN<7, 1, 0, 0>, KERN<7, 1, 1, 0>}, {KERN<8, 4, 0, 0>, KERN<8, 4, 1, 0>}},  \
+     {{KERN<4, 4, 0, 1>, KERN<4, 4, 1, 1>}, {KERN<7, 1, 0, 1>, KERN<7, 1, 1, 1>}, {KERN<8, 4, 0, 1>, KERN<8, 4, 1, 1>}}}
+#define NODE_RR_FWD_TABLE(KERN) {NODE_RR_K(KERN), {NODE_RR_SHAPES(KERN, 2, 0), NODE_RR_SHAPES(KERN, 2, 0)}}
+#define NODE_RR_BWD_TABLE(KERN) {NODE_RR_K(KERN), {NODE_RR_SHAPES(KERN, 2, 0), NODE_RR_SHAPES(KERN, 2, 1)}}
+
+// launch the instance of `t` for nets `hid` wide and this acts_bits over n rows, one 32-row tile per workgroup
+template <typename Launch>
+static void node_rr_start(const NodeRrTable<Launch>& t, const Launch& A, int hid, int n, int acts_bits, bool split,
+                          size_t lds_floats, hipStream_t s) {
+    const int shape = nlbac_node_rr_shape(hid);
+    const auto k = (acts_bits == 2) ? t.rows[split][shape] : t.k[split][shape][acts_bits ? 1 : 0];
+    hipLaunchKernelGGL(k, dim3(nlbac_ceil_div(n, NLBAC_MLP_TILE)), dim3(256), lds_floats * sizeof(float), s, A);
+}
+
+// (the forward is split in mask mode only: with activation rows kept — the NODE fit, 32768 rows, two workgroups per
+//  CU — the two waves' store bursts and the hand-over cost more than the balance gains: 140 against 124 us per launch)
+template <typename Launch>
+static void node_rr_fwd_start(const NodeRrTable<Launch>& t, const Launch& A, int hid, int n, int acts_bits, hipStream_t s) {
+    node_rr_start(t, A, hid, n, acts_bits, nlbac_node_rr_split() && acts_bits == 1,
+                  RkFwdTile::floats() + NLBAC_MLP_TILE * 8 + 2 * 3 * 8 * 64 + 2 * 32 * 64 + NLBAC_MLP_TILE * RK_MAX_NS +
+                      2 * 2 * 64 + 4, s);
+}
+
+template <typename Launch>
+static void node_rr_bwd_start(const NodeRrTable<Launch>& t, const Launch& A, int hid, int n, int acts_bits, hipStream_t s) {
+    node_rr_start(t, A, hid, n, acts_bits, nlbac_node_rr_split(),
+                  RkBwdTile::floats() + 2 * 4 * 8 * 64 + 2 * 32 * 64 + 2 * 16 * 64 + 4, s);
+}

@@ -58,46 +58,19 @@ bool nlbac_node_rr_split() {
     return on;
 }
 
+// which instance and how much LDS: node_rr_body.h's host section, shared with the trajectory launchers
 int nlbac_node_rr_fwd_launch(NodeRkLaunch& L, hipStream_t s) {
     if (!nlbac_node_rr_eligible(&L.net[0], &L.net[1])) return 1;
-    using KernelF = void (*)(const NodeRkLaunch);
-    static const KernelF kf[2][3][2] = {{{node_rr_fwd_kernel<4, 4, 0, 0>, node_rr_fwd_kernel<4, 4, 1, 0>},
-                                         {node_rr_fwd_kernel<7, 1, 0, 0>, node_rr_fwd_kernel<7, 1, 1, 0>},
-                                         {node_rr_fwd_kernel<8, 4, 0, 0>, node_rr_fwd_kernel<8, 4, 1, 0>}},
-                                        {{node_rr_fwd_kernel<4, 4, 0, 1>, node_rr_fwd_kernel<4, 4, 1, 1>},
-                                         {node_rr_fwd_kernel<7, 1, 0, 1>, node_rr_fwd_kernel<7, 1, 1, 1>},
-                                         {node_rr_fwd_kernel<8, 4, 0, 1>, node_rr_fwd_kernel<8, 4, 1, 1>}}};
-    const size_t lds = (size_t)(RkFwdTile::floats() + NLBAC_MLP_TILE * 8 + 2 * 3 * 8 * 64 +
-                                2 * 32 * 64 + NLBAC_MLP_TILE * RK_MAX_NS + 2 * 2 * 64 + 4) * sizeof(float);
-    // rows + words (acts_bits 2, the NODE fit): the unsplit forward, whose sums are those of the rows-only one
-    static const KernelF kfw[3] = {node_rr_fwd_kernel<4, 4, 2, 0>, node_rr_fwd_kernel<7, 1, 2, 0>, node_rr_fwd_kernel<8, 4, 2, 0>};
-    const dim3 grid(nlbac_ceil_div(L.n, NLBAC_MLP_TILE));
-    const int shape = nlbac_node_rr_shape(L.net[0].hid);
-    // (the forward is split in mask mode only: with activation rows kept — the NODE fit, 32768 rows, two workgroups per
-    //  CU — the two waves' store bursts and the hand-over cost more than the balance gains: 140 against 124 us per launch)
-    const KernelF k = (L.acts_bits == 2) ? kfw[shape] : kf[(nlbac_node_rr_split() && L.acts_bits) ? 1 : 0][shape][L.acts_bits ? 1 : 0];
-    hipLaunchKernelGGL(k, grid, dim3(256), lds, s, L);
+    static const NodeRrTable<NodeRkLaunch> table = NODE_RR_FWD_TABLE(node_rr_fwd_kernel);
+    node_rr_fwd_start(table, L, L.net[0].hid, L.n, L.acts_bits, s);
     NLBAC_CHECK_LAUNCH("nlbac_node_rk_fwd(rr)");
     return 0;
 }
 
 int nlbac_node_rr_bwd_launch(NodeRkBwdLaunch& L, hipStream_t s) {
     if (!nlbac_node_rr_eligible(&L.net[0], &L.net[1])) return 1;
-    using KernelB = void (*)(const NodeRkBwdLaunch);
-    static const KernelB kb[2][3][2] = {{{node_rr_bwd_kernel<4, 4, 0, 0>, node_rr_bwd_kernel<4, 4, 1, 0>},
-                                         {node_rr_bwd_kernel<7, 1, 0, 0>, node_rr_bwd_kernel<7, 1, 1, 0>},
-                                         {node_rr_bwd_kernel<8, 4, 0, 0>, node_rr_bwd_kernel<8, 4, 1, 0>}},
-                                        {{node_rr_bwd_kernel<4, 4, 0, 1>, node_rr_bwd_kernel<4, 4, 1, 1>},
-                                         {node_rr_bwd_kernel<7, 1, 0, 1>, node_rr_bwd_kernel<7, 1, 1, 1>},
-                                         {node_rr_bwd_kernel<8, 4, 0, 1>, node_rr_bwd_kernel<8, 4, 1, 1>}}};
-    // rows + words (acts_bits 2, the NODE fit): gates from the words, dz rows stored as in activation mode
-    static const KernelB kbw[2][3] = {{node_rr_bwd_kernel<4, 4, 2, 0>, node_rr_bwd_kernel<7, 1, 2, 0>, node_rr_bwd_kernel<8, 4, 2, 0>},
-                                      {node_rr_bwd_kernel<4, 4, 2, 1>, node_rr_bwd_kernel<7, 1, 2, 1>, node_rr_bwd_kernel<8, 4, 2, 1>}};
-    const size_t lds = (size_t)(RkBwdTile::floats() + 2 * 4 * 8 * 64 + 2 * 32 * 64 + 2 * 16 * 64 + 4) * sizeof(float);
-    const dim3 grid(nlbac_ceil_div(L.n, NLBAC_MLP_TILE));
-    const int split = nlbac_node_rr_split() ? 1 : 0, shape = nlbac_node_rr_shape(L.net[0].hid);
-    const KernelB k = (L.acts_bits == 2) ? kbw[split][shape] : kb[split][shape][L.acts_bits ? 1 : 0];
-    hipLaunchKernelGGL(k, grid, dim3(256), lds, s, L);
+    static const NodeRrTable<NodeRkBwdLaunch> table = NODE_RR_BWD_TABLE(node_rr_bwd_kernel);
+    node_rr_bwd_start(table, L, L.net[0].hid, L.n, L.acts_bits, s);
     NLBAC_CHECK_LAUNCH("nlbac_node_rk_bwd(rr)");
     return 0;
 }

@@ -75,11 +75,25 @@ static int traj_check(const nlbac_mlp* f, const nlbac_mlp* g, int n, int H, int 
     return 0;
 }
 
-// what the scalar-step launch and the time-grid launch share: the descriptor of the interval's one-step launch
-static int traj_fwd_fill(NodeRkLaunch& L, const nlbac_mlp* f, const nlbac_mlp* g, const float* x0, const float* u, int n,
-                         int n_stages, const float* beta, const float* c_out, float h, float* out, float* K, float* Y,
-                         float* G, float* acts_f, long acts_f_ls, float* acts_g, long acts_g_ls, int acts_bits,
-                         const char* who) {
+// a time-grid launch carries a step size per interval
+template <typename Launch>
+constexpr bool traj_on_grid = std::is_same<Launch, NodeRkGridFwdLaunch>::value || std::is_same<Launch, NodeRkGridBwdLaunch>::value;
+
+// The forward launch of `who` (an entry point below) over H intervals: the instances of its kernel template in `table`
+// (chosen as the one-step launcher chooses, node_rr_body.h, so that the sums are the same), its step — h for every
+// interval, or (time grid) hs [H] on the device for the kernel with hs_host [H] beside it for the checks here — and
+// what the interval's one-step launch takes.
+template <typename Launch>
+static int traj_fwd(const NodeRrTable<Launch>& table, const char* who, float h, const float* hs, const float* hs_host,
+                    const nlbac_mlp* f, const nlbac_mlp* g, const float* x0, const float* u, int n, int H, int n_stages,
+                    const float* beta, const float* c_out, float* out, float* K, float* Y, float* G, float* acts_f,
+                    long acts_f_ls, float* acts_g, long acts_g_ls, int acts_bits, nlbac_stream_t s) {
+    constexpr bool grid = traj_on_grid<Launch>;
+    if (traj_check(f, g, n, H, n_stages, beta, c_out, grid ? 1.f : h, acts_bits, who)) return -1;
+    if (grid && nlbac_grid_steps_check(hs, hs_host, H, who)) return -1;
+    Launch A;
+    memset(&A, 0, sizeof(A));
+    NodeRkLaunch& L = A.L;
     NLBAC_REQUIRE(x0 && u && out && K && Y && G, "%s: null pointer", who);
     NLBAC_REQUIRE((acts_f == nullptr) == (acts_g == nullptr), "%s: acts_f and acts_g go together", who);
     NLBAC_REQUIRE(acts_f || acts_bits == 0, "%s: acts_bits without acts", who);
@@ -87,67 +101,38 @@ static int traj_fwd_fill(NodeRkLaunch& L, const nlbac_mlp* f, const nlbac_mlp* g
     L.y0 = x0; L.u = u;
     L.n = n; L.rpp = n; L.n_s = f->in_dim; L.n_u = g->out_dim / f->in_dim;
     L.stage_begin = 0; L.stage_end = n_stages; L.S_total = n_stages;
-    for (int i = 0; i < n_stages; ++i) {
-        for (int j = 0; j < n_stages; ++j) L.beta[i][j] = beta[i * n_stages + j];
-        L.c_out[i] = c_out[i];
-    }
-    L.n_out = n_stages;
-    L.h_val[0] = h;
+    nlbac_tableau_copy(L.beta, L.c_out, L.n_out, n_stages, beta, c_out);
+    L.h_val[0] = grid ? hs_host[0] : h;
     L.K = K; L.Y = Y; L.G = G;
     L.acts[0] = acts_f; L.acts[1] = acts_g; L.acts_ls[0] = acts_f_ls; L.acts_ls[1] = acts_g_ls;
     L.acts_bits = acts_bits;
     L.out = out;
     L.norm_mode = -1;
-    return 0;
-}
-
-// the one-step launcher's choice of instance (nlbac_node_rr_fwd_launch), so that the sums are the same: the instances of
-// one kernel template as a table, [SPLIT][shape][BITS != 0] and the activation-row instances [shape]
-template <typename KernelF>
-struct NodeTrajFwdTable {
-    KernelF kf[2][3][2];
-    KernelF kfw[3];
-};
-
-#define NODE_TRAJ_FWD_TABLE(KERN)                                                                                       \
-    {{{{KERN<4, 4, 0, 0>, KERN<4, 4, 1, 0>}, {KERN<7, 1, 0, 0>, KERN<7, 1, 1, 0>}, {KERN<8, 4, 0, 0>, KERN<8, 4, 1, 0>}},  \
-      {{KERN<4, 4, 0, 1>, KERN<4, 4, 1, 1>}, {KERN<7, 1, 0, 1>, KERN<7, 1, 1, 1>}, {KERN<8, 4, 0, 1>, KERN<8, 4, 1, 1>}}}, \
-     {KERN<4, 4, 2, 0>, KERN<7, 1, 2, 0>, KERN<8, 4, 2, 0>}}
-
-template <typename KernelF>
-static KernelF node_traj_fwd_pick(const NodeTrajFwdTable<KernelF>& t, const nlbac_mlp* f, int acts_bits) {
-    const int shape = nlbac_node_rr_shape(f->hid);
-    return (acts_bits == 2) ? t.kfw[shape] : t.kf[(nlbac_node_rr_split() && acts_bits) ? 1 : 0][shape][acts_bits ? 1 : 0];
-}
-
-static size_t traj_fwd_lds() {
-    return (size_t)(RkFwdTile::floats() + NLBAC_MLP_TILE * 8 + 2 * 3 * 8 * 64 + 2 * 32 * 64 + NLBAC_MLP_TILE * RK_MAX_NS +
-                    2 * 2 * 64 + 4) * sizeof(float);
-}
-
-extern "C" int nlbac_node_rk_traj_fwd(const nlbac_mlp* f, const nlbac_mlp* g, const float* x0, const float* u, int n,
-                                      int H, int n_stages, const float* beta, const float* c_out, float h, float* out,
-                                      float* K, float* Y, float* G, float* acts_f, long acts_f_ls, float* acts_g,
-                                      long acts_g_ls, int acts_bits, nlbac_stream_t s) {
-    if (traj_check(f, g, n, H, n_stages, beta, c_out, h, acts_bits, "nlbac_node_rk_traj_fwd")) return -1;
-    NodeRkTrajFwdLaunch A;
-    memset(&A, 0, sizeof(A));
-    if (traj_fwd_fill(A.L, f, g, x0, u, n, n_stages, beta, c_out, h, out, K, Y, G, acts_f, acts_f_ls, acts_g, acts_g_ls,
-                      acts_bits, "nlbac_node_rk_traj_fwd")) return -1;
     A.H = H;
-    using KernelF = void (*)(const NodeRkTrajFwdLaunch);
-    static const NodeTrajFwdTable<KernelF> table = NODE_TRAJ_FWD_TABLE(node_traj_fwd_kernel);
-    const KernelF k = node_traj_fwd_pick(table, f, acts_bits);
-    hipLaunchKernelGGL(k, dim3(nlbac_ceil_div(n, NLBAC_MLP_TILE)), dim3(256), traj_fwd_lds(), (hipStream_t)s, A);
-    NLBAC_CHECK_LAUNCH("nlbac_node_rk_traj_fwd");
+    if constexpr (grid) {
+        // the kernel rewrites the step slot sH with no barrier in front of the interval's first stage: that stage has
+        // to be stage 0, the one whose input uses no step size
+        NLBAC_REQUIRE(L.stage_begin == 0, "%s: a time-grid launch starts every interval at stage 0", who);
+        A.hs = hs;
+    }
+    node_rr_fwd_start(table, A, f->hid, n, acts_bits, (hipStream_t)s);
+    NLBAC_CHECK_LAUNCH(who);
     return 0;
 }
 
-static int traj_bwd_fill(NodeRkBwdLaunch& L, NodeRkTrajBwd& X, const nlbac_mlp* f, const nlbac_mlp* g, const float* u,
-                         int n, int H, int n_stages, const float* beta, const float* c_out, float h, const float* G,
-                         const float* acts_f, long acts_f_ls, const float* acts_g, long acts_g_ls, int acts_bits,
-                         const float* dout, float* dx0, float* du, float* dK, float* dG, float* dz_f, float* dz_g,
-                         const char* who) {
+// The backward launch of `who`: as traj_fwd.
+template <typename Launch>
+static int traj_bwd(const NodeRrTable<Launch>& table, const char* who, float h, const float* hs, const float* hs_host,
+                    const nlbac_mlp* f, const nlbac_mlp* g, const float* u, int n, int H, int n_stages, const float* beta,
+                    const float* c_out, const float* G, const float* acts_f, long acts_f_ls, const float* acts_g,
+                    long acts_g_ls, int acts_bits, const float* dout, float* dx0, float* du, float* dK, float* dG,
+                    float* dz_f, float* dz_g, nlbac_stream_t s) {
+    constexpr bool grid = traj_on_grid<Launch>;
+    if (traj_check(f, g, n, H, n_stages, beta, c_out, grid ? 1.f : h, acts_bits, who)) return -1;
+    if (grid && nlbac_grid_steps_check(hs, hs_host, H, who)) return -1;
+    Launch A;
+    memset(&A, 0, sizeof(A));
+    NodeRkBwdLaunch& L = A.L;
     NLBAC_REQUIRE(u && G && acts_f && acts_g && dout && dx0 && du, "%s: null pointer", who);
     NLBAC_REQUIRE((dz_f == nullptr) == (dz_g == nullptr) && (dz_f == nullptr) == (dG == nullptr) &&
                       (dz_f == nullptr) == (dK == nullptr), "%s: dz_f, dz_g, dG and dK go together", who);
@@ -160,36 +145,22 @@ static int traj_bwd_fill(NodeRkBwdLaunch& L, NodeRkTrajBwd& X, const nlbac_mlp* 
     L.du = du;
     L.n = n; L.rpp = n; L.n_s = f->in_dim; L.n_u = g->out_dim / f->in_dim;
     L.S_total = n_stages; L.st_lo = 0; L.st_hi = n_stages; L.dx_stage0 = 1;
-    for (int i = 0; i < n_stages; ++i)
-        for (int j = 0; j < n_stages; ++j) L.beta[i][j] = beta[i * n_stages + j];
-    L.h_val[0] = h;
-    X.H = H; X.dout = dout; X.dx0 = dx0;
-    for (int j = 0; j < n_stages; ++j) X.c_out[j] = c_out[j];
-    X.n_out = n_stages;
+    nlbac_tableau_copy(L.beta, A.X.c_out, A.X.n_out, n_stages, beta, c_out);
+    L.h_val[0] = grid ? hs_host[H - 1] : h;
+    A.X.H = H; A.X.dout = dout; A.X.dx0 = dx0;
+    if constexpr (grid) A.hs = hs;
+    node_rr_bwd_start(table, A, f->hid, n, acts_bits, (hipStream_t)s);
+    NLBAC_CHECK_LAUNCH(who);
     return 0;
 }
 
-// the one-step launcher's choice of instance (nlbac_node_rr_bwd_launch): [SPLIT][shape][BITS != 0] and the
-// activation-row instances [SPLIT][shape]
-template <typename KernelB>
-struct NodeTrajBwdTable {
-    KernelB kb[2][3][2];
-    KernelB kbw[2][3];
-};
-
-#define NODE_TRAJ_BWD_TABLE(KERN)                                                                                       \
-    {{{{KERN<4, 4, 0, 0>, KERN<4, 4, 1, 0>}, {KERN<7, 1, 0, 0>, KERN<7, 1, 1, 0>}, {KERN<8, 4, 0, 0>, KERN<8, 4, 1, 0>}},  \
-      {{KERN<4, 4, 0, 1>, KERN<4, 4, 1, 1>}, {KERN<7, 1, 0, 1>, KERN<7, 1, 1, 1>}, {KERN<8, 4, 0, 1>, KERN<8, 4, 1, 1>}}}, \
-     {{KERN<4, 4, 2, 0>, KERN<7, 1, 2, 0>, KERN<8, 4, 2, 0>}, {KERN<4, 4, 2, 1>, KERN<7, 1, 2, 1>, KERN<8, 4, 2, 1>}}}
-
-template <typename KernelB>
-static KernelB node_traj_bwd_pick(const NodeTrajBwdTable<KernelB>& t, const nlbac_mlp* f, int acts_bits) {
-    const int split = nlbac_node_rr_split() ? 1 : 0, shape = nlbac_node_rr_shape(f->hid);
-    return (acts_bits == 2) ? t.kbw[split][shape] : t.kb[split][shape][acts_bits ? 1 : 0];
-}
-
-static size_t traj_bwd_lds() {
-    return (size_t)(RkBwdTile::floats() + 2 * 4 * 8 * 64 + 2 * 32 * 64 + 2 * 16 * 64 + 4) * sizeof(float);
+extern "C" int nlbac_node_rk_traj_fwd(const nlbac_mlp* f, const nlbac_mlp* g, const float* x0, const float* u, int n,
+                                      int H, int n_stages, const float* beta, const float* c_out, float h, float* out,
+                                      float* K, float* Y, float* G, float* acts_f, long acts_f_ls, float* acts_g,
+                                      long acts_g_ls, int acts_bits, nlbac_stream_t s) {
+    static const NodeRrTable<NodeRkTrajFwdLaunch> table = NODE_RR_FWD_TABLE(node_traj_fwd_kernel);
+    return traj_fwd(table, "nlbac_node_rk_traj_fwd", h, nullptr, nullptr, f, g, x0, u, n, H, n_stages, beta, c_out, out,
+                    K, Y, G, acts_f, acts_f_ls, acts_g, acts_g_ls, acts_bits, s);
 }
 
 extern "C" int nlbac_node_rk_traj_bwd(const nlbac_mlp* f, const nlbac_mlp* g, const float* u, int n, int H,
@@ -197,17 +168,9 @@ extern "C" int nlbac_node_rk_traj_bwd(const nlbac_mlp* f, const nlbac_mlp* g, co
                                       const float* acts_f, long acts_f_ls, const float* acts_g, long acts_g_ls,
                                       int acts_bits, const float* dout, float* dx0, float* du, float* dK, float* dG,
                                       float* dz_f, float* dz_g, nlbac_stream_t s) {
-    if (traj_check(f, g, n, H, n_stages, beta, c_out, h, acts_bits, "nlbac_node_rk_traj_bwd")) return -1;
-    NodeRkTrajBwdLaunch A;
-    memset(&A, 0, sizeof(A));
-    if (traj_bwd_fill(A.L, A.X, f, g, u, n, H, n_stages, beta, c_out, h, G, acts_f, acts_f_ls, acts_g, acts_g_ls,
-                      acts_bits, dout, dx0, du, dK, dG, dz_f, dz_g, "nlbac_node_rk_traj_bwd")) return -1;
-    using KernelB = void (*)(const NodeRkTrajBwdLaunch);
-    static const NodeTrajBwdTable<KernelB> table = NODE_TRAJ_BWD_TABLE(node_traj_bwd_kernel);
-    const KernelB k = node_traj_bwd_pick(table, f, acts_bits);
-    hipLaunchKernelGGL(k, dim3(nlbac_ceil_div(n, NLBAC_MLP_TILE)), dim3(256), traj_bwd_lds(), (hipStream_t)s, A);
-    NLBAC_CHECK_LAUNCH("nlbac_node_rk_traj_bwd");
-    return 0;
+    static const NodeRrTable<NodeRkTrajBwdLaunch> table = NODE_RR_BWD_TABLE(node_traj_bwd_kernel);
+    return traj_bwd(table, "nlbac_node_rk_traj_bwd", h, nullptr, nullptr, f, g, u, n, H, n_stages, beta, c_out, G,
+                    acts_f, acts_f_ls, acts_g, acts_g_ls, acts_bits, dout, dx0, du, dK, dG, dz_f, dz_g, s);
 }
 
 // ---- the solution on a time grid: a step size per interval (hs [H] on the device for the kernel, hs_host [H] beside it
@@ -217,22 +180,9 @@ extern "C" int nlbac_node_rk_grid_fwd(const nlbac_mlp* f, const nlbac_mlp* g, co
                                       int H, int n_stages, const float* beta, const float* c_out, const float* hs,
                                       const float* hs_host, float* out, float* K, float* Y, float* G, float* acts_f,
                                       long acts_f_ls, float* acts_g, long acts_g_ls, int acts_bits, nlbac_stream_t s) {
-    if (traj_check(f, g, n, H, n_stages, beta, c_out, 1.f, acts_bits, "nlbac_node_rk_grid_fwd")) return -1;
-    if (nlbac_grid_steps_check(hs, hs_host, H, "nlbac_node_rk_grid_fwd")) return -1;
-    NodeRkGridFwdLaunch A;
-    memset(&A, 0, sizeof(A));
-    if (traj_fwd_fill(A.L, f, g, x0, u, n, n_stages, beta, c_out, hs_host[0], out, K, Y, G, acts_f, acts_f_ls, acts_g,
-                      acts_g_ls, acts_bits, "nlbac_node_rk_grid_fwd")) return -1;
-    // the kernel rewrites the step slot sH with no barrier in front of the interval's first stage: that stage has to
-    // be stage 0, the one whose input uses no step size
-    NLBAC_REQUIRE(A.L.stage_begin == 0, "nlbac_node_rk_grid_fwd: a time-grid launch starts every interval at stage 0");
-    A.H = H; A.hs = hs;
-    using KernelF = void (*)(const NodeRkGridFwdLaunch);
-    static const NodeTrajFwdTable<KernelF> table = NODE_TRAJ_FWD_TABLE(node_grid_fwd_kernel);
-    const KernelF k = node_traj_fwd_pick(table, f, acts_bits);
-    hipLaunchKernelGGL(k, dim3(nlbac_ceil_div(n, NLBAC_MLP_TILE)), dim3(256), traj_fwd_lds(), (hipStream_t)s, A);
-    NLBAC_CHECK_LAUNCH("nlbac_node_rk_grid_fwd");
-    return 0;
+    static const NodeRrTable<NodeRkGridFwdLaunch> table = NODE_RR_FWD_TABLE(node_grid_fwd_kernel);
+    return traj_fwd(table, "nlbac_node_rk_grid_fwd", 0.f, hs, hs_host, f, g, x0, u, n, H, n_stages, beta, c_out, out, K,
+                    Y, G, acts_f, acts_f_ls, acts_g, acts_g_ls, acts_bits, s);
 }
 
 extern "C" int nlbac_node_rk_grid_bwd(const nlbac_mlp* f, const nlbac_mlp* g, const float* u, int n, int H,
@@ -240,17 +190,7 @@ extern "C" int nlbac_node_rk_grid_bwd(const nlbac_mlp* f, const nlbac_mlp* g, co
                                       const float* hs_host, const float* G, const float* acts_f, long acts_f_ls,
                                       const float* acts_g, long acts_g_ls, int acts_bits, const float* dout, float* dx0,
                                       float* du, float* dK, float* dG, float* dz_f, float* dz_g, nlbac_stream_t s) {
-    if (traj_check(f, g, n, H, n_stages, beta, c_out, 1.f, acts_bits, "nlbac_node_rk_grid_bwd")) return -1;
-    if (nlbac_grid_steps_check(hs, hs_host, H, "nlbac_node_rk_grid_bwd")) return -1;
-    NodeRkGridBwdLaunch A;
-    memset(&A, 0, sizeof(A));
-    if (traj_bwd_fill(A.L, A.X, f, g, u, n, H, n_stages, beta, c_out, hs_host[H - 1], G, acts_f, acts_f_ls, acts_g,
-                      acts_g_ls, acts_bits, dout, dx0, du, dK, dG, dz_f, dz_g, "nlbac_node_rk_grid_bwd")) return -1;
-    A.hs = hs;
-    using KernelB = void (*)(const NodeRkGridBwdLaunch);
-    static const NodeTrajBwdTable<KernelB> table = NODE_TRAJ_BWD_TABLE(node_grid_bwd_kernel);
-    const KernelB k = node_traj_bwd_pick(table, f, acts_bits);
-    hipLaunchKernelGGL(k, dim3(nlbac_ceil_div(n, NLBAC_MLP_TILE)), dim3(256), traj_bwd_lds(), (hipStream_t)s, A);
-    NLBAC_CHECK_LAUNCH("nlbac_node_rk_grid_bwd");
-    return 0;
+    static const NodeRrTable<NodeRkGridBwdLaunch> table = NODE_RR_BWD_TABLE(node_grid_bwd_kernel);
+    return traj_bwd(table, "nlbac_node_rk_grid_bwd", 0.f, hs, hs_host, f, g, u, n, H, n_stages, beta, c_out, G, acts_f,
+                    acts_f_ls, acts_g, acts_g_ls, acts_bits, dout, dx0, du, dK, dG, dz_f, dz_g, s);
 }

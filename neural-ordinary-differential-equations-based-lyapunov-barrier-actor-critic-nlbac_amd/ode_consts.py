@@ -41,7 +41,7 @@ TABLEAU = {
 #   NLBAC_NORM_DEFER_ATTEMPT  ... and the attempts' error norm as tile partials + nlbac_dopri_control_tiles
 #   NLBAC_INTERP_FOLD         the interpolation at t_end inside the attempt launches (ode_dopri: _interp_fold)
 #   NLBAC_FIT_WORDS           activation rows AND ReLU mask words for solves that want weight gradients
-#                             (odeint._fit_words_on, rollout._Traj)
+#                             (odeint._fit_words_on, ode_traj.AffineTraj)
 _ENV = dict(norm_defer="NLBAC_NORM_DEFER", norm_defer_attempt="NLBAC_NORM_DEFER_ATTEMPT",
             interp_fold="NLBAC_INTERP_FOLD", fit_words="NLBAC_FIT_WORDS")
 

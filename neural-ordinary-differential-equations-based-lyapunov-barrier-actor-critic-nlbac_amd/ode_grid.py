@@ -17,13 +17,10 @@ import math
 
 import torch
 
-from . import _lib
-from . import rollout as _R
-from ._lib import fptr
-from .arena import stream_ptr
+from . import ode_traj as T
+from . import rollout
 
 METHODS = ("euler", "rk4")
-_SOLVERS_KEY = "_odeint_grid_solvers"
 
 
 def _steps_of(t):
@@ -96,13 +93,7 @@ def odeint_grid(func, y0, t, *, method="rk4"):
     (memory grows linearly with T; see ``rollout`` on the last bits of the values under input gradients only)."""
     hs = _steps(func, y0, t, method)
     params = tuple(func.parameters())
-    grad_on = torch.is_grad_enabled()
-    if grad_on and any(p.requires_grad for p in params):
-        mode = "params"
-    elif grad_on and y0.requires_grad:
-        mode = "inputs"
-    else:
-        mode = "none"
+    mode = T.keep_mode(params, y0)
     func.refresh_device_weights()
     return _GridFunction.apply(func, method, hs, mode, y0, *params)
 
@@ -115,32 +106,8 @@ class _GridFunction(torch.autograd.Function):
         x0, c = y0[:, :ns].contiguous(), y0[:, ns:].contiguous()
         dev = y0.device
         xs = torch.empty(H, n, ns, dtype=torch.float32, device=dev)        # the states behind each interval
-        ctx.func, ctx.mode, ctx.n_params, ctx.path = func, mode, len(params), None
-        if _R._one_launch_ok(func, method):
-            # the steps twice: on the device for the kernels, in host memory for the launcher's checks
-            steps = (torch.tensor(hs, dtype=torch.float32, device=dev), fptr(*hs))
-            if func.affine:
-                tj = _R._Traj(func, n, H, method, mode, dev)
-                _lib.call("nlbac_node_rk_grid_fwd", C.byref(tj.f.desc), C.byref(tj.g.desc), x0.data_ptr(), c.data_ptr(),
-                          n, H, tj.S, tj.beta, tj.c_out, steps[0].data_ptr(), steps[1], xs.data_ptr(), tj.K.data_ptr(),
-                          tj.Y.data_ptr(), tj.G.data_ptr(), tj.ptr(0), tj.ls[0], tj.ptr(1), tj.ls[1], tj.bits,
-                          stream_ptr())
-            else:
-                tj = _R._ConcatTraj(func, n, H, method, mode, dev)
-                _lib.call("nlbac_concat_rk_grid_fwd", C.byref(tj.net.desc), x0.data_ptr(), c.data_ptr(), n, H, tj.S,
-                          tj.beta, tj.c_out, steps[0].data_ptr(), steps[1], xs.data_ptr(), _R._ptr(tj.Xin),
-                          _R._ptr(tj.acts), tj.ls, tj.bits, _R._ptr(tj.norm), stream_ptr())
-            if mode != "none":
-                ctx.path = ("traj", tj, c, steps)
-        else:
-            svs = _R._chain_solvers(func, mode, H, _SOLVERS_KEY)
-            x = x0
-            for k in range(H):
-                sv = svs[k if mode != "none" else 0]
-                xs[k].copy_(sv.forward(x, c, 1, n, method, hs[k], 1e-7, 1e-5))
-                x = xs[k]
-            if mode != "none":
-                ctx.path = ("chain", svs[:H], [sv.stats["solves"] for sv in svs[:H]])
+        ctx.func, ctx.mode, ctx.n_params = func, mode, len(params)
+        ctx.kept = T.solve(func, T.GridSteps(hs, dev), method, mode, rollout._one_launch_ok(func, method), x0, c, xs)
         out = torch.empty(H + 1, n, y0.shape[1], dtype=torch.float32, device=dev)
         out[0].copy_(y0)
         out[1:, :, :ns].copy_(xs)
@@ -149,48 +116,15 @@ class _GridFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        func, path = ctx.func, ctx.path
-        assert path is not None, "odeint_grid: nothing was kept for a backward (the forward ran without gradients)"
-        ns = func.n_s
+        assert ctx.kept is not None, "odeint_grid: nothing was kept for a backward (the forward ran without gradients)"
+        ns = ctx.func.n_s
         dout = dout.float()
-        dxs = dout[:, :, :ns].contiguous()
         need_p = ctx.mode == "params" and any(ctx.needs_input_grad[5:])
-        if path[0] == "traj":
-            _, tj, c, steps = path
-            if func.affine:
-                dx0, dc, flat = _R._traj_backward(func, tj, c, None, dxs, need_p, hs=steps)
-            else:
-                dx0, dc, flat = _R._concat_traj_backward(func, tj, None, dxs, need_p, hs=steps)
-        else:
-            dx0, dc, flat = _chain_backward(func, path[1], path[2], dxs, need_p)
+        dx0, dc, flat = ctx.kept.backward(dout[:, :, :ns].contiguous(), need_p)
         gy0 = None
         if ctx.needs_input_grad[4]:
-            # d/d carried columns: out[0]'s share, then per interval its control gradient (summed above, k = H-1 .. 0)
-            # and out[k+1]'s share
+            # d/d carried columns: out[0]'s share, then per interval its control gradient (summed k = H-1 .. 0 by the
+            # backward) and out[k+1]'s share
             gy0 = torch.cat([dx0, dout[0][:, ns:] + (dc + dout[1:, :, ns:].sum(0))], dim=1)
-        gp = [None] * ctx.n_params
-        if need_p:
-            arena = func.device_handles()[0].arena
-            gp = []
-            for p in func.parameters():
-                off = arena.offset_of[id(p)]
-                gp.append(flat[off:off + p.numel()].view(p.shape))
+        gp = T.param_grads(ctx.func, flat) if need_p else [None] * ctx.n_params
         return (None, None, None, None, gy0, *gp)
-
-
-def _chain_backward(func, svs, solve_ids, dxs, need_p):
-    assert all(sv.stats["solves"] == i for sv, i in zip(svs, solve_ids)), \
-        "odeint_grid: backward must run before the next odeint_grid of the same shape and mode with the same model"
-    H = len(svs)
-    arena = func.device_handles()[0].arena if need_p else None
-    carry, dc, flat = None, None, None
-    for k in range(H - 1, -1, -1):            # dL/dx_{k+1} = dout[k+1] + what interval k+1 sends back
-        sv = svs[k]
-        gk = dxs[k + 1] if carry is None else (dxs[k + 1] + carry)
-        du, dy0 = sv.backward(gk.contiguous(), need_du=True, need_params=need_p, need_dy0=True)
-        dc = du.clone() if dc is None else dc + du      # (the order of the one-launch kernels' sum)
-        carry = dy0.clone()
-        if need_p:
-            fk = _R._reduce(arena, sv.accumulate_param_grads(arena, arena.n_slabs))
-            flat = fk if flat is None else flat + fk
-    return dxs[0] + carry, dc, flat

@@ -173,7 +173,7 @@ int nlbac_mlp_bwd_data_head(const nlbac_mlp *nets, const nlbac_mlp_io *io, int n
  *     the slabs (slab s = rows [s*rows_per_slab, ...)); the skinny first/last layers and all biases are reduced over all
  *     rows into slab 0 through `ws` (>= nlbac_mlp_bwd_weights_ws_floats() floats, always required) and their entries
  *     in slabs 1 .. n_slabs-1 are written as zeros;
- *   - nets of hid <= 112 (the NODEs) whose partials are NOT in `ws` (NLBAC_MLP_DW16=0 switches this path off): every
+ *   - nets of hid <= 112 (the NODEs) whose partials are NOT in `ws`: every
  *     gradient — biases and skinny layers too — is a partial in every slab (slab s = the 4-row k-steps 4s+w,
  *     4s+w+4 n_slabs, ... of wave w: mlp_dw16_kernels.hip); `ws` is not read; rows * hid must stay below 2^29 - 2^16. */
 long nlbac_mlp_bwd_weights_ws_floats(const nlbac_mlp *nets, int n_nets, int B);

@@ -18,7 +18,6 @@
 // stage additionally go out as rows, for nlbac_mlp_bwd_weights.
 #include "concat_rk_shared.h"
 #include "rr_device.h"
-#include <cstdlib>
 #include <cstring>
 #include <type_traits>
 
@@ -442,13 +441,8 @@ __global__ __launch_bounds__(64 * NW) void concat_adj_rr_kernel(const ConcatAdjL
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-static bool cadj_enabled() {
-    static const bool on = [] { const char* e = getenv("NLBAC_CONCAT_ADJ_RR"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
 extern "C" int nlbac_concat_adj_step_ok(const nlbac_mlp* net) {
-    return (net && cadj_enabled() && nlbac_concat_rr_eligible(net) && net->in_dim <= CADJ_MAX_IN) ? 1 : 0;
+    return (net && nlbac_concat_rr_eligible(net) && net->in_dim <= CADJ_MAX_IN) ? 1 : 0;
 }
 
 extern "C" int nlbac_concat_adj_step(const nlbac_mlp* net, const float* c, int P, int rows_per_problem, int st_lo, int st_hi,
@@ -495,24 +489,21 @@ extern "C" int nlbac_concat_adj_step(const nlbac_mlp* net, const float* c, int P
                       "nlbac_concat_adj_step: interp_out goes with an attempt launch of a device-driven dopri5 solve");
         L.ip_out = interp_out; L.t_end = t_end;
     }
+    // four waves per workgroup (rows of done problems are skipped per row, nothing else is per tile: a tile may straddle
+    // problems)
+    constexpr int nw = 4, tile = 16 * nw;
     using Kernel = void (*)(const ConcatAdjLaunch);
-    static const Kernel kt[2][3][2] = {{{concat_adj_rr_kernel<4, 4, 0, 2>, concat_adj_rr_kernel<4, 4, 1, 2>},
-                                        {concat_adj_rr_kernel<7, 1, 0, 2>, concat_adj_rr_kernel<7, 1, 1, 2>},
-                                        {concat_adj_rr_kernel<8, 4, 0, 2>, concat_adj_rr_kernel<8, 4, 1, 2>}},
-                                       {{concat_adj_rr_kernel<4, 4, 0, 4>, concat_adj_rr_kernel<4, 4, 1, 4>},
-                                        {concat_adj_rr_kernel<7, 1, 0, 4>, concat_adj_rr_kernel<7, 1, 1, 4>},
-                                        {concat_adj_rr_kernel<8, 4, 0, 4>, concat_adj_rr_kernel<8, 4, 1, 4>}}};
+    static const Kernel kt[3][2] = {{concat_adj_rr_kernel<4, 4, 0, nw>, concat_adj_rr_kernel<4, 4, 1, nw>},
+                                    {concat_adj_rr_kernel<7, 1, 0, nw>, concat_adj_rr_kernel<7, 1, 1, nw>},
+                                    {concat_adj_rr_kernel<8, 4, 0, nw>, concat_adj_rr_kernel<8, 4, 1, nw>}};
     const int shape = net->hid == 64 ? 0 : (net->hid == 100 ? 1 : 2);
-    // (rows of done problems are skipped per row, nothing else is per tile: a tile may straddle problems)
-    static const int forced_nw = [] { const char* e = getenv("NLBAC_CONCAT_NW"); return e ? atoi(e) : 0; }();
-    const int nw = forced_nw == 2 ? 2 : 4, tile = 16 * nw;
     const size_t lds = (size_t)((n_stages_total + 1) * tile * L.WP + tile * (CK_NC + 2) + 2 * 4 * 8 * 64) * sizeof(float);
-    const Kernel k = kt[nw == 4][shape][keep ? 1 : 0];
+    const Kernel k = kt[shape][keep ? 1 : 0];
     if (lds > 64 * 1024) {
-        static bool attr_set[2][3][2] = {};
-        if (!attr_set[nw == 4][shape][keep ? 1 : 0]) {
+        static bool attr_set[3][2] = {};
+        if (!attr_set[shape][keep ? 1 : 0]) {
             (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
-            attr_set[nw == 4][shape][keep ? 1 : 0] = true;
+            attr_set[shape][keep ? 1 : 0] = true;
         }
     }
     hipLaunchKernelGGL(k, dim3(nlbac_ceil_div(L.n, tile)), dim3(64 * nw), lds, (hipStream_t)s, L);

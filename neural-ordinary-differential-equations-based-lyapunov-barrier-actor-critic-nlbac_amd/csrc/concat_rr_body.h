@@ -4,7 +4,6 @@
 #pragma once
 #include "concat_rk_shared.h"
 #include "rr_device.h"
-#include <cstdlib>
 #include <type_traits>
 
 #define CRR_MAX_IN 15       /* in_dim + the bias column <= 16: four k-steps of layer 0 */
@@ -940,12 +939,8 @@ __device__ __forceinline__ void concat_rr_bwd_body(const ConcatRkBwdLaunch& L, c
 // ---- what the one-step launchers and the rollout's share: the instance per width, waves per workgroup, LDS sizes
 static inline int crr_shape_index(int hid) { return hid == 64 ? 0 : (hid == 100 ? 1 : (hid == 128 ? 2 : -1)); }
 
-// waves per workgroup: four (64-row tiles) unless a tile would then straddle two problems; NLBAC_CONCAT_NW=2 keeps two
-static inline int crr_waves(int n, int rpp) {
-    static const int forced = [] { const char* e = getenv("NLBAC_CONCAT_NW"); return e ? atoi(e) : 0; }();
-    if (forced == 2) return 2;
-    return (rpp >= n || rpp % 64 == 0) ? 4 : 2;
-}
+// waves per workgroup: four (64-row tiles) unless a tile would then straddle two problems
+static inline int crr_waves(int n, int rpp) { return (rpp >= n || rpp % 64 == 0) ? 4 : 2; }
 static inline size_t crr_fwd_lds(int tile) {
     return (size_t)(CK_MAX_STAGES * tile * CK_LD + tile * (CK_LD + CK_NC + 1) + 4 * 8 * 64) * sizeof(float);
 }
@@ -953,22 +948,21 @@ static inline size_t crr_bwd_lds(int tile) {
     return (size_t)(CK_MAX_STAGES * tile * CK_LD + tile * (1 + CK_LD + CK_NC + 16 + CK_LD) + 4 * 8 * 64) * sizeof(float);
 }
 
-// the instances of one kernel template KERN<NB, R, BITS, NW>, [NW == 4][shape][BITS]
+// the instances of one kernel template KERN<NB, R, BITS, NW> for one NW, [shape][BITS]
 template <typename Launch>
 struct ConcatRrTable {
-    void (*k[2][3][2])(const Launch);
+    void (*k[3][2])(const Launch);
 };
 
-#define CONCAT_RR_TABLE(KERN)                                                                                           \
-    {{{{KERN<4, 4, 0, 2>, KERN<4, 4, 1, 2>}, {KERN<7, 1, 0, 2>, KERN<7, 1, 1, 2>}, {KERN<8, 4, 0, 2>, KERN<8, 4, 1, 2>}},  \
-      {{KERN<4, 4, 0, 4>, KERN<4, 4, 1, 4>}, {KERN<7, 1, 0, 4>, KERN<7, 1, 1, 4>}, {KERN<8, 4, 0, 4>, KERN<8, 4, 1, 4>}}}}
+#define CONCAT_RR_TABLE(KERN, NW)                                                                                       \
+    {{{KERN<4, 4, 0, NW>, KERN<4, 4, 1, NW>}, {KERN<7, 1, 0, NW>, KERN<7, 1, 1, NW>}, {KERN<8, 4, 0, NW>, KERN<8, 4, 1, NW>}}}
 
-// launch the instance of `t` for a net `hid` wide and this acts_bits over n rows in problems of rpp rows; `lds` is
-// crr_fwd_lds or crr_bwd_lds
+// launch the instance of `t` (the table of nw waves per workgroup) for a net `hid` wide and this acts_bits over n rows;
+// `lds` is crr_fwd_lds or crr_bwd_lds
 template <typename Launch>
-static void crr_start(const ConcatRrTable<Launch>& t, const Launch& A, int hid, int n, int rpp, int acts_bits,
+static void crr_start(const ConcatRrTable<Launch>& t, int nw, const Launch& A, int hid, int n, int acts_bits,
                       size_t (*lds)(int), hipStream_t s) {
-    const int nw = crr_waves(n, rpp), tile = 16 * nw;
-    hipLaunchKernelGGL(t.k[nw == 4][crr_shape_index(hid)][acts_bits ? 1 : 0], dim3(nlbac_ceil_div(n, tile)),
-                       dim3(64 * nw), lds(tile), s, A);
+    const int tile = 16 * nw;
+    hipLaunchKernelGGL(t.k[crr_shape_index(hid)][acts_bits ? 1 : 0], dim3(nlbac_ceil_div(n, tile)), dim3(64 * nw),
+                       lds(tile), s, A);
 }

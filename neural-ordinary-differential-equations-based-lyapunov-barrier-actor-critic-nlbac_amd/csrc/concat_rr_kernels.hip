@@ -21,31 +21,29 @@ __global__ __launch_bounds__(64 * NW) void concat_rr_bwd_kernel(const ConcatRkBw
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-static bool crr_enabled() {
-    static const bool on = [] { const char* e = getenv("NLBAC_CONCAT_RR"); return !(e && e[0] == '0'); }();
-    return on;
-}
-static bool crr_eligible(const nlbac_mlp& net);
-
-bool nlbac_concat_rr_eligible(const nlbac_mlp* net) { return crr_eligible(*net); }
-static bool crr_eligible(const nlbac_mlp& net) {
-    return crr_enabled() && net.n_layers == 4 && crr_shape_index(net.hid) >= 0 && net.rr_kind == RR_KIND_CHAIN &&
+bool nlbac_concat_rr_eligible(const nlbac_mlp* np) {
+    const nlbac_mlp& net = *np;
+    return net.n_layers == 4 && crr_shape_index(net.hid) >= 0 && net.rr_kind == RR_KIND_CHAIN &&
            net.rr_fwd_off >= 0 && net.rr_bwd_off >= 0 && net.in_dim <= CRR_MAX_IN && net.out_dim <= CK_NS;
 }
 
 // which instance, how many waves and how much LDS: concat_rr_body.h's host section, shared with the trajectory launchers
 int nlbac_concat_rr_fwd_launch(ConcatRkLaunch& L, hipStream_t s) {
-    if (!crr_eligible(L.net)) return 1;
-    static const ConcatRrTable<ConcatRkLaunch> table = CONCAT_RR_TABLE(concat_rr_fwd_kernel);
-    crr_start(table, L, L.net.hid, L.n, L.rpp, L.acts_bits, crr_fwd_lds, s);
+    if (!nlbac_concat_rr_eligible(&L.net)) return 1;
+    static const ConcatRrTable<ConcatRkLaunch> table[2] = {CONCAT_RR_TABLE(concat_rr_fwd_kernel, 2),
+                                                           CONCAT_RR_TABLE(concat_rr_fwd_kernel, 4)};
+    const int nw = crr_waves(L.n, L.rpp);
+    crr_start(table[nw == 4], nw, L, L.net.hid, L.n, L.acts_bits, crr_fwd_lds, s);
     NLBAC_CHECK_LAUNCH("nlbac_concat_rk_fwd(rr)");
     return 0;
 }
 
 int nlbac_concat_rr_bwd_launch(ConcatRkBwdLaunch& L, hipStream_t s) {
-    if (!crr_eligible(L.net)) return 1;
-    static const ConcatRrTable<ConcatRkBwdLaunch> table = CONCAT_RR_TABLE(concat_rr_bwd_kernel);
-    crr_start(table, L, L.net.hid, L.n, L.rpp, L.acts_bits, crr_bwd_lds, s);
+    if (!nlbac_concat_rr_eligible(&L.net)) return 1;
+    static const ConcatRrTable<ConcatRkBwdLaunch> table[2] = {CONCAT_RR_TABLE(concat_rr_bwd_kernel, 2),
+                                                              CONCAT_RR_TABLE(concat_rr_bwd_kernel, 4)};
+    const int nw = crr_waves(L.n, L.rpp);
+    crr_start(table[nw == 4], nw, L, L.net.hid, L.n, L.acts_bits, crr_bwd_lds, s);
     NLBAC_CHECK_LAUNCH("nlbac_concat_rk_bwd(rr)");
     return 0;
 }

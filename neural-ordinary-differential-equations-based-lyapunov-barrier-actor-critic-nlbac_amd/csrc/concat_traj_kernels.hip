@@ -20,6 +20,9 @@
 #undef RR_TIMING          // (the ablation stamps belong to the one-step kernels)
 #include "concat_rr_body.h"
 
+// waves per workgroup: a rollout is one problem (rpp == n), for which the one-step launcher's rule (crr_waves) gives four
+#define CTRAJ_NW 4
+
 struct ConcatRkTrajFwdLaunch {
     ConcatRkLaunch L;
     int H;
@@ -116,7 +119,7 @@ static int ctraj_fwd(const ConcatRrTable<Launch>& table, const char* who, float 
     L.norm_mode = -1;
     A.H = H;
     if constexpr (grid) A.hs = hs;
-    crr_start(table, A, net->hid, n, n, acts_bits, crr_fwd_lds, (hipStream_t)s);
+    crr_start(table, CTRAJ_NW, A, net->hid, n, acts_bits, crr_fwd_lds, (hipStream_t)s);
     NLBAC_CHECK_LAUNCH(who);
     return 0;
 }
@@ -147,7 +150,7 @@ static int ctraj_bwd(const ConcatRrTable<Launch>& table, const char* who, float 
     L.norm = norm;
     A.X.H = H; A.X.dout = dout; A.X.dx0 = dx0;
     if constexpr (grid) A.hs = hs;
-    crr_start(table, A, net->hid, n, n, acts_bits, crr_bwd_lds, (hipStream_t)s);
+    crr_start(table, CTRAJ_NW, A, net->hid, n, acts_bits, crr_bwd_lds, (hipStream_t)s);
     NLBAC_CHECK_LAUNCH(who);
     return 0;
 }
@@ -156,7 +159,7 @@ extern "C" int nlbac_concat_rk_traj_fwd(const nlbac_mlp* net, const float* x0, c
                                         int n_stages, const float* beta, const float* c_out, float h, float* out,
                                         float* Xin, float* acts, long acts_ls, int acts_bits, const float* norm,
                                         nlbac_stream_t s) {
-    static const ConcatRrTable<ConcatRkTrajFwdLaunch> table = CONCAT_RR_TABLE(concat_traj_fwd_kernel);
+    static const ConcatRrTable<ConcatRkTrajFwdLaunch> table = CONCAT_RR_TABLE(concat_traj_fwd_kernel, CTRAJ_NW);
     return ctraj_fwd(table, "nlbac_concat_rk_traj_fwd", h, nullptr, nullptr, net, x0, c, n, H, n_stages, beta, c_out, out,
                      Xin, acts, acts_ls, acts_bits, norm, s);
 }
@@ -165,7 +168,7 @@ extern "C" int nlbac_concat_rk_traj_bwd(const nlbac_mlp* net, int n, int H, int 
                                         const float* c_out, float h, const float* acts, long acts_ls, int acts_bits,
                                         const float* norm, const float* dout, float* dx0, float* dc, float* dK,
                                         float* dz, nlbac_stream_t s) {
-    static const ConcatRrTable<ConcatRkTrajBwdLaunch> table = CONCAT_RR_TABLE(concat_traj_bwd_kernel);
+    static const ConcatRrTable<ConcatRkTrajBwdLaunch> table = CONCAT_RR_TABLE(concat_traj_bwd_kernel, CTRAJ_NW);
     return ctraj_bwd(table, "nlbac_concat_rk_traj_bwd", h, nullptr, nullptr, net, n, H, n_stages, beta, c_out, acts,
                      acts_ls, acts_bits, norm, dout, dx0, dc, dK, dz, s);
 }
@@ -177,7 +180,7 @@ extern "C" int nlbac_concat_rk_grid_fwd(const nlbac_mlp* net, const float* x0, c
                                         int n_stages, const float* beta, const float* c_out, const float* hs,
                                         const float* hs_host, float* out, float* Xin, float* acts, long acts_ls,
                                         int acts_bits, const float* norm, nlbac_stream_t s) {
-    static const ConcatRrTable<ConcatRkGridFwdLaunch> table = CONCAT_RR_TABLE(concat_grid_fwd_kernel);
+    static const ConcatRrTable<ConcatRkGridFwdLaunch> table = CONCAT_RR_TABLE(concat_grid_fwd_kernel, CTRAJ_NW);
     return ctraj_fwd(table, "nlbac_concat_rk_grid_fwd", 0.f, hs, hs_host, net, x0, c, n, H, n_stages, beta, c_out, out,
                      Xin, acts, acts_ls, acts_bits, norm, s);
 }
@@ -186,7 +189,7 @@ extern "C" int nlbac_concat_rk_grid_bwd(const nlbac_mlp* net, int n, int H, int 
                                         const float* c_out, const float* hs, const float* hs_host, const float* acts,
                                         long acts_ls, int acts_bits, const float* norm, const float* dout, float* dx0,
                                         float* dc, float* dK, float* dz, nlbac_stream_t s) {
-    static const ConcatRrTable<ConcatRkGridBwdLaunch> table = CONCAT_RR_TABLE(concat_grid_bwd_kernel);
+    static const ConcatRrTable<ConcatRkGridBwdLaunch> table = CONCAT_RR_TABLE(concat_grid_bwd_kernel, CTRAJ_NW);
     return ctraj_bwd(table, "nlbac_concat_rk_grid_bwd", 0.f, hs, hs_host, net, n, H, n_stages, beta, c_out, acts, acts_ls,
                      acts_bits, norm, dout, dx0, dc, dK, dz, s);
 }

@@ -226,8 +226,6 @@ __global__ __launch_bounds__(256) void mlp_dw16_kernel(const MlpLaunch L) {
 }
 
 bool nlbac_mlp_dw16_eligible(const nlbac_mlp* nets, int n_nets, int B) {
-    static const bool on = [] { const char* e = getenv("NLBAC_MLP_DW16"); return !(e && e[0] == '0'); }();
-    if (!on) return false;
     for (int i = 0; i < n_nets; ++i)
         if (nets[i].hid > 112) return false;
     return true;

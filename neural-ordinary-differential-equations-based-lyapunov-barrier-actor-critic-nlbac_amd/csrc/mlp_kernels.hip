@@ -20,7 +20,6 @@
 //     flight, no LDS round trip (each wave owns its own output columns);
 //   * the skinny first-input / last-output contractions (K or N <= 16) stay
 //     on the VALU.
-#include <cstdlib>
 #include "common.h"
 #include "mlp_device.h"
 #include "rr_device.h"
@@ -149,10 +148,10 @@ __global__ __launch_bounds__(256) void mlp_pack_kernel(const MlpLaunch L) {
 // ---------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------
-// MODE 1: every net has <= 4 column tiles (one per wave); MODE 2: every net has 8 (two per wave);
+// MODE 1: every net has <= 4 column tiles (one per wave);
 // MODE 0: mixed / other widths (both register sets live).
 // MODE 3: every net has 8 column tiles and the workgroup has 8 waves, one tile each (same code path as MODE 1):
-// half the per-tile latency of MODE 2 and twice the waves per CU.
+// half the per-tile latency of four waves with two tiles each (the data backward's MODE 2) and twice the waves per CU.
 // OCC (MODE 3): cap the kernel at 128 VGPRs so that two workgroups share a CU (a few spills): pays once the grid has
 // more tiles than CUs (6 nets x 128 tiles: 45 -> 43 us), costs ~1 us on the one- and two-net launches.
 template <int MODE, int OCC = 0>
@@ -172,12 +171,12 @@ __global__ __launch_bounds__(MODE == 3 ? 512 : 256, OCC ? 4 : 2) void mlp_fwd_ke
     float* in = smem;
     float* out = smem + NLBAC_MLP_TILE * LD;
 
-    const bool active = wave < NT, two = (MODE == 2) || (MODE == 0 && (wave + 4) < NT);
-    WaveGemm<ONE ? 1 : 2> wg2;              // MODE 1/3 never touch wg2 / MODE 2 never touches wg1:
-    WaveGemm<1> wg1;                        // the unused one is dead code
+    const bool active = wave < NT, two = !ONE && (wave + 4) < NT;
+    WaveGemm<ONE ? 1 : 2> wg2;              // MODE 1/3 never touch wg2: dead code there
+    WaveGemm<1> wg1;
     if (active) {          // weights do not depend on the input: start streaming them before staging it
         if constexpr (!ONE) { if (two) fwd_prime<2>(wg2, net, inp, false, wave, lane); }
-        if constexpr (MODE != 2) { if (!two) fwd_prime<1>(wg1, net, inp, false, wave, lane); }
+        if (!two) fwd_prime<1>(wg1, net, inp, false, wave, lane);
     }
     for (int idx = tid; idx < NLBAC_MLP_TILE * inp; idx += NTHR) {
         const int r = idx / inp, c = idx - r * inp, row = row0 + r;
@@ -194,8 +193,7 @@ __global__ __launch_bounds__(MODE == 3 ? 512 : 256, OCC ? 4 : 2) void mlp_fwd_ke
         const long ls = io.acts_ls ? io.acts_ls : (long)B * hid;
         float* acts_tile = io.acts ? io.acts + (long)row0 * hid : nullptr;
         const int n_rows = min(NLBAC_MLP_TILE, B - row0);
-        if constexpr (MODE == 2) fwd_wide_layers<2>(wg2, net, active, wave, lane, LD, inp, in, out, acts_tile, ls, n_rows, nwide, false);
-        else if constexpr (ONE) fwd_wide_layers<1>(wg1, net, active, wave, lane, LD, inp, in, out, acts_tile, ls, n_rows, nwide, false);
+        if constexpr (ONE) fwd_wide_layers<1>(wg1, net, active, wave, lane, LD, inp, in, out, acts_tile, ls, n_rows, nwide, false);
         else {
             if (two) fwd_wide_layers<2>(wg2, net, active, wave, lane, LD, inp, in, out, acts_tile, ls, n_rows, nwide, false);
             else fwd_wide_layers<1>(wg1, net, active, wave, lane, LD, inp, in, out, acts_tile, ls, n_rows, nwide, false);
@@ -463,6 +461,8 @@ __device__ __forceinline__ void skinny_reduce_block(const MlpLaunch& L, const Sk
 // reduction (mlp_bwd_skinny_reduce_kernel's work: independent of the GEMM, both only read what the data backward left):
 // they are dispatched first and finish under the GEMM tiles instead of in a launch of their own.  Block index within the
 // planes -> (net, reduce block) with red_per_net blocks per net.
+// Launched for nets wider than 128 whose layers hold 2^29 elements or more (B * 256 >= 2^29), which is past the 32-bit
+// offsets of mlp_bwd_wide64_kernel below; every smaller batch of such nets runs on that kernel.
 __global__ __launch_bounds__(256) void mlp_bwd_wide_kernel(const MlpLaunch L, const SkinnyLaunch S,
                                                            const float* __restrict__ ws, int red_planes, int red_per_net,
                                                            int n_nets) {
@@ -978,24 +978,6 @@ static int tile_mode(const nlbac_mlp* nets, int n_nets) {
     return all_le4 ? 1 : (all_8 ? 2 : 0);
 }
 
-// 256-wide nets: 8 waves x one column tile (default) or 4 waves x two tiles (NLBAC_MLP_WAVES8=0, kept for A/B runs)
-static bool waves8() {
-    static const bool on = [] { const char* e = getenv("NLBAC_MLP_WAVES8"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
-// the LDS-free weight gradients of nets wider than 128 (mlp_bwd_wide64_kernel); NLBAC_MLP_DW64=0 keeps mlp_bwd_wide_kernel
-static bool dw64_enabled() {
-    static const bool on = [] { const char* e = getenv("NLBAC_MLP_DW64"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
-// two-workgroups-per-CU forward variant: -1 = by grid size (default), 0 / 1 = forced (NLBAC_MLP_OCC, for A/B runs)
-static int occ_mode() {
-    static const int m = [] { const char* e = getenv("NLBAC_MLP_OCC"); return e ? (e[0] == '1' ? 1 : (e[0] == '0' ? 0 : -1)) : -1; }();
-    return m;
-}
-
 static int fill_launch(MlpLaunch& L, const nlbac_mlp* nets, const nlbac_mlp_io* io, int n_nets, int B, const char* who) {
     NLBAC_REQUIRE(n_nets >= 1 && n_nets <= NLBAC_MAX_NETS, "%s: n_nets %d out of [1,%d]", who, n_nets, NLBAC_MAX_NETS);
     NLBAC_REQUIRE(B >= 1, "%s: B must be >= 1", who);
@@ -1021,7 +1003,7 @@ extern "C" int nlbac_mlp_pack_layout(nlbac_mlp* net) {
     long off = 0;
     for (int l = 0; l < NLBAC_MAX_LAYERS; ++l) { net->pf_off[l] = -1; net->pb_off[l] = -1; }
     // (nets whose every launch runs on the register-resident kernels get no 32x32x2 packs: pf_off / pb_off stay -1)
-    const bool tile_packs = !nlbac_mlp_rr_serves_shape(net->n_layers, net->in_dim, hid, net->out_dim);
+    const bool tile_packs = !mlp_panel_shape(net->n_layers, net->in_dim, hid, net->out_dim);
     for (int l = 0; l < nwide && tile_packs; ++l) {
         const int K = (l == 0) ? net->in_dim : hid;
         net->pf_off[l] = (int)off;
@@ -1067,9 +1049,10 @@ static int mlp_fwd_launch(const nlbac_mlp* nets, const nlbac_mlp_io* io, int n_n
         NLBAC_REQUIRE(io[i].x0_dim == nets[i].in_dim || (io[i].x1 && io[i].x0_dim + io[i].x1_dim == nets[i].in_dim),
                       "%s: net %d input dims %d+%d != in_dim %d", who, i, io[i].x0_dim, io[i].x1_dim, nets[i].in_dim);
     }
-    {   // nets with one hid x hid layer of 64 / 128 / 256 units run on the register-resident kernels (mlp_rr_kernels.hip)
-        const int rr = nlbac_mlp_rr_fwd_launch(L, n_nets, G, who, (hipStream_t)s);
-        if (rr <= 0) return rr;
+    switch (mlp_family(nets, n_nets)) {
+        case MLP_HALF_PANEL: return nlbac_mlp_rr_fwd_launch(L, n_nets, G, who, (hipStream_t)s);
+        case MLP_QUARTER_PANEL: return nlbac_mlp_rrq_fwd_launch(L, n_nets, G, who, (hipStream_t)s);
+        case MLP_TILED: break;
     }
     for (int i = 0; i < n_nets; ++i)
         NLBAC_REQUIRE(!io[i].masks, "%s: net %d: ReLU mask words are written by the register-resident kernels only "
@@ -1081,12 +1064,10 @@ static int mlp_fwd_launch(const nlbac_mlp* nets, const nlbac_mlp_io* io, int n_n
     const dim3 grid(nlbac_ceil_div(B, NLBAC_MLP_TILE), n_nets);
     switch (tile_mode(nets, n_nets)) {
         case 1: hipLaunchKernelGGL(mlp_fwd_kernel<1>, grid, dim3(256), lds, (hipStream_t)s, L, G); break;
-        case 2:
-            if (waves8() && lds <= 80 * 1024 &&
-                (occ_mode() == 1 || (occ_mode() < 0 && (long)grid.x * grid.y > 256)))
+        case 2:     // 8 waves, one column tile each; two workgroups per CU once the grid has more tiles than CUs
+            if (lds <= 80 * 1024 && (long)grid.x * grid.y > 256)
                 hipLaunchKernelGGL((mlp_fwd_kernel<3, 1>), grid, dim3(512), lds, (hipStream_t)s, L, G);
-            else if (waves8()) hipLaunchKernelGGL(mlp_fwd_kernel<3>, grid, dim3(512), lds, (hipStream_t)s, L, G);
-            else hipLaunchKernelGGL(mlp_fwd_kernel<2>, grid, dim3(256), lds, (hipStream_t)s, L, G);
+            else hipLaunchKernelGGL(mlp_fwd_kernel<3>, grid, dim3(512), lds, (hipStream_t)s, L, G);
             break;
         default: hipLaunchKernelGGL(mlp_fwd_kernel<0>, grid, dim3(256), lds, (hipStream_t)s, L, G);
     }
@@ -1110,8 +1091,14 @@ extern "C" int nlbac_mlp_fwd_gauss(const nlbac_mlp* nets, const nlbac_mlp_io* io
     return mlp_fwd_launch(nets, io, n_nets, B, *head, who, s);
 }
 
+// 1 when the register-resident kernels take the launches of these nets, i.e. when nlbac_mlp_io::masks may replace acts
+extern "C" int nlbac_mlp_masks_ok(const nlbac_mlp* nets, int n_nets) {
+    return (nets && n_nets >= 1 && mlp_family(nets, n_nets) != MLP_TILED) ? 1 : 0;
+}
+
+// (the constraint head is the quarter-panel forward's)
 extern "C" int nlbac_mlp_fwd_head_ok(const nlbac_mlp* nets, int n_nets) {
-    return (nets && n_nets >= 1 && nlbac_mlp_rrq_eligible(nets, n_nets)) ? 1 : 0;
+    return (nets && n_nets >= 1 && mlp_family(nets, n_nets) == MLP_QUARTER_PANEL) ? 1 : 0;
 }
 
 extern "C" int nlbac_mlp_fwd_head(const nlbac_mlp* nets, const nlbac_mlp_io* io, int n_nets, int B,
@@ -1144,9 +1131,10 @@ static int mlp_bwd_data_launch(const nlbac_mlp* nets, const nlbac_mlp_io* io, in
     for (int i = 0; i < n_nets; ++i)
         NLBAC_REQUIRE(!io[i].skinny_ws || (B <= 32768 && io[i].x0 && io[i].dz && nets[i].hid <= 256),
                       "%s: net %d: skinny-gradient partials need x0, dz, hid <= 256 and B <= 32768", who, i);
-    {   // nets with one hid x hid layer of 64 / 128 / 256 units run on the register-resident kernel (mlp_rr_kernels.hip)
-        const int rr = nlbac_mlp_rr_bwd_launch(L, n_nets, H, who, (hipStream_t)s);
-        if (rr <= 0) return rr;
+    switch (mlp_family(nets, n_nets)) {
+        case MLP_HALF_PANEL: return nlbac_mlp_rr_bwd_launch(L, n_nets, H, who, (hipStream_t)s);
+        case MLP_QUARTER_PANEL: return nlbac_mlp_rrq_bwd_launch(L, n_nets, H, who, (hipStream_t)s);
+        case MLP_TILED: break;
     }
     for (int i = 0; i < n_nets; ++i)
         NLBAC_REQUIRE(io[i].acts, "%s: net %d: the LDS-tiled kernel gates with the saved activations (acts), not mask words", who, i);
@@ -1285,7 +1273,7 @@ extern "C" int nlbac_mlp_bwd_weights(const nlbac_mlp* nets, const nlbac_mlp_io* 
                 attr_set = true;
             }
             hipLaunchKernelGGL(mlp_bwd_wide128_kernel, dim3(max_layers, n_slabs, n_nets), dim3(256), lds, (hipStream_t)s, L);
-        } else if (dw64_enabled() && (long)B * 256 < (1L << 29)) {
+        } else if ((long)B * 256 < (1L << 29)) {
             // (with the partial sums already there, the skinny reduction's blocks lead the GEMM tiles)
             const int red_per_net = max_q * 4, red_blocks = partials_ready ? red_per_net * n_nets : 0;
             const int groups8 = (n_slabs * n_nets + 7) / 8;
@@ -1294,6 +1282,7 @@ extern "C" int nlbac_mlp_bwd_weights(const nlbac_mlp* nets, const nlbac_mlp_io* 
                                max_blocks);
             reduced = partials_ready;
         } else {
+            // (2^29 elements per layer and more — past mlp_bwd_wide64_kernel's 32-bit offsets: mlp_bwd_wide_kernel)
             // (with the partial sums already there, the skinny reduction's blocks ride behind the GEMM tiles of slab 0)
             const int per_plane = max_blocks * n_slabs, red_per_net = max_q * 4;
             const int red_planes = partials_ready ? (red_per_net * n_nets + per_plane - 1) / per_plane : 0;

@@ -11,9 +11,6 @@
 // what its MFMAs cost.
 #include "mlp_launch.h"
 #include "rr_device.h"
-#include <cstdlib>
-
-#define MRR_MAX_IN 15       /* in_dim + the bias column <= 16: four k-steps of layer 0 */
 
 #ifdef RR_TIMING      // ablation build: wave 0 of workgroup 0 stamps the shader clock behind the first net's outputs (as int64)
 #define MSTAMP(k_) if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) reinterpret_cast<long long*>(io.y + (long)B * io.y_ld)[k_] = (long long)__builtin_readcyclecounter();
@@ -448,96 +445,29 @@ __global__ __launch_bounds__(256, 2) void mlp_rr_bwd_kernel(const MlpLaunch L, c
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-static bool mrr_enabled() {
-    static const bool on = [] { const char* e = getenv("NLBAC_MLP_RR"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
-bool nlbac_mlp_rr_eligible(const nlbac_mlp* nets, int n_nets) {
-    if (!mrr_enabled()) return false;
-    for (int i = 0; i < n_nets; ++i) {
-        const nlbac_mlp& n = nets[i];
-        if (n.rr_kind != RR_KIND_PANEL || n.rr_fwd_off < 0 || n.hid != nets[0].hid) return false;
-        if (n.hid != 64 && n.hid != 128 && n.hid != 256) return false;
-        if (n.in_dim > MRR_MAX_IN || n.out_dim > 16) return false;
-    }
-    return true;
-}
-
+// the launchers of MLP_HALF_PANEL (mlp_launch.h): hid = 64, two 32-column blocks per panel half
 int nlbac_mlp_rr_fwd_launch(const MlpLaunch& L, int n_nets, const nlbac_gauss_head& G, const char* who, hipStream_t s) {
-    if (!nlbac_mlp_rr_eligible(L.net, n_nets)) return 1;
-    {
-        const int rq = nlbac_mlp_rrq_fwd_launch(L, n_nets, G, who, s);      // (hid 128 / 256: the quarter-panel kernels)
-        if (rq <= 0) return rq;
-    }
-    const int hid = L.net[0].hid;
     bool bits = false;
     for (int i = 0; i < n_nets; ++i) bits = bits || L.io[i].masks != nullptr;
     const size_t lds = (size_t)(2 * NLBAC_MLP_TILE * 16) * sizeof(float);
     const dim3 grid(nlbac_ceil_div(L.B, NLBAC_MLP_TILE), n_nets);
-#define MRR_FWD(NBH_)                                                                                            \
-    if (bits) hipLaunchKernelGGL((mlp_rr_fwd_kernel<NBH_, 1>), grid, dim3(256), lds, s, L, G);                   \
-    else hipLaunchKernelGGL((mlp_rr_fwd_kernel<NBH_, 0>), grid, dim3(256), lds, s, L, G);
-    switch (hid) {
-        case 64: MRR_FWD(2) break;
-        case 128: MRR_FWD(4) break;
-        default: MRR_FWD(8)
-    }
-#undef MRR_FWD
+    if (bits) hipLaunchKernelGGL((mlp_rr_fwd_kernel<2, 1>), grid, dim3(256), lds, s, L, G);
+    else hipLaunchKernelGGL((mlp_rr_fwd_kernel<2, 0>), grid, dim3(256), lds, s, L, G);
     NLBAC_CHECK_LAUNCH(who);
     return 0;
-}
-
-// data backward: 0 = launched, 1 = not these nets' kernel (the LDS-tiled one takes the launch), < 0 = error
-static bool mrr_bwd_enabled() {
-    static const bool on = [] { const char* e = getenv("NLBAC_MLP_RR_BWD"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
-// Every launch of a net of this shape — forward and data backward — is served by the register-resident kernels (so its
-// 32x32x2 fragment packs are never read: nlbac_mlp_pack_layout then leaves them out, and the optimiser has half as many
-// fragment slots to refresh per weight).  Shape and the process-wide switches only: the per-launch conditions of
-// nlbac_mlp_rr_eligible beyond them compare the nets of ONE launch (equal widths), and a launch that mixes widths is
-// refused by the LDS-tiled launcher for such a net instead of reading packs that do not exist.
-bool nlbac_mlp_rr_serves_shape(int n_layers, int in_dim, int hid, int out_dim) {
-    return mrr_enabled() && mrr_bwd_enabled() && rr_kind_of(n_layers, hid) == RR_KIND_PANEL &&
-           (hid == 64 || hid == 128 || hid == 256) && in_dim <= MRR_MAX_IN && out_dim <= 16;
 }
 
 int nlbac_mlp_rr_bwd_launch(const MlpLaunch& L, int n_nets, const nlbac_dy_head& H, const char* who, hipStream_t s) {
-    if (!mrr_bwd_enabled() || !nlbac_mlp_rr_eligible(L.net, n_nets)) return 1;
-    {
-        const int rq = nlbac_mlp_rrq_bwd_launch(L, n_nets, H, who, s);
-        if (rq <= 0) return rq;
-    }
+    MlpBwdFacts F;
+    if (mlp_bwd_facts(F, L, n_nets, who)) return -1;
     const int hid = L.net[0].hid;
-    bool sk = false, wide_out = false;
-    int n_bits = 0;
-    for (int i = 0; i < n_nets; ++i) {
-        sk = sk || (L.io[i].skinny_ws != nullptr && L.io[i].dz != nullptr);
-        wide_out = wide_out || L.net[i].out_dim > 4;
-        n_bits += L.io[i].masks != nullptr;
-    }
-    NLBAC_REQUIRE(n_bits == 0 || n_bits == n_nets, "%s: ReLU mask words (nlbac_mlp_io::masks) for all nets of a launch or for none", who);
-    const size_t lds = (size_t)(4 * NLBAC_MLP_TILE * 16 + (sk ? 2 * NLBAC_MLP_TILE * (hid + 4) : 0)) * sizeof(float);
+    const size_t lds = (size_t)(4 * NLBAC_MLP_TILE * 16 + (F.sk ? 2 * NLBAC_MLP_TILE * (hid + 4) : 0)) * sizeof(float);
     const dim3 grid(nlbac_ceil_div(L.B, NLBAC_MLP_TILE), n_nets);
-#define MRR_BWD2(NBH_, KLO_)                                                                                       \
-    if (n_bits) hipLaunchKernelGGL((mlp_rr_bwd_kernel<NBH_, KLO_, 1>), grid, dim3(256), lds, s, L, H);              \
-    else hipLaunchKernelGGL((mlp_rr_bwd_kernel<NBH_, KLO_, 0>), grid, dim3(256), lds, s, L, H);
-#define MRR_BWD(NBH_)                                                                                              \
-    if (wide_out) { MRR_BWD2(NBH_, 4) } else { MRR_BWD2(NBH_, 1) }
-    switch (hid) {
-        case 64: MRR_BWD(2) break;
-        case 128: MRR_BWD(4) break;
-        default: MRR_BWD(8)
-    }
+#define MRR_BWD(KLO_)                                                                                              \
+    if (F.bits) hipLaunchKernelGGL((mlp_rr_bwd_kernel<2, KLO_, 1>), grid, dim3(256), lds, s, L, H);                 \
+    else hipLaunchKernelGGL((mlp_rr_bwd_kernel<2, KLO_, 0>), grid, dim3(256), lds, s, L, H);
+    if (F.wide_out) { MRR_BWD(4) } else { MRR_BWD(1) }
 #undef MRR_BWD
-#undef MRR_BWD2
     NLBAC_CHECK_LAUNCH(who);
     return 0;
-}
-
-// 1 when both register-resident kernels take launches of these nets, i.e. when nlbac_mlp_io::masks may replace acts
-extern "C" int nlbac_mlp_masks_ok(const nlbac_mlp* nets, int n_nets) {
-    return (n_nets >= 1 && mrr_bwd_enabled() && nlbac_mlp_rr_eligible(nets, n_nets)) ? 1 : 0;
 }

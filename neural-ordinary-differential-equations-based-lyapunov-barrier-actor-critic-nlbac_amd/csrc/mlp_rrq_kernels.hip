@@ -19,10 +19,8 @@
 #include "mlp_launch.h"
 #include "rr_device.h"
 #include "auglag_device.h"
-#include <cstdlib>
 
 #define QT 16               /* rows per workgroup */
-#define MRQ_MAX_IN 15       /* in_dim + the bias column <= 16: four k-steps of layer 0 */
 
 #ifdef RR_TIMING      // ablation build: wave 0 of workgroup 0 stamps the shader clock (as int64) behind the first net's y / dz
 #define QFSTAMP(k_) if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) reinterpret_cast<long long*>(io.y + (long)B * io.y_ld)[k_] = (long long)__builtin_readcyclecounter();
@@ -481,19 +479,8 @@ __global__ __launch_bounds__(256, 3) void mlp_rrq_bwd_kernel(const MlpLaunch L, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-static bool mrq_enabled() {
-    static const bool on = [] { const char* e = getenv("NLBAC_MLP_RRQ"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
-// the widths the quarter-panel kernels serve (everything else nlbac_mlp_rr_eligible accepts stays on the half-panel ones)
-bool nlbac_mlp_rrq_eligible(const nlbac_mlp* nets, int n_nets) {
-    if (!mrq_enabled() || !nlbac_mlp_rr_eligible(nets, n_nets)) return false;
-    return nets[0].hid == 128 || nets[0].hid == 256;
-}
-
+// the launchers of MLP_QUARTER_PANEL (mlp_launch.h): hid = 128 / 256
 int nlbac_mlp_rrq_fwd_launch(const MlpLaunch& L, int n_nets, const nlbac_gauss_head& G, const char* who, hipStream_t s) {
-    if (!nlbac_mlp_rrq_eligible(L.net, n_nets)) return 1;
     const int hid = L.net[0].hid;
     bool bits = false;
     for (int i = 0; i < n_nets; ++i) bits = bits || L.io[i].masks != nullptr;
@@ -509,23 +496,16 @@ int nlbac_mlp_rrq_fwd_launch(const MlpLaunch& L, int n_nets, const nlbac_gauss_h
 }
 
 int nlbac_mlp_rrq_bwd_launch(const MlpLaunch& L, int n_nets, const nlbac_dy_head& H, const char* who, hipStream_t s) {
-    if (!nlbac_mlp_rrq_eligible(L.net, n_nets)) return 1;
+    MlpBwdFacts F;
+    if (mlp_bwd_facts(F, L, n_nets, who)) return -1;
     const int hid = L.net[0].hid;
-    bool sk = false, wide_out = false;
-    int n_bits = 0;
-    for (int i = 0; i < n_nets; ++i) {
-        sk = sk || (L.io[i].skinny_ws != nullptr && L.io[i].dz != nullptr);
-        wide_out = wide_out || L.net[i].out_dim > 4;
-        n_bits += L.io[i].masks != nullptr;
-    }
-    NLBAC_REQUIRE(n_bits == 0 || n_bits == n_nets, "%s: ReLU mask words (nlbac_mlp_io::masks) for all nets of a launch or for none", who);
-    const size_t lds = (size_t)(6 * QT * 16 + (sk ? 2 : 1) * QT * (hid + 4)) * sizeof(float);
+    const size_t lds = (size_t)(6 * QT * 16 + (F.sk ? 2 : 1) * QT * (hid + 4)) * sizeof(float);
     const dim3 grid(nlbac_ceil_div(L.B, QT), n_nets);
 #define MRQ_BWD2(NBQ_, KLO_)                                                                                       \
-    if (n_bits) hipLaunchKernelGGL((mlp_rrq_bwd_kernel<NBQ_, KLO_, 1>), grid, dim3(256), lds, s, L, H);             \
+    if (F.bits) hipLaunchKernelGGL((mlp_rrq_bwd_kernel<NBQ_, KLO_, 1>), grid, dim3(256), lds, s, L, H);             \
     else hipLaunchKernelGGL((mlp_rrq_bwd_kernel<NBQ_, KLO_, 0>), grid, dim3(256), lds, s, L, H);
 #define MRQ_BWD(NBQ_)                                                                                              \
-    if (wide_out) { MRQ_BWD2(NBQ_, 4) } else { MRQ_BWD2(NBQ_, 1) }
+    if (F.wide_out) { MRQ_BWD2(NBQ_, 4) } else { MRQ_BWD2(NBQ_, 1) }
     if (hid == 128) { MRQ_BWD(2) } else { MRQ_BWD(4) }
 #undef MRQ_BWD
 #undef MRQ_BWD2

@@ -14,7 +14,6 @@
 // k_au = g^T a_x, k_ax = dX_f + dX_g, step result and error estimate) is the LDS-tiled kernel's, operation for operation.
 #include "node_adj_shared.h"
 #include "rr_device.h"
-#include <cstdlib>
 #include <type_traits>
 
 bool nlbac_node_rr_eligible(const nlbac_mlp* f, const nlbac_mlp* g);      // (node_rr_kernels.hip)
@@ -431,19 +430,9 @@ __global__ __launch_bounds__(256) void node_adj_rr_kernel(const NodeAdjLaunch L)
     }
 }
 
-static bool adj_rr_enabled() {
-    static const bool on = [] { const char* e = getenv("NLBAC_ADJ_RR"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
-static bool adj_rr_keep_enabled() {
-    static const bool on = [] { const char* e = getenv("NLBAC_ADJ_RR_KEEP"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
 int nlbac_node_adj_rr_launch(NodeAdjLaunch& L, hipStream_t s) {
+    if (!nlbac_node_rr_eligible(&L.net[0], &L.net[1])) return 1;
     const bool keep = L.ZS != nullptr;
-    if (!adj_rr_enabled() || (keep && !adj_rr_keep_enabled()) || !nlbac_node_rr_eligible(&L.net[0], &L.net[1])) return 1;
     using Kernel = void (*)(const NodeAdjLaunch);
     const int hid = L.net[0].hid;
     const Kernel k = keep ? (hid == 64 ? node_adj_rr_kernel<4, 4, 1> : (hid == 100 ? node_adj_rr_kernel<7, 1, 1> : node_adj_rr_kernel<8, 4, 1>))
@@ -459,5 +448,5 @@ int nlbac_node_adj_rr_launch(NodeAdjLaunch& L, hipStream_t s) {
 }
 
 extern "C" int nlbac_node_adj_interp_ok(const nlbac_mlp* f, const nlbac_mlp* g) {
-    return (f && g && adj_rr_enabled() && nlbac_node_rr_eligible(f, g)) ? 1 : 0;
+    return (f && g && nlbac_node_rr_eligible(f, g)) ? 1 : 0;
 }

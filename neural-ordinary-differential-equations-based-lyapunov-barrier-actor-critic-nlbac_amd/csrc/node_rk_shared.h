@@ -81,11 +81,9 @@ struct NodeRkBwdLaunch {
 int nlbac_node_rr_fwd_launch(NodeRkLaunch& L, hipStream_t s);
 int nlbac_node_rr_bwd_launch(NodeRkBwdLaunch& L, hipStream_t s);
 bool nlbac_node_rr_eligible(const nlbac_mlp* f, const nlbac_mlp* g);
-// what the trajectory kernels (node_traj_kernels.hip) select by, as the one-step launchers do: the kernels are on
-// (NLBAC_NODE_RR), the width's template shape (0, 1, 2 for 64, 100, 128; -1 none), the f_net / g_net wave balance
-bool nlbac_node_rr_enabled();
+// what the trajectory kernels (node_traj_kernels.hip) select by, as the one-step launchers do: the width's template
+// shape (0, 1, 2 for 64, 100, 128; -1 none)
 int nlbac_node_rr_shape(int hid);
-bool nlbac_node_rr_split();
 
 // ---------------------------------------------------------------------------------------------------------------
 // forward: the small per-tile arrays in LDS

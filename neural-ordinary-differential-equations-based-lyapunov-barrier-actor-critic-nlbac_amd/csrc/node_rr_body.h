@@ -930,43 +930,39 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
 // one-step launchers (node_rr_kernels.hip) and the trajectory / time-grid launchers (node_traj_kernels.hip), whose
 // results are the one-step launches' bit for bit only while they pick the same instance.
 // ---------------------------------------------------------------------------------------------------------------------
-// the instances of one kernel template KERN<NB, R, BITS, SPLIT>: k [SPLIT][shape][BITS != 0], and those that keep
-// activation rows + mask words (acts_bits 2, the NODE fit) rows [SPLIT][shape].  The forward is never split with rows:
-// its rows + words instances are the unsplit ones, whose sums are those of the rows-only forward
+// the instances of one kernel template KERN<NB, R, BITS, SPLIT>: k [shape][acts_bits].  The f_net / g_net wave balance
+// (SPLIT, see the kernels) is a property of the direction and of acts_bits, not a choice: the backward is always split,
+// the forward in mask mode only.  With activation rows kept (acts_bits 0 / 2; the NODE fit: 32768 rows, two workgroups
+// per CU) the two waves' store bursts and the hand-over cost the forward more than the balance gains — 140 against
+// 124 us per launch — and its rows + words instance has to give the sums of the rows-only one
 template <typename Launch>
 struct NodeRrTable {
     using Kernel = void (*)(const Launch);
-    Kernel k[2][3][2];
-    Kernel rows[2][3];
+    Kernel k[3][3];
 };
 
-#define NODE_RR_SHAPES(KERN, BITS, SPLIT) {KERN<4, 4, BITS, SPLIT>, KERN<7, 1, BITS, SPLIT>, KERN<8, 4, BITS, SPLIT>}
-#define NODE_RR_K(KERN)                                                                                                 \
-    {{{KERN<4, 4, 0, 0>, KERN<4, 4, 1, 0>}, {KERN<7, 1, 0, 0>, KERN<7, 1, 1, 0>}, {KERN<8, 4, 0, 0>, KERN<8, 4, 1, 0>}},  \
-     {{KERN<4, 4, 0, 1>, KERN<4, 4, 1, 1>}, {KERN<7, 1, 0, 1>, KERN<7, 1, 1, 1>}, {KERN<8, 4, 0, 1>, KERN<8, 4, 1, 1>}}}
-#define NODE_RR_FWD_TABLE(KERN) {NODE_RR_K(KERN), {NODE_RR_SHAPES(KERN, 2, 0), NODE_RR_SHAPES(KERN, 2, 0)}}
-#define NODE_RR_BWD_TABLE(KERN) {NODE_RR_K(KERN), {NODE_RR_SHAPES(KERN, 2, 0), NODE_RR_SHAPES(KERN, 2, 1)}}
+#define NODE_RR_BITS(KERN, NB, R, S0, S1, S2) {KERN<NB, R, 0, S0>, KERN<NB, R, 1, S1>, KERN<NB, R, 2, S2>}
+#define NODE_RR_TABLE(KERN, S0, S1, S2)                                                                                 \
+    {{NODE_RR_BITS(KERN, 4, 4, S0, S1, S2), NODE_RR_BITS(KERN, 7, 1, S0, S1, S2), NODE_RR_BITS(KERN, 8, 4, S0, S1, S2)}}
+#define NODE_RR_FWD_TABLE(KERN) NODE_RR_TABLE(KERN, 0, 1, 0)
+#define NODE_RR_BWD_TABLE(KERN) NODE_RR_TABLE(KERN, 1, 1, 1)
 
 // launch the instance of `t` for nets `hid` wide and this acts_bits over n rows, one 32-row tile per workgroup
 template <typename Launch>
-static void node_rr_start(const NodeRrTable<Launch>& t, const Launch& A, int hid, int n, int acts_bits, bool split,
+static void node_rr_start(const NodeRrTable<Launch>& t, const Launch& A, int hid, int n, int acts_bits,
                           size_t lds_floats, hipStream_t s) {
-    const int shape = nlbac_node_rr_shape(hid);
-    const auto k = (acts_bits == 2) ? t.rows[split][shape] : t.k[split][shape][acts_bits ? 1 : 0];
-    hipLaunchKernelGGL(k, dim3(nlbac_ceil_div(n, NLBAC_MLP_TILE)), dim3(256), lds_floats * sizeof(float), s, A);
+    hipLaunchKernelGGL(t.k[nlbac_node_rr_shape(hid)][acts_bits], dim3(nlbac_ceil_div(n, NLBAC_MLP_TILE)), dim3(256),
+                       lds_floats * sizeof(float), s, A);
 }
 
-// (the forward is split in mask mode only: with activation rows kept — the NODE fit, 32768 rows, two workgroups per
-//  CU — the two waves' store bursts and the hand-over cost more than the balance gains: 140 against 124 us per launch)
 template <typename Launch>
 static void node_rr_fwd_start(const NodeRrTable<Launch>& t, const Launch& A, int hid, int n, int acts_bits, hipStream_t s) {
-    node_rr_start(t, A, hid, n, acts_bits, nlbac_node_rr_split() && acts_bits == 1,
+    node_rr_start(t, A, hid, n, acts_bits,
                   RkFwdTile::floats() + NLBAC_MLP_TILE * 8 + 2 * 3 * 8 * 64 + 2 * 32 * 64 + NLBAC_MLP_TILE * RK_MAX_NS +
                       2 * 2 * 64 + 4, s);
 }
 
 template <typename Launch>
 static void node_rr_bwd_start(const NodeRrTable<Launch>& t, const Launch& A, int hid, int n, int acts_bits, hipStream_t s) {
-    node_rr_start(t, A, hid, n, acts_bits, nlbac_node_rr_split(),
-                  RkBwdTile::floats() + 2 * 4 * 8 * 64 + 2 * 32 * 64 + 2 * 16 * 64 + 4, s);
+    node_rr_start(t, A, hid, n, acts_bits, RkBwdTile::floats() + 2 * 4 * 8 * 64 + 2 * 32 * 64 + 2 * 16 * 64 + 4, s);
 }

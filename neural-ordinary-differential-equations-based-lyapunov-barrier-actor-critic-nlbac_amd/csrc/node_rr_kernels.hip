@@ -2,7 +2,6 @@
 // side.  What they run — one 32-row tile per workgroup, four waves, one (net, 16 rows) chain per wave — is
 // node_rr_body.h, shared with the one-launch trajectory kernels (node_traj_kernels.hip).
 #include "node_rr_body.h"
-#include <cstdlib>
 
 #ifdef RR_TIMING
 extern "C" int nlbac_debug_bwd_stamps(long long* out) {
@@ -23,19 +22,10 @@ __global__ __launch_bounds__(256) void node_rr_bwd_kernel(const NodeRkBwdLaunch 
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-bool nlbac_node_rr_enabled() {
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("NLBAC_NODE_RR");
-        on = (e && e[0] == '0') ? 0 : 1;
-    }
-    return on == 1;
-}
-
 int nlbac_node_rr_shape(int hid) { return hid == 64 ? 0 : (hid == 100 ? 1 : (hid == 128 ? 2 : -1)); }
 
 bool nlbac_node_rr_eligible(const nlbac_mlp* f, const nlbac_mlp* g) {
-    if (!nlbac_node_rr_enabled() || !f || !g) return false;
+    if (!f || !g) return false;
     if (f->hid != g->hid || nlbac_node_rr_shape(f->hid) < 0) return false;
     if (f->n_layers != 5 || g->n_layers != 4) return false;      // the layer chains are unrolled for the reference's depths
     if (f->rr_fwd_off < 0 || g->rr_fwd_off < 0 || f->rr_bwd_off < 0 || g->rr_bwd_off < 0) return false;
@@ -50,12 +40,6 @@ extern "C" int nlbac_node_rk_mask_words(const nlbac_mlp* f, const nlbac_mlp* g, 
     if (nlbac_node_rr_eligible(f, g)) return 4;            // one word per lane quarter
     const nlbac_mlp* net = which ? g : f;
     return (net->hid + 31) >> 5;
-}
-
-// the f_net / g_net wave balance (SPLIT, see the kernels); NLBAC_NODE_SPLIT=0 keeps one net per wave
-bool nlbac_node_rr_split() {
-    static const bool on = [] { const char* e = getenv("NLBAC_NODE_SPLIT"); return !(e && e[0] == '0'); }();
-    return on;
 }
 
 // which instance and how much LDS: node_rr_body.h's host section, shared with the trajectory launchers

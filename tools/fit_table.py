@@ -6,7 +6,7 @@ import sys
 
 rows = list(csv.DictReader(open(sys.argv[1])))
 ks = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].split("(")[0].replace("void ", "")[:50]) for r in rows)
-# the fit's weight gradients are the one launch of mlp_dw16 (or, NLBAC_MLP_DW16=0, of mlp_bwd_wide128) per RK step
+# the fit's weight gradients are the one launch of mlp_dw16 (of mlp_bwd_wide128 for nets wider than 112) per RK step
 idx = [i for i, k in enumerate(ks) if k[2].startswith(("mlp_dw16", "mlp_bwd_wide128"))]
 spans = []
 for i in idx:

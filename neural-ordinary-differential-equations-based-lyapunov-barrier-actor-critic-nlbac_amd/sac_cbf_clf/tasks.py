@@ -7,8 +7,19 @@ lives in ``sac_cbf_clf.SAC_CBF_CLF`` and each environment contributes a task):
   * the rollout of the learned dynamics under both controllers, the CBF / CLF
     terms, and the gradient of the augmented-Lagrangian loss w.r.t. the actions.
 
+``_Task`` holds what every task shares: the schedules' defaults, the descriptor of V(current Lyapunov input), the
+NODE fit's inputs / buffers / first half (a task names its state kernel in ``state_rows``).
+
+Hand-written constraints, two controllers (primary + backup):
 ``UnicycleTask``   U/sac_cbf_clf/sac_cbf_clf.py:364-640, U/sac_cbf_clf/model.py:177-260
 ``CarsTask``       C/sac_cbf_clf/sac_cbf_clf.py:364-681, C/sac_cbf_clf/model.py:179-252
+``PvtolTask``      P/sac_cbf_clf/sac_cbf_clf.py:376-1048, P/sac_cbf_clf/model.py:224-266
+
+Learned barrier certificate, one controller: ``_LearnedBarrierTask`` is the whole update; an environment names its
+widths, its constants and its maps x' -> Lyapunov input / observation with their backward:
+``UnicycleBarrierTask``    NU/sac_cbf_clf/sac_cbf_clf.py:339-477
+``PvtolBarrierTask``       NP/sac_cbf_clf/sac_cbf_clf.py:334-480
+``QuadrotorBarrierTask``   no reference code (README prose only): checked against the oracle
 """
 import ctypes as C
 
@@ -19,6 +30,15 @@ from .. import _lib
 from ..arena import mlp_array, stream_ptr
 from ..odeint import AffineNodeSolver, ConcatNodeSolver
 from .model import NeuralODEModel
+from .update_plan import io_copy_and_one, io_set
+
+
+def _fit_in_first_100_episodes(self, i_episode):
+    return i_episode is None or i_episode <= 100
+
+
+def _lya_on_observations(self, lay):
+    return lay.obs, lay.nobs
 
 
 class _Task:
@@ -85,12 +105,40 @@ class _Task:
         """Columns of the minibatch row the Lyapunov critic is regressed on: (input, next input)."""
         return lay.lya, lay.nlya
 
-    # value-only nets riding in the Q(s, pi) launch besides V(current Lyapunov input)
+    # V(current Lyapunov input) rides in the Q(s, pi) launch of the shared part: tell it where to read and write
+    def value_now_io(self, ws, io, i):
+        lay = self.agent.lay
+        io_set(io[i], x0=(ws.mb.data_ptr() + 4 * lay.lya, self.lya_dim, lay.LD), y=(ws.V, 1))
+
+    # value-only nets riding in that launch besides it
     def extra_value_nets(self):
         return []
 
     def extra_value_io(self, ws, io, i):
         pass
+
+    # -- NODE fit: one solve from (state, action) against the next state ---------------------------
+    def state_rows(self, p_obs, obs_ld, n, dst):
+        """The NODE state (n, n_s) of n observation rows, written to ``dst``: the task's state kernel."""
+        raise NotImplementedError
+
+    def fit_inputs(self, rows):
+        """(obs ptr, ld, action (N, act_dim), next_obs ptr, ld, N) of minibatch-layout rows."""
+        lay = self.agent.lay
+        return (rows.data_ptr(), rows.shape[1], rows[:, lay.act:lay.act + self.act_dim],
+                rows.data_ptr() + 4 * lay.nobs, rows.shape[1], rows.shape[0])
+
+    def fit_ws(self, N):
+        z, n_s = self.z, self.n_s
+        return dict(st=z(N, n_s), nst=z(N, n_s), dpred=z(N, n_s), part=z((N + 255) // 256), u=z(N, 2))
+
+    def fit_part1(self, w, p_obs, obs_ld, p_nobs, nobs_ld, N):
+        a = self.agent
+        self.state_rows(p_obs, obs_ld, N, w["st"])
+        self.state_rows(p_nobs, nobs_ld, N, w["nst"])
+        if not isinstance(self.fit_solver, ConcatNodeSolver):
+            self.reserve(self.fit_solver, N, 1)
+        self.fit_solver.forward_begin(w["st"], w["u"], 1, N, a.solver, self.env.dt, a.atol, a.rtol)
 
 
 # =====================================================================================
@@ -133,41 +181,24 @@ class UnicycleTask(_Task):
         ws.dx_next2 = z(2 * B, 3)
 
     def plan(self, ws, P):
-        a, lay = self.agent, self.agent.lay
+        a = self.agent
         P.cf_head = P.head_actor_q_cb = None       # launch arguments built on first use (loss_and_backward)
         P.n_l = mlp_array([a.h_l.desc])
-        io = P.io_vn = P.io(1)                     # V(p(x')) forward + data backward
-        io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.ps_next2.data_ptr(), 2, 2
-        io[0].y, io[0].y_ld = ws.Vn.data_ptr(), 1
-        io[0].acts = ws.acts_vn.data_ptr()
-        io[0].dy, io[0].dy_ld = ws.dVn.data_ptr(), 1
-        io[0].dx, io[0].dx_ld = ws.dps_v2.data_ptr(), 2
-        P.io_vc = P.io(1)                          # V(centre), value only
-        P.io_vc[0].x0, P.io_vc[0].x0_dim, P.io_vc[0].x0_ld = ws.mb.data_ptr() + 4 * lay.lya, 2, lay.LD
-        P.io_vc[0].y, P.io_vc[0].y_ld = ws.V.data_ptr(), 1
+        P.io_vn = P.io(1)                          # V(p(x')) forward + data backward
+        io_set(P.io_vn[0], x0=(ws.ps_next2, 2, 2), y=(ws.Vn, 1), acts=ws.acts_vn, dy=(ws.dVn, 1), dx=(ws.dps_v2, 2))
         # the data backward of V(p(x')) and of the Q(s, pi) nets do not depend on each other and are both due when the
         # constraints' gradients exist: one launch (the Q nets' dL/dq from the dy head, V's from io.dy) instead of a
         # 128-tile launch on 256 CUs followed by a second one
         n2 = 2 * P.NP
         P.n_q5v = mlp_array([a.h_q1.desc, a.h_q2.desc] * P.NP + [a.h_l.desc])
         P.io_q5v = P.io(n2 + 1)
-        for i in range(n2):
-            C.memmove(C.byref(P.io_q5v, i * C.sizeof(_lib.MlpIO)), C.byref(P.io_q5, i * C.sizeof(_lib.MlpIO)), C.sizeof(_lib.MlpIO))
-        C.memmove(C.byref(P.io_q5v, n2 * C.sizeof(_lib.MlpIO)), C.byref(P.io_vn, 0), C.sizeof(_lib.MlpIO))
+        io_copy_and_one(P.io_q5v, P.io_q5, n2, P.io_vn)
         # likewise forward: Q(s, pi) [+ V(centre)] is the last piece of part 1 and V(p(x')) the first launch behind the
         # rollout — when that piece is still pending at that point, both go out as one launch
         nq = P.n_q5_count
         P.n_q5f = mlp_array([a.h_q1.desc, a.h_q2.desc] * P.NP + [a.h_l.desc] * (nq - n2) + [a.h_l.desc])
         P.io_q5f = P.io(nq + 1)
-        for i in range(nq):
-            C.memmove(C.byref(P.io_q5f, i * C.sizeof(_lib.MlpIO)), C.byref(P.io_q5, i * C.sizeof(_lib.MlpIO)), C.sizeof(_lib.MlpIO))
-        C.memmove(C.byref(P.io_q5f, nq * C.sizeof(_lib.MlpIO)), C.byref(P.io_vn, 0), C.sizeof(_lib.MlpIO))
-
-    # V(centre) rides in the 5-net launch of the shared part: tell it where to write
-    def value_now_io(self, ws, io, i):
-        lay = self.agent.lay
-        io[i].x0, io[i].x0_dim, io[i].x0_ld = ws.mb.data_ptr() + 4 * lay.lya, self.lya_dim, lay.LD
-        io[i].y, io[i].y_ld = ws.V.data_ptr(), 1
+        io_copy_and_one(P.io_q5f, P.io_q5, nq, P.io_vn)
 
     # -- rollout under both controllers ------------------------------------------------------
     def rollout_begin(self, ws, P):
@@ -284,122 +315,8 @@ class UnicycleTask(_Task):
     def first_step_done(self):
         return self.solver.first_step_done()
 
-    # -- NODE fit (U/model.py:221-260 via U/sac_cbf_clf.py:205-219) -------------------------------
-    def fit_inputs(self, rows):
-        """(obs ptr, ld, action (N,2), next_obs ptr, ld, N) of minibatch-layout rows."""
-        lay = self.agent.lay
-        return (rows.data_ptr(), rows.shape[1], rows[:, lay.act:lay.act + 2], rows.data_ptr() + 4 * lay.nobs,
-                rows.shape[1], rows.shape[0])
-
-    def fit_ws(self, N):
-        z = self.z
-        return dict(st=z(N, 3), nst=z(N, 3), dpred=z(N, 3), part=z((N + 255) // 256), u=z(N, 2))
-
-    def fit_part1(self, w, p_obs, obs_ld, p_nobs, nobs_ld, N):
-        a, s = self.agent, stream_ptr()
-        _lib.call("nlbac_unicycle_state", p_obs, obs_ld, N, self.l_p, w["st"].data_ptr(), 1, None, s)
-        _lib.call("nlbac_unicycle_state", p_nobs, nobs_ld, N, self.l_p, w["nst"].data_ptr(), 1, None, s)
-        if isinstance(self.fit_solver, AffineNodeSolver) and not isinstance(self.fit_solver, ConcatNodeSolver):
-            self.reserve(self.fit_solver, N, 1)
-        self.fit_solver.forward_begin(w["st"], w["u"], 1, N, a.solver, self.env.dt, a.atol, a.rtol)
-
-
-# =====================================================================================
-class UnicycleBarrierTask(UnicycleTask):
-    """Learned-barrier-certificate Unicycle (NU/sac_cbf_clf/sac_cbf_clf.py:339-477): one controller; the CBF is a
-    network B(obs, a) trained with the critics; its term needs the predicted next observation get_obs(x')
-    (differentiable) and a re-sampled, detached next action; no ratio in the loss."""
-    name = "UnicycleBarrier"
-    n_pol, backup_mode, has_signal, n_extra_critics = 1, 0, True, 1
-    ratio_mode = 0
-    n_eps = 3                 # next-obs sample, obs sample, sample on the predicted next observation
-    graph_ok = True
-    GOAL = (2.5, 2.5)         # NU/sac_cbf_clf/dynamics.py:104-105
-
-    def __init__(self, agent, env, args):
-        super().__init__(agent, env, args)
-        self.num_cbfs = 1
-
-    def alloc(self, ws):
-        B, z, H = ws.B, self.z, self.agent.hidden
-        ws.y0 = z(B, 3)
-        ws.V, ws.Vn, ws.dVn = z(B), z(B), z(B)
-        ws.acts_vn = z(2, B, H)
-        ws.ps_next, ws.dps_v = z(B, 2), z(B, 2)
-        ws.Bv, ws.Bn, ws.dBn = z(B), z(B), z(B)
-        ws.acts_bn = z(2, B, H)
-        ws.obs_pred, ws.heads_nx, ws.pi_next, ws.logp_nx = z(B, 7), z(B, 4), z(B, 2), z(B)
-        ws.dxb = z(B, 9)                               # d B(obs', a') / d [obs', a']
-        ws.matr = z(B, 2)
-        ws.part_c = z(ws.nblk, 2)
-        ws.dx_next = z(B, 3)
-
-    def extra_value_nets(self):
-        return [self.agent.h_extra[0]]
-
-    def extra_value_io(self, ws, io, i):               # B(obs, pi), value only (detached in the reference)
-        lay = self.agent.lay
-        io[i].x0, io[i].x0_dim, io[i].x0_ld = ws.mb.data_ptr() + 4 * lay.obs, 7, lay.LD
-        io[i].x1, io[i].x1_dim, io[i].x1_ld = ws.pi2.data_ptr(), 2, 2
-        io[i].y, io[i].y_ld = ws.Bv.data_ptr(), 1
-
-    def plan(self, ws, P):
-        a = self.agent
-        P.n_l = mlp_array([a.h_l.desc])
-        io = P.io_vn = P.io(1)                         # V(p(x')) forward + data backward
-        io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.ps_next.data_ptr(), 2, 2
-        io[0].y, io[0].y_ld = ws.Vn.data_ptr(), 1
-        io[0].acts = ws.acts_vn.data_ptr()
-        io[0].dy, io[0].dy_ld = ws.dVn.data_ptr(), 1
-        io[0].dx, io[0].dx_ld = ws.dps_v.data_ptr(), 2
-        P.n_pi = mlp_array([a.h_p.desc])
-        io = P.io_nx = P.io(1)                         # policy on the predicted next observation
-        io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.obs_pred.data_ptr(), 7, 7
-        io[0].y, io[0].y_ld = ws.heads_nx.data_ptr(), 4
-        P.n_bar = mlp_array([a.h_extra[0].desc])
-        io = P.io_bn = P.io(1)                         # B(obs', a') forward + data backward
-        io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.obs_pred.data_ptr(), 7, 7
-        io[0].x1, io[0].x1_dim, io[0].x1_ld = ws.pi_next.data_ptr(), 2, 2
-        io[0].y, io[0].y_ld = ws.Bn.data_ptr(), 1
-        io[0].acts = ws.acts_bn.data_ptr()
-        io[0].dy, io[0].dy_ld = ws.dBn.data_ptr(), 1
-        io[0].dx, io[0].dx_ld = ws.dxb.data_ptr(), 9
-
-    def rollout_begin(self, ws, P):
-        a, s = self.agent, stream_ptr()
-        if self.solver.fused and a.fold_launches:       # (the state is formed by the rollout's first launch: UnicycleTask)
-            self.solver.set_in_map(1, ws.mb, a.lay.LD, self.l_p, None)
-        else:
-            _lib.call("nlbac_unicycle_state", ws.mb.data_ptr(), a.lay.LD, ws.B, self.l_p, ws.y0.data_ptr(), 1, None, s)
-        self.reserve(self.solver, ws.B, 1)
-        self.solver._out_map = None
-        self.solver.forward_begin(ws.y0, ws.pi2, 1, ws.B, a.solver, float(self.env.dt), a.atol, a.rtol)
-
-    def loss_and_backward(self, ws, P, lam_upd, assume_single):
-        a, s, call = self.agent, stream_ptr(), _lib.call
-        B, sc, dt = ws.B, a.sc.data_ptr(), float(self.env.dt)
-        pol = a.policy
-        gx, gy = self.GOAL
-        x_next = self.solver.forward_finish(assume_single_step=assume_single)
-        a.drain_fill()
-        call("nlbac_unicycle_lookahead", x_next.data_ptr(), B, self.l_p, ws.ps_next.data_ptr(), s)
-        call("nlbac_mlp_fwd", P.n_l, P.io_vn, 1, B, s)
-        call("nlbac_unicycle_obs_fwd", x_next.data_ptr(), B, gx, gy, ws.obs_pred.data_ptr(), 7, s)
-        self.policy_sample(ws, "nx", P.n_pi, P.io_nx, 1, B, ws.heads_nx, ws.eps[2], 2, ws.pi_next, 2, ws.logp_nx)
-        call("nlbac_mlp_fwd", P.n_bar, P.io_bn, 1, B, s)
-        call("nlbac_barrier_constraints_fwd", ws.Bv.data_ptr(), ws.Bn.data_ptr(), ws.V.data_ptr(), ws.Vn.data_ptr(),
-             dt, float(a.gamma_b), self.gamma_l, B, ws.matr.data_ptr(), ws.part_c.data_ptr(),
-             *a.auglag_fused(ws, 1, lam_upd), s)
-        a.auglag(ws, 1, lam_upd)
-        call("nlbac_barrier_constraints_bwd", ws.matr.data_ptr(), dt, float(a.batch_size), B, sc, ws.dBn.data_ptr(),
-             ws.dVn.data_ptr(), s)
-        call("nlbac_mlp_bwd_data", P.n_l, P.io_vn, 1, B, s)          # dV' -> d p(x')
-        call("nlbac_mlp_bwd_data", P.n_bar, P.io_bn, 1, B, s)        # dB' -> d [obs', a'] (a' is detached)
-        call("nlbac_unicycle_lookahead_bwd", x_next.data_ptr(), ws.dps_v.data_ptr(), None, B, self.l_p,
-             ws.dx_next.data_ptr(), s)
-        call("nlbac_unicycle_obs_bwd", x_next.data_ptr(), ws.dxb.data_ptr(), 9, B, gx, gy, ws.dx_next.data_ptr(), 1, s)
-        du, _ = self.solver.backward(ws.dx_next, need_du=True)
-        return du, self.act_dim
+    def state_rows(self, p_obs, obs_ld, n, dst):      # (U/model.py:221-260 via U/sac_cbf_clf.py:205-219)
+        _lib.call("nlbac_unicycle_state", p_obs, obs_ld, n, self.l_p, dst.data_ptr(), 1, None, stream_ptr())
 
 
 # =====================================================================================
@@ -449,21 +366,12 @@ class CarsTask(_Task):
     def plan(self, ws, P):
         a, B = self.agent, ws.B
         P.n_l = mlp_array([a.h_l.desc])
-        io = P.io_v1 = P.io(1)                     # V(x_t+1[4:8]) forward + data backward
-        io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.x1_2.data_ptr() + 4 * 4, 4, 10
-        io[0].y, io[0].y_ld = ws.V1.data_ptr(), 1
-        io[0].acts = ws.acts_v1.data_ptr()
-        io[0].dy, io[0].dy_ld = ws.dV1.data_ptr(), 1
-        io[0].dx, io[0].dx_ld = ws.dlya.data_ptr(), 4
+        P.io_v1 = P.io(1)                          # V(x_t+1[4:8]) forward + data backward
+        io_set(P.io_v1[0], x0=(ws.x1_2.data_ptr() + 4 * 4, 4, 10), y=(ws.V1, 1), acts=ws.acts_v1, dy=(ws.dV1, 1),
+               dx=(ws.dlya, 4))
         io = P.io_nx = P.io(2)                     # both policies on the predicted next observation
         for i in range(2):
-            io[i].x0, io[i].x0_dim, io[i].x0_ld = ws.obs1_2[i * B:].data_ptr(), 10, 10
-            io[i].y, io[i].y_ld = ws.heads_nx[i * B:].data_ptr(), 2
-
-    def value_now_io(self, ws, io, i):
-        lay = self.agent.lay
-        io[i].x0, io[i].x0_dim, io[i].x0_ld = ws.mb.data_ptr() + 4 * lay.lya, self.lya_dim, lay.LD
-        io[i].y, io[i].y_ld = ws.V.data_ptr(), 1
+            io_set(io[i], x0=(ws.obs1_2[i * B:], 10, 10), y=(ws.heads_nx[i * B:], 2))
 
     def rollout_begin(self, ws, P):
         a, s = self.agent, stream_ptr()
@@ -477,7 +385,6 @@ class CarsTask(_Task):
     def loss_and_backward(self, ws, P, lam_upd, assume_single):
         a, s, call = self.agent, stream_ptr(), _lib.call
         B, sc, dt = ws.B, a.sc.data_ptr(), float(self.env.dt)
-        pol = a.policy
         x1 = self.solver1.forward_finish()
         if x1.data_ptr() != ws.x1_2.data_ptr():
             ws.x1_2.copy_(x1)         # (normally the solver has written there itself: out_into, rollout_begin)
@@ -505,22 +412,13 @@ class CarsTask(_Task):
         return self.solver1.first_step_done()
 
     # -- NODE fit (C/model.py:208-252 via C/sac_cbf_clf.py:201-217) --------------------------------
-    def fit_inputs(self, rows):
+    def fit_inputs(self, rows):                        # (the carried inputs: action and time stacked)
         lay = self.agent.lay
         c = torch.stack((rows[:, lay.act], rows[:, lay.t]), 1)
         return (rows.data_ptr(), rows.shape[1], c, rows.data_ptr() + 4 * lay.nobs, rows.shape[1], rows.shape[0])
 
-    def fit_ws(self, N):
-        z = self.z
-        return dict(st=z(N, 10), nst=z(N, 10), dpred=z(N, 10), part=z((N + 255) // 256), u=z(N, 2))
-
-    def fit_part1(self, w, p_obs, obs_ld, p_nobs, nobs_ld, N):
-        a, s = self.agent, stream_ptr()
-        _lib.call("nlbac_cars_state", p_obs, obs_ld, N, w["st"].data_ptr(), s)
-        _lib.call("nlbac_cars_state", p_nobs, nobs_ld, N, w["nst"].data_ptr(), s)
-        if isinstance(self.fit_solver, AffineNodeSolver) and not isinstance(self.fit_solver, ConcatNodeSolver):
-            self.reserve(self.fit_solver, N, 1)
-        self.fit_solver.forward_begin(w["st"], w["u"], 1, N, a.solver, self.env.dt, a.atol, a.rtol)
+    def state_rows(self, p_obs, obs_ld, n, dst):
+        _lib.call("nlbac_cars_state", p_obs, obs_ld, n, dst.data_ptr(), stream_ptr())
 
 
 # =====================================================================================
@@ -556,11 +454,8 @@ class PvtolTask(_Task):
     def backup_lam_due(self, updates, interval):
         return 1 if updates % (interval * self.backup_interval) == 0 else 0
 
-    def fit_due(self, i_episode):
-        return i_episode is None or i_episode <= 100
-
-    def lya_train_cols(self, lay):
-        return lay.obs, lay.nobs          # P:243-252: the Lyapunov critic is regressed on observations
+    fit_due = _fit_in_first_100_episodes
+    lya_train_cols = _lya_on_observations     # P:243-252: the Lyapunov critic is regressed on observations
 
     def setup(self):
         a = self.agent
@@ -574,8 +469,8 @@ class PvtolTask(_Task):
 
     def alloc(self, ws):
         B, z, H = ws.B, self.z, self.agent.hidden
-        ws.st6, ws.op0 = z(B, 6), z(B)
-        ws.y0 = z(2 * B, 6)
+        ws.op0 = z(B)
+        ws.y0 = z(2 * B, 6)                         # (rollout_begin: st6 is its first block)
         ws.x1, ws.x2, ws.x3 = z(2 * B, 6), z(2 * B, 6), z(2 * B, 6)
         ws.obs1, ws.obs2 = z(2 * B, 11), z(2 * B, 11)
         ws.op1, ws.op2 = z(2 * B), z(2 * B)
@@ -588,27 +483,17 @@ class PvtolTask(_Task):
         ws.part_c = z(ws.nblk, 2 * self.num_cbfs + 1)
         ws.dx1, ws.dx2, ws.dx3 = z(2 * B, 6), z(2 * B, 6), z(2 * B, 6)
 
-    def value_now_io(self, ws, io, i):
-        lay = self.agent.lay
-        io[i].x0, io[i].x0_dim, io[i].x0_ld = ws.mb.data_ptr() + 4 * lay.lya, self.lya_dim, lay.LD
-        io[i].y, io[i].y_ld = ws.V.data_ptr(), 1
-
     def plan(self, ws, P):
         a, B, NP = self.agent, ws.B, P.NP
         P.n_l = mlp_array([a.h_l.desc])
-        io = P.io_v1 = P.io(1)                     # V(obs(x_t+1)) forward + data backward
-        io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.obs1.data_ptr(), 11, 11
-        io[0].y, io[0].y_ld = ws.V1.data_ptr(), 1
-        io[0].acts = ws.acts_v1.data_ptr()
-        io[0].dy, io[0].dy_ld = ws.dV1.data_ptr(), 1
-        io[0].dx, io[0].dx_ld = ws.dobs1.data_ptr(), 11
+        P.io_v1 = P.io(1)                          # V(obs(x_t+1)) forward + data backward
+        io_set(P.io_v1[0], x0=(ws.obs1, 11, 11), y=(ws.V1, 1), acts=ws.acts_v1, dy=(ws.dV1, 1), dx=(ws.dobs1, 11))
         P.n_pols = mlp_array([h.desc for h in a.h_pols[:NP]])
         P.io_nx = []
         for obs, heads in ((ws.obs1, ws.heads_n1), (ws.obs2, ws.heads_n2)):
             io = P.io(NP)                          # each controller on its own rows of the predicted observation
             for i in range(NP):
-                io[i].x0, io[i].x0_dim, io[i].x0_ld = obs[i * B:].data_ptr(), 11, 11
-                io[i].y, io[i].y_ld = heads[i * B:].data_ptr(), 4
+                io_set(io[i], x0=(obs[i * B:], 11, 11), y=(heads[i * B:], 4))
             P.io_nx.append(io)
 
     def rollout_begin(self, ws, P):
@@ -629,8 +514,6 @@ class PvtolTask(_Task):
         a, s, call = self.agent, stream_ptr(), _lib.call
         B, NP, sc, dt, env = ws.B, P.NP, a.sc.data_ptr(), float(self.env.dt), self.env
         n = NP * B
-        pol = a.policy
-        p_scale, p_bias = pol.action_scale.data_ptr(), pol.action_bias.data_ptr()
         follow, (gx, gy) = float(env.safety_operator_follow), self.GOAL
         s1, s2, s3 = self.steps
         # (x_t+1 .. x_t+3 are read where the solvers left them — three solvers, three output buffers, none re-used before
@@ -672,41 +555,32 @@ class PvtolTask(_Task):
     def first_step_done(self):
         return self.steps[0].first_step_done()
 
-    # -- NODE fit (P/model.py:224-266 via P/sac_cbf_clf.py:205-219) --------------------------------
-    def fit_inputs(self, rows):
-        lay = self.agent.lay
-        return (rows.data_ptr(), rows.shape[1], rows[:, lay.act:lay.act + 2], rows.data_ptr() + 4 * lay.nobs,
-                rows.shape[1], rows.shape[0])
-
-    def fit_ws(self, N):
-        z = self.z
-        return dict(st=z(N, 6), nst=z(N, 6), dpred=z(N, 6), part=z((N + 255) // 256), u=z(N, 2))
-
-    def fit_part1(self, w, p_obs, obs_ld, p_nobs, nobs_ld, N):
-        a, s = self.agent, stream_ptr()
-        _lib.call("nlbac_pvtol_state", p_obs, obs_ld, N, w["st"].data_ptr(), None, s)
-        _lib.call("nlbac_pvtol_state", p_nobs, nobs_ld, N, w["nst"].data_ptr(), None, s)
-        if isinstance(self.fit_solver, AffineNodeSolver) and not isinstance(self.fit_solver, ConcatNodeSolver):
-            self.reserve(self.fit_solver, N, 1)
-        self.fit_solver.forward_begin(w["st"], w["u"], 1, N, a.solver, self.env.dt, a.atol, a.rtol)
+    def state_rows(self, p_obs, obs_ld, n, dst):      # (P/model.py:224-266 via P/sac_cbf_clf.py:205-219)
+        _lib.call("nlbac_pvtol_state", p_obs, obs_ld, n, dst.data_ptr(), None, stream_ptr())
 
 
 # =====================================================================================
-class PvtolBarrierTask(PvtolTask):
-    """Learned-barrier-certificate Pvtol (NP/sac_cbf_clf/sac_cbf_clf.py:334-480): one controller, one NODE step, the
-    learned CBF term on get_obs(x') with a re-sampled detached next action, CLF (V' - V)/1 + 0.1 V on the predicted
-    observation, ratio clamped at 0.002."""
-    rollout_waits = 1
-    name = "PvtolBarrier"
-    n_pol, backup_mode, has_signal, n_extra_critics = 1, 0, True, 1
-    n_eps, eps_order = 3, None
-    lam_hi, ratio_mode = 400.0, 2
+class _LearnedBarrierTask(_Task):
+    """The learned-barrier-certificate update (NU / NP sac_cbf_clf.py): one controller and no backup; the CBF is a
+    network B(obs, a) trained with the critics on the barrier signal of the replay rows; one NODE step x -> x'; the CBF
+    term needs the predicted next observation get_obs(x') (differentiable) and a re-sampled, detached next action a';
+    the CLF term (V' - V) / step + gamma_l V needs V on the Lyapunov input of x'.
 
-    def __init__(self, agent, env, args):
-        _Task.__init__(self, agent, env, args)
-        self.num_cbfs = 1
-        self.gamma_l = 0.1
-        self.backup_interval = 1
+    An environment declares its widths, ``ratio_mode`` / ``gamma_l`` / ``lam_hi`` / ``graph_ok`` / ``GOAL``, its NODE-fit
+    schedule (``fit_due``) and the columns the Lyapunov critic is regressed on (``lya_train_cols``), and supplies
+    ``build_node``, ``state_rows``, ``rollout_begin``, ``clf_step`` and the maps of x':
+
+      ``alloc_env(ws)``          ``ws.lya_next`` (B, lya_dim): what V reads of x' — ``ws.obs_pred`` itself where that is the
+                                 observation; ``ws.dlya_next``: where V's data backward leaves d / d that input
+      ``lya_next_fwd(ws, x, s)`` forms ``ws.lya_next``: launched before V's forward
+      ``obs_next_fwd(ws, x, s)`` forms ``ws.obs_pred`` where the launch above has not: launched behind V's forward
+      ``x_next_bwd(ws, x, s)``   ``ws.dx_next`` = d / dx' from ``ws.dlya_next`` and ``ws.dxb`` (d B' / d [obs', a'])
+
+    The order of the launches is part of the contract: captured updates are compared bit for bit with eager ones."""
+    n_pol, backup_mode, has_signal, n_extra_critics = 1, 0, True, 1
+    n_eps, eps_order = 3, None                 # next-obs sample, obs sample, sample on the predicted next observation
+    num_cbfs, backup_interval, rollout_waits = 1, 1, 1
+    solver_cls = AffineNodeSolver              # the policy-loss rollout's and the NODE fit's
 
     def n_pol_now(self, updates):
         return 1
@@ -716,196 +590,209 @@ class PvtolBarrierTask(PvtolTask):
 
     def setup(self):
         a = self.agent
-        self.solver = AffineNodeSolver(a.neural_ode_model, a.device)
-        self.solver.keep_acts = False
-        self.fit_solver = AffineNodeSolver(a.neural_ode_model, a.device)
+        self.solver = self.solver_cls(a.neural_ode_model, a.device)       # policy-loss rollout (B rows)
+        self.solver.keep_acts = False                                     # differentiated w.r.t. the action only
+        self.fit_solver = self.solver_cls(a.neural_ode_model, a.device)   # NODE fit rollouts
         self.solvers = [self.solver, self.fit_solver]
 
     def alloc(self, ws):
-        B, z, H = ws.B, self.z, self.agent.hidden
-        ws.st6, ws.op0 = z(B, 6), z(B)
-        ws.V, ws.V1, ws.dV1 = z(B), z(B), z(B)
-        ws.acts_v1 = z(2, B, H)
-        ws.obs_pred, ws.dobs1 = z(B, 11), z(B, 11)
-        ws.heads_nx, ws.pi_next, ws.logp_nx = z(B, 4), z(B, 2), z(B)
+        B, z, H, Do, Da = ws.B, self.z, self.agent.hidden, self.obs_dim, self.act_dim
+        ws.y0 = z(B, self.n_s)
+        ws.V, ws.Vn, ws.dVn = z(B), z(B), z(B)
+        ws.acts_vn = z(2, B, H)
+        ws.obs_pred, ws.heads_nx, ws.pi_next, ws.logp_nx = z(B, Do), z(B, 2 * Da), z(B, Da), z(B)
         ws.Bv, ws.Bn, ws.dBn = z(B), z(B), z(B)
         ws.acts_bn = z(2, B, H)
-        ws.dxb = z(B, 13)                              # d B(obs', a') / d [obs', a']
+        ws.dxb = z(B, Do + Da)                         # d B(obs', a') / d [obs', a']
         ws.matr = z(B, 2)
         ws.part_c = z(ws.nblk, 2)
-        ws.dx_next = z(B, 6)
+        ws.dx_next = z(B, self.n_s)
+        self.alloc_env(ws)
 
     def extra_value_nets(self):
         return [self.agent.h_extra[0]]
 
     def extra_value_io(self, ws, io, i):               # B(obs, pi), value only (detached in the reference)
-        lay = self.agent.lay
-        io[i].x0, io[i].x0_dim, io[i].x0_ld = ws.mb.data_ptr() + 4 * lay.obs, 11, lay.LD
-        io[i].x1, io[i].x1_dim, io[i].x1_ld = ws.pi2.data_ptr(), 2, 2
-        io[i].y, io[i].y_ld = ws.Bv.data_ptr(), 1
+        lay, Da = self.agent.lay, self.act_dim
+        io_set(io[i], x0=(ws.mb.data_ptr() + 4 * lay.obs, self.obs_dim, lay.LD), x1=(ws.pi2, Da, Da), y=(ws.Bv, 1))
 
     def plan(self, ws, P):
-        a = self.agent
+        a, Do, Da, Dl = self.agent, self.obs_dim, self.act_dim, self.lya_dim
         P.n_l = mlp_array([a.h_l.desc])
-        io = P.io_v1 = P.io(1)                         # V(obs(x')) forward + data backward
-        io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.obs_pred.data_ptr(), 11, 11
-        io[0].y, io[0].y_ld = ws.V1.data_ptr(), 1
-        io[0].acts = ws.acts_v1.data_ptr()
-        io[0].dy, io[0].dy_ld = ws.dV1.data_ptr(), 1
-        io[0].dx, io[0].dx_ld = ws.dobs1.data_ptr(), 11
+        P.io_vn = P.io(1)                              # V(Lyapunov input of x') forward + data backward
+        io_set(P.io_vn[0], x0=(ws.lya_next, Dl, Dl), y=(ws.Vn, 1), acts=ws.acts_vn, dy=(ws.dVn, 1),
+               dx=(ws.dlya_next, Dl))
         P.n_pi = mlp_array([a.h_p.desc])
-        io = P.io_nx = P.io(1)                         # policy on the predicted next observation
-        io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.obs_pred.data_ptr(), 11, 11
-        io[0].y, io[0].y_ld = ws.heads_nx.data_ptr(), 4
+        P.io_nx = P.io(1)                              # policy on the predicted next observation
+        io_set(P.io_nx[0], x0=(ws.obs_pred, Do, Do), y=(ws.heads_nx, 2 * Da))
         P.n_bar = mlp_array([a.h_extra[0].desc])
-        io = P.io_bn = P.io(1)                         # B(obs', a') forward + data backward
-        io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.obs_pred.data_ptr(), 11, 11
-        io[0].x1, io[0].x1_dim, io[0].x1_ld = ws.pi_next.data_ptr(), 2, 2
-        io[0].y, io[0].y_ld = ws.Bn.data_ptr(), 1
-        io[0].acts = ws.acts_bn.data_ptr()
-        io[0].dy, io[0].dy_ld = ws.dBn.data_ptr(), 1
-        io[0].dx, io[0].dx_ld = ws.dxb.data_ptr(), 13
-
-    def rollout_begin(self, ws, P):
-        a, s = self.agent, stream_ptr()
-        _lib.call("nlbac_pvtol_state", ws.mb.data_ptr(), a.lay.LD, ws.B, ws.st6.data_ptr(), ws.op0.data_ptr(), s)
-        self.reserve(self.solver, ws.B, 1)
-        self.solver.forward_begin(ws.st6, ws.pi2, 1, ws.B, a.solver, float(self.env.dt), a.atol, a.rtol)
+        P.io_bn = P.io(1)                              # B(obs', a') forward + data backward
+        io_set(P.io_bn[0], x0=(ws.obs_pred, Do, Do), x1=(ws.pi_next, Da, Da), y=(ws.Bn, 1), acts=ws.acts_bn,
+               dy=(ws.dBn, 1), dx=(ws.dxb, Do + Da))
 
     def loss_and_backward(self, ws, P, lam_upd, assume_single):
         a, s, call = self.agent, stream_ptr(), _lib.call
-        B, sc, env = ws.B, a.sc.data_ptr(), self.env
-        pol = a.policy
-        follow, (gx, gy) = float(env.safety_operator_follow), self.GOAL
-        x1 = self.solver.forward_finish(assume_single_step=assume_single)
+        B, Da, sc, step = ws.B, self.act_dim, a.sc.data_ptr(), self.clf_step()
+        x_next = self.solver.forward_finish(assume_single_step=assume_single)
         a.drain_fill()
-        call("nlbac_pvtol_obs_fwd", x1.data_ptr(), ws.op0.data_ptr(), B, follow, gx, gy, B, ws.obs_pred.data_ptr(), 11,
-             None, s)
-        call("nlbac_mlp_fwd", P.n_l, P.io_v1, 1, B, s)
-        self.policy_sample(ws, "nx", P.n_pi, P.io_nx, 1, B, ws.heads_nx, ws.eps[2], 2, ws.pi_next, 2, ws.logp_nx)
+        self.lya_next_fwd(ws, x_next, s)
+        call("nlbac_mlp_fwd", P.n_l, P.io_vn, 1, B, s)
+        self.obs_next_fwd(ws, x_next, s)
+        self.policy_sample(ws, "nx", P.n_pi, P.io_nx, 1, B, ws.heads_nx, ws.eps[2], Da, ws.pi_next, Da, ws.logp_nx)
         call("nlbac_mlp_fwd", P.n_bar, P.io_bn, 1, B, s)
-        call("nlbac_barrier_constraints_fwd", ws.Bv.data_ptr(), ws.Bn.data_ptr(), ws.V.data_ptr(), ws.V1.data_ptr(),
-             1.0, float(a.gamma_b), self.gamma_l, B, ws.matr.data_ptr(), ws.part_c.data_ptr(),
+        call("nlbac_barrier_constraints_fwd", ws.Bv.data_ptr(), ws.Bn.data_ptr(), ws.V.data_ptr(), ws.Vn.data_ptr(),
+             step, float(a.gamma_b), self.gamma_l, B, ws.matr.data_ptr(), ws.part_c.data_ptr(),
              *a.auglag_fused(ws, 1, lam_upd), s)
         a.auglag(ws, 1, lam_upd)
-        call("nlbac_barrier_constraints_bwd", ws.matr.data_ptr(), 1.0, float(a.batch_size), B, sc, ws.dBn.data_ptr(),
-             ws.dV1.data_ptr(), s)
-        call("nlbac_mlp_bwd_data", P.n_l, P.io_v1, 1, B, s)          # dV' -> d obs'
+        call("nlbac_barrier_constraints_bwd", ws.matr.data_ptr(), step, float(a.batch_size), B, sc, ws.dBn.data_ptr(),
+             ws.dVn.data_ptr(), s)
+        call("nlbac_mlp_bwd_data", P.n_l, P.io_vn, 1, B, s)          # dV' -> d (Lyapunov input of x')
         call("nlbac_mlp_bwd_data", P.n_bar, P.io_bn, 1, B, s)        # dB' -> d [obs', a'] (a' is detached)
-        call("nlbac_pvtol_obs_bwd", x1.data_ptr(), ws.dobs1.data_ptr(), 11, follow, gx, gy, B, ws.dx_next.data_ptr(), 0, s)
-        call("nlbac_pvtol_obs_bwd", x1.data_ptr(), ws.dxb.data_ptr(), 13, follow, gx, gy, B, ws.dx_next.data_ptr(), 1, s)
+        self.x_next_bwd(ws, x_next, s)
         du, _ = self.solver.backward(ws.dx_next, need_du=True)
-        return du, self.act_dim
+        return du, Da
+
+    def obs_next_fwd(self, ws, x, s):
+        pass                                           # (V reads obs': ``lya_next_fwd`` has formed it)
 
     def first_step_done(self):
         return self.solver.first_step_done()
 
-# =====================================================================================
-class QuadrotorBarrierTask(PvtolBarrierTask):
+
+class UnicycleBarrierTask(_LearnedBarrierTask):
+    """Learned-barrier-certificate Unicycle (NU/sac_cbf_clf/sac_cbf_clf.py:339-477): V reads the look-ahead point
+    p(x'), the CLF term divides by the environment's dt, no ratio in the loss."""
+    name = "UnicycleBarrier"
+    obs_dim, act_dim, lya_dim, n_s = 7, 2, 2, 3
+    ratio_mode, gamma_l, lam_hi = 0, 1.0, 400.0
+    graph_ok = True
+    l_p = 0.03
+    GOAL = (2.5, 2.5)         # NU/sac_cbf_clf/dynamics.py:104-105
+    fit_due = _Task.fit_due                    # every episode
+    lya_train_cols = _Task.lya_train_cols      # the look-ahead point columns of the replay rows
+    # the backup-multiplier flag follows the shared schedule here: it is part of the launch arguments and of the captured
+    # graphs' keys, which stay as they are (with backup_mode 0 no kernel reads it)
+    backup_lam_due = _Task.backup_lam_due
+
+    def build_node(self):
+        return NeuralODEModel(3, 3, 6)
+
+    def clf_step(self):
+        return float(self.env.dt)
+
+    def state_rows(self, p_obs, obs_ld, n, dst):
+        _lib.call("nlbac_unicycle_state", p_obs, obs_ld, n, self.l_p, dst.data_ptr(), 1, None, stream_ptr())
+
+    def alloc_env(self, ws):
+        ws.lya_next, ws.dlya_next = self.z(ws.B, 2), self.z(ws.B, 2)
+
+    def rollout_begin(self, ws, P):
+        a = self.agent
+        if self.solver.fused and a.fold_launches:       # the state is formed by the rollout's first launch
+            self.solver.set_in_map(1, ws.mb, a.lay.LD, self.l_p, None)
+        else:
+            self.state_rows(ws.mb.data_ptr(), a.lay.LD, ws.B, ws.y0)
+        self.reserve(self.solver, ws.B, 1)
+        self.solver._out_map = None
+        self.solver.forward_begin(ws.y0, ws.pi2, 1, ws.B, a.solver, float(self.env.dt), a.atol, a.rtol)
+
+    def lya_next_fwd(self, ws, x, s):
+        _lib.call("nlbac_unicycle_lookahead", x.data_ptr(), ws.B, self.l_p, ws.lya_next.data_ptr(), s)
+
+    def obs_next_fwd(self, ws, x, s):
+        gx, gy = self.GOAL
+        _lib.call("nlbac_unicycle_obs_fwd", x.data_ptr(), ws.B, gx, gy, ws.obs_pred.data_ptr(), 7, s)
+
+    def x_next_bwd(self, ws, x, s):
+        gx, gy = self.GOAL
+        _lib.call("nlbac_unicycle_lookahead_bwd", x.data_ptr(), ws.dlya_next.data_ptr(), None, ws.B, self.l_p,
+                  ws.dx_next.data_ptr(), s)
+        _lib.call("nlbac_unicycle_obs_bwd", x.data_ptr(), ws.dxb.data_ptr(), 9, ws.B, gx, gy, ws.dx_next.data_ptr(), 1, s)
+
+
+class PvtolBarrierTask(_LearnedBarrierTask):
+    """Learned-barrier-certificate Pvtol (NP/sac_cbf_clf/sac_cbf_clf.py:334-480): V reads the predicted observation,
+    CLF (V' - V)/1 + 0.1 V, ratio clamped at 0.002."""
+    name = "PvtolBarrier"
+    obs_dim, act_dim, lya_dim, n_s = 11, 2, 11, 6
+    ratio_mode, gamma_l, lam_hi = 2, 0.1, 400.0
+    graph_ok = False
+    GOAL = (4.5, 4.5)
+    fit_due = _fit_in_first_100_episodes
+    lya_train_cols = _lya_on_observations
+
+    def build_node(self):
+        return NeuralODEModel(6, 6, 12)
+
+    def clf_step(self):
+        return 1.0
+
+    def state_rows(self, p_obs, obs_ld, n, dst):
+        _lib.call("nlbac_pvtol_state", p_obs, obs_ld, n, dst.data_ptr(), None, stream_ptr())
+
+    def alloc_env(self, ws):
+        ws.op0 = self.z(ws.B)                          # the safety operator's position
+        ws.lya_next, ws.dlya_next = ws.obs_pred, self.z(ws.B, 11)
+
+    def rollout_begin(self, ws, P):
+        a = self.agent
+        _lib.call("nlbac_pvtol_state", ws.mb.data_ptr(), a.lay.LD, ws.B, ws.y0.data_ptr(), ws.op0.data_ptr(), stream_ptr())
+        self.reserve(self.solver, ws.B, 1)
+        self.solver.forward_begin(ws.y0, ws.pi2, 1, ws.B, a.solver, float(self.env.dt), a.atol, a.rtol)
+
+    def lya_next_fwd(self, ws, x, s):
+        follow, (gx, gy) = float(self.env.safety_operator_follow), self.GOAL
+        _lib.call("nlbac_pvtol_obs_fwd", x.data_ptr(), ws.op0.data_ptr(), ws.B, follow, gx, gy, ws.B,
+                  ws.obs_pred.data_ptr(), 11, None, s)
+
+    def x_next_bwd(self, ws, x, s):
+        follow, (gx, gy) = float(self.env.safety_operator_follow), self.GOAL
+        for d, ld, accumulate in ((ws.dlya_next, 11, 0), (ws.dxb, 13, 1)):
+            _lib.call("nlbac_pvtol_obs_bwd", x.data_ptr(), d.data_ptr(), ld, follow, gx, gy, ws.B, ws.dx_next.data_ptr(),
+                      accumulate, s)
+
+
+class QuadrotorBarrierTask(_LearnedBarrierTask):
     """BASELINE configs[4] "Quadrotor + neural barrier certificate" as far as the reference describes it
     (/root/reference/README.md:66-72, 190-192; its code is an empty submodule — NO REFERENCE PARITY, checked against
-    the oracle only): the learned-barrier agent pattern of NP (one controller, BarrierNetwork trained on the barrier
-    signal D1 = -1 / D2 = -10, one NODE step, CLF (V' - V)/1 + 0.1 V, ratio clamped at 0.002) on a NON-affine
-    single-net NODE  dx/dt = out_mu + out_sig * net(([x | u] - in_mu) / in_sig)  (8 -> 6, inputs normalised, outputs
-    de-normalised inside the fused RK kernels).  The observation is the state, so get_state / get_obs are identities."""
+    the oracle only): the learned-barrier agent pattern of NP (BarrierNetwork trained on the barrier signal D1 = -1 /
+    D2 = -10, CLF (V' - V)/1 + 0.1 V, ratio clamped at 0.002) on a NON-affine single-net NODE
+    dx/dt = out_mu + out_sig * net(([x | u] - in_mu) / in_sig)  (8 -> 6, inputs normalised, outputs de-normalised inside
+    the fused RK kernels).  The observation is the state, so get_state / get_obs are identities.  Like PvtolBarrier it
+    fits the NODE only in episodes <= 100 and regresses the Lyapunov critic on observations."""
     name = "QuadrotorBarrier"
     obs_dim, act_dim, lya_dim, n_s = 6, 2, 6, 6
+    ratio_mode, gamma_l, lam_hi = 2, 0.1, 400.0
+    graph_ok = False
+    GOAL = None               # (no goal enters the observation)
+    fit_due = _fit_in_first_100_episodes
+    lya_train_cols = _lya_on_observations
     NODE_HIDDEN = 128
+    solver_cls = ConcatNodeSolver              # carried inputs = the action
 
     def build_node(self):
         return NeuralODEModel(8, 6, hidden_dim=self.NODE_HIDDEN, normalizer=self.env.node_normalizer)
 
-    def setup(self):
-        a = self.agent
-        self.solver = ConcatNodeSolver(a.neural_ode_model, a.device)       # carried inputs = the action
-        self.solver.keep_acts = False                                      # differentiated w.r.t. the action only
-        self.fit_solver = ConcatNodeSolver(a.neural_ode_model, a.device)
-        self.solvers = [self.solver, self.fit_solver]
+    def clf_step(self):
+        return 1.0
 
-    def alloc(self, ws):
-        B, z, H = ws.B, self.z, self.agent.hidden
-        ws.st6 = z(B, 6)
-        ws.V, ws.V1, ws.dV1 = z(B), z(B), z(B)
-        ws.acts_v1 = z(2, B, H)
-        ws.obs_pred = z(B, 6)
-        ws.heads_nx, ws.pi_next, ws.logp_nx = z(B, 4), z(B, 2), z(B)
-        ws.Bv, ws.Bn, ws.dBn = z(B), z(B), z(B)
-        ws.acts_bn = z(2, B, H)
-        ws.dxb = z(B, 8)                               # d B(obs', a') / d [obs', a']
-        ws.matr = z(B, 2)
-        ws.part_c = z(ws.nblk, 2)
-        ws.dx_next = z(B, 6)
-
-    def extra_value_io(self, ws, io, i):               # B(obs, pi), value only
-        lay = self.agent.lay
-        io[i].x0, io[i].x0_dim, io[i].x0_ld = ws.mb.data_ptr() + 4 * lay.obs, 6, lay.LD
-        io[i].x1, io[i].x1_dim, io[i].x1_ld = ws.pi2.data_ptr(), 2, 2
-        io[i].y, io[i].y_ld = ws.Bv.data_ptr(), 1
-
-    def plan(self, ws, P):
-        a = self.agent
-        P.n_l = mlp_array([a.h_l.desc])
-        io = P.io_v1 = P.io(1)                         # V(obs') forward + data backward, d obs' lands in dx_next
-        io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.obs_pred.data_ptr(), 6, 6
-        io[0].y, io[0].y_ld = ws.V1.data_ptr(), 1
-        io[0].acts = ws.acts_v1.data_ptr()
-        io[0].dy, io[0].dy_ld = ws.dV1.data_ptr(), 1
-        io[0].dx, io[0].dx_ld = ws.dx_next.data_ptr(), 6
-        P.n_pi = mlp_array([a.h_p.desc])
-        io = P.io_nx = P.io(1)                         # policy on the predicted next observation
-        io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.obs_pred.data_ptr(), 6, 6
-        io[0].y, io[0].y_ld = ws.heads_nx.data_ptr(), 4
-        P.n_bar = mlp_array([a.h_extra[0].desc])
-        io = P.io_bn = P.io(1)                         # B(obs', a') forward + data backward
-        io[0].x0, io[0].x0_dim, io[0].x0_ld = ws.obs_pred.data_ptr(), 6, 6
-        io[0].x1, io[0].x1_dim, io[0].x1_ld = ws.pi_next.data_ptr(), 2, 2
-        io[0].y, io[0].y_ld = ws.Bn.data_ptr(), 1
-        io[0].acts = ws.acts_bn.data_ptr()
-        io[0].dy, io[0].dy_ld = ws.dBn.data_ptr(), 1
-        io[0].dx, io[0].dx_ld = ws.dxb.data_ptr(), 8
-
-    def _obs_cols(self, src, src_ld, n, dst):
+    def state_rows(self, p_obs, obs_ld, n, dst):
         """the state IS the observation: its six columns of a minibatch-layout row block, made contiguous"""
-        _lib.call("nlbac_copy_blocks", src, src_ld, dst.data_ptr(), 6, 6, n, stream_ptr())
+        _lib.call("nlbac_copy_blocks", p_obs, obs_ld, dst.data_ptr(), 6, 6, n, stream_ptr())
 
-    def rollout_begin(self, ws, P):
+    def alloc_env(self, ws):
+        ws.lya_next, ws.dlya_next = ws.obs_pred, ws.dx_next       # (d obs' IS d x': V's data backward writes it there)
+
+    def rollout_begin(self, ws, P):                    # (a ConcatNodeSolver sizes its buffers itself: no reserve)
         a = self.agent
-        self._obs_cols(ws.mb.data_ptr() + 4 * a.lay.obs, a.lay.LD, ws.B, ws.st6)
-        self.solver.forward_begin(ws.st6, ws.pi2, 1, ws.B, a.solver, float(self.env.dt), a.atol, a.rtol)
+        self.state_rows(ws.mb.data_ptr() + 4 * a.lay.obs, a.lay.LD, ws.B, ws.y0)
+        self.solver.forward_begin(ws.y0, ws.pi2, 1, ws.B, a.solver, float(self.env.dt), a.atol, a.rtol)
 
-    def loss_and_backward(self, ws, P, lam_upd, assume_single):
-        a, s, call = self.agent, stream_ptr(), _lib.call
-        B, sc = ws.B, a.sc.data_ptr()
-        pol = a.policy
-        x1 = self.solver.forward_finish(assume_single_step=assume_single)
-        a.drain_fill()
-        call("nlbac_copy_blocks", x1.data_ptr(), 6 * B, ws.obs_pred.data_ptr(), 6 * B, 6 * B, 1, s)   # obs' = x'
-        call("nlbac_mlp_fwd", P.n_l, P.io_v1, 1, B, s)
-        self.policy_sample(ws, "nx", P.n_pi, P.io_nx, 1, B, ws.heads_nx, ws.eps[2], 2, ws.pi_next, 2, ws.logp_nx)
-        call("nlbac_mlp_fwd", P.n_bar, P.io_bn, 1, B, s)
-        call("nlbac_barrier_constraints_fwd", ws.Bv.data_ptr(), ws.Bn.data_ptr(), ws.V.data_ptr(), ws.V1.data_ptr(),
-             1.0, float(a.gamma_b), self.gamma_l, B, ws.matr.data_ptr(), ws.part_c.data_ptr(),
-             *a.auglag_fused(ws, 1, lam_upd), s)
-        a.auglag(ws, 1, lam_upd)
-        call("nlbac_barrier_constraints_bwd", ws.matr.data_ptr(), 1.0, float(a.batch_size), B, sc, ws.dBn.data_ptr(),
-             ws.dV1.data_ptr(), s)
-        call("nlbac_mlp_bwd_data", P.n_l, P.io_v1, 1, B, s)          # dV' -> d obs' (written to dx_next)
-        call("nlbac_mlp_bwd_data", P.n_bar, P.io_bn, 1, B, s)        # dB' -> d [obs', a'] (a' is detached)
-        call("nlbac_add_cols", ws.dx_next.data_ptr(), 6, 0, ws.dxb.data_ptr(), 8, 6, B, s)
-        dc, _ = self.solver.backward(ws.dx_next, need_du=True)       # (B, 2): d / d action (the carried inputs)
-        return dc, self.act_dim
+    def lya_next_fwd(self, ws, x, s):                  # obs' = x'
+        _lib.call("nlbac_copy_blocks", x.data_ptr(), 6 * ws.B, ws.obs_pred.data_ptr(), 6 * ws.B, 6 * ws.B, 1, s)
 
-    # -- NODE fit: one solve from (obs, action) against next_obs ---------------------------------------
-    def fit_inputs(self, rows):
-        lay = self.agent.lay
-        return (rows.data_ptr() + 4 * lay.obs, rows.shape[1], rows[:, lay.act:lay.act + 2],
-                rows.data_ptr() + 4 * lay.nobs, rows.shape[1], rows.shape[0])
-
-    def fit_part1(self, w, p_obs, obs_ld, p_nobs, nobs_ld, N):
-        a = self.agent
-        self._obs_cols(p_obs, obs_ld, N, w["st"])
-        self._obs_cols(p_nobs, nobs_ld, N, w["nst"])
-        self.fit_solver.forward_begin(w["st"], w["u"], 1, N, a.solver, self.env.dt, a.atol, a.rtol)
+    def x_next_bwd(self, ws, x, s):
+        _lib.call("nlbac_add_cols", ws.dx_next.data_ptr(), 6, 0, ws.dxb.data_ptr(), 8, 6, ws.B, s)
 
 
 TASKS = {"Unicycle": UnicycleTask, "SimulatedCars": CarsTask, "UnicycleBarrier": UnicycleBarrierTask,

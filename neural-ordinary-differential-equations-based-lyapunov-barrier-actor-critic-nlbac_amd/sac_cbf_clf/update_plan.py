@@ -3,6 +3,8 @@ and per-update host state (``_Workspace``), the ctypes launch descriptors (``Pla
 activation rows for ReLU mask words (``keep_masks_drop_unpaired_acts``), and the captured hipGraphs (``GraphCache``).
 ``SAC_CBF_CLF`` (sac_cbf_clf.py) and the tasks (tasks.py) fill and launch these; nothing here launches a kernel.
 """
+import ctypes as C
+
 import torch
 
 from .. import _lib
@@ -137,6 +139,34 @@ def keep_masks_drop_unpaired_acts(io_arrays, bufs, alloc):
                     e.acts = None
 
 
+def _addr(buf):
+    return buf if buf is None or isinstance(buf, int) else buf.data_ptr()
+
+
+def io_set(e, x0=None, x1=None, y=None, acts=None, dy=None, dx=None):
+    """Fill one ``nlbac_mlp_io`` entry: ``x0`` / ``x1`` = (buffer, dim, ld) of an input block, ``y`` / ``dy`` / ``dx`` =
+    (buffer, ld), ``acts`` = buffer.  A buffer is a tensor or a device address; what is not named stays as it is."""
+    if x0 is not None:
+        e.x0, e.x0_dim, e.x0_ld = _addr(x0[0]), x0[1], x0[2]
+    if x1 is not None:
+        e.x1, e.x1_dim, e.x1_ld = _addr(x1[0]), x1[1], x1[2]
+    if y is not None:
+        e.y, e.y_ld = _addr(y[0]), y[1]
+    if acts is not None:
+        e.acts = _addr(acts)
+    if dy is not None:
+        e.dy, e.dy_ld = _addr(dy[0]), dy[1]
+    if dx is not None:
+        e.dx, e.dx_ld = _addr(dx[0]), dx[1]
+
+
+def io_copy_and_one(dst, src, n, last):
+    """dst = src[:n] + last[:1]: the entries of one launch with one more net's entry behind them."""
+    sz = C.sizeof(_lib.MlpIO)
+    C.memmove(dst, src, n * sz)
+    C.memmove(C.byref(dst, n * sz), last, sz)
+
+
 class Plan:
     """ctypes launch descriptors of one workspace: every pointer is static (arenas, workspace tensors), so they are
     built once (per number of controllers updated: Pvtol trains its backup every 20th update); an update is then a
@@ -155,19 +185,15 @@ class Plan:
         col = lambda c: mb + 4 * c
         lc, lnc = task.lya_train_cols(lay)       # inputs the Lyapunov critic is regressed on
         p_obs, p_act, p_cen, p_ncen, p_nobs = col(lay.obs), col(lay.act), col(lc), col(lnc), col(lay.nobs)
-
-        def x(io, i, p0, d0, ld0, p1=None, d1=0, ld1=0):
-            io[i].x0, io[i].x0_dim, io[i].x0_ld = p0, d0, ld0
-            if p1 is not None:
-                io[i].x1, io[i].x1_dim, io[i].x1_ld = p1, d1, ld1
+        obs, nobs = (p_obs, Do, LD), (p_nobs, Do, LD)                      # input blocks (buffer, dim, ld) ...
+        act, nact = (p_act, Da, LD), (ws.na, Da, Da)                       # ... stored / re-sampled next action
         P = self
         P.p_obs, P.p_rew, P.p_con, P.p_mask, P.LD = p_obs, col(lay.rew), col(lay.con), col(lay.mask), LD
         q1, q2, l, pi = agent.h_q1, agent.h_q2, agent.h_l, agent.h_p
         P.NP, NX = NP, len(agent.h_extra)
         # A: pi(s')
         P.n_pol, P.io_pol_next = mlp_array([pi.desc]), P.io(1)
-        x(P.io_pol_next, 0, p_nobs, Do, LD)
-        P.io_pol_next[0].y, P.io_pol_next[0].y_ld = ws.heads_n.data_ptr(), 2 * Da
+        io_set(P.io_pol_next[0], x0=nobs, y=(ws.heads_n, 2 * Da))
         # A: targets + critic / Lyapunov forward (6 nets)
         descs = [q1.desc_target, q2.desc_target, l.desc_target, q1.desc, q2.desc, l.desc]
         for h in agent.h_extra:
@@ -175,46 +201,38 @@ class Plan:
         P.n_six, P.n_six_count = mlp_array(descs), len(descs)
         io = P.io_six = P.io(len(descs))
         for i in range(len(descs)):
-            io[i].y, io[i].y_ld = ws.q6[i].data_ptr(), 1
+            io_set(io[i], y=(ws.q6[i], 1))
         for k in range(NX):            # extra critic-type nets on (s', a') [target] and (s, a)
-            x(io, 6 + 2 * k, p_nobs, Do, LD, ws.na.data_ptr(), Da, Da)
-            x(io, 7 + 2 * k, p_obs, Do, LD, p_act, Da, LD)
-            io[7 + 2 * k].acts = ws.acts_c[3 + k].data_ptr()
+            io_set(io[6 + 2 * k], x0=nobs, x1=nact)
+            io_set(io[7 + 2 * k], x0=obs, x1=act, acts=ws.acts_c[3 + k])
         for i in (0, 1):
-            x(io, i, p_nobs, Do, LD, ws.na.data_ptr(), Da, Da)
-        x(io, 2, p_ncen, Dl, LD)
+            io_set(io[i], x0=nobs, x1=nact)
+        io_set(io[2], x0=(p_ncen, Dl, LD))
         for i in (3, 4):
-            x(io, i, p_obs, Do, LD, p_act, Da, LD)
-            io[i].acts = ws.acts_c[i - 3].data_ptr()
-        x(io, 5, p_cen, Dl, LD)
-        io[5].acts = ws.acts_c[2].data_ptr()
+            io_set(io[i], x0=obs, x1=act, acts=ws.acts_c[i - 3])
+        io_set(io[5], x0=(p_cen, Dl, LD), acts=ws.acts_c[2])
         # B: critic / Lyapunov backward
         P.n_crit = mlp_array([h.desc for h in agent.h_crit])
         io = P.io_crit = P.io(3 + NX)
         for i in range(3 + NX):
-            io[i].dy, io[i].dy_ld = ws.dq3[i].data_ptr(), 1
-            io[i].acts, io[i].dz = ws.acts_c[i].data_ptr(), ws.dz_c[i].data_ptr()
-            io[i].grad = agent.ar_c.grad.data_ptr()
+            io_set(io[i], acts=ws.acts_c[i], dy=(ws.dq3[i], 1))
+            io[i].dz, io[i].grad = ws.dz_c[i].data_ptr(), agent.ar_c.grad.data_ptr()
         for i in [0, 1] + list(range(3, 3 + NX)):
-            x(io, i, p_obs, Do, LD, p_act, Da, LD)
-        x(io, 2, p_cen, Dl, LD)
+            io_set(io[i], x0=obs, x1=act)
+        io_set(io[2], x0=(p_cen, Dl, LD))
         # (its data backward leaves the skinny-gradient partial sums for the weight backward: one launch less)
         P.sk_crit = skinny_partials_ws(P.n_crit, (io,), 3 + NX, B, agent.device)
         # C: both actors (forward and backward share one descriptor)
         def act_io(io, j, i):            # entry j of an io array describes controller i
-            x(io, j, p_obs, Do, LD)
-            io[j].y, io[j].y_ld = ws.heads2[i * B:].data_ptr(), 2 * Da
-            io[j].acts, io[j].dz = ws.acts_p[i].data_ptr(), ws.dz_p[i].data_ptr()
-            io[j].dy, io[j].dy_ld = ws.dheads2[i * B:].data_ptr(), 2 * Da
-            io[j].grad = agent.pol_arena[i].grad.data_ptr()
+            io_set(io[j], x0=obs, y=(ws.heads2[i * B:], 2 * Da), acts=ws.acts_p[i], dy=(ws.dheads2[i * B:], 2 * Da))
+            io[j].dz, io[j].grad = ws.dz_p[i].data_ptr(), agent.pol_arena[i].grad.data_ptr()
         P.n_act = mlp_array([h.desc for h in agent.h_pols[:NP]])
         io = P.io_act = P.io(NP)
         for i in range(NP):
             act_io(io, i, i)
         P.n_pol3 = mlp_array([pi.desc] + [h.desc for h in agent.h_pols[:NP]])     # pi(s') + the actors on s
         io3 = P.io_pol3 = P.io(1 + NP)
-        x(io3, 0, p_nobs, Do, LD)
-        io3[0].y, io3[0].y_ld = ws.heads_n.data_ptr(), 2 * Da
+        io_set(io3[0], x0=nobs, y=(ws.heads_n, 2 * Da))
         for i in range(NP):
             act_io(io3, 1 + i, i)
         P.act_groups = []                # per Adam group: the nets whose weight gradients land in its arena
@@ -237,11 +255,8 @@ class Plan:
         io = P.io_q5 = P.io(P.n_q5_count)
         for i in range(2 * NP):
             half = i // 2                                      # 0 primary, 1 backup
-            x(io, i, p_obs, Do, LD, ws.pi2[half * B:].data_ptr(), Da, Da)
-            io[i].y, io[i].y_ld = ws.qpi[i % 2, half * B:].data_ptr(), 1
-            io[i].acts = ws.acts_q[i].data_ptr()
-            io[i].dy, io[i].dy_ld = ws.dq_pi[i % 2, half * B:].data_ptr(), 1
-            io[i].dx, io[i].dx_ld = ws.dxq[i % 2, half * B:].data_ptr(), Do + Da
+            io_set(io[i], x0=obs, x1=(ws.pi2[half * B:], Da, Da), y=(ws.qpi[i % 2, half * B:], 1), acts=ws.acts_q[i],
+                   dy=(ws.dq_pi[i % 2, half * B:], 1), dx=(ws.dxq[i % 2, half * B:], Do + Da))
             io[i].dx_first = Do                                # (only dQ / da is consumed)
         task.value_now_io(ws, io, 2 * NP)
         task.extra_value_io(ws, io, 2 * NP + 1)

@@ -200,7 +200,7 @@ class SAC_CBF_CLF(object):
         # nlbac_dy_head, nlbac_in_map / nlbac_out_map, results written to pinned memory by the kernels): False (or
         # NLBAC_FOLD=0) runs every step as the launch of its own it was — same numbers, for A/B runs and the tests
         self.fold_launches = os.environ.get("NLBAC_FOLD", "1") != "0"
-        self.sums_defer = os.environ.get("NLBAC_SUMS_DEFER", "1") != "0"      # (see _sums_defer)
+        self.sums_defer = os.environ.get("NLBAC_SUMS_DEFER", "1") != "0"      # (Plan.heads; both switches are read there)
         self.adjoint = bool(getattr(args, "adjoint", False))
         self.dp = None          # nlbac_amd.parallel.DataParallel when sharded over GPUs
         self._xb = {}
@@ -487,23 +487,18 @@ class SAC_CBF_CLF(object):
 
     # -- the update proper --------------------------------------------------------
     def _plan(self, ws, NP=None):
-        """The launch descriptors of ``ws`` for an update of ``NP`` controllers (update_plan.Plan), built once."""
+        """The launch arguments of ``ws`` for an update of ``NP`` controllers (update_plan.Plan), built once."""
         NP = NP or self.task.n_pol
         return ws.plan.get(NP) or ws.plan.setdefault(NP, Plan(self, ws, NP))
 
-    def auglag_fused(self, ws, n_cbf, lam_upd):
+    def auglag_fused(self, ws, P, lam_upd):
         """The (fused, ticket, sc) tail of a ``*_constraints_fwd`` call: on one GPU the launch's last workgroup runs the
-        augmented-Lagrangian step (``nlbac_auglag``) itself; under data parallelism the sums are all-reduced first."""
+        augmented-Lagrangian step (``nlbac_auglag``) itself; under data parallelism the sums are all-reduced first.
+        Per update: the two lambda-update flags of the plan's ``nlbac_auglag_args``."""
         if self.world > 1:
             return None, None, None
-        A = _lib.AuglagArgs()
-        A.n_cbf, A.n_clf, A.batch_size = n_cbf, 1, float(self.batch_size)
-        A.do_lambda_update, A.do_backup_lambda_update = lam_upd, ws.blam_upd
-        A.ratio_mode = self.task.ratio_mode
-        A.backup_mode = self.task.backup_mode if ws.np_now == 2 else 0
-        A.lam_lo, A.lam_hi = 0.01, self.task.lam_hi
-        ws._auglag_args = A          # (kept alive until the call has been made)
-        return C.byref(A), self._tickets.data_ptr() + 4 * 12, self.sc.data_ptr()
+        P.auglag.do_lambda_update, P.auglag.do_backup_lambda_update = lam_upd, ws.blam_upd
+        return C.byref(P.auglag), self._tickets.data_ptr() + 4 * 12, self.sc.data_ptr()
 
     def auglag(self, ws, n_cbf, lam_upd):
         """required_matrix, ratio, lambda / rho updates and loss coefficients from the constraint partial sums
@@ -522,7 +517,7 @@ class SAC_CBF_CLF(object):
         self.dp.all_reduce_(xs)
         ws.p_part_q, ws.n_part_q = xs.data_ptr() + 4 * 32, 1
         call("nlbac_auglag", xs.data_ptr(), 1, n_cbf, 1, float(self.batch_size), lam_upd, ws.blam_upd,
-             self.task.ratio_mode, self.task.backup_mode if NP == 2 else 0, 0.01, self.task.lam_hi,
+             self.task.ratio_mode, self.task.backup_mode if NP == 2 else 0, self.task.lam_lo, self.task.lam_hi,
              self.sc.data_ptr(), s)
 
     def update_on_device(self, ws, updates, sync=True, eps_ready=False, prefetch=None):
@@ -619,19 +614,14 @@ class SAC_CBF_CLF(object):
         launch, and all (1+NP)*B samples are drawn by one launch - eps[0 .. NP] are contiguous.)"""
         B, A = ws.B, self.lay.act_dim
         s, call = stream_ptr(), _lib.call
-        pol = self.policy
-        p_scale, p_bias = pol.action_scale.data_ptr(), pol.action_bias.data_ptr()
         if self.fold_launches:      # (the samples are drawn by the policy launch itself: nlbac_gauss_head)
-            gh = P.head_pol3
-            if gh is None:
-                gh = P.head_pol3 = _lib.GaussHead()
-                gh.eps, gh.scale, gh.bias, gh.n_u = ws.eps.data_ptr(), p_scale, p_bias, A
-                gh.action, gh.action_ld, gh.logp = ws.act3.data_ptr(), A, ws.logp3.data_ptr()
-            call("nlbac_mlp_fwd_gauss", P.n_pol3, P.io_pol3, 1 + NP, B, C.byref(gh), s)
+            assert P.head_pol3 is not None
+            call("nlbac_mlp_fwd_gauss", P.n_pol3, P.io_pol3, 1 + NP, B, C.byref(P.head_pol3), s)
         else:
+            pol = self.policy
             call("nlbac_mlp_fwd", P.n_pol3, P.io_pol3, 1 + NP, B, s)
-            call("nlbac_gauss_sample_fwd", ws.heads3.data_ptr(), 2 * A, ws.eps.data_ptr(), p_scale, p_bias, A, (1 + NP) * B,
-                 ws.act3.data_ptr(), A, ws.logp3.data_ptr(), s)
+            call("nlbac_gauss_sample_fwd", ws.heads3.data_ptr(), 2 * A, ws.eps.data_ptr(), pol.action_scale.data_ptr(),
+                 pol.action_bias.data_ptr(), A, (1 + NP) * B, ws.act3.data_ptr(), A, ws.logp3.data_ptr(), s)
 
     def _prefetch_next(self, ws, updates):
         """Behind this update's last launch: the next update's minibatch draw and first launches (update_on_device)."""
@@ -689,27 +679,8 @@ class SAC_CBF_CLF(object):
         if one and len(self.h_extra) <= 1 and self.fold_launches:
             # single GPU, no extra critic: targets, dL/dq and the three losses are produced by the critics' data backward
             # itself (nlbac_dy_head kind 2) — no launch between the six-net forward and the backward
-            H = P.head_td
-            if H is None:
-                H = P.head_td = _lib.DyHead()
-                H.kind, H.B_norm = 2, G
-                H.q1t, H.q2t, H.lt, H.nlogp = q[0].data_ptr(), q[1].data_ptr(), q[2].data_ptr(), ws.nlogp.data_ptr()
-                H.reward, H.constraint, H.mask, H.rcm_ld = P.p_rew, P.p_con, P.p_mask, LD
-                H.alpha, H.gamma = sc + 4 * SC.SC_ALPHA, self.gamma
-                for k in range(3):
-                    H.q[k], H.dq[k] = q[3 + k].data_ptr(), ws.dq3[k].data_ptr()
-                H.next_q, H.next_l = ws.next_q.data_ptr(), ws.next_l.data_ptr()
-                H.partials, H.ticket = ws.part_td32.data_ptr(), ws.tickets_td.data_ptr()
-                H.mul, H.out = 1.0 / G, sc + 4 * SC.SC_QF1
-                if self._sums_defer():
-                    # no election at the end of this launch: its tiles leave their squared-error sums, a workgroup of
-                    # the actors' data backward (the last MLP launch of the update) adds them up (nlbac_head_sums)
-                    H.sums_defer, H.sums_tiles = 1, ws.sums_tiles.data_ptr()
-                if self.h_extra:        # BarrierNet TD step (NU/sac_cbf_clf.py:224-233): the launch's 4th net
-                    H.xt, H.xq, H.dxq = q[6].data_ptr(), q[7].data_ptr(), ws.dq3[3].data_ptr()
-                    H.xsig, H.xsig_ld = ws.mb.data_ptr() + 4 * self.lay.sig, LD
-                    H.out_x = sc + 4 * SC.SC_XLOSS
-            call("nlbac_mlp_bwd_data_head", P.n_crit, P.io_crit, len(self.h_crit), B, C.byref(H), s)
+            assert P.head_td is not None
+            call("nlbac_mlp_bwd_data_head", P.n_crit, P.io_crit, len(self.h_crit), B, C.byref(P.head_td), s)
             return
         call("nlbac_td_targets", q[0].data_ptr(), q[1].data_ptr(), q[2].data_ptr(), ws.nlogp.data_ptr(),
              P.p_rew, P.p_con, P.p_mask, LD, q[3].data_ptr(), q[4].data_ptr(), q[5].data_ptr(),
@@ -739,48 +710,13 @@ class SAC_CBF_CLF(object):
         sc, call = self.sc.data_ptr(), _lib.call
         call("nlbac_mlp_fwd", P.n_q5, P.io_q5, P.n_q5_count, B, s)
         if self.world == 1 and self.fold_launches:
-            return               # (the branch terms and their sums come out of the Q(s, pi) data backward: _actor_q_head)
-        fused = None
+            return               # (the branch terms and their sums come out of the Q(s, pi) data backward: P.head_actor_q)
+        fused = ticket = None
         if self.world == 1:      # policy_loss_1 / alpha losses / d log_alpha by the launch's last workgroup (nlbac_actor_scalars)
-            fused = P.actor_scalars
-            if fused is None:
-                fused = P.actor_scalars = _lib.ActorScalarArgs()
-                fused.target_entropy, fused.sc = self.target_entropy, sc
-                for g in self.actor_groups:
-                    for k in range(min(g.count, NP - g.first)):
-                        off = g.la_off + k * g.la_stride
-                        fused.log_alpha[g.first + k] = g.arena.theta.data_ptr() + 4 * off
-                        fused.g_log_alpha[g.first + k] = g.arena.grad.data_ptr() + 4 * off
+            assert P.actor_scalars is not None
+            fused, ticket = C.byref(P.actor_scalars), self._tickets.data_ptr() + 4 * 8
         call("nlbac_actor_q_terms", ws.qpi[0].data_ptr(), ws.qpi[1].data_ptr(), ws.logp2.data_ptr(),
-             sc + 4 * SC.SC_ALPHA, B, G, NP, ws.dq_pi[0].data_ptr(), ws.dq_pi[1].data_ptr(), ws.part_q.data_ptr(),
-             C.byref(fused) if fused is not None else None, self._tickets.data_ptr() + 4 * 8 if fused is not None else None, s)
-
-    def _actor_q_head(self, ws, P, NP, G):
-        H = P.head_actor_q
-        if H is None:
-            sc = self.sc.data_ptr()
-            H = P.head_actor_q = _lib.DyHead()
-            H.kind, H.B_norm, H.n_prob = 3, G, NP
-            H.qa, H.qb, H.logp = ws.qpi[0].data_ptr(), ws.qpi[1].data_ptr(), ws.logp2.data_ptr()
-            H.dqa, H.dqb = ws.dq_pi[0].data_ptr(), ws.dq_pi[1].data_ptr()
-            H.alpha = sc + 4 * SC.SC_ALPHA
-            H.actor.target_entropy, H.actor.sc = self.target_entropy, sc
-            for g in self.actor_groups:
-                for k in range(min(g.count, NP - g.first)):
-                    off = g.la_off + k * g.la_stride
-                    H.actor.log_alpha[g.first + k] = g.arena.theta.data_ptr() + 4 * off
-                    H.actor.g_log_alpha[g.first + k] = g.arena.grad.data_ptr() + 4 * off
-            H.partials, H.ticket = ws.part_q32.data_ptr(), ws.tickets_q.data_ptr()
-            if self._sums_defer():
-                H.sums_defer, H.sums_tiles = 1, ws.sums_tiles.data_ptr() + 4      # (as the td head's, see _part1_targets)
-        return H
-
-    def _sums_defer(self):
-        """The batch sums of the td / actor-q dy heads are finished by a workgroup of the actors' data backward instead of
-        by an election at the end of their own launches (nlbac_dy_head::sums_defer / finish): single GPU with the launch
-        folds (the heads exist and the actors' backward follows them in every update).  ``sums_defer = False``
-        (NLBAC_SUMS_DEFER=0): the elections."""
-        return bool(self.sums_defer and self.world == 1 and self.fold_launches)
+             sc + 4 * SC.SC_ALPHA, B, G, NP, ws.dq_pi[0].data_ptr(), ws.dq_pi[1].data_ptr(), ws.part_q.data_ptr(), fused, ticket, s)
 
     def _upd_part2(self, ws, lam_upd, assume_single):
         """Constraints, augmented-Lagrangian scalars, the whole actor backward and the actor Adam step."""
@@ -789,10 +725,7 @@ class SAC_CBF_CLF(object):
         s = stream_ptr()
         NP = ws.np_now
         P = self._plan(ws, NP)
-        sc = self.sc.data_ptr()
-        call = _lib.call
-        p_scale = self.policy.action_scale.data_ptr()
-        eps2 = ws.eps[1:1 + NP]
+        sc, call = self.sc.data_ptr(), _lib.call
         ws.q5_bwd_done = False       # (a task may run the Q(s, pi) data backward inside one of its own launches)
         du2, du_ld = self.task.loss_and_backward(ws, P, lam_upd, assume_single)
 
@@ -801,50 +734,29 @@ class SAC_CBF_CLF(object):
         if ws.q5_bwd_done:
             pass
         elif self.world == 1 and self.fold_launches:
-            call("nlbac_mlp_bwd_data_head", P.n_q5, P.io_q5, 2 * NP, B, C.byref(self._actor_q_head(ws, P, NP, G)), s)
+            assert P.head_actor_q is not None
+            call("nlbac_mlp_bwd_data_head", P.n_q5, P.io_q5, 2 * NP, B, C.byref(P.head_actor_q), s)
         else:
             call("nlbac_mlp_bwd_data", P.n_q5, P.io_q5, 2 * NP, B, s)
         # the actors: d heads from d action (two Q nets + the rollout) and d logp, inside their data backward (kind 1)
-        D = Do + A
-        if not self.fold_launches:
-            call("nlbac_gauss_sample_bwd", ws.heads2.data_ptr(), 2 * A, eps2.data_ptr(), p_scale, A,
-                 NP * B, B, ws.dxq[0].data_ptr() + 4 * Do, D, ws.dxq[1].data_ptr() + 4 * Do, D, du2.data_ptr(), du_ld,
-                 sc + 4 * SC.SC_ALPHA, 1.0 / G, ws.dheads2.data_ptr(), 2 * A, s)
-            call("nlbac_mlp_bwd_data", P.n_act, P.io_act, NP, B, s)
-        H = P.head_gauss if self.fold_launches else False
-        if H is None:
-            H = P.head_gauss = _lib.DyHead()
-            H.kind, H.B_norm = 1, G
-            H.heads, H.heads_ld, H.eps, H.scale, H.n_u = ws.heads2.data_ptr(), 2 * A, eps2.data_ptr(), p_scale, A
-            H.da[0], H.da_ld[0] = ws.dxq[0].data_ptr() + 4 * Do, D
-            H.da[1], H.da_ld[1] = ws.dxq[1].data_ptr() + 4 * Do, D
-            H.alpha, H.dlogp_mul = sc + 4 * SC.SC_ALPHA, 1.0 / G
-            H.dheads, H.dheads_ld = ws.dheads2.data_ptr(), 2 * A
-            # the sums the td head and the actor-q head of this update left as tile partials (sums_defer): two workgroups
-            # of this launch finish them — before the Adam step that reads d log_alpha and mirrors the losses
-            J = 0
-            for src in (P.head_td, P.head_actor_q):
-                if src is None or not src.sums_defer:
-                    continue
-                F = H.finish[J]
-                F.kind, F.partials, F.n_tiles = src.kind, src.partials, src.sums_tiles
-                if src.kind == 2:
-                    F.n_nets, F.mul, F.out, F.out_x = len(self.h_crit), src.mul, src.out, src.out_x
-                else:
-                    F.n_nets, F.B_norm = src.n_prob, src.B_norm
-                    C.memmove(C.byref(F.actor), C.byref(src.actor), C.sizeof(_lib.ActorScalarArgs))
-                J += 1
-        if H is not False:
-            # (per call: the step's lambda-update flags change from update to update) the augmented-Lagrangian step a
-            # constraint head deferred (tasks.py: cf_job) is committed by this launch
+        if self.fold_launches:
+            H = P.head_gauss
+            assert H is not None
+            # per update: the rollout's d action, and the augmented-Lagrangian step a constraint head deferred (tasks.py:
+            # cf_job; its lambda-update flags change from update to update), which this launch commits
+            H.da[2], H.da_ld[2] = du2.data_ptr(), du_ld
             job = P.cf_job
             F = H.finish[2]
             F.kind = 4 if job else 0
             if job:
                 F.partials, F.sc = job[4], job[3]        # (the stepped block the constraint backward staged)
-        if H is not False:
-            H.da[2], H.da_ld[2] = du2.data_ptr(), du_ld
             call("nlbac_mlp_bwd_data_head", P.n_act, P.io_act, NP, B, C.byref(H), s)
+        else:
+            D = Do + A
+            call("nlbac_gauss_sample_bwd", ws.heads2.data_ptr(), 2 * A, ws.eps[1:1 + NP].data_ptr(),
+                 self.policy.action_scale.data_ptr(), A, NP * B, B, ws.dxq[0].data_ptr() + 4 * Do, D, ws.dxq[1].data_ptr() + 4 * Do,
+                 D, du2.data_ptr(), du_ld, sc + 4 * SC.SC_ALPHA, 1.0 / G, ws.dheads2.data_ptr(), 2 * A, s)
+            call("nlbac_mlp_bwd_data", P.n_act, P.io_act, NP, B, s)
         tune = self.automatic_entropy_tuning
         p_part_q, n_part = ws.p_part_q, ws.n_part_q
         for g, cnt, nets, gio, sk_ws in P.act_groups:

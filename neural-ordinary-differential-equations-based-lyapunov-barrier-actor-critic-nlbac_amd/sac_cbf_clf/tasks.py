@@ -30,7 +30,7 @@ from .. import _lib
 from ..arena import mlp_array, stream_ptr
 from ..odeint import AffineNodeSolver, ConcatNodeSolver
 from .model import NeuralODEModel
-from .update_plan import io_copy_and_one, io_set
+from .update_plan import gauss_head, io_copy_and_one, io_set
 
 
 def _fit_in_first_100_episodes(self, i_episode):
@@ -46,7 +46,7 @@ class _Task:
     rollout_waits = 1        # adaptive solves chained inside one update's rollout: each ends in a host wait (dopri5)
     obs_dim = act_dim = lya_dim = n_s = 0
     n_eps = 3                 # N(0,1) draws per update: next-obs sample, obs sample, backup sample [, ...]
-    lam_hi = 400.0
+    lam_lo, lam_hi = 0.01, 400.0   # bounds of the Lagrange multipliers
     ratio_mode = 1            # 1 plain ratio (U), 2 clamped at 0.002 (C)
     graph_ok = False          # whole update replayable as hipGraphs
     n_pol = 2                 # controllers trained per update (primary + backup); 1 in the learned-barrier copies
@@ -59,7 +59,6 @@ class _Task:
     def __init__(self, agent, env, args):
         self.agent, self.env = agent, env
         self._reserved = set()      # (solver, rows, problems, method) whose buffers ``reserve`` has pre-allocated
-        self._cf_ok = None          # nlbac_mlp_fwd_head_ok of the V(p(x')) launch, asked once (UnicycleTask)
 
     def z(self, *shape):
         return torch.zeros(*shape, dtype=torch.float32, device=self.agent.device)
@@ -74,23 +73,18 @@ class _Task:
             self._reserved.add(key)
             solver.reserve(n, P, self.agent.solver)
 
-    def policy_sample(self, ws, key, nets, io, n_nets, B, heads, eps, n_u, action, action_ld, logp):
+    def policy_sample(self, gh, nets, io, n_nets, B, heads, eps, n_u, action, action_ld, logp):
         """pi(. | obs) of ``n_nets`` stacked policies on B rows each + GaussianPolicy.sample of every row (model.py:116-128):
-        one launch — the MLP launch applies the head itself (nlbac_gauss_head) — or, with the launch folds off
-        (NLBAC_FOLD=0), the forward and nlbac_gauss_sample_fwd on its (n_nets * B, 2 n_u) output ``heads``."""
+        one launch — the MLP launch applies the head ``gh`` itself (nlbac_gauss_head, built by ``plan``) — or, with the
+        launch folds off (NLBAC_FOLD=0), the forward and nlbac_gauss_sample_fwd on its (n_nets * B, 2 n_u) output ``heads``."""
         a, s, pol = self.agent, stream_ptr(), self.agent.policy
-        p_scale, p_bias = pol.action_scale.data_ptr(), pol.action_bias.data_ptr()
-        if not a.fold_launches:
-            _lib.call("nlbac_mlp_fwd", nets, io, n_nets, B, s)
-            _lib.call("nlbac_gauss_sample_fwd", heads.data_ptr(), 2 * n_u, eps.data_ptr(), p_scale, p_bias, n_u, n_nets * B,
-                      action.data_ptr(), action_ld, logp.data_ptr(), s)
+        if a.fold_launches:
+            assert gh is not None
+            _lib.call("nlbac_mlp_fwd_gauss", nets, io, n_nets, B, C.byref(gh), s)
             return
-        gh = ws._gauss_heads.get(key)
-        if gh is None:
-            gh = ws._gauss_heads[key] = _lib.GaussHead()
-            gh.eps, gh.scale, gh.bias, gh.n_u = eps.data_ptr(), p_scale, p_bias, n_u
-            gh.action, gh.action_ld, gh.logp = action.data_ptr(), action_ld, logp.data_ptr()
-        _lib.call("nlbac_mlp_fwd_gauss", nets, io, n_nets, B, C.byref(gh), s)
+        _lib.call("nlbac_mlp_fwd", nets, io, n_nets, B, s)
+        _lib.call("nlbac_gauss_sample_fwd", heads.data_ptr(), 2 * n_u, eps.data_ptr(), pol.action_scale.data_ptr(),
+                  pol.action_bias.data_ptr(), n_u, n_nets * B, action.data_ptr(), action_ld, logp.data_ptr(), s)
 
     def n_pol_now(self, updates):
         return self.n_pol
@@ -160,6 +154,7 @@ class UnicycleTask(_Task):
         a = self.agent
         self.hazards = torch.tensor(np.asarray(self.env.hazards_locations), dtype=torch.float32,
                                     device=a.device).contiguous()
+        self.r_coll = 1.05 * float(self.env.hazards_radius)
         self.solver = AffineNodeSolver(a.neural_ode_model, a.device)      # policy-loss rollouts (2B rows)
         self.solver.keep_acts = False                                     # differentiated w.r.t. the actions only
         self.fit_solver = AffineNodeSolver(a.neural_ode_model, a.device)  # NODE fit rollouts
@@ -182,7 +177,6 @@ class UnicycleTask(_Task):
 
     def plan(self, ws, P):
         a = self.agent
-        P.cf_head = P.head_actor_q_cb = None       # launch arguments built on first use (loss_and_backward)
         P.n_l = mlp_array([a.h_l.desc])
         P.io_vn = P.io(1)                          # V(p(x')) forward + data backward
         io_set(P.io_vn[0], x0=(ws.ps_next2, 2, 2), y=(ws.Vn, 1), acts=ws.acts_vn, dy=(ws.dVn, 1), dx=(ws.dps_v2, 2))
@@ -199,6 +193,34 @@ class UnicycleTask(_Task):
         P.n_q5f = mlp_array([a.h_q1.desc, a.h_q2.desc] * P.NP + [a.h_l.desc] * (nq - n2) + [a.h_l.desc])
         P.io_q5f = P.io(nq + 1)
         io_copy_and_one(P.io_q5f, P.io_q5, nq, P.io_vn)
+        P.cf_head = P.head_actor_q_cb = None
+        if not (a.fold_launches and a.world == 1):
+            return
+        sc, dt, hz = a.sc.data_ptr(), float(self.env.dt), self.hazards.data_ptr()
+        # the constraint head of V(p(x'))'s own launch (nlbac_gauss_head::cf_kind 1): both controllers in the update, and
+        # the forward kernels that serve the net evaluate constraint heads
+        if P.NP == 2 and self.num_cbfs == 7 and _lib.load().nlbac_mlp_fwd_head_ok(P.n_l, 1):
+            G = P.cf_head = _lib.GaussHead()
+            G.cf_kind, G.cf_net, G.cf_nh = 1, 0, self.num_cbfs
+            G.cf_ps, G.cf_ps_next, G.cf_V, G.cf_hazards = ws.ps.data_ptr(), ws.ps_next2.data_ptr(), ws.V.data_ptr(), hz
+            rc = float(np.float32(self.r_coll))      # (r_coll^2 as nlbac_unicycle_constraints_fwd forms it from its float argument)
+            G.cf_r2, G.cf_dt, G.cf_gamma_b, G.cf_gamma_l = float(np.float32(rc * rc)), dt, float(a.gamma_b), self.gamma_l
+            G.cf_matr, G.cf_bmatr = ws.matr.data_ptr(), ws.bmatr.data_ptr()
+            G.cf_partials, G.cf_tickets, G.cf_sc = ws.part_c16.data_ptr(), ws.tickets_c.data_ptr(), sc
+            G.cf_n_cbf, G.cf_n_clf, G.cf_batch_size = self.num_cbfs, 1, float(a.batch_size)
+            G.cf_ratio_mode, G.cf_backup_mode, G.cf_lam_lo, G.cf_lam_hi = self.ratio_mode, self.backup_mode, self.lam_lo, self.lam_hi
+            if P.sums_defer:
+                # ... without the election and the step: the tiles' column sums go out, the workgroups of the constraint
+                # backward sum them and run the step on a private copy of the scalars block, a workgroup of the actors'
+                # data backward commits it (nlbac_gauss_head::cf_defer, nlbac_dy_head::cb_defer, nlbac_head_sums 4)
+                G.cf_defer, G.cf_tiles = 1, ws.sums_tiles.data_ptr() + 8
+        # the Q(s, pi) nets' dy head + the constraint backward (d ps_next of both controllers from the CBF terms, dV_next
+        # from the CLF term) as the prologue of V's workgroups (nlbac_dy_head::cb_kind 1)
+        H = P.head_actor_q_cb = _lib.DyHead.from_buffer_copy(P.head_actor_q)
+        H.cb_kind, H.cb_nh = 1, self.num_cbfs
+        H.cb_ps_next, H.cb_matr, H.cb_bmatr = ws.ps_next2.data_ptr(), ws.matr.data_ptr(), ws.bmatr.data_ptr()
+        H.cb_hazards, H.cb_sc, H.cb_dt, H.cb_batch = hz, sc, dt, float(a.batch_size)
+        H.cb_dps_next, H.cb_dV = ws.dps_next2.data_ptr(), ws.dVn.data_ptr()
 
     # -- rollout under both controllers ------------------------------------------------------
     def rollout_begin(self, ws, P):
@@ -229,65 +251,43 @@ class UnicycleTask(_Task):
         # the constraint terms ride in V(p(x'))'s own launch where its kernels evaluate them (below); that launch is then
         # never merged with the pending Q(s, pi) forward: V(c), which the CLF term needs, would be computed by another
         # net's workgroups of the same launch — and eager and captured updates keep the same launches' arithmetic
-        use_head = self._constraint_head_ok(P.n_l, 1, ws)
+        use_head = P.cf_head is not None
         merged = mapped and a.world == 1 and a.fold_launches and not a.h_extra and len(a._fill) == 1 and not use_head
         if merged:
             a._fill.clear()      # (the pending piece is exactly the Q(s, pi) forward: it rides with V(p(x')) below)
         a.drain_fill()           # what is left of part 1 (critic step, Q(s, pi)): everything below uses the stepped nets
         if not mapped:
             call("nlbac_unicycle_lookahead", x_next2.data_ptr(), 2 * B, self.l_p, ws.ps_next2.data_ptr(), s)
-        r_coll = 1.05 * float(self.env.hazards_radius)
         nets, io, cnt = (P.n_q5f, P.io_q5f, P.n_q5_count + 1) if merged else (P.n_l, P.io_vn, 1)
+        fused = a.auglag_fused(ws, P, lam_upd)       # (stores this update's lambda-update flags in P.auglag)
         P.cf_job = None
         if use_head:
             # the constraint terms, their column sums and the augmented-Lagrangian step are the epilogue of V(p(x'))'s
-            # workgroups in this launch (nlbac_gauss_head::cf_kind 1): no nlbac_unicycle_constraints_fwd launch
-            A = a.auglag_fused(ws, self.num_cbfs, lam_upd)[0]._obj
-            G = P.cf_head                       # (built once per plan: ~40 ctypes field stores sit between the accept
-            if G is None:                       #  decision and this launch; only the lambda-update flags change per update)
-                G = P.cf_head = _lib.GaussHead()
-                G.cf_kind, G.cf_net, G.cf_nh = 1, cnt - 1, self.num_cbfs
-                G.cf_ps, G.cf_ps_next, G.cf_V, G.cf_hazards = ws.ps.data_ptr(), ws.ps_next2.data_ptr(), ws.V.data_ptr(), self.hazards.data_ptr()
-                rc = float(np.float32(r_coll))           # (r_coll^2 as nlbac_unicycle_constraints_fwd forms it from its float argument)
-                G.cf_r2, G.cf_dt, G.cf_gamma_b, G.cf_gamma_l = float(np.float32(rc * rc)), dt, float(a.gamma_b), self.gamma_l
-                G.cf_matr, G.cf_bmatr = ws.matr.data_ptr(), ws.bmatr.data_ptr()
-                G.cf_partials, G.cf_tickets, G.cf_sc = ws.part_c16.data_ptr(), ws.tickets_c.data_ptr(), sc
-                G.cf_n_cbf, G.cf_n_clf, G.cf_batch_size = A.n_cbf, A.n_clf, A.batch_size
-                G.cf_ratio_mode, G.cf_backup_mode, G.cf_lam_lo, G.cf_lam_hi = A.ratio_mode, A.backup_mode, A.lam_lo, A.lam_hi
-            assert G.cf_net == cnt - 1
-            G.cf_do_lambda_update, G.cf_do_backup_lambda_update = A.do_lambda_update, A.do_backup_lambda_update
-            cf_defer = a._sums_defer()
-            if cf_defer:
-                # ... without the election and the step: the tiles' column sums go out, the workgroups of the constraint
-                # backward (below) sum them and run the step on a private copy of the scalars block, a workgroup of the
-                # actors' data backward commits it (nlbac_gauss_head::cf_defer, nlbac_dy_head::cb_defer, nlbac_head_sums 4)
-                G.cf_defer, G.cf_tiles = 1, ws.sums_tiles.data_ptr() + 8
-                P.cf_job = (ws.part_c16.data_ptr(), ws.sums_tiles.data_ptr() + 8, A, sc, ws.sc_stage.data_ptr())
+            # workgroups in this launch (P.cf_head): no nlbac_unicycle_constraints_fwd launch
+            G = P.cf_head
+            assert cnt == 1 and G.cf_net == 0
+            # per update: the lambda-update flags and, where the step is deferred, the job of those who run and commit it
+            G.cf_do_lambda_update, G.cf_do_backup_lambda_update = lam_upd, ws.blam_upd
+            if G.cf_defer:
+                P.cf_job = (ws.part_c16.data_ptr(), ws.sums_tiles.data_ptr() + 8, P.auglag, sc, ws.sc_stage.data_ptr())
             call("nlbac_mlp_fwd_head", nets, io, cnt, B, C.byref(G), s)
         else:
             call("nlbac_mlp_fwd", nets, io, cnt, B, s)
             call("nlbac_unicycle_constraints_fwd", ws.ps.data_ptr(), ws.ps_next2.data_ptr(), ws.V.data_ptr(),
-                 ws.Vn.data_ptr(), self.hazards.data_ptr(), self.num_cbfs, r_coll, dt, float(a.gamma_b), self.gamma_l, B,
-                 ws.matr.data_ptr(), ws.bmatr.data_ptr(), ws.part_c.data_ptr(), *a.auglag_fused(ws, self.num_cbfs, lam_upd), s)
+                 ws.Vn.data_ptr(), self.hazards.data_ptr(), self.num_cbfs, self.r_coll, dt, float(a.gamma_b), self.gamma_l,
+                 B, ws.matr.data_ptr(), ws.bmatr.data_ptr(), ws.part_c.data_ptr(), *fused, s)
         a.auglag(ws, self.num_cbfs, lam_upd)
         if a.world == 1 and a.fold_launches:
-            # dV_next -> d ps_next (rows [0,B)), together with the Q(s, pi) nets' dx; the constraint backward itself (d ps_next
-            # of both controllers from the CBF terms, dV_next from the CLF term) is the prologue of V's workgroups in that
-            # launch (nlbac_dy_head::cb_kind 1): no nlbac_unicycle_constraints_bwd launch
-            NP = ws.np_now
+            # dV_next -> d ps_next (rows [0,B)), together with the Q(s, pi) nets' dx and the constraint backward itself
+            # (P.head_actor_q_cb): no nlbac_unicycle_constraints_bwd launch
             H = P.head_actor_q_cb
-            if H is None:
-                H = P.head_actor_q_cb = _lib.DyHead.from_buffer_copy(a._actor_q_head(ws, P, NP, B * a.world))
-                H.cb_kind, H.cb_nh = 1, self.num_cbfs
-                H.cb_ps_next, H.cb_matr, H.cb_bmatr = ws.ps_next2.data_ptr(), ws.matr.data_ptr(), ws.bmatr.data_ptr()
-                H.cb_hazards, H.cb_sc, H.cb_dt, H.cb_batch = self.hazards.data_ptr(), sc, dt, float(a.batch_size)
-                H.cb_dps_next, H.cb_dV = ws.dps_next2.data_ptr(), ws.dVn.data_ptr()
-            job = P.cf_job if use_head else None
+            assert H is not None
+            job = P.cf_job                           # per update: the deferred augmented-Lagrangian step
             H.cb_defer = 1 if job else 0
             if job:
                 H.cb_partials, H.cb_tiles, H.cb_stage = job[0], job[1], job[4]
                 C.memmove(C.byref(H.cb_auglag), C.byref(job[2]), C.sizeof(_lib.AuglagArgs))
-            call("nlbac_mlp_bwd_data_head", P.n_q5v, P.io_q5v, 2 * NP + 1, B, C.byref(H), s)
+            call("nlbac_mlp_bwd_data_head", P.n_q5v, P.io_q5v, 2 * ws.np_now + 1, B, C.byref(H), s)
             ws.q5_bwd_done = True
         else:
             call("nlbac_unicycle_constraints_bwd", ws.ps_next2.data_ptr(), ws.matr.data_ptr(), ws.bmatr.data_ptr(),
@@ -301,16 +301,6 @@ class UnicycleTask(_Task):
                  self.l_p, ws.dx_next2.data_ptr(), s)
             du2, _ = self.solver.backward(ws.dx_next2, need_du=True)
         return du2, self.act_dim
-
-    def _constraint_head_ok(self, nets, cnt, ws):
-        """Single GPU, launch folds on, both controllers in the update, and the forward kernels that serve these nets
-        evaluate constraint heads (``nlbac_mlp_fwd_head_ok``)."""
-        a = self.agent
-        if not (a.world == 1 and a.fold_launches and ws.np_now == 2 and self.num_cbfs == 7):
-            return False
-        if self._cf_ok is None:
-            self._cf_ok = bool(_lib.load().nlbac_mlp_fwd_head_ok(nets, cnt))
-        return self._cf_ok
 
     def first_step_done(self):
         return self.solver.first_step_done()
@@ -372,6 +362,7 @@ class CarsTask(_Task):
         io = P.io_nx = P.io(2)                     # both policies on the predicted next observation
         for i in range(2):
             io_set(io[i], x0=(ws.obs1_2[i * B:], 10, 10), y=(ws.heads_nx[i * B:], 2))
+        P.head_nx = gauss_head(a.policy, ws.eps[3:5], 1, ws.c2, 2, ws.logp_nx) if a.fold_launches else None
 
     def rollout_begin(self, ws, P):
         a, s = self.agent, stream_ptr()
@@ -390,13 +381,13 @@ class CarsTask(_Task):
             ws.x1_2.copy_(x1)         # (normally the solver has written there itself: out_into, rollout_begin)
         # u_(t+1) ~ pi(. | get_obs(x_t+1)), detached (C/sac_cbf_clf.py:441-451, 585-595)
         call("nlbac_cars_obs", ws.x1_2.data_ptr(), 2 * B, ws.obs1_2.data_ptr(), s)
-        self.policy_sample(ws, "nx", P.n_act, P.io_nx, 2, B, ws.heads_nx, ws.eps[3:5], 1, ws.c2, 2, ws.logp_nx)
+        self.policy_sample(P.head_nx, P.n_act, P.io_nx, 2, B, ws.heads_nx, ws.eps[3:5], 1, ws.c2, 2, ws.logp_nx)
         x2 = self.solver2.forward(ws.x1_2, ws.c2, 2, B, a.solver, dt, a.atol, a.rtol)
         a.drain_fill()
         call("nlbac_mlp_fwd", P.n_l, P.io_v1, 1, B, s)
         call("nlbac_cars_constraints_fwd", ws.state.data_ptr(), ws.x1_2.data_ptr(), x2.data_ptr(), ws.V.data_ptr(),
              ws.V1.data_ptr(), float(a.gamma_b), self.gamma_l, self.collision_radius, B, ws.matr.data_ptr(),
-             ws.bmatr.data_ptr(), ws.part_c.data_ptr(), *a.auglag_fused(ws, self.num_cbfs, lam_upd), s)
+             ws.bmatr.data_ptr(), ws.part_c.data_ptr(), *a.auglag_fused(ws, P, lam_upd), s)
         a.auglag(ws, self.num_cbfs, lam_upd)
         call("nlbac_cars_constraints_bwd", ws.matr.data_ptr(), ws.bmatr.data_ptr(), float(a.gamma_b),
              float(a.batch_size), B, sc, ws.dx1.data_ptr(), ws.dx2.data_ptr(), ws.dV1.data_ptr(), s)
@@ -489,12 +480,14 @@ class PvtolTask(_Task):
         P.io_v1 = P.io(1)                          # V(obs(x_t+1)) forward + data backward
         io_set(P.io_v1[0], x0=(ws.obs1, 11, 11), y=(ws.V1, 1), acts=ws.acts_v1, dy=(ws.dV1, 1), dx=(ws.dobs1, 11))
         P.n_pols = mlp_array([h.desc for h in a.h_pols[:NP]])
-        P.io_nx = []
+        P.io_nx, P.head_nx = [], [None, None]      # the controllers on the predicted observations of steps 1 and 2
         for obs, heads in ((ws.obs1, ws.heads_n1), (ws.obs2, ws.heads_n2)):
             io = P.io(NP)                          # each controller on its own rows of the predicted observation
             for i in range(NP):
                 io_set(io[i], x0=(obs[i * B:], 11, 11), y=(heads[i * B:], 4))
             P.io_nx.append(io)
+        if a.fold_launches:
+            P.head_nx = [gauss_head(a.policy, ws.eps[3 + 2 * k:], 2, act, 2, ws.logp_nx) for k, act in enumerate((ws.a1, ws.a2))]
 
     def rollout_begin(self, ws, P):
         a, s = self.agent, stream_ptr()
@@ -522,11 +515,11 @@ class PvtolTask(_Task):
         # u_(t+1), u_(t+2) ~ pi(. | get_obs(x)), detached (P:474-526)
         call("nlbac_pvtol_obs_fwd", ws.x1.data_ptr(), ws.op0.data_ptr(), B, follow, gx, gy, n, ws.obs1.data_ptr(), 11,
              ws.op1.data_ptr(), s)
-        self.policy_sample(ws, ("n1", NP), P.n_pols, P.io_nx[0], NP, B, ws.heads_n1, ws.eps[3:3 + NP], 2, ws.a1, 2, ws.logp_nx)
+        self.policy_sample(P.head_nx[0], P.n_pols, P.io_nx[0], NP, B, ws.heads_n1, ws.eps[3:3 + NP], 2, ws.a1, 2, ws.logp_nx)
         ws.x2 = s2.forward(ws.x1[:n], ws.a1[:n], NP, B, a.solver, dt, a.atol, a.rtol)
         call("nlbac_pvtol_obs_fwd", ws.x2.data_ptr(), ws.op1.data_ptr(), n, follow, gx, gy, n, ws.obs2.data_ptr(), 11,
              ws.op2.data_ptr(), s)
-        self.policy_sample(ws, ("n2", NP), P.n_pols, P.io_nx[1], NP, B, ws.heads_n2, ws.eps[5:5 + NP], 2, ws.a2, 2, ws.logp_nx)
+        self.policy_sample(P.head_nx[1], P.n_pols, P.io_nx[1], NP, B, ws.heads_n2, ws.eps[5:5 + NP], 2, ws.a2, 2, ws.logp_nx)
         ws.x3 = s3.forward(ws.x2[:n], ws.a2[:n], NP, B, a.solver, dt, a.atol, a.rtol)
         a.drain_fill()
         call("nlbac_mlp_fwd", P.n_l, P.io_v1, 1, B, s)
@@ -535,7 +528,7 @@ class PvtolTask(_Task):
              ws.x3.data_ptr(), ws.V.data_ptr(), ws.V1.data_ptr(), hz, len(env.hazard_locations),
              1.2 * float(env.hazards_radius), 0.9 * float(env.operator_dist), float(env.y_max), float(env.y_min),
              follow, float(a.gamma_b), self.gamma_l, B, NP, ws.matr.data_ptr(), ws.bmatr.data_ptr(),
-             ws.part_c.data_ptr(), *a.auglag_fused(ws, self.num_cbfs, lam_upd), s)
+             ws.part_c.data_ptr(), *a.auglag_fused(ws, P, lam_upd), s)
         a.auglag(ws, self.num_cbfs, lam_upd)
         call("nlbac_pvtol_constraints_bwd", ws.matr.data_ptr(), ws.bmatr.data_ptr(), ws.x1.data_ptr(),
              ws.x2.data_ptr(), ws.x3.data_ptr(), hz, len(env.hazard_locations), follow, float(a.gamma_b),
@@ -629,6 +622,7 @@ class _LearnedBarrierTask(_Task):
         P.io_bn = P.io(1)                              # B(obs', a') forward + data backward
         io_set(P.io_bn[0], x0=(ws.obs_pred, Do, Do), x1=(ws.pi_next, Da, Da), y=(ws.Bn, 1), acts=ws.acts_bn,
                dy=(ws.dBn, 1), dx=(ws.dxb, Do + Da))
+        P.head_nx = gauss_head(a.policy, ws.eps[2], Da, ws.pi_next, Da, ws.logp_nx) if a.fold_launches else None
 
     def loss_and_backward(self, ws, P, lam_upd, assume_single):
         a, s, call = self.agent, stream_ptr(), _lib.call
@@ -638,11 +632,11 @@ class _LearnedBarrierTask(_Task):
         self.lya_next_fwd(ws, x_next, s)
         call("nlbac_mlp_fwd", P.n_l, P.io_vn, 1, B, s)
         self.obs_next_fwd(ws, x_next, s)
-        self.policy_sample(ws, "nx", P.n_pi, P.io_nx, 1, B, ws.heads_nx, ws.eps[2], Da, ws.pi_next, Da, ws.logp_nx)
+        self.policy_sample(P.head_nx, P.n_pi, P.io_nx, 1, B, ws.heads_nx, ws.eps[2], Da, ws.pi_next, Da, ws.logp_nx)
         call("nlbac_mlp_fwd", P.n_bar, P.io_bn, 1, B, s)
         call("nlbac_barrier_constraints_fwd", ws.Bv.data_ptr(), ws.Bn.data_ptr(), ws.V.data_ptr(), ws.Vn.data_ptr(),
              step, float(a.gamma_b), self.gamma_l, B, ws.matr.data_ptr(), ws.part_c.data_ptr(),
-             *a.auglag_fused(ws, 1, lam_upd), s)
+             *a.auglag_fused(ws, P, lam_upd), s)
         a.auglag(ws, 1, lam_upd)
         call("nlbac_barrier_constraints_bwd", ws.matr.data_ptr(), step, float(a.batch_size), B, sc, ws.dBn.data_ptr(),
              ws.dVn.data_ptr(), s)

@@ -80,9 +80,7 @@ class _Workspace:
         self.np_now, self.updates_now, self.blam_upd = task.n_pol, 0, 0     # controllers updated, update index, backup lambda step due
         self.q5_bwd_done = False     # the task ran the Q(s, pi) data backward inside one of its own launches
         self.p_part_q, self.n_part_q = None, 0      # where the actor step reads the Q(s, pi) sums (data parallel: all-reduced)
-        self._auglag_args = None     # nlbac_auglag_args of the constraints launch (kept alive until the call is made)
         self._mask_bufs = {}         # activation buffer address -> its ReLU mask words, shared by this workspace's plans
-        self._gauss_heads = {}       # key -> nlbac_gauss_head of a task's policy_sample launch
         task.alloc(self)
 
 
@@ -167,16 +165,34 @@ def io_copy_and_one(dst, src, n, last):
     C.memmove(C.byref(dst, n * sz), last, sz)
 
 
+def gauss_head(pol, eps, n_u, action, action_ld, logp):
+    """The ``nlbac_gauss_head`` of a launch of policy nets that draws its own samples (launch folds on)."""
+    gh = _lib.GaussHead()
+    gh.eps, gh.scale, gh.bias, gh.n_u = eps.data_ptr(), pol.action_scale.data_ptr(), pol.action_bias.data_ptr(), n_u
+    gh.action, gh.action_ld, gh.logp = action.data_ptr(), action_ld, logp.data_ptr()
+    return gh
+
+
+def actor_scalars_set(S, agent, NP):
+    """Fill an ``nlbac_actor_scalar_args``: where log alpha and its gradient live, per controller updated."""
+    S.target_entropy, S.sc = agent.target_entropy, agent.sc.data_ptr()
+    for g in agent.actor_groups:
+        for k in range(min(g.count, NP - g.first)):
+            off = g.la_off + k * g.la_stride
+            S.log_alpha[g.first + k] = g.arena.theta.data_ptr() + 4 * off
+            S.g_log_alpha[g.first + k] = g.arena.grad.data_ptr() + 4 * off
+
+
 class Plan:
-    """ctypes launch descriptors of one workspace: every pointer is static (arenas, workspace tensors), so they are
-    built once (per number of controllers updated: Pvtol trains its backup every 20th update); an update is then a
-    plain sequence of C calls.  Every ``nlbac_mlp_io`` array is made by ``io()``, which is how the mask pass finds
-    them all — wherever the plan keeps them.  The task's ``plan()`` adds its own fields as plain attributes."""
+    """ctypes launch arguments of one workspace: every pointer is static (arenas, workspace tensors) and every constant
+    follows from the agent and its switches ``fold_launches`` / ``sums_defer`` as they stand when the plan is constructed,
+    so all are built here, once (per number of controllers updated: Pvtol trains its backup every 20th update); an update
+    is then a plain sequence of C calls.  Every ``nlbac_mlp_io`` array is made by ``io()``, which is how the mask pass
+    finds them all — wherever the plan keeps them.  A head structure (the folded per-row steps) that the update will not
+    use is None; a launch site stores only what changes per update.  The task's ``plan()`` adds its own arrays and heads."""
 
     def __init__(self, agent, ws, NP):
         self.io_arrays = []
-        # launch arguments that need the first update's state: built by the launch sites on first use
-        self.head_pol3 = self.head_td = self.head_actor_q = self.head_gauss = self.actor_scalars = None
         # per update: the augmented-Lagrangian step a task's constraint head left for the update's last MLP launch
         self.cf_job = None
         B, lay, task = ws.B, agent.lay, agent.task
@@ -260,6 +276,7 @@ class Plan:
             io[i].dx_first = Do                                # (only dQ / da is consumed)
         task.value_now_io(ws, io, 2 * NP)
         task.extra_value_io(ws, io, 2 * NP + 1)
+        P.heads(agent, ws)
         task.plan(ws, P)
         # mask words wherever the register-resident kernels serve the heads' launches (see the pass above).  The mask
         # buffer is sized for what those kernels take: two hidden layers of at most 256 units (8 words per row and layer)
@@ -270,6 +287,79 @@ class Plan:
             assert all(h.n_layers == 3 and h.hid <= 256 for h in nets), "mask words: (2, B, 8) per net"
             keep_masks_drop_unpaired_acts(P.io_arrays, ws._mask_bufs,
                                           lambda: torch.zeros(2, B, 8, dtype=torch.int32, device=agent.device))
+
+    def heads(self, agent, ws):
+        """The head structures of the shared launches, each under the condition its launch site asks (sac_cbf_clf.py),
+        and the constant part of ``nlbac_auglag``'s arguments."""
+        P, task, lay, NP, B = self, agent.task, agent.lay, self.NP, ws.B
+        A, Do, LD = lay.act_dim, lay.obs_dim, lay.LD
+        G = B * agent.world                      # rows the batch means run over
+        sc, q, tiles = agent.sc.data_ptr(), ws.q6, ws.sums_tiles.data_ptr()
+        one, fold = agent.world == 1, agent.fold_launches
+        # the batch sums of the td / actor-q dy heads (and of a task's constraint head) are finished by a workgroup of the
+        # actors' data backward instead of by an election at the end of their own launches (nlbac_dy_head::sums_defer /
+        # finish): single GPU with the launch folds.  ``agent.sums_defer = False`` (NLBAC_SUMS_DEFER=0): the elections
+        P.sums_defer = bool(agent.sums_defer and one and fold)
+        P.auglag = P.head_pol3 = P.head_td = P.actor_scalars = P.head_actor_q = P.head_gauss = None
+        if one:                 # (SAC_CBF_CLF.auglag_fused stores the two lambda-update flags per update)
+            L = P.auglag = _lib.AuglagArgs()
+            L.n_cbf, L.n_clf, L.batch_size = task.num_cbfs, 1, float(agent.batch_size)
+            L.ratio_mode, L.backup_mode = task.ratio_mode, task.backup_mode if NP == 2 else 0
+            L.lam_lo, L.lam_hi = task.lam_lo, task.lam_hi
+        if one and not fold:    # nlbac_actor_q_terms: its last workgroup runs nlbac_actor_scalars
+            P.actor_scalars = _lib.ActorScalarArgs()
+            actor_scalars_set(P.actor_scalars, agent, NP)
+        if not fold:
+            return
+        # pi(s') + the actors on s: all (1 + NP) * B samples are drawn by the policy launch itself
+        P.head_pol3 = gauss_head(agent.policy, ws.eps, A, ws.act3, A, ws.logp3)
+        if one and len(agent.h_extra) <= 1:
+            # dy head kind 2: targets, dL/dq and the three losses are produced by the critics' data backward itself
+            H = P.head_td = _lib.DyHead()
+            H.kind, H.B_norm = 2, G
+            H.q1t, H.q2t, H.lt, H.nlogp = q[0].data_ptr(), q[1].data_ptr(), q[2].data_ptr(), ws.nlogp.data_ptr()
+            H.reward, H.constraint, H.mask, H.rcm_ld = P.p_rew, P.p_con, P.p_mask, LD
+            H.alpha, H.gamma = sc + 4 * SC.SC_ALPHA, agent.gamma
+            for k in range(3):
+                H.q[k], H.dq[k] = q[3 + k].data_ptr(), ws.dq3[k].data_ptr()
+            H.next_q, H.next_l = ws.next_q.data_ptr(), ws.next_l.data_ptr()
+            H.partials, H.ticket = ws.part_td32.data_ptr(), ws.tickets_td.data_ptr()
+            H.mul, H.out = 1.0 / G, sc + 4 * SC.SC_QF1
+            if P.sums_defer:    # no election: the launch's tiles leave their squared-error sums (finish[0] below)
+                H.sums_defer, H.sums_tiles = 1, tiles
+            if agent.h_extra:   # BarrierNet TD step (NU/sac_cbf_clf.py:224-233): the launch's 4th net
+                H.xt, H.xq, H.dxq = q[6].data_ptr(), q[7].data_ptr(), ws.dq3[3].data_ptr()
+                H.xsig, H.xsig_ld = ws.mb.data_ptr() + 4 * lay.sig, LD
+                H.out_x = sc + 4 * SC.SC_XLOSS
+        if one:
+            # dy head kind 3 of the Q(s, pi) data backward: d min(Q1, Q2), policy_loss_1, the alpha losses, d log_alpha
+            H = P.head_actor_q = _lib.DyHead()
+            H.kind, H.B_norm, H.n_prob = 3, G, NP
+            H.qa, H.qb, H.logp = ws.qpi[0].data_ptr(), ws.qpi[1].data_ptr(), ws.logp2.data_ptr()
+            H.dqa, H.dqb = ws.dq_pi[0].data_ptr(), ws.dq_pi[1].data_ptr()
+            H.alpha = sc + 4 * SC.SC_ALPHA
+            actor_scalars_set(H.actor, agent, NP)
+            H.partials, H.ticket = ws.part_q32.data_ptr(), ws.tickets_q.data_ptr()
+            if P.sums_defer:
+                H.sums_defer, H.sums_tiles = 1, tiles + 4
+        # dy head kind 1 of the actors' data backward: d heads from d action (two Q nets; per update the rollout's) and d logp
+        H = P.head_gauss = _lib.DyHead()
+        H.kind, H.B_norm, H.scale, H.n_u = 1, G, agent.policy.action_scale.data_ptr(), A
+        H.heads, H.heads_ld, H.eps = ws.heads2.data_ptr(), 2 * A, ws.eps[1:1 + NP].data_ptr()
+        for k in (0, 1):
+            H.da[k], H.da_ld[k] = ws.dxq[k].data_ptr() + 4 * Do, Do + A
+        H.alpha, H.dlogp_mul = sc + 4 * SC.SC_ALPHA, 1.0 / G
+        H.dheads, H.dheads_ld = ws.dheads2.data_ptr(), 2 * A
+        # the sums the td head and the actor-q head left as tile partials (sums_defer): two workgroups of this launch
+        # finish them — before the Adam step that reads d log_alpha and mirrors the losses
+        deferred = [h for h in (P.head_td, P.head_actor_q) if h is not None and h.sums_defer]
+        for F, src in zip(H.finish, deferred):
+            F.kind, F.partials, F.n_tiles = src.kind, src.partials, src.sums_tiles
+            if src.kind == 2:
+                F.n_nets, F.mul, F.out, F.out_x = len(agent.h_crit), src.mul, src.out, src.out_x
+            else:
+                F.n_nets, F.B_norm = src.n_prob, src.B_norm
+                C.memmove(C.byref(F.actor), C.byref(src.actor), C.sizeof(_lib.ActorScalarArgs))
 
     def io(self, n):
         """A zeroed ``nlbac_mlp_io[n]`` that belongs to this plan."""

@@ -653,6 +653,41 @@ int nlbac_concat_rk_grid_bwd(const nlbac_mlp *net, int n, int H, int n_stages, c
                              const float *hs, const float *hs_host, const float *acts, long acts_ls, int acts_bits,
                              const float *norm, const float *dout, float *dx0, float *dc, float *dK, float *dz,
                              nlbac_stream_t s);
+/* The same time grid under a step size (torchdiffeq's options=dict(step_size=s); declarations added under ABI 17, no
+ * existing signature or struct changes): the launch's H intervals are the N fine intervals of the solver's own grid,
+ * steps hs / hs_host [N], and its outputs are the T - 1 points 1 .. T-1 of the caller's grid, read off the fine
+ * intervals by linear interpolation: fine interval i holds the outputs ofs[i] <= j < ofs[i+1] (ofs [N+1], CSR,
+ * ofs[0] = 1, ofs[N] = T, not decreasing), and with y_i, y_i+1 the fine states at its ends
+ *     out[j-1] = y_i+1 at theta[j-1] == 1,  y_i at theta[j-1] == 0,  else  y_i + theta[j-1] (y_i+1 - y_i)   (fp32),
+ * theta [T-1] in [0, 1].  ofs / theta are device arrays (what the kernels read), ofs_host / theta_host host copies
+ * beside them (what the launcher checks), as hs / hs_host.  out [T-1][n][n_s]; dout [T][n][n_s] (dout[0]: d loss /
+ * d x0 direct).  Everything kept per stage (K / Y / G, Xin, acts, dK / dG / dz) is per FINE stage: [N * n_stages][n][..],
+ * and the weight-gradient launch runs over all N * n_stages * n rows.  Backward, intervals i = N-1 .. 0: d = 0, then
+ * d = d + theta[j-1] dout[j] for the interval's outputs (j ascending), then + the dy0 carried from interval i+1; behind
+ * the interval sum_j (1 - theta[j-1]) dout[j] (outputs with theta < 1, j ascending) joins its dy0 before that is carried
+ * to interval i-1 (at i = 0: before dx0 = dout[0] + dy0).  With every weight 1 these are nlbac_*_rk_grid_*'s fp32
+ * operations on the fine grid with zero dout at the unused points.  No barrier is added to the grid kernels. */
+int nlbac_node_rk_subgrid_fwd(const nlbac_mlp *f, const nlbac_mlp *g, const float *x0, const float *u, int n, int H,
+                              int n_stages, const float *beta, const float *c_out, const float *hs,
+                              const float *hs_host, const int *ofs, const int *ofs_host, const float *theta,
+                              const float *theta_host, int T, float *out, float *K, float *Y, float *G, float *acts_f,
+                              long acts_f_ls, float *acts_g, long acts_g_ls, int acts_bits, nlbac_stream_t s);
+int nlbac_node_rk_subgrid_bwd(const nlbac_mlp *f, const nlbac_mlp *g, const float *u, int n, int H, int n_stages,
+                              const float *beta, const float *c_out, const float *hs, const float *hs_host,
+                              const int *ofs, const int *ofs_host, const float *theta, const float *theta_host, int T,
+                              const float *G, const float *acts_f, long acts_f_ls, const float *acts_g, long acts_g_ls,
+                              int acts_bits, const float *dout, float *dx0, float *du, float *dK, float *dG,
+                              float *dz_f, float *dz_g, nlbac_stream_t s);
+int nlbac_concat_rk_subgrid_fwd(const nlbac_mlp *net, const float *x0, const float *c, int n, int H, int n_stages,
+                                const float *beta, const float *c_out, const float *hs, const float *hs_host,
+                                const int *ofs, const int *ofs_host, const float *theta, const float *theta_host, int T,
+                                float *out, float *Xin, float *acts, long acts_ls, int acts_bits, const float *norm,
+                                nlbac_stream_t s);
+int nlbac_concat_rk_subgrid_bwd(const nlbac_mlp *net, int n, int H, int n_stages, const float *beta, const float *c_out,
+                                const float *hs, const float *hs_host, const int *ofs, const int *ofs_host,
+                                const float *theta, const float *theta_host, int T, const float *acts, long acts_ls,
+                                int acts_bits, const float *norm, const float *dout, float *dx0, float *dc, float *dK,
+                                float *dz, nlbac_stream_t s);
 /* The same one-launch RK step for the single-net NODE dx/dt = net([x | c]) with carried inputs c = (u, t)
  * (SimulatedCars, C/sac_cbf_clf/model.py:179-205; odeint call sites C/sac_cbf_clf/sac_cbf_clf.py:437,458,581,603,
  * C/model.py:245): n_s = net->out_dim state columns, n_c = net->in_dim - n_s carried columns (c: (rows, n_c)),

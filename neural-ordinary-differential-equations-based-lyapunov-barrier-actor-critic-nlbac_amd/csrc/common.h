@@ -37,6 +37,56 @@ static inline int nlbac_grid_steps_check(const float* hs, const float* hs_host, 
     return 0;
 }
 
+// The output points of a sub-stepped time-grid launch (nlbac_node_rk_subgrid_* / nlbac_concat_rk_subgrid_*): the N fine
+// intervals are the launch's intervals, and the T - 1 outputs 1 .. T-1 are read off them — interval i holds the outputs
+// ofs[i] <= j < ofs[i+1] (CSR), output j is y_i + theta[j-1] (y_{i+1} - y_i), the fine state itself at theta 1 / 0.
+struct NlbacSubGrid {
+    const int* ofs;                   // [N+1] (device)
+    const float* theta;               // [T-1] (device)
+};
+
+// What an entry point passes on to its launcher: ofs / theta on the device are what the kernel reads, ofs_host /
+// theta_host in host memory beside them what the launcher checks (every output index the kernel forms from them lies in
+// [1, T)); T time points.
+struct NlbacSubGridArgs {
+    const int* ofs; const int* ofs_host;
+    const float* theta; const float* theta_host;
+    int T;
+};
+
+static inline int nlbac_subgrid_check(const NlbacSubGridArgs* sg, int N, const char* who) {
+    NLBAC_REQUIRE(sg, "%s: null pointer", who);
+    const int* ofs = sg->ofs; const int* ofs_host = sg->ofs_host;
+    const float* theta = sg->theta; const float* theta_host = sg->theta_host;
+    const int T = sg->T;
+    NLBAC_REQUIRE(ofs && ofs_host && theta && theta_host, "%s: null pointer", who);
+    NLBAC_REQUIRE(T >= 2, "%s: at least two time points", who);
+    NLBAC_REQUIRE(ofs_host[0] == 1 && ofs_host[N] == T, "%s: ofs runs from 1 to the number of time points", who);
+    for (int i = 0; i < N; ++i) NLBAC_REQUIRE(ofs_host[i] <= ofs_host[i + 1], "%s: ofs must not decrease", who);
+    for (int j = 0; j < T - 1; ++j)
+        NLBAC_REQUIRE(theta_host[j] >= 0.f && theta_host[j] <= 1.f, "%s: every interpolation weight lies in [0, 1]", who);
+    return 0;
+}
+
+// output point with weight th between the fine states y0 and y1
+__device__ __forceinline__ float nlbac_sub_point(float y0, float y1, float th) {
+    return th == 1.f ? y1 : (th == 0.f ? y0 : y0 + th * (y1 - y0));
+}
+
+// acc + the share of fine interval i's output gradients dout[j][rc] (j ascending; dout [T][stride]) that reaches the
+// interval's END state (UPPER: weights theta_j) or its INITIAL state (weights 1 - theta_j, outputs with theta_j < 1 only)
+template <bool UPPER>
+__device__ __forceinline__ float nlbac_sub_gather(const NlbacSubGrid& G, const float* dout, long stride, long rc, int i,
+                                                  float acc) {
+    const int j1 = G.ofs[i + 1];
+    for (int j = G.ofs[i]; j < j1; ++j) {
+        const float th = G.theta[j - 1];
+        if (UPPER) acc = acc + th * dout[(long)j * stride + rc];
+        else if (th < 1.f) acc = acc + (1.f - th) * dout[(long)j * stride + rc];
+    }
+    return acc;
+}
+
 // The tableau of such a launch, beta [n_stages][n_stages] row-major and c_out [n_stages], into a launch descriptor's arrays.
 template <int S>
 static inline void nlbac_tableau_copy(float (&beta_to)[S][S], float (&c_out_to)[S], int& n_out_to, int n_stages,

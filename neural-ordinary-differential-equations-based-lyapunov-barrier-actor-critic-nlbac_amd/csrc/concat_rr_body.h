@@ -38,9 +38,14 @@ __device__ __forceinline__ float crr_step_output(const ConcatRkLaunch& L, const 
 // GRID (with TRAJ; nlbac_concat_rk_grid_fwd: the solution on a time grid): interval k's step size is hs[k] (device
 // array), written to sH by the wave that owns the rows at the top of the interval, and the carried columns L.c [n][n_c]
 // are the same for every interval (sC is filled once).
-template <int NB, int R, int BITS, int NW, bool TRAJ = false, bool GRID = false>
-__device__ __forceinline__ void concat_rr_fwd_body(const ConcatRkLaunch& L, const int H = 1, const float* hs = nullptr) {
+// SUB (with GRID; nlbac_concat_rk_subgrid_fwd: a time grid under step_size): the intervals are the N fine intervals, and
+// L.out takes the T - 1 output points read off them (NlbacSubGrid, common.h): out[j-1] for the outputs j of interval k,
+// written by the lane that holds the old state and the new one, before sY0 is overwritten.
+template <int NB, int R, int BITS, int NW, bool TRAJ = false, bool GRID = false, bool SUB = false>
+__device__ __forceinline__ void concat_rr_fwd_body(const ConcatRkLaunch& L, const int H = 1, const float* hs = nullptr,
+                                                   const NlbacSubGrid* sub = nullptr) {
     static_assert(TRAJ || !GRID, "a time grid is a trajectory");
+    static_assert(GRID || !SUB, "sub-steps are a time grid's");
     constexpr int TILE = 16 * NW, NTHR = 64 * NW;
     (void)NTHR;
     using S = RRShape<NB, R>;
@@ -387,7 +392,14 @@ __device__ __forceinline__ void concat_rr_fwd_body(const ConcatRkLaunch& L, cons
             const int mm = 16 * half + idx / ns, r = idx % ns, row = row0 + mm;
             if (row >= n) continue;
             const float a = crr_step_output<TILE>(L, sY0, sK, mm, r, sH[mm]);
-            L.out[(long)k * n * ns + (long)row * ns + r] = a;
+            if constexpr (SUB) {
+                const float y_old = sY0[mm * CK_LD + r];
+                const int j1 = sub->ofs[k + 1];
+                for (int j = sub->ofs[k]; j < j1; ++j)
+                    L.out[(long)(j - 1) * n * ns + (long)row * ns + r] = nlbac_sub_point(y_old, a, sub->theta[j - 1]);
+            } else {
+                L.out[(long)k * n * ns + (long)row * ns + r] = a;
+            }
             sY0[mm * CK_LD + r] = a;
         }
         if constexpr (!GRID) {
@@ -535,10 +547,15 @@ struct ConcatRkTrajBwd {
 // intervals' gradients w.r.t. the (one set of) carried columns, formed by the wave that owns the rows in the order
 // k = H-1 .. 0 — total = dc_{H-1}; total = total + dc_k, the fp32 adds the chained path does between its launches —
 // in sDYup, which only the interpolant's backward uses otherwise.
-template <int NB, int R, int BITS, int NW, bool TRAJ = false, bool GRID = false>
+// SUB (with GRID; nlbac_concat_rk_subgrid_bwd): X->dout [T][n][n_s] belongs to the output points: interval k's d is
+// sum_j theta_j dout[j] over its outputs (j ascending; + the dy0 of interval k+1), and sum_j (1 - theta_j) dout[j] joins
+// the interval's dy0 before it is handed to interval k-1 resp. enters dx0 — by the lane that holds the entry.  With every
+// weight 1: the GRID kernel's fp32 operations on the fine grid with zero dout at the unused points.
+template <int NB, int R, int BITS, int NW, bool TRAJ = false, bool GRID = false, bool SUB = false>
 __device__ __forceinline__ void concat_rr_bwd_body(const ConcatRkBwdLaunch& L, const ConcatRkTrajBwd* X = nullptr,
-                                                   const float* hs = nullptr) {
+                                                   const float* hs = nullptr, const NlbacSubGrid* sub = nullptr) {
     static_assert(TRAJ || !GRID, "a time grid is a trajectory");
+    static_assert(GRID || !SUB, "sub-steps are a time grid's");
     constexpr int TILE = 16 * NW;
     using S = RRShape<NB, R>;
     constexpr int KS = S::KS, HID = S::HID, TB = NB - 2, NT = KS - 4 * TB;
@@ -727,18 +744,32 @@ __device__ __forceinline__ void concat_rr_bwd_body(const ConcatRkBwdLaunch& L, c
             }
         }
     };
+    // (SUB) this lane's (row, column) offset into an output point's gradient rows, formed anew wherever it is needed: kept
+    // in registers through an interval, four of them would cost what dnext would (see above)
+    auto sub_rc = [&](int it) __attribute__((always_inline)) {
+        int idx = lane + 64 * it;
+        asm volatile("" : "+v"(idx));
+        return (long)min(row0 + 16 * half + idx / CK_NS, n - 1) * ns + min(idx % CK_NS, ns - 1);
+    };
+    (void)sub_rc;
     for (int kk = 0; kk < H; ++kk) {
     const int k = H - 1 - kk, kS = TRAJ ? k * L.S_total : 0;      // interval k's first stage in the [k][stage][row] layout
     if constexpr (TRAJ) {       // d = dout[k+1] (+ interval k+1's dy0): dy0 = 0 + d, dK_j = 0 + (c_out[j] h) d; dc = 0
-        request_dout(k + 1);
+        if constexpr (!SUB) request_dout(k + 1);
         if constexpr (GRID) { if (lane < 16) sH[16 * half + lane] = hs[k]; }
 #pragma unroll
         for (int it = 0; it < NITD; ++it) {
             const int idx = lane + 64 * it, mm = 16 * half + idx / CK_NS, c = idx % CK_NS;
             const bool ok = row0 + mm < n && c < ns;
             const float vh = sH[mm];
-            float d = dnext[it];
-            if (kk > 0) d = d + sDY0[mm * CK_LD + c];
+            float d = SUB ? 0.f : dnext[it];
+            if constexpr (SUB) {      // the outputs' gradients come in here, entry by entry, by the lane that holds the entry
+                const long rc = sub_rc(it);
+                d = nlbac_sub_gather<true>(*sub, X->dout, (long)n * ns, rc, k, d);
+                if (kk > 0) d = d + nlbac_sub_gather<false>(*sub, X->dout, (long)n * ns, rc, k + 1, sDY0[mm * CK_LD + c]);
+            } else {
+                if (kk > 0) d = d + sDY0[mm * CK_LD + c];
+            }
             sDY0[mm * CK_LD + c] = ok ? 0.f + d : 0.f;
 #pragma unroll 1
             for (int j = 0; j < L.S_total; ++j) {       // (a rolled loop: the tableau's weights stay out of the SGPRs)
@@ -912,7 +943,12 @@ __device__ __forceinline__ void concat_rr_bwd_body(const ConcatRkBwdLaunch& L, c
 #pragma unroll
         for (int it = 0; it < NITD; ++it) {
             const int idx = lane + 64 * it, mm = 16 * half + idx / CK_NS, c = idx % CK_NS, row = row0 + mm;
-            if (row < n && c < ns) X->dx0[(long)row * ns + c] = dnext[it] + sDY0[mm * CK_LD + c];
+            if constexpr (SUB) {
+                if (row < n && c < ns)
+                    X->dx0[(long)row * ns + c] = dnext[it] + nlbac_sub_gather<false>(*sub, X->dout, (long)n * ns, sub_rc(it), 0, sDY0[mm * CK_LD + c]);
+            } else {
+                if (row < n && c < ns) X->dx0[(long)row * ns + c] = dnext[it] + sDY0[mm * CK_LD + c];
+            }
         }
         return;
     }

@@ -17,6 +17,10 @@
 // nlbac_concat_rk_grid_*: the solution on a whole time grid, torchdiffeq's fixed-grid rule (one RK step per grid
 // interval): the same kernels with a step size per interval and one set of carried columns for all of them (GRID in
 // concat_rr_body.h), the carried columns' gradient summed over the intervals inside the launch.
+//
+// nlbac_concat_rk_subgrid_*: the same grid under step_size — the launch's intervals are the N fine intervals, its
+// outputs the T - 1 points read off them by linear interpolation (SUB in concat_rr_body.h, NlbacSubGrid in common.h); the
+// backward takes the output points' gradients in between the fine intervals.
 #undef RR_TIMING          // (the ablation stamps belong to the one-step kernels)
 #include "concat_rr_body.h"
 
@@ -44,6 +48,32 @@ struct ConcatRkGridBwdLaunch {
     ConcatRkTrajBwd X;
     const float* hs;
 };
+
+struct ConcatRkSubgridFwdLaunch {
+    ConcatRkLaunch L;
+    int H;                            // the N fine intervals
+    const float* hs;
+    NlbacSubGrid sub;
+};
+
+struct ConcatRkSubgridBwdLaunch {
+    ConcatRkBwdLaunch L;
+    ConcatRkTrajBwd X;
+    const float* hs;
+    NlbacSubGrid sub;
+};
+
+template <int NB, int R, int BITS, int NW>
+__global__ __launch_bounds__(64 * NW) void concat_subgrid_fwd_kernel(const ConcatRkSubgridFwdLaunch A) {
+    concat_rr_fwd_body<NB, R, BITS, NW, true, true, true>(A.L, A.H, A.hs, &A.sub);
+}
+
+// (waves per SIMD as concat_traj_bwd_kernel below)
+template <int NB, int R, int BITS, int NW>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((BITS == 1 && NB < 8) ? 3 : 2)))
+void concat_subgrid_bwd_kernel(const ConcatRkSubgridBwdLaunch A) {
+    concat_rr_bwd_body<NB, R, BITS, NW, true, true, true>(A.L, &A.X, A.hs, &A.sub);
+}
 
 template <int NB, int R, int BITS, int NW>
 __global__ __launch_bounds__(64 * NW) void concat_grid_fwd_kernel(const ConcatRkGridFwdLaunch A) {
@@ -85,22 +115,28 @@ static int ctraj_check(const nlbac_mlp* net, int n, int H, int n_stages, const f
     return 0;
 }
 
+// a sub-stepped time-grid launch carries the output points' offsets and weights as well
+template <typename Launch>
+constexpr bool ctraj_on_subgrid = std::is_same<Launch, ConcatRkSubgridFwdLaunch>::value || std::is_same<Launch, ConcatRkSubgridBwdLaunch>::value;
+
 // a time-grid launch carries a step size per interval
 template <typename Launch>
-constexpr bool ctraj_on_grid = std::is_same<Launch, ConcatRkGridFwdLaunch>::value || std::is_same<Launch, ConcatRkGridBwdLaunch>::value;
+constexpr bool ctraj_on_grid = std::is_same<Launch, ConcatRkGridFwdLaunch>::value ||
+                               std::is_same<Launch, ConcatRkGridBwdLaunch>::value || ctraj_on_subgrid<Launch>;
 
 // The forward launch of `who` (an entry point below) over H intervals: the instances of its kernel template in `table`
 // (chosen as the one-step launcher chooses, concat_rr_body.h, so that the sums are the same), its step — h for every
 // interval, or (time grid) hs [H] on the device for the kernel with hs_host [H] beside it for the checks here — and
-// what the interval's one-step launch takes.
+// what the interval's one-step launch takes.  (Sub-stepped time grid) sg: the output points; out is [T-1][n][n_s].
 template <typename Launch>
 static int ctraj_fwd(const ConcatRrTable<Launch>& table, const char* who, float h, const float* hs, const float* hs_host,
                      const nlbac_mlp* net, const float* x0, const float* c, int n, int H, int n_stages, const float* beta,
                      const float* c_out, float* out, float* Xin, float* acts, long acts_ls, int acts_bits,
-                     const float* norm, nlbac_stream_t s) {
+                     const float* norm, nlbac_stream_t s, const NlbacSubGridArgs* sg = nullptr) {
     constexpr bool grid = ctraj_on_grid<Launch>;
     if (ctraj_check(net, n, H, n_stages, beta, c_out, grid ? 1.f : h, acts_bits, who)) return -1;
     if (grid && nlbac_grid_steps_check(hs, hs_host, H, who)) return -1;
+    if (ctraj_on_subgrid<Launch> && nlbac_subgrid_check(sg, H, who)) return -1;
     Launch A;
     memset(&A, 0, sizeof(A));
     ConcatRkLaunch& L = A.L;
@@ -119,6 +155,7 @@ static int ctraj_fwd(const ConcatRrTable<Launch>& table, const char* who, float 
     L.norm_mode = -1;
     A.H = H;
     if constexpr (grid) A.hs = hs;
+    if constexpr (ctraj_on_subgrid<Launch>) { A.sub.ofs = sg->ofs; A.sub.theta = sg->theta; }
     crr_start(table, CTRAJ_NW, A, net->hid, n, acts_bits, crr_fwd_lds, (hipStream_t)s);
     NLBAC_CHECK_LAUNCH(who);
     return 0;
@@ -129,10 +166,11 @@ template <typename Launch>
 static int ctraj_bwd(const ConcatRrTable<Launch>& table, const char* who, float h, const float* hs, const float* hs_host,
                      const nlbac_mlp* net, int n, int H, int n_stages, const float* beta, const float* c_out,
                      const float* acts, long acts_ls, int acts_bits, const float* norm, const float* dout, float* dx0,
-                     float* dc, float* dK, float* dz, nlbac_stream_t s) {
+                     float* dc, float* dK, float* dz, nlbac_stream_t s, const NlbacSubGridArgs* sg = nullptr) {
     constexpr bool grid = ctraj_on_grid<Launch>;
     if (ctraj_check(net, n, H, n_stages, beta, c_out, grid ? 1.f : h, acts_bits, who)) return -1;
     if (grid && nlbac_grid_steps_check(hs, hs_host, H, who)) return -1;
+    if (ctraj_on_subgrid<Launch> && nlbac_subgrid_check(sg, H, who)) return -1;
     Launch A;
     memset(&A, 0, sizeof(A));
     ConcatRkBwdLaunch& L = A.L;
@@ -150,6 +188,7 @@ static int ctraj_bwd(const ConcatRrTable<Launch>& table, const char* who, float 
     L.norm = norm;
     A.X.H = H; A.X.dout = dout; A.X.dx0 = dx0;
     if constexpr (grid) A.hs = hs;
+    if constexpr (ctraj_on_subgrid<Launch>) { A.sub.ofs = sg->ofs; A.sub.theta = sg->theta; }
     crr_start(table, CTRAJ_NW, A, net->hid, n, acts_bits, crr_bwd_lds, (hipStream_t)s);
     NLBAC_CHECK_LAUNCH(who);
     return 0;
@@ -192,4 +231,31 @@ extern "C" int nlbac_concat_rk_grid_bwd(const nlbac_mlp* net, int n, int H, int 
     static const ConcatRrTable<ConcatRkGridBwdLaunch> table = CONCAT_RR_TABLE(concat_grid_bwd_kernel, CTRAJ_NW);
     return ctraj_bwd(table, "nlbac_concat_rk_grid_bwd", 0.f, hs, hs_host, net, n, H, n_stages, beta, c_out, acts, acts_ls,
                      acts_bits, norm, dout, dx0, dc, dK, dz, s);
+}
+
+// ---- the same grid under step_size: H = N fine intervals with steps hs / hs_host [N]; the T - 1 output points 1 .. T-1
+//      are read off them — interval i holds the outputs ofs[i] <= j < ofs[i+1], weights theta [T-1] (device arrays for
+//      the kernel, ofs_host / theta_host beside them for the checks here, nlbac_subgrid_check).  out [T-1][n][n_s],
+//      dout [T][n][n_s]; Xin / acts / dK / dz per fine stage, [N * n_stages][n][..]
+extern "C" int nlbac_concat_rk_subgrid_fwd(const nlbac_mlp* net, const float* x0, const float* c, int n, int H,
+                                           int n_stages, const float* beta, const float* c_out, const float* hs,
+                                           const float* hs_host, const int* ofs, const int* ofs_host, const float* theta,
+                                           const float* theta_host, int T, float* out, float* Xin, float* acts,
+                                           long acts_ls, int acts_bits, const float* norm, nlbac_stream_t s) {
+    static const ConcatRrTable<ConcatRkSubgridFwdLaunch> table = CONCAT_RR_TABLE(concat_subgrid_fwd_kernel, CTRAJ_NW);
+    const NlbacSubGridArgs sg = {ofs, ofs_host, theta, theta_host, T};
+    return ctraj_fwd(table, "nlbac_concat_rk_subgrid_fwd", 0.f, hs, hs_host, net, x0, c, n, H, n_stages, beta, c_out, out,
+                     Xin, acts, acts_ls, acts_bits, norm, s, &sg);
+}
+
+extern "C" int nlbac_concat_rk_subgrid_bwd(const nlbac_mlp* net, int n, int H, int n_stages, const float* beta,
+                                           const float* c_out, const float* hs, const float* hs_host, const int* ofs,
+                                           const int* ofs_host, const float* theta, const float* theta_host, int T,
+                                           const float* acts, long acts_ls, int acts_bits, const float* norm,
+                                           const float* dout, float* dx0, float* dc, float* dK, float* dz,
+                                           nlbac_stream_t s) {
+    static const ConcatRrTable<ConcatRkSubgridBwdLaunch> table = CONCAT_RR_TABLE(concat_subgrid_bwd_kernel, CTRAJ_NW);
+    const NlbacSubGridArgs sg = {ofs, ofs_host, theta, theta_host, T};
+    return ctraj_bwd(table, "nlbac_concat_rk_subgrid_bwd", 0.f, hs, hs_host, net, n, H, n_stages, beta, c_out, acts,
+                     acts_ls, acts_bits, norm, dout, dx0, dc, dK, dz, s, &sg);
 }

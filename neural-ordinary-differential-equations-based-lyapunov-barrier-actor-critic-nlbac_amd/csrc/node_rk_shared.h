@@ -684,6 +684,11 @@ __device__ __forceinline__ void rk_bwd_outputs(const NodeRkBwdLaunch& L, const R
 // by the body at the top of interval k) and ONE set of actions u [n][n_u] for all of them; the backward sums the
 // intervals' du in the tile's LDS (sDYup, which only the interpolant's backward uses otherwise), k = H-1 .. 0:
 //     total = du_{H-1};  total = total + du_k  —  the fp32 adds the chained path does between its launches
+// SUB (with GRID; nlbac_node_rk_subgrid_*: a time grid under step_size): the intervals are the N fine intervals and the
+// outputs are the T - 1 points read off them (NlbacSubGrid, common.h): the forward writes out[j-1] for the outputs j of
+// interval k in place of the interval's state; the backward forms interval k's d from sum_j theta_j dout[j] and adds
+// sum_j (1 - theta_j) dout[j] to the dy0 it hands to interval k-1 (resp. to dx0).  With every weight 1 these are the
+// GRID kernels' fp32 operations on the fine grid with zero dout at the unused points.
 // ---------------------------------------------------------------------------------------------------------------
 struct NodeRkTrajBwd {
     int H;
@@ -695,8 +700,9 @@ struct NodeRkTrajBwd {
 // forward, behind interval k's last stage: out[k] = y0 + h sum_j c_j K_j (rk_fwd_outputs_and_control's arithmetic) to
 // global and, as interval k+1's y0, to sY0; interval k+1's actions to sU.  One (row, component) per thread; ends with a
 // barrier (every thread must call it).
-template <int NTHR, bool GRID = false>
-__device__ __forceinline__ void rk_traj_advance(const NodeRkLaunch& L, const RkFwdTile& T, int row0, int k, int H, int tid) {
+template <int NTHR, bool GRID = false, bool SUB = false>
+__device__ __forceinline__ void rk_traj_advance(const NodeRkLaunch& L, const RkFwdTile& T, int row0, int k, int H, int tid,
+                                                const NlbacSubGrid* sub = nullptr) {
     static_assert(NTHR >= NLBAC_MLP_TILE * RK_MAX_NS, "one (row, component) per thread");
     const int n = L.n, ns = L.n_s, nu = L.n_u;
     const bool more = !GRID && k + 1 < H;      // (GRID: the actions in sU are every interval's)
@@ -712,7 +718,14 @@ __device__ __forceinline__ void rk_traj_advance(const NodeRkLaunch& L, const RkF
             float a = T.sY0[m * RK_MAX_NS + r];
             for (int j = 0; j < L.n_out; ++j)
                 if (L.c_out[j] != 0.f) a = a + T.sK[(j * NLBAC_MLP_TILE + m) * RK_MAX_NS + r] * (L.c_out[j] * h);
-            L.out[(long)k * n * ns + (long)row * ns + r] = a;
+            if constexpr (SUB) {      // (before sY0 is overwritten: the thread holds the old state and the new one)
+                const float y_old = T.sY0[m * RK_MAX_NS + r];
+                const int j1 = sub->ofs[k + 1];
+                for (int j = sub->ofs[k]; j < j1; ++j)
+                    L.out[(long)(j - 1) * n * ns + (long)row * ns + r] = nlbac_sub_point(y_old, a, sub->theta[j - 1]);
+            } else {
+                L.out[(long)k * n * ns + (long)row * ns + r] = a;
+            }
             T.sY0[m * RK_MAX_NS + r] = a;
         }
     }
@@ -726,9 +739,10 @@ __device__ __forceinline__ void rk_traj_advance(const NodeRkLaunch& L, const RkF
 // backward, before interval k's stages (kk = H-1-k intervals done): u_k -> sU, du = 0, and from
 // d = dout[k+1] (+ the dy0 of interval k+1, in sDY0 when kk > 0): dy0 = 0 + d, dK_j = 0 + (c_j h) d — what
 // nlbac_rk_stage_bwd leaves for the one-step backward (same arithmetic).  No barrier inside.
-template <int NTHR, bool GRID = false>
+template <int NTHR, bool GRID = false, bool SUB = false>
 __device__ __forceinline__ void rk_traj_bwd_begin(const NodeRkBwdLaunch& L, const NodeRkTrajBwd& X, const RkBwdTile& T,
-                                                  int row0, int k, int kk, int tid, const float* hs = nullptr) {
+                                                  int row0, int k, int kk, int tid, const float* hs = nullptr,
+                                                  const NlbacSubGrid* sub = nullptr) {
     static_assert(NTHR >= NLBAC_MLP_TILE * RK_MAX_NS, "one (row, component) per thread");
     const int n = L.n, ns = L.n_s, nu = L.n_u;
     float vu = 0.f, vd = 0.f;
@@ -739,7 +753,8 @@ __device__ __forceinline__ void rk_traj_bwd_begin(const NodeRkBwdLaunch& L, cons
     }
     if (tid < NLBAC_MLP_TILE * RK_MAX_NS) {
         const int m = tid >> 3, c = tid & 7;
-        vd = X.dout[(long)(k + 1) * n * ns + (long)min(row0 + m, n - 1) * ns + min(c, ns - 1)];
+        if constexpr (SUB) vd = nlbac_sub_gather<true>(*sub, X.dout, (long)n * ns, (long)min(row0 + m, n - 1) * ns + min(c, ns - 1), k, 0.f);
+        else vd = X.dout[(long)(k + 1) * n * ns + (long)min(row0 + m, n - 1) * ns + min(c, ns - 1)];
     }
     if (tid < NLBAC_MLP_TILE * RK_MAX_NU) {
         const int m = tid >> 2, c = tid & 3;
@@ -752,7 +767,11 @@ __device__ __forceinline__ void rk_traj_bwd_begin(const NodeRkBwdLaunch& L, cons
         const int m = tid >> 3, c = tid & 7;
         const bool ok = row0 + m < n && c < ns;
         float d = vd;
-        if (kk > 0) d = d + T.sDY0[tid];
+        if constexpr (SUB) {      // interval k+1's outputs' share of its initial state joins its dy0 here, by the thread that holds it
+            if (kk > 0) d = d + nlbac_sub_gather<false>(*sub, X.dout, (long)n * ns, (long)min(row0 + m, n - 1) * ns + min(c, ns - 1), k + 1, T.sDY0[tid]);
+        } else {
+            if (kk > 0) d = d + T.sDY0[tid];
+        }
         T.sDY0[tid] = ok ? 0.f + d : 0.f;
         for (int j = 0; j < RK_MAX_STAGES; ++j) {
             float v = 0.f;
@@ -764,9 +783,10 @@ __device__ __forceinline__ void rk_traj_bwd_begin(const NodeRkBwdLaunch& L, cons
 
 // backward, behind interval k's stages: du_k (and dK when the weight gradients want it) to global; the dy0 stays in sDY0
 // for interval k-1, after interval 0 dx0 = dout[0] + dy0.  No barrier inside.
-template <int NTHR, bool GRID = false>
+template <int NTHR, bool GRID = false, bool SUB = false>
 __device__ __forceinline__ void rk_traj_bwd_end(const NodeRkBwdLaunch& L, const NodeRkTrajBwd& X, const RkBwdWhere& w,
-                                                const RkBwdTile& T, int row0, int k, int tid) {
+                                                const RkBwdTile& T, int row0, int k, int tid,
+                                                const NlbacSubGrid* sub = nullptr) {
     const int n = L.n, ns = L.n_s, nu = L.n_u;
     if (w.gdK)
         for (int idx = tid; idx < L.st_hi * NLBAC_MLP_TILE * ns; idx += NTHR) {
@@ -788,6 +808,12 @@ __device__ __forceinline__ void rk_traj_bwd_end(const NodeRkBwdLaunch& L, const 
     if (k == 0)
         for (int idx = tid; idx < NLBAC_MLP_TILE * ns; idx += NTHR) {
             const int m = idx / ns, c = idx - m * ns, row = row0 + m;
-            if (row < n) X.dx0[(long)row * ns + c] = X.dout[(long)row * ns + c] + T.sDY0[m * RK_MAX_NS + c];
+            if constexpr (SUB) {      // interval 0's outputs' share of the initial state joins its dy0 first
+                if (row < n)
+                    X.dx0[(long)row * ns + c] = X.dout[(long)row * ns + c] +
+                        nlbac_sub_gather<false>(*sub, X.dout, (long)n * ns, (long)row * ns + c, 0, T.sDY0[m * RK_MAX_NS + c]);
+            } else {
+                if (row < n) X.dx0[(long)row * ns + c] = X.dout[(long)row * ns + c] + T.sDY0[m * RK_MAX_NS + c];
+            }
         }
 }

@@ -62,9 +62,13 @@ __device__ long long g_bwd_stamps[2 * 256];      // (defined in the one translat
 // stage index k S + st of H S stages, and out[k] = L.out + k n n_s.  TRAJ = false, H = 1: the one-step kernel.
 // GRID (with TRAJ; nlbac_node_rk_grid_fwd): interval k's step size is hs[k] (device array), put into sH at the top of
 // the interval, and the actions L.u [n][n_u] are the same for every interval (node_rk_shared.h).
-template <int NB, int R, int BITS, int SPLIT, bool TRAJ = false, bool GRID = false>
-__device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 1, const float* hs = nullptr) {
+// SUB (with GRID; nlbac_node_rk_subgrid_fwd): the intervals are the fine intervals of a time grid under step_size; L.out
+// takes the output points read off them (node_rk_shared.h).
+template <int NB, int R, int BITS, int SPLIT, bool TRAJ = false, bool GRID = false, bool SUB = false>
+__device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 1, const float* hs = nullptr,
+                                                 const NlbacSubGrid* sub = nullptr) {
     static_assert(TRAJ || !GRID, "a time grid is a trajectory");
+    static_assert(GRID || !SUB, "sub-steps are a time grid's");
     static_assert(BITS != 2 || SPLIT == 0, "rows + words: the fit's forward is the unsplit one (same sums as mode 0)");
     constexpr bool WORDS = BITS != 0, ROWS = BITS != 1;
     using S = RRShape<NB, R>;
@@ -491,7 +495,7 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
         __syncthreads();
         RSTAMP(sb + 7)
     }
-    if constexpr (TRAJ) rk_traj_advance<256, GRID>(L, T, row0, k, H, tid);
+    if constexpr (TRAJ) rk_traj_advance<256, GRID, SUB>(L, T, row0, k, H, tid, sub);
     }
     if constexpr (TRAJ) return;
 #ifdef RR_TIMING
@@ -515,10 +519,13 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
 // interval 0.  TRAJ = false (X null): the one-step kernel.
 // GRID (with TRAJ; nlbac_node_rk_grid_bwd): step size hs[k] per interval, one set of actions L.u [n][n_u], and L.du
 // [n][n_u] the sum of the intervals' du, formed in the tile's LDS in the order k = H-1 .. 0 (node_rk_shared.h).
-template <int NB, int R, int BITS, int SPLIT, bool TRAJ = false, bool GRID = false>
+// SUB (with GRID; nlbac_node_rk_subgrid_bwd): X.dout [T][n][n_s] belongs to the output points, injected between the fine
+// intervals (node_rk_shared.h).
+template <int NB, int R, int BITS, int SPLIT, bool TRAJ = false, bool GRID = false, bool SUB = false>
 __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const NodeRkTrajBwd* X = nullptr,
-                                                 const float* hs = nullptr) {
+                                                 const float* hs = nullptr, const NlbacSubGrid* sub = nullptr) {
     static_assert(TRAJ || !GRID, "a time grid is a trajectory");
+    static_assert(GRID || !SUB, "sub-steps are a time grid's");
     constexpr bool WORDS = BITS != 0;          // the gates come from the mask words (1, 2) or from the activation rows (0)
     constexpr bool DZ = BITS != 1;             // dz rows are stored when asked for (0; 2: the fit, words behind the rows)
     using S = RRShape<NB, R>;
@@ -629,7 +636,7 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
         w.gG = L.G + (long)kS * n * gout;
         w.gdG = L.dG ? L.dG + (long)kS * n * gout : nullptr;
         w.gdK = L.dK ? L.dK + (long)kS * n * ns : nullptr;
-        rk_traj_bwd_begin<256, GRID>(L, *X, T, row0, k, kk, tid, hs);
+        rk_traj_bwd_begin<256, GRID, SUB>(L, *X, T, row0, k, kk, tid, hs, sub);
         __syncthreads();
     }
 #pragma unroll
@@ -918,7 +925,7 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
     __syncthreads();
     BWSTAMP(2 + 8 * 7)
     if constexpr (TRAJ) {
-        rk_traj_bwd_end<256, GRID>(L, *X, w, T, row0, k, tid);
+        rk_traj_bwd_end<256, GRID, SUB>(L, *X, w, T, row0, k, tid, sub);
         __syncthreads();
     }
     }

@@ -15,6 +15,11 @@
 // nlbac_node_rk_grid_*: the solution on a whole time grid, torchdiffeq's fixed-grid rule (one RK step per grid
 // interval): the same kernels with a step size per interval and one set of actions for all of them (GRID in
 // node_rr_body.h), the actions' gradient summed over the intervals inside the launch.
+//
+// nlbac_node_rk_subgrid_*: the same grid under step_size — the launch's intervals are the N fine intervals, its outputs
+// the T - 1 points read off them by linear interpolation (SUB in node_rr_body.h, NlbacSubGrid in common.h); the backward
+// takes the output points' gradients in between the fine intervals.  K / Y / G, mask words and activation rows per fine
+// stage, as the grid kernels keep them per interval.
 #undef RR_TIMING          // (the ablation stamps belong to the one-step kernels)
 #include "node_rr_body.h"
 
@@ -39,6 +44,30 @@ struct NodeRkGridBwdLaunch {
     NodeRkTrajBwd X;
     const float* hs;
 };
+
+struct NodeRkSubgridFwdLaunch {
+    NodeRkLaunch L;
+    int H;                            // the N fine intervals
+    const float* hs;
+    NlbacSubGrid sub;
+};
+
+struct NodeRkSubgridBwdLaunch {
+    NodeRkBwdLaunch L;
+    NodeRkTrajBwd X;
+    const float* hs;
+    NlbacSubGrid sub;
+};
+
+template <int NB, int R, int BITS, int SPLIT>
+__global__ __launch_bounds__(256) void node_subgrid_fwd_kernel(const NodeRkSubgridFwdLaunch A) {
+    node_rr_fwd_body<NB, R, BITS, SPLIT, true, true, true>(A.L, A.H, A.hs, &A.sub);
+}
+
+template <int NB, int R, int BITS, int SPLIT>
+__global__ __launch_bounds__(256) void node_subgrid_bwd_kernel(const NodeRkSubgridBwdLaunch A) {
+    node_rr_bwd_body<NB, R, BITS, SPLIT, true, true, true>(A.L, &A.X, A.hs, &A.sub);
+}
 
 template <int NB, int R, int BITS, int SPLIT>
 __global__ __launch_bounds__(256) void node_grid_fwd_kernel(const NodeRkGridFwdLaunch A) {
@@ -75,22 +104,29 @@ static int traj_check(const nlbac_mlp* f, const nlbac_mlp* g, int n, int H, int 
     return 0;
 }
 
+// a sub-stepped time-grid launch carries the output points' offsets and weights as well
+template <typename Launch>
+constexpr bool traj_on_subgrid = std::is_same<Launch, NodeRkSubgridFwdLaunch>::value || std::is_same<Launch, NodeRkSubgridBwdLaunch>::value;
+
 // a time-grid launch carries a step size per interval
 template <typename Launch>
-constexpr bool traj_on_grid = std::is_same<Launch, NodeRkGridFwdLaunch>::value || std::is_same<Launch, NodeRkGridBwdLaunch>::value;
+constexpr bool traj_on_grid = std::is_same<Launch, NodeRkGridFwdLaunch>::value ||
+                              std::is_same<Launch, NodeRkGridBwdLaunch>::value || traj_on_subgrid<Launch>;
 
 // The forward launch of `who` (an entry point below) over H intervals: the instances of its kernel template in `table`
 // (chosen as the one-step launcher chooses, node_rr_body.h, so that the sums are the same), its step — h for every
 // interval, or (time grid) hs [H] on the device for the kernel with hs_host [H] beside it for the checks here — and
-// what the interval's one-step launch takes.
+// what the interval's one-step launch takes.  (Sub-stepped time grid) sg: the output points; out is [T-1][n][n_s].
 template <typename Launch>
 static int traj_fwd(const NodeRrTable<Launch>& table, const char* who, float h, const float* hs, const float* hs_host,
                     const nlbac_mlp* f, const nlbac_mlp* g, const float* x0, const float* u, int n, int H, int n_stages,
                     const float* beta, const float* c_out, float* out, float* K, float* Y, float* G, float* acts_f,
-                    long acts_f_ls, float* acts_g, long acts_g_ls, int acts_bits, nlbac_stream_t s) {
+                    long acts_f_ls, float* acts_g, long acts_g_ls, int acts_bits, nlbac_stream_t s,
+                    const NlbacSubGridArgs* sg = nullptr) {
     constexpr bool grid = traj_on_grid<Launch>;
     if (traj_check(f, g, n, H, n_stages, beta, c_out, grid ? 1.f : h, acts_bits, who)) return -1;
     if (grid && nlbac_grid_steps_check(hs, hs_host, H, who)) return -1;
+    if (traj_on_subgrid<Launch> && nlbac_subgrid_check(sg, H, who)) return -1;
     Launch A;
     memset(&A, 0, sizeof(A));
     NodeRkLaunch& L = A.L;
@@ -115,6 +151,7 @@ static int traj_fwd(const NodeRrTable<Launch>& table, const char* who, float h, 
         NLBAC_REQUIRE(L.stage_begin == 0, "%s: a time-grid launch starts every interval at stage 0", who);
         A.hs = hs;
     }
+    if constexpr (traj_on_subgrid<Launch>) { A.sub.ofs = sg->ofs; A.sub.theta = sg->theta; }
     node_rr_fwd_start(table, A, f->hid, n, acts_bits, (hipStream_t)s);
     NLBAC_CHECK_LAUNCH(who);
     return 0;
@@ -126,10 +163,11 @@ static int traj_bwd(const NodeRrTable<Launch>& table, const char* who, float h, 
                     const nlbac_mlp* f, const nlbac_mlp* g, const float* u, int n, int H, int n_stages, const float* beta,
                     const float* c_out, const float* G, const float* acts_f, long acts_f_ls, const float* acts_g,
                     long acts_g_ls, int acts_bits, const float* dout, float* dx0, float* du, float* dK, float* dG,
-                    float* dz_f, float* dz_g, nlbac_stream_t s) {
+                    float* dz_f, float* dz_g, nlbac_stream_t s, const NlbacSubGridArgs* sg = nullptr) {
     constexpr bool grid = traj_on_grid<Launch>;
     if (traj_check(f, g, n, H, n_stages, beta, c_out, grid ? 1.f : h, acts_bits, who)) return -1;
     if (grid && nlbac_grid_steps_check(hs, hs_host, H, who)) return -1;
+    if (traj_on_subgrid<Launch> && nlbac_subgrid_check(sg, H, who)) return -1;
     Launch A;
     memset(&A, 0, sizeof(A));
     NodeRkBwdLaunch& L = A.L;
@@ -149,6 +187,7 @@ static int traj_bwd(const NodeRrTable<Launch>& table, const char* who, float h, 
     L.h_val[0] = grid ? hs_host[H - 1] : h;
     A.X.H = H; A.X.dout = dout; A.X.dx0 = dx0;
     if constexpr (grid) A.hs = hs;
+    if constexpr (traj_on_subgrid<Launch>) { A.sub.ofs = sg->ofs; A.sub.theta = sg->theta; }
     node_rr_bwd_start(table, A, f->hid, n, acts_bits, (hipStream_t)s);
     NLBAC_CHECK_LAUNCH(who);
     return 0;
@@ -193,4 +232,33 @@ extern "C" int nlbac_node_rk_grid_bwd(const nlbac_mlp* f, const nlbac_mlp* g, co
     static const NodeRrTable<NodeRkGridBwdLaunch> table = NODE_RR_BWD_TABLE(node_grid_bwd_kernel);
     return traj_bwd(table, "nlbac_node_rk_grid_bwd", 0.f, hs, hs_host, f, g, u, n, H, n_stages, beta, c_out, G, acts_f,
                     acts_f_ls, acts_g, acts_g_ls, acts_bits, dout, dx0, du, dK, dG, dz_f, dz_g, s);
+}
+
+// ---- the same grid under step_size: H = N fine intervals with steps hs / hs_host [N]; the T - 1 output points 1 .. T-1
+//      are read off them — interval i holds the outputs ofs[i] <= j < ofs[i+1], weights theta [T-1] (device arrays for
+//      the kernel, ofs_host / theta_host beside them for the checks here, nlbac_subgrid_check).  out [T-1][n][n_s],
+//      dout [T][n][n_s]; K / Y / G / acts / dK / dG / dz per fine stage, [N * n_stages][n][..]
+extern "C" int nlbac_node_rk_subgrid_fwd(const nlbac_mlp* f, const nlbac_mlp* g, const float* x0, const float* u, int n,
+                                         int H, int n_stages, const float* beta, const float* c_out, const float* hs,
+                                         const float* hs_host, const int* ofs, const int* ofs_host, const float* theta,
+                                         const float* theta_host, int T, float* out, float* K, float* Y, float* G,
+                                         float* acts_f, long acts_f_ls, float* acts_g, long acts_g_ls, int acts_bits,
+                                         nlbac_stream_t s) {
+    static const NodeRrTable<NodeRkSubgridFwdLaunch> table = NODE_RR_FWD_TABLE(node_subgrid_fwd_kernel);
+    const NlbacSubGridArgs sg = {ofs, ofs_host, theta, theta_host, T};
+    return traj_fwd(table, "nlbac_node_rk_subgrid_fwd", 0.f, hs, hs_host, f, g, x0, u, n, H, n_stages, beta, c_out, out,
+                    K, Y, G, acts_f, acts_f_ls, acts_g, acts_g_ls, acts_bits, s, &sg);
+}
+
+extern "C" int nlbac_node_rk_subgrid_bwd(const nlbac_mlp* f, const nlbac_mlp* g, const float* u, int n, int H,
+                                         int n_stages, const float* beta, const float* c_out, const float* hs,
+                                         const float* hs_host, const int* ofs, const int* ofs_host, const float* theta,
+                                         const float* theta_host, int T, const float* G, const float* acts_f,
+                                         long acts_f_ls, const float* acts_g, long acts_g_ls, int acts_bits,
+                                         const float* dout, float* dx0, float* du, float* dK, float* dG, float* dz_f,
+                                         float* dz_g, nlbac_stream_t s) {
+    static const NodeRrTable<NodeRkSubgridBwdLaunch> table = NODE_RR_BWD_TABLE(node_subgrid_bwd_kernel);
+    const NlbacSubGridArgs sg = {ofs, ofs_host, theta, theta_host, T};
+    return traj_bwd(table, "nlbac_node_rk_subgrid_bwd", 0.f, hs, hs_host, f, g, u, n, H, n_stages, beta, c_out, G,
+                    acts_f, acts_f_ls, acts_g, acts_g_ls, acts_bits, dout, dx0, du, dK, dG, dz_f, dz_g, s, &sg);
 }

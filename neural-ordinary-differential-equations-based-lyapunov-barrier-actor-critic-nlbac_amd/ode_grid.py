@@ -1,15 +1,21 @@
 """``odeint_grid``: the solution of this build's NODE models at every point of a time grid, euler / rk4 —
-``torchdiffeq.odeint(func, y0, t)`` for ``len(t) >= 2`` under the fixed-grid rule without ``step_size``: one RK step per
-grid interval.  (``odeint`` itself serves exactly two time points, the only call the reference makes.)
+``torchdiffeq.odeint(func, y0, t)`` for ``len(t) >= 2`` under the fixed-grid rule: one RK step per grid interval, or
+(``step_size=s``, torchdiffeq's ``options=dict(step_size=s)``) steps of ``s`` on a fine grid of the solver's own from
+which the output points are read off by linear interpolation (``_sub_grid`` is the rule).  (``odeint`` itself serves
+exactly two time points, the only call the reference makes.)
 
 Two paths, same results, as in ``rollout``:
   * one launch (either NODE form at its register-resident kernels' shapes): the whole grid is one
     ``nlbac_node_rk_grid_fwd`` / ``nlbac_concat_rk_grid_fwd`` launch, its backward one ``nlbac_node_rk_grid_bwd`` /
     ``nlbac_concat_rk_grid_bwd`` launch (+ the weight-gradient launch over all H * stages * rows when parameter
     gradients are wanted).  They are the trajectory kernels of ``rollout`` with a step size per interval and one set of
-    carried columns for all intervals, whose gradient is summed over the intervals inside the launch;
+    carried columns for all intervals, whose gradient is summed over the intervals inside the launch; with
+    ``step_size`` the ``*_subgrid_*`` twins of the four: the same kernels over the N fine intervals, which write the
+    T - 1 interpolated output points instead of every interval's state and take the output gradients in between the
+    intervals of the one backward launch;
   * chained (nets wider than 128, shapes the register-resident kernels refuse): H one-interval solves on the existing
-    solvers, one solver per interval when a backward follows, cached on the model under a key of their own.
+    solvers, one solver per interval when a backward follows, cached on the model under a key of their own (with
+    ``step_size``: per fine interval, the interpolation and its gradient as torch ops, ``ode_traj.SubGridSteps``).
 ``rollout.ONE_LAUNCH = False`` (env ``NLBAC_ROLLOUT_ONE_LAUNCH=0``) runs the chained path everywhere: the A/B baseline.
 """
 import ctypes as C
@@ -19,6 +25,7 @@ import torch
 
 from . import ode_traj as T
 from . import rollout
+from .ode_consts import TABLEAU
 
 METHODS = ("euler", "rk4")
 
@@ -45,8 +52,58 @@ def _steps_of(t):
     return tuple(hs)
 
 
-def _steps(func, y0, t, method):
-    """Every argument check, before anything touches a device; returns the intervals' step sizes (``_steps_of``)."""
+def _check_step_size(step_size):
+    if isinstance(step_size, bool) or not isinstance(step_size, (int, float)):
+        raise TypeError("odeint_grid: step_size must be a Python number; got %s" % type(step_size).__name__)
+    if not math.isfinite(step_size) or step_size <= 0:
+        raise ValueError("odeint_grid: step_size must be positive and finite; got %r" % (step_size,))
+    return float(step_size)
+
+
+def _sub_grid(t, step_size):
+    """torchdiffeq 0.2.3's fixed-grid rule under ``options=dict(step_size=s)``, in Python floats (no device): the fine
+    grid of ``_grid_constructor_from_step_size`` — ``niters = ceil((t[-1] - t[0]) / s + 1)`` points ``i s + t[0]``, the
+    last one replaced by ``t[-1]`` — and where ``integrate`` reads the output points off it.  Returns
+
+        taus   the N + 1 fine times (N = niters - 1 fine intervals),
+        hs     the N fine steps as float32 values, each formed as ``_steps_of`` forms its own,
+        ofs    N + 1 offsets, CSR over the outputs 1 .. T-1: interval i holds the outputs ofs[i] <= j < ofs[i+1]
+               (those with taus[i+1] >= t[j] that no earlier interval took),
+        theta  T - 1 weights, theta[j-1] of output j in its interval i: 1.0 when t[j] == taus[i+1], 0.0 when
+               t[j] == taus[i], else the float32 of (t[j] - taus[i]) / (taus[i+1] - taus[i]):
+               out[j] = y_i + theta (y_{i+1} - y_i), with y_{i+1} resp. y_i themselves at 1 resp. 0."""
+    s = _check_step_size(step_size)
+    _steps_of(t)                      # (the grid's own checks)
+    # (a tensor's entries as _steps_of takes them; a Python sequence's numbers as they are, not rounded to float32 first:
+    #  whether an output point IS a fine-grid point is decided on these values)
+    tt = t if isinstance(t, torch.Tensor) else torch.as_tensor(t, dtype=torch.float64)
+    times = [float(v) for v in tt.detach().cpu()]
+    span = (times[-1] - times[0]) / s + 1
+    if not math.isfinite(span) or span >= 2 ** 31:
+        raise ValueError("odeint_grid: step_size %r cuts [%r, %r] into 2^31 fine intervals or more" % (s, times[0], times[-1]))
+    niters = math.ceil(span)
+    taus = [i * s + times[0] for i in range(niters)]
+    taus[-1] = times[-1]
+    N = niters - 1
+    hs = [C.c_float(b - a).value for a, b in zip(taus, taus[1:])]
+    for i, h in enumerate(hs):
+        if not (math.isfinite(h) and h > 0.0):
+            raise ValueError("odeint_grid: fine interval %d of %d, [%r, %r], is not a positive finite float32 step (%r): "
+                             "rounding left a degenerate last interval; choose another step_size" % (i, N, taus[i], taus[i + 1], h))
+    ofs, theta, j = [1], [], 1
+    for i in range(N):
+        t0, t1 = taus[i], taus[i + 1]
+        while j < len(times) and t1 >= times[j]:
+            theta.append(1.0 if times[j] == t1 else (0.0 if times[j] == t0 else C.c_float((times[j] - t0) / (t1 - t0)).value))
+            j += 1
+        ofs.append(j)
+    assert j == len(times) and all(0.0 <= th <= 1.0 for th in theta)
+    return tuple(taus), tuple(hs), tuple(ofs), tuple(theta)
+
+
+def _steps(func, y0, t, method, step_size=None):
+    """Every argument check, before anything touches a device; returns the intervals: their step sizes (``_steps_of``),
+    or with ``step_size`` what ``_sub_grid`` returns."""
     from .sac_cbf_clf.model import NeuralODEModel
     if not isinstance(func, NeuralODEModel):
         raise TypeError("nlbac_amd.ode_grid.odeint_grid integrates this build's NeuralODEModel (its field runs as HIP "
@@ -58,7 +115,7 @@ def _steps(func, y0, t, method):
             "(ode_dopri.py) does not emit interior points yet.  Use method='euler' or 'rk4', or odeint per interval")
     if method not in METHODS:
         raise ValueError("odeint_grid: method is one of %s; got %r" % (", ".join(METHODS), method))
-    hs = _steps_of(t)
+    hs = _steps_of(t) if step_size is None else _sub_grid(t, step_size)
     if not isinstance(y0, torch.Tensor):
         raise TypeError("odeint_grid: y0 must be a tensor; got %s" % type(y0).__name__)
     if y0.dtype != torch.float32:
@@ -66,12 +123,15 @@ def _steps(func, y0, t, method):
     width = func.n_s + (func.n_u if func.affine else func.n_carry)
     if y0.dim() != 2 or y0.shape[1] != width or y0.shape[0] < 1:
         raise ValueError("odeint_grid: y0 must be (batch, %d) = [x | carried columns]; got %s" % (width, tuple(y0.shape)))
+    if step_size is not None and len(hs[1]) * len(TABLEAU[method]["c_sol"]) * y0.shape[0] >= 2 ** 31:
+        raise ValueError("odeint_grid: %d fine intervals x %d stages x %d rows is 2^31 or more (the launch's limit); "
+                         "use a larger step_size or fewer rows" % (len(hs[1]), len(TABLEAU[method]["c_sol"]), y0.shape[0]))
     if y0.device.type != "cuda":
         raise ValueError("odeint_grid: y0 must be on a CUDA device; got %s" % y0.device)
     return hs
 
 
-def odeint_grid(func, y0, t, *, method="rk4"):
+def odeint_grid(func, y0, t, *, method="rk4", step_size=None):
     """The solution of the NODE ``func`` (either form; a model owned by an agent included) at every point of the time
     grid ``t`` (1-D tensor or sequence, T >= 2 finite strictly increasing times): returns ``out`` (T, B, n_s + n_c) with
     ``out[0] = y0`` and
@@ -83,15 +143,25 @@ def odeint_grid(func, y0, t, *, method="rk4"):
     ``[x | carried columns]`` as ``odeint`` takes it; the carried columns (the action, or SimulatedCars' [u | t]) are
     the same over all intervals and are copied through to every ``out[k]``.
 
-    ``'dopri5'`` raises ``NotImplementedError``: on a grid it is one adaptive solve interpolated at the interior points,
-    which the step driver does not offer yet; it is not approximated by restarting at every grid point.
+    ``step_size=s`` (a positive finite Python number; torchdiffeq's ``options=dict(step_size=s)``): the solver steps on
+    a fine grid of its own instead — ``t[0] + i s``, ending at ``t[-1]`` (``_sub_grid``) — so that the accuracy does not
+    depend on where the outputs are wanted; each fine state is the one-step ``odeint`` result over its fine interval bit
+    for bit, and ``out[j]`` is read off the fine interval [tau_i, tau_i+1] that holds ``t[j]``: the fine state itself
+    where ``t[j]`` is a fine-grid point, else ``y_i + theta_j (y_i+1 - y_i)`` in float32, ``theta_j`` the float32 of
+    ``(t[j] - tau_i) / (tau_i+1 - tau_i)``.
+
+    ``'dopri5'`` raises ``NotImplementedError`` (with or without ``step_size``): on a grid it is one adaptive solve
+    interpolated at the interior points, which the step driver does not offer yet; it is not approximated by restarting
+    at every grid point.
 
     Differentiable w.r.t. ``y0`` (state and carried columns) and ``func.parameters()`` through one autograd node for the
     whole grid; ``t`` is a constant (no gradient w.r.t. the times).  The weight copies are refreshed first, as in
     ``odeint``.  What is kept for the backward follows what needs a gradient, as in ``rollout``: nothing under
     ``torch.no_grad``, ReLU mask words for input gradients only, activation rows as well for parameter gradients
-    (memory grows linearly with T; see ``rollout`` on the last bits of the values under input gradients only)."""
-    hs = _steps(func, y0, t, method)
+    (memory grows linearly with the number of steps — T - 1, or with ``step_size`` the N fine intervals, not T: the fine
+    states themselves and their gradients are never stored; see ``rollout`` on the last bits of the values under input
+    gradients only)."""
+    hs = _steps(func, y0, t, method, step_size)
     params = tuple(func.parameters())
     mode = T.keep_mode(params, y0)
     func.refresh_device_weights()
@@ -101,13 +171,16 @@ def odeint_grid(func, y0, t, *, method="rk4"):
 class _GridFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, func, method, hs, mode, y0, *params):
-        H, n, ns = len(hs), y0.shape[0], func.n_s
+        n, ns = y0.shape[0], func.n_s
         y0 = y0.detach().contiguous()
         x0, c = y0[:, :ns].contiguous(), y0[:, ns:].contiguous()
         dev = y0.device
-        xs = torch.empty(H, n, ns, dtype=torch.float32, device=dev)        # the states behind each interval
-        ctx.func, ctx.mode, ctx.n_params = func, mode, len(params)
-        ctx.kept = T.solve(func, T.GridSteps(hs, dev), method, mode, rollout._one_launch_ok(func, method), x0, c, xs)
+        # (hs: the intervals' steps, or with step_size _sub_grid's (fine times, steps, offsets, weights))
+        iv = T.SubGridSteps(*hs[1:], dev) if isinstance(hs[0], tuple) else T.GridSteps(hs, dev)
+        H = iv.n_out
+        xs = torch.empty(H, n, ns, dtype=torch.float32, device=dev)        # the states at the output points 1 .. H
+        ctx.func, ctx.mode, ctx.n_params, ctx.iv = func, mode, len(params), iv
+        ctx.kept = T.solve(func, iv, method, mode, rollout._one_launch_ok(func, method), x0, c, xs)
         out = torch.empty(H + 1, n, y0.shape[1], dtype=torch.float32, device=dev)
         out[0].copy_(y0)
         out[1:, :, :ns].copy_(xs)
@@ -124,7 +197,7 @@ class _GridFunction(torch.autograd.Function):
         gy0 = None
         if ctx.needs_input_grad[4]:
             # d/d carried columns: out[0]'s share, then per interval its control gradient (summed k = H-1 .. 0 by the
-            # backward) and out[k+1]'s share
-            gy0 = torch.cat([dx0, dout[0][:, ns:] + (dc + dout[1:, :, ns:].sum(0))], dim=1)
+            # backward) and every later output point's share
+            gy0 = torch.cat([dx0, dout[0][:, ns:] + (dc + ctx.iv.sum_copied(dout[1:, :, ns:]))], dim=1)
         gp = T.param_grads(ctx.func, flat) if need_p else [None] * ctx.n_params
         return (None, None, None, None, gy0, *gp)

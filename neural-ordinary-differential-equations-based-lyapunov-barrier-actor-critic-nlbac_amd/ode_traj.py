@@ -1,8 +1,9 @@
 """What ``rollout`` and ``ode_grid.odeint_grid`` share: a NODE solved over H intervals as one autograd node.
 
   * the intervals (``EqualSteps``: one ``dt`` and a control per interval, ``rollout``; ``GridSteps``: a step per
-    interval and one set of controls, ``odeint_grid``): the entry points' infix, their step arguments, what the controls'
-    gradient looks like;
+    interval and one set of controls, ``odeint_grid``; ``SubGridSteps``: the fine intervals of ``odeint_grid`` under
+    ``step_size``, whose output points are interpolated): the entry points' infix, their step arguments, what the
+    controls' gradient looks like, where the outputs and their gradients meet the intervals;
   * what a solve keeps and how its backward becomes gradients, one class per path — ``AffineTraj`` / ``ConcatTraj`` (one
     launch forward, one backward, + the weight-gradient launch over all H * stages * rows) and ``Chain`` (H one-interval
     solves on the existing solvers) — each with ``forward(x0, u, xs)`` and ``backward(dout, need_p)``; ``solve`` picks.
@@ -27,7 +28,27 @@ def keep_mode(params, *inputs):
     return "inputs" if any(t.requires_grad for t in inputs) else "none"
 
 
-class EqualSteps:
+class _OutputPerInterval:
+    """Output k + 1 is the state behind interval k (the chained path's hooks; the one-launch kernels do the same)."""
+
+    @property
+    def n_out(self):
+        return self.H
+
+    def emit(self, xs, k, x_old, x_new):      # interval k's result into the outputs; returns the next interval's state
+        return xs[k].copy_(x_new)
+
+    def grad_in(self, dout, k, carry):        # dL/dx_{k+1} = dout[k+1] + what interval k+1 sends back
+        return dout[k + 1] if carry is None else (dout[k + 1] + carry)
+
+    def grad_carry(self, dout, k, dy0):       # what interval k sends back to interval k-1
+        return dy0.clone()
+
+    def sum_copied(self, d):                  # d (n_out, n, n_c): the gradients of the columns copied to every output
+        return d.sum(0)
+
+
+class EqualSteps(_OutputPerInterval):
     """H intervals of ``dt`` with a control per interval: controls (H, n, n_c), their gradient stacked per interval."""
     api, infix, solvers_key = "rollout", "traj", "_rollout_solvers"
 
@@ -57,7 +78,7 @@ class EqualSteps:
         return max(1, arena.n_slabs // n_steps)
 
 
-class GridSteps:
+class GridSteps(_OutputPerInterval):
     """The intervals of a time grid, steps ``hs``, with one set of controls (n, n_c) for all of them, whose gradient is
     summed over the intervals."""
     api, infix, solvers_key = "odeint_grid", "grid", "_odeint_grid_solvers"
@@ -84,6 +105,60 @@ class GridSteps:
 
     def slabs(self, arena, sv):
         return arena.n_slabs
+
+
+class SubGridSteps(GridSteps):
+    """The N fine intervals of a time grid solved under ``step_size`` (``ode_grid._sub_grid``): steps ``hs``, and the
+    T - 1 output points 1 .. T-1 read off them — interval i holds the outputs ofs[i] <= j < ofs[i+1], output j is
+    y_i + theta[j-1] (y_{i+1} - y_i), the fine state itself at theta 1 / 0.  The one-launch kernels
+    (``nlbac_*_rk_subgrid_*``) take ``ofs`` / ``theta`` beside the steps; the chained path interpolates, and injects the
+    output gradients between the fine intervals, with the torch ops below — in the kernels' order."""
+    infix, solvers_key = "subgrid", "_odeint_subgrid_solvers"
+
+    def __init__(self, hs, ofs, theta, device):
+        GridSteps.__init__(self, hs, device)
+        self.ofs, self.theta = ofs, theta
+
+    @property
+    def n_out(self):
+        return len(self.theta)
+
+    def step_args(self):
+        if self.arrays is None:      # steps, offsets and weights twice each: device for the kernels, host for the launcher
+            dev = lambda v, dt: torch.tensor(v, dtype=dt, device=self.device)
+            self.arrays = (dev(self.hs, torch.float32), fptr(*self.hs), dev(self.ofs, torch.int32),
+                           (C.c_int * len(self.ofs))(*self.ofs), dev(self.theta, torch.float32), fptr(*self.theta))
+        a = self.arrays
+        return (a[0].data_ptr(), a[1], a[2].data_ptr(), a[3], a[4].data_ptr(), a[5], len(self.theta) + 1)
+
+    def emit(self, xs, k, x_old, x_new):
+        x_new = x_new.clone()
+        for j in range(self.ofs[k], self.ofs[k + 1]):
+            th = self.theta[j - 1]
+            xs[j - 1].copy_(x_new if th == 1.0 else (x_old if th == 0.0 else x_old + th * (x_new - x_old)))
+        return x_new
+
+    def grad_in(self, dout, k, carry):        # sum_j theta_j dout[j] (j ascending), then what interval k+1 sends back
+        d = torch.zeros_like(dout[0])
+        for j in range(self.ofs[k], self.ofs[k + 1]):
+            d = d + self.theta[j - 1] * dout[j]
+        return d if carry is None else d + carry
+
+    def grad_carry(self, dout, k, dy0):       # the outputs' share of the interval's own initial state
+        dy0 = dy0.clone()
+        for j in range(self.ofs[k], self.ofs[k + 1]):
+            if self.theta[j - 1] < 1.0:
+                dy0 = dy0 + C.c_float(1.0 - self.theta[j - 1]).value * dout[j]
+        return dy0
+
+    def sum_copied(self, d):
+        # per fine interval first (j ascending), then over the fine intervals as GridSteps sums over its intervals: with
+        # every weight 1 the bits of the solve on the fine grid itself with zero gradients at the unused points
+        per = torch.zeros(self.H, *d.shape[1:], dtype=d.dtype, device=d.device)
+        for k in range(self.H):
+            for j in range(self.ofs[k], self.ofs[k + 1]):
+                per[k] += d[j - 1]
+        return per.sum(0)
 
 
 def _tableau(method):
@@ -256,7 +331,7 @@ class Chain:
         iv, x = self.iv, x0
         for k in range(iv.H):
             sv = self.svs[k if self.mode != "none" else 0]
-            x = xs[k].copy_(sv.forward(x, iv.control(u, k), 1, self.n, self.method, iv.step(k), *self.tol))
+            x = iv.emit(xs, k, x, sv.forward(x, iv.control(u, k), 1, self.n, self.method, iv.step(k), *self.tol))
         self.solve_ids = [sv.stats["solves"] for sv in self.svs]
 
     def backward(self, dout, need_p):
@@ -267,10 +342,10 @@ class Chain:
         carry, du_all, flat = None, None, None
         for k in range(iv.H - 1, -1, -1):            # dL/dx_{k+1} = dout[k+1] + what interval k+1 sends back
             sv = svs[k]
-            gk = dout[k + 1] if carry is None else (dout[k + 1] + carry)
+            gk = iv.grad_in(dout, k, carry)
             du, dy0 = sv.backward(gk.contiguous(), need_du=True, need_params=need_p, need_dy0=True)
             du_all = iv.add_du(du_all, k, du)
-            carry = dy0.clone()
+            carry = iv.grad_carry(dout, k, dy0)
             if need_p:
                 fk = _reduce(arena, sv.accumulate_param_grads(arena, iv.slabs(arena, sv)))
                 flat = fk if flat is None else flat + fk
@@ -278,9 +353,10 @@ class Chain:
 
 
 def solve(func, iv, method, mode, one_launch, x0, u, xs, atol=1e-7, rtol=1e-5):
-    """Solve the intervals ``iv`` from ``x0`` (n, n_s) under the controls ``u`` into ``xs`` (H, n, n_s), in one launch
-    (``one_launch``: the caller asked ``traj_class(func).ok``) or chained.  Returns what ``mode`` keeps: an object whose
-    ``backward(dout (H + 1, n, n_s), need_p)`` gives (dx0, the controls' gradient, the flat parameter gradient or None),
+    """Solve the intervals ``iv`` from ``x0`` (n, n_s) under the controls ``u`` into ``xs`` (iv.n_out, n, n_s) — H, one
+    output per interval, unless the intervals say otherwise — in one launch (``one_launch``: the caller asked
+    ``traj_class(func).ok``) or chained.  Returns what ``mode`` keeps: an object whose
+    ``backward(dout (iv.n_out + 1, n, n_s), need_p)`` gives (dx0, the controls' gradient, the flat parameter gradient or None),
     or None without gradients."""
     n = x0.shape[0]
     kept = traj_class(func)(func, n, iv, method, mode, x0.device) if one_launch else Chain(func, n, iv, method, mode, atol, rtol)

@@ -675,8 +675,25 @@ class _OdeintFunction(torch.autograd.Function):
 
 
 def _odeint(func, y0, t, method, atol, rtol, adjoint, options):
+    # the one option served: options=dict(step_size=s) under euler / rk4 (ode_grid.odeint_grid's step_size)
+    sub = options.pop("options", None)
     if options:
         raise TypeError("odeint: unsupported options %s" % sorted(options))
+    if sub is not None:
+        if not isinstance(sub, dict) or set(sub) - {"step_size"}:
+            raise TypeError("odeint: unsupported options %s" % (sorted(sub, key=str) if isinstance(sub, dict) else type(sub).__name__))
+        if sub.get("step_size") is not None:
+            if adjoint:
+                raise NotImplementedError("odeint_adjoint: step_size is not offered (the adjoint solve steps once over "
+                                          "[t0, t1]); use odeint")
+            if method == "dopri5":
+                raise ValueError("odeint: step_size goes with method='euler' or 'rk4'; torchdiffeq's dopri5 ignores it, "
+                                 "which this build does not do silently")
+            if torch.as_tensor(t).numel() > 2:
+                raise NotImplementedError("odeint: the reference only ever integrates over t = [0, dt]; got %d time "
+                                          "points (ode_grid.odeint_grid takes a longer grid)" % torch.as_tensor(t).numel())
+            from .ode_grid import odeint_grid
+            return odeint_grid(func, y0, t, method=method, step_size=sub["step_size"])
     from .sac_cbf_clf.model import NeuralODEModel
     if not isinstance(func, NeuralODEModel):
         raise TypeError("nlbac_amd.odeint integrates this build's NeuralODEModel (its field runs as HIP kernels); "
@@ -693,7 +710,9 @@ def _odeint(func, y0, t, method, atol, rtol, adjoint, options):
 def odeint(func, y0, t, *, method="dopri5", atol=1e-7, rtol=1e-5, **options):
     """``torchdiffeq.odeint`` for this build's NODE models on ``t = [t0, t1]``: returns ``stack([y0, y(t1)])`` with the
     carried control columns passed through, differentiable w.r.t. ``y0`` and ``func.parameters()``.  ``method`` is
-    ``'euler'`` / ``'rk4'`` (one step over the interval, torchdiffeq's fixed-grid semantics) or ``'dopri5'``.
+    ``'euler'`` / ``'rk4'`` (one step over the interval, torchdiffeq's fixed-grid semantics; with
+    ``options=dict(step_size=s)`` steps of ``s``, the last one cut at ``t1``: ``ode_grid.odeint_grid``'s ``step_size``)
+    or ``'dopri5'`` (which refuses ``step_size``; no other option is served).
     The packed MFMA copies of the weights are refreshed first, so a ``torch.optim`` step on ``func.parameters()``
     between calls is picked up.  For several intervals ahead with a new control each, differentiated as a whole, use
     ``nlbac_amd.rollout.rollout``; for the solution at every point of a longer time grid (euler / rk4), use

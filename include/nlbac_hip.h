@@ -688,6 +688,38 @@ int nlbac_concat_rk_subgrid_bwd(const nlbac_mlp *net, int n, int H, int n_stages
                                 const float *theta, const float *theta_host, int T, const float *acts, long acts_ls,
                                 int acts_bits, const float *norm, const float *dout, float *dx0, float *dc, float *dK,
                                 float *dz, nlbac_stream_t s);
+/* A rollout under a step size (rollout(..., step_size=s); declarations added under ABI 17, no existing signature or
+ * struct changes): H control intervals, each solved in m fine steps hs / hs_host [m] (device array / host copy, as in
+ * the _grid_ functions; the same schedule in every control interval) with its control held: the launch walks the
+ * N = H m fine intervals i = k m + r, control u[k] resp. c[k] and step hs[r].  u [H][n][n_u] resp. c [H][n][n_c];
+ * out [H][n][n_s], the states behind each CONTROL interval (written behind r = m-1 only); dout [H+1][n][n_s];
+ * du [H][n][n_u] resp. dc [H][n][n_c].  Everything kept per stage (K / Y / G, Xin, acts, dK / dG / dz) is per FINE
+ * stage: [H * m * n_stages][n][..], and the weight-gradient launch runs over all H * m * n_stages * n rows.  Backward,
+ * i = N-1 .. 0: at r = m-1 d = dout[k+1] + the dy0 carried from fine interval i+1 (none at i = N-1), at every other r
+ * d = 0 + the carried dy0 (the _subgrid_ kernels' fine interval without an output); after i = 0 dx0 = dout[0] + dy0.
+ * du / dc is summed inside a control interval by the tile that owns the rows, total = du_{m-1}; total = total + du_r for
+ * r = m-2 .. 0 (the _grid_ order), afresh in every control interval, and written at r = 0.  Per control interval these
+ * are the fp32 operations of the _subgrid_ functions for t = [0, dt], between control intervals those of the _traj_
+ * functions; with m = 1 and hs[0] = h the _traj_ functions' results.  The launcher refuses, without launching: H < 1,
+ * m < 1, a step that is not positive and finite, H * m * n_stages * n >= 2^31, and what the _traj_ functions refuse
+ * (nlbac_*_rk_traj_ok decides).  No barrier is added to the grid kernels. */
+int nlbac_node_rk_hold_fwd(const nlbac_mlp *f, const nlbac_mlp *g, const float *x0, const float *u, int n, int H,
+                           int n_stages, const float *beta, const float *c_out, const float *hs, const float *hs_host,
+                           int m, float *out, float *K, float *Y, float *G, float *acts_f, long acts_f_ls,
+                           float *acts_g, long acts_g_ls, int acts_bits, nlbac_stream_t s);
+int nlbac_node_rk_hold_bwd(const nlbac_mlp *f, const nlbac_mlp *g, const float *u, int n, int H, int n_stages,
+                           const float *beta, const float *c_out, const float *hs, const float *hs_host, int m,
+                           const float *G, const float *acts_f, long acts_f_ls, const float *acts_g, long acts_g_ls,
+                           int acts_bits, const float *dout, float *dx0, float *du, float *dK, float *dG, float *dz_f,
+                           float *dz_g, nlbac_stream_t s);
+int nlbac_concat_rk_hold_fwd(const nlbac_mlp *net, const float *x0, const float *c, int n, int H, int n_stages,
+                             const float *beta, const float *c_out, const float *hs, const float *hs_host, int m,
+                             float *out, float *Xin, float *acts, long acts_ls, int acts_bits, const float *norm,
+                             nlbac_stream_t s);
+int nlbac_concat_rk_hold_bwd(const nlbac_mlp *net, int n, int H, int n_stages, const float *beta, const float *c_out,
+                             const float *hs, const float *hs_host, int m, const float *acts, long acts_ls,
+                             int acts_bits, const float *norm, const float *dout, float *dx0, float *dc, float *dK,
+                             float *dz, nlbac_stream_t s);
 /* The same one-launch RK step for the single-net NODE dx/dt = net([x | c]) with carried inputs c = (u, t)
  * (SimulatedCars, C/sac_cbf_clf/model.py:179-205; odeint call sites C/sac_cbf_clf/sac_cbf_clf.py:437,458,581,603,
  * C/model.py:245): n_s = net->out_dim state columns, n_c = net->in_dim - n_s carried columns (c: (rows, n_c)),

@@ -230,6 +230,15 @@ _PROTOS = {
                                     _P, c_float_p, _I, _P, _P, _P, _L, _I, _P, _P],
     "nlbac_concat_rk_subgrid_bwd": [C.POINTER(Mlp), _I, _I, _I, c_float_p, c_float_p, _P, c_float_p, _P, c_int_p, _P,
                                     c_float_p, _I, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P],
+    # (the grid entry points with m behind hs_host)
+    "nlbac_node_rk_hold_fwd": [C.POINTER(Mlp), C.POINTER(Mlp), _P, _P, _I, _I, _I, c_float_p, c_float_p, _P, c_float_p, _I,
+                               _P, _P, _P, _P, _P, _L, _P, _L, _I, _P],
+    "nlbac_node_rk_hold_bwd": [C.POINTER(Mlp), C.POINTER(Mlp), _P, _I, _I, _I, c_float_p, c_float_p, _P, c_float_p, _I, _P,
+                               _P, _L, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "nlbac_concat_rk_hold_fwd": [C.POINTER(Mlp), _P, _P, _I, _I, _I, c_float_p, c_float_p, _P, c_float_p, _I, _P, _P, _P,
+                                 _L, _I, _P, _P],
+    "nlbac_concat_rk_hold_bwd": [C.POINTER(Mlp), _I, _I, _I, c_float_p, c_float_p, _P, c_float_p, _I, _P, _L, _I, _P, _P,
+                                 _P, _P, _P, _P, _P],
     "nlbac_concat_rk_fwd": [C.POINTER(Mlp), _P, _P, _I, _I, _I, _I, _I, c_float_p, c_float_p, _I, c_float_p, _I, c_float_p,
                             _P, _I, _P, _P, _P, _L, _I, _P, _P, _P, _P, C.POINTER(RkChain), _P],
     "nlbac_concat_rk_mask_words": [C.POINTER(Mlp)],

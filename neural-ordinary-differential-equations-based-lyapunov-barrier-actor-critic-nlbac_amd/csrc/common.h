@@ -37,6 +37,22 @@ static inline int nlbac_grid_steps_check(const float* hs, const float* hs_host, 
     return 0;
 }
 
+// A held-control launch (nlbac_node_rk_hold_* / nlbac_concat_rk_hold_*: rollout under step_size): H control intervals of
+// m fine steps each, steps hs [m] the same in every control interval.  Its N = H m fine intervals are the launch's
+// intervals; fine interval i = k m + r runs under control k with step hs[r].  *N on success.
+static inline int nlbac_hold_intervals(int H, int m, int n_stages, int n, const char* who, int* N) {
+    NLBAC_REQUIRE(H >= 1 && m >= 1, "%s: at least one control interval and one fine step each", who);
+    NLBAC_REQUIRE(n >= 1 && n_stages >= 1, "%s: bad rows / stage count", who);
+    long v = (long)H * m;             // (each product of two values below 2^31: no overflow on the way)
+    NLBAC_REQUIRE(v < (1L << 31), "%s: bad rows / intervals", who);
+    v *= n_stages;
+    NLBAC_REQUIRE(v < (1L << 31), "%s: bad rows / intervals", who);
+    v *= n;
+    NLBAC_REQUIRE(v < (1L << 31), "%s: bad rows / intervals", who);
+    *N = H * m;
+    return 0;
+}
+
 // The output points of a sub-stepped time-grid launch (nlbac_node_rk_subgrid_* / nlbac_concat_rk_subgrid_*): the N fine
 // intervals are the launch's intervals, and the T - 1 outputs 1 .. T-1 are read off them — interval i holds the outputs
 // ofs[i] <= j < ofs[i+1] (CSR), output j is y_i + theta[j-1] (y_{i+1} - y_i), the fine state itself at theta 1 / 0.

@@ -41,11 +41,16 @@ __device__ __forceinline__ float crr_step_output(const ConcatRkLaunch& L, const 
 // SUB (with GRID; nlbac_concat_rk_subgrid_fwd: a time grid under step_size): the intervals are the N fine intervals, and
 // L.out takes the T - 1 output points read off them (NlbacSubGrid, common.h): out[j-1] for the outputs j of interval k,
 // written by the lane that holds the old state and the new one, before sY0 is overwritten.
-template <int NB, int R, int BITS, int NW, bool TRAJ = false, bool GRID = false, bool SUB = false>
+// HOLD (with GRID, not SUB; nlbac_concat_rk_hold_fwd: a rollout under step_size): H = N fine intervals, hm of them per
+// control interval, i = k hm + r: the step size is hs[r], the carried columns L.c + k n n_c are held in sC through the
+// control interval and replaced behind r = hm-1 (TRAJ's hand-over, every hm-th fine interval), and L.out + k n n_s is
+// written there only.
+template <int NB, int R, int BITS, int NW, bool TRAJ = false, bool GRID = false, bool SUB = false, bool HOLD = false>
 __device__ __forceinline__ void concat_rr_fwd_body(const ConcatRkLaunch& L, const int H = 1, const float* hs = nullptr,
-                                                   const NlbacSubGrid* sub = nullptr) {
+                                                   const NlbacSubGrid* sub = nullptr, const int hm = 1) {
     static_assert(TRAJ || !GRID, "a time grid is a trajectory");
     static_assert(GRID || !SUB, "sub-steps are a time grid's");
+    static_assert((GRID && !SUB) || !HOLD, "a held control's fine steps are a time grid's, its outputs their end points");
     constexpr int TILE = 16 * NW, NTHR = 64 * NW;
     (void)NTHR;
     using S = RRShape<NB, R>;
@@ -217,11 +222,19 @@ __device__ __forceinline__ void concat_rr_fwd_body(const ConcatRkLaunch& L, cons
     // behind the previous interval's store burst — not between two fragment loads of a layer (vmcnt is in order); they
     // reach sC behind the interval's last stage
     float cnext = 0.f;
+    const int kc = HOLD ? k / hm : k;                    // (HOLD) the control interval; `last`: behind its last fine step
+    const bool last = !HOLD || k - kc * hm == hm - 1;
     if constexpr (TRAJ && !GRID) {
         const int mm = 16 * half + (lane >> 2), c = lane & 3, row = row0 + mm;
         cnext = L.c[(long)min(k + 1, H - 1) * n * nc + (long)min(row, n - 1) * nc + min(c, max(nc - 1, 0))];
     }
-    if constexpr (GRID) { if (lane < 16) sH[16 * half + lane] = hs[k]; }      // (the wave's own rows: no barrier)
+    if constexpr (HOLD) {
+        if (last) {      // (uniform)
+            const int mm = 16 * half + (lane >> 2), c = lane & 3, row = row0 + mm;
+            cnext = L.c[(long)(min(k + 1, H - 1) / hm) * n * nc + (long)min(row, n - 1) * nc + min(c, max(nc - 1, 0))];
+        }
+    }
+    if constexpr (GRID) { if (lane < 16) sH[16 * half + lane] = hs[HOLD ? k - kc * hm : k]; }      // (the wave's own rows: no barrier)
     const long kS = TRAJ ? (long)k * L.S_total : 0;      // interval k's first stage in the [k][stage][row] layout
     for (int st = L.stage_begin; st < stage_end; ++st) {
         const int sb = 2 + 8 * (st - L.stage_begin);
@@ -398,13 +411,19 @@ __device__ __forceinline__ void concat_rr_fwd_body(const ConcatRkLaunch& L, cons
                 for (int j = sub->ofs[k]; j < j1; ++j)
                     L.out[(long)(j - 1) * n * ns + (long)row * ns + r] = nlbac_sub_point(y_old, a, sub->theta[j - 1]);
             } else {
-                L.out[(long)k * n * ns + (long)row * ns + r] = a;
+                if (last) L.out[(long)kc * n * ns + (long)row * ns + r] = a;
             }
             sY0[mm * CK_LD + r] = a;
         }
         if constexpr (!GRID) {
             const int mm = 16 * half + (lane >> 2), c = lane & 3;
             sC[mm * CK_NC + c] = (row0 + mm < n && c < nc) ? cnext : 0.f;
+        }
+        if constexpr (HOLD) {
+            if (last) {
+                const int mm = 16 * half + (lane >> 2), c = lane & 3;
+                sC[mm * CK_NC + c] = (row0 + mm < n && c < nc) ? cnext : 0.f;
+            }
         }
     }
     }
@@ -551,11 +570,17 @@ struct ConcatRkTrajBwd {
 // sum_j theta_j dout[j] over its outputs (j ascending; + the dy0 of interval k+1), and sum_j (1 - theta_j) dout[j] joins
 // the interval's dy0 before it is handed to interval k-1 resp. enters dx0 — by the lane that holds the entry.  With every
 // weight 1: the GRID kernel's fp32 operations on the fine grid with zero dout at the unused points.
-template <int NB, int R, int BITS, int NW, bool TRAJ = false, bool GRID = false, bool SUB = false>
+// HOLD (with GRID, not SUB; nlbac_concat_rk_hold_bwd): X->H = N fine intervals, hm per control interval, i = k hm + r;
+// X->dout [N/hm + 1][n][n_s] and L.dc [N/hm][n][n_c] belong to the control intervals: d takes dout[k+1] at r = hm-1 and 0
+// elsewhere (SUB's fine interval without an output), dc is summed inside a control interval in GRID's order
+// (total = dc_{hm-1}; total = total + dc_r, afresh in every control interval) and written at r = 0.
+template <int NB, int R, int BITS, int NW, bool TRAJ = false, bool GRID = false, bool SUB = false, bool HOLD = false>
 __device__ __forceinline__ void concat_rr_bwd_body(const ConcatRkBwdLaunch& L, const ConcatRkTrajBwd* X = nullptr,
-                                                   const float* hs = nullptr, const NlbacSubGrid* sub = nullptr) {
+                                                   const float* hs = nullptr, const NlbacSubGrid* sub = nullptr,
+                                                   const int hm = 1) {
     static_assert(TRAJ || !GRID, "a time grid is a trajectory");
     static_assert(GRID || !SUB, "sub-steps are a time grid's");
+    static_assert((GRID && !SUB) || !HOLD, "a held control's fine steps are a time grid's, its outputs their end points");
     constexpr int TILE = 16 * NW;
     using S = RRShape<NB, R>;
     constexpr int KS = S::KS, HID = S::HID, TB = NB - 2, NT = KS - 4 * TB;
@@ -755,8 +780,16 @@ __device__ __forceinline__ void concat_rr_bwd_body(const ConcatRkBwdLaunch& L, c
     for (int kk = 0; kk < H; ++kk) {
     const int k = H - 1 - kk, kS = TRAJ ? k * L.S_total : 0;      // interval k's first stage in the [k][stage][row] layout
     if constexpr (TRAJ) {       // d = dout[k+1] (+ interval k+1's dy0): dy0 = 0 + d, dK_j = 0 + (c_out[j] h) d; dc = 0
-        if constexpr (!SUB) request_dout(k + 1);
-        if constexpr (GRID) { if (lane < 16) sH[16 * half + lane] = hs[k]; }
+        const int kc = HOLD ? k / hm : k, kr = k - kc * hm;      // (HOLD) control interval and fine step inside it
+        (void)kr;
+        if constexpr (HOLD) {
+            if (kr == hm - 1) request_dout(kc + 1);      // (uniform)
+            else {
+#pragma unroll
+                for (int it = 0; it < NITD; ++it) dnext[it] = 0.f;
+            }
+        } else if constexpr (!SUB) request_dout(k + 1);
+        if constexpr (GRID) { if (lane < 16) sH[16 * half + lane] = hs[HOLD ? kr : k]; }
 #pragma unroll
         for (int it = 0; it < NITD; ++it) {
             const int idx = lane + 64 * it, mm = 16 * half + idx / CK_NS, c = idx % CK_NS;
@@ -927,7 +960,13 @@ __device__ __forceinline__ void concat_rr_bwd_body(const ConcatRkBwdLaunch& L, c
     if constexpr (TRAJ) {      // ---- interval k's gradient w.r.t. its carried columns, this wave's rows
         for (int idx = lane; idx < 16 * nc; idx += 64) {
             const int mm = 16 * half + idx / nc, c = idx % nc, row = row0 + mm;
-            if constexpr (GRID) {
+            if constexpr (HOLD) {       // (GRID's sum below, afresh in every control interval)
+                const int kc = k / hm, kr = k - kc * hm;
+                float a = sDC[mm * CK_NC + c];
+                if (kr != hm - 1) a = sDYup[mm * CK_NC + c] + a;
+                sDYup[mm * CK_NC + c] = a;
+                if (kr == 0 && row < n) L.dc[(long)kc * n * nc + (long)row * nc + c] = a;
+            } else if constexpr (GRID) {
                 float a = sDC[mm * CK_NC + c];
                 if (kk > 0) a = sDYup[mm * CK_NC + c] + a;
                 sDYup[mm * CK_NC + c] = a;

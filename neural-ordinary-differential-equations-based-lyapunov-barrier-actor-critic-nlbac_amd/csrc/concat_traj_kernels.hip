@@ -21,6 +21,10 @@
 // nlbac_concat_rk_subgrid_*: the same grid under step_size — the launch's intervals are the N fine intervals, its
 // outputs the T - 1 points read off them by linear interpolation (SUB in concat_rr_body.h, NlbacSubGrid in common.h); the
 // backward takes the output points' gradients in between the fine intervals.
+//
+// nlbac_concat_rk_hold_*: a rollout under step_size — H control intervals of m fine steps each, the carried columns held
+// through a control interval (HOLD in concat_rr_body.h): the grid kernels over the H m fine intervals with the step
+// schedule hs [m] repeated, the trajectory kernels' change of carried columns and outputs behind every m-th of them.
 #undef RR_TIMING          // (the ablation stamps belong to the one-step kernels)
 #include "concat_rr_body.h"
 
@@ -62,6 +66,32 @@ struct ConcatRkSubgridBwdLaunch {
     const float* hs;
     NlbacSubGrid sub;
 };
+
+struct ConcatRkHoldFwdLaunch {
+    ConcatRkLaunch L;
+    int H;                            // the N = (control intervals) * m fine intervals
+    const float* hs;                  // [m] the fine steps of a control interval (device)
+    int m;
+};
+
+struct ConcatRkHoldBwdLaunch {
+    ConcatRkBwdLaunch L;
+    ConcatRkTrajBwd X;                // (H: the N fine intervals; dout [N/m + 1][n][n_s])
+    const float* hs;
+    int m;
+};
+
+template <int NB, int R, int BITS, int NW>
+__global__ __launch_bounds__(64 * NW) void concat_hold_fwd_kernel(const ConcatRkHoldFwdLaunch A) {
+    concat_rr_fwd_body<NB, R, BITS, NW, true, true, false, true>(A.L, A.H, A.hs, nullptr, A.m);
+}
+
+// (waves per SIMD as concat_traj_bwd_kernel below)
+template <int NB, int R, int BITS, int NW>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((BITS == 1 && NB < 8) ? 3 : 2)))
+void concat_hold_bwd_kernel(const ConcatRkHoldBwdLaunch A) {
+    concat_rr_bwd_body<NB, R, BITS, NW, true, true, false, true>(A.L, &A.X, A.hs, nullptr, A.m);
+}
 
 template <int NB, int R, int BITS, int NW>
 __global__ __launch_bounds__(64 * NW) void concat_subgrid_fwd_kernel(const ConcatRkSubgridFwdLaunch A) {
@@ -119,23 +149,30 @@ static int ctraj_check(const nlbac_mlp* net, int n, int H, int n_stages, const f
 template <typename Launch>
 constexpr bool ctraj_on_subgrid = std::is_same<Launch, ConcatRkSubgridFwdLaunch>::value || std::is_same<Launch, ConcatRkSubgridBwdLaunch>::value;
 
+// a held-control launch carries the m fine steps of a control interval; its intervals are the fine ones
+template <typename Launch>
+constexpr bool ctraj_on_hold = std::is_same<Launch, ConcatRkHoldFwdLaunch>::value || std::is_same<Launch, ConcatRkHoldBwdLaunch>::value;
+
 // a time-grid launch carries a step size per interval
 template <typename Launch>
 constexpr bool ctraj_on_grid = std::is_same<Launch, ConcatRkGridFwdLaunch>::value ||
-                               std::is_same<Launch, ConcatRkGridBwdLaunch>::value || ctraj_on_subgrid<Launch>;
+                               std::is_same<Launch, ConcatRkGridBwdLaunch>::value || ctraj_on_subgrid<Launch> ||
+                               ctraj_on_hold<Launch>;
 
 // The forward launch of `who` (an entry point below) over H intervals: the instances of its kernel template in `table`
 // (chosen as the one-step launcher chooses, concat_rr_body.h, so that the sums are the same), its step — h for every
 // interval, or (time grid) hs [H] on the device for the kernel with hs_host [H] beside it for the checks here — and
 // what the interval's one-step launch takes.  (Sub-stepped time grid) sg: the output points; out is [T-1][n][n_s].
+// (Held controls) H: the fine intervals, a multiple of m (nlbac_hold_intervals); hs / hs_host [m]; out is [H/m][n][n_s].
 template <typename Launch>
 static int ctraj_fwd(const ConcatRrTable<Launch>& table, const char* who, float h, const float* hs, const float* hs_host,
                      const nlbac_mlp* net, const float* x0, const float* c, int n, int H, int n_stages, const float* beta,
                      const float* c_out, float* out, float* Xin, float* acts, long acts_ls, int acts_bits,
-                     const float* norm, nlbac_stream_t s, const NlbacSubGridArgs* sg = nullptr) {
+                     const float* norm, nlbac_stream_t s, const NlbacSubGridArgs* sg = nullptr, int m = 1) {
     constexpr bool grid = ctraj_on_grid<Launch>;
+    const int n_hs = ctraj_on_hold<Launch> ? m : H;      // the step sizes the launch carries
     if (ctraj_check(net, n, H, n_stages, beta, c_out, grid ? 1.f : h, acts_bits, who)) return -1;
-    if (grid && nlbac_grid_steps_check(hs, hs_host, H, who)) return -1;
+    if (grid && nlbac_grid_steps_check(hs, hs_host, n_hs, who)) return -1;
     if (ctraj_on_subgrid<Launch> && nlbac_subgrid_check(sg, H, who)) return -1;
     Launch A;
     memset(&A, 0, sizeof(A));
@@ -156,6 +193,7 @@ static int ctraj_fwd(const ConcatRrTable<Launch>& table, const char* who, float 
     A.H = H;
     if constexpr (grid) A.hs = hs;
     if constexpr (ctraj_on_subgrid<Launch>) { A.sub.ofs = sg->ofs; A.sub.theta = sg->theta; }
+    if constexpr (ctraj_on_hold<Launch>) A.m = m;
     crr_start(table, CTRAJ_NW, A, net->hid, n, acts_bits, crr_fwd_lds, (hipStream_t)s);
     NLBAC_CHECK_LAUNCH(who);
     return 0;
@@ -166,10 +204,11 @@ template <typename Launch>
 static int ctraj_bwd(const ConcatRrTable<Launch>& table, const char* who, float h, const float* hs, const float* hs_host,
                      const nlbac_mlp* net, int n, int H, int n_stages, const float* beta, const float* c_out,
                      const float* acts, long acts_ls, int acts_bits, const float* norm, const float* dout, float* dx0,
-                     float* dc, float* dK, float* dz, nlbac_stream_t s, const NlbacSubGridArgs* sg = nullptr) {
+                     float* dc, float* dK, float* dz, nlbac_stream_t s, const NlbacSubGridArgs* sg = nullptr, int m = 1) {
     constexpr bool grid = ctraj_on_grid<Launch>;
+    const int n_hs = ctraj_on_hold<Launch> ? m : H;
     if (ctraj_check(net, n, H, n_stages, beta, c_out, grid ? 1.f : h, acts_bits, who)) return -1;
-    if (grid && nlbac_grid_steps_check(hs, hs_host, H, who)) return -1;
+    if (grid && nlbac_grid_steps_check(hs, hs_host, n_hs, who)) return -1;
     if (ctraj_on_subgrid<Launch> && nlbac_subgrid_check(sg, H, who)) return -1;
     Launch A;
     memset(&A, 0, sizeof(A));
@@ -184,11 +223,12 @@ static int ctraj_bwd(const ConcatRrTable<Launch>& table, const char* who, float 
     L.n = n; L.rpp = n; L.n_s = net->out_dim; L.n_c = net->in_dim - net->out_dim;
     L.S_total = n_stages; L.st_lo = 0; L.st_hi = n_stages; L.dx_stage0 = 1;
     nlbac_tableau_copy(L.beta, A.X.c_out, A.X.n_out, n_stages, beta, c_out);
-    L.h_val[0] = grid ? hs_host[H - 1] : h;
+    L.h_val[0] = grid ? hs_host[n_hs - 1] : h;
     L.norm = norm;
     A.X.H = H; A.X.dout = dout; A.X.dx0 = dx0;
     if constexpr (grid) A.hs = hs;
     if constexpr (ctraj_on_subgrid<Launch>) { A.sub.ofs = sg->ofs; A.sub.theta = sg->theta; }
+    if constexpr (ctraj_on_hold<Launch>) A.m = m;
     crr_start(table, CTRAJ_NW, A, net->hid, n, acts_bits, crr_bwd_lds, (hipStream_t)s);
     NLBAC_CHECK_LAUNCH(who);
     return 0;
@@ -258,4 +298,31 @@ extern "C" int nlbac_concat_rk_subgrid_bwd(const nlbac_mlp* net, int n, int H, i
     const NlbacSubGridArgs sg = {ofs, ofs_host, theta, theta_host, T};
     return ctraj_bwd(table, "nlbac_concat_rk_subgrid_bwd", 0.f, hs, hs_host, net, n, H, n_stages, beta, c_out, acts,
                      acts_ls, acts_bits, norm, dout, dx0, dc, dK, dz, s, &sg);
+}
+
+// ---- a rollout under step_size: H control intervals of m fine steps each, steps hs / hs_host [m] (the same schedule in
+//      every control interval; device array for the kernel, host copy for the checks here), the carried columns
+//      c [H][n][n_c] held through their control interval.  out [H][n][n_s], dout [H+1][n][n_s], dc [H][n][n_c]; Xin /
+//      acts / dK / dz per fine stage, [H * m * n_stages][n][..]
+extern "C" int nlbac_concat_rk_hold_fwd(const nlbac_mlp* net, const float* x0, const float* c, int n, int H, int n_stages,
+                                        const float* beta, const float* c_out, const float* hs, const float* hs_host,
+                                        int m, float* out, float* Xin, float* acts, long acts_ls, int acts_bits,
+                                        const float* norm, nlbac_stream_t s) {
+    static const ConcatRrTable<ConcatRkHoldFwdLaunch> table = CONCAT_RR_TABLE(concat_hold_fwd_kernel, CTRAJ_NW);
+    int N = 0;
+    if (nlbac_hold_intervals(H, m, n_stages, n, "nlbac_concat_rk_hold_fwd", &N)) return -1;
+    return ctraj_fwd(table, "nlbac_concat_rk_hold_fwd", 0.f, hs, hs_host, net, x0, c, n, N, n_stages, beta, c_out, out,
+                     Xin, acts, acts_ls, acts_bits, norm, s, nullptr, m);
+}
+
+extern "C" int nlbac_concat_rk_hold_bwd(const nlbac_mlp* net, int n, int H, int n_stages, const float* beta,
+                                        const float* c_out, const float* hs, const float* hs_host, int m,
+                                        const float* acts, long acts_ls, int acts_bits, const float* norm,
+                                        const float* dout, float* dx0, float* dc, float* dK, float* dz,
+                                        nlbac_stream_t s) {
+    static const ConcatRrTable<ConcatRkHoldBwdLaunch> table = CONCAT_RR_TABLE(concat_hold_bwd_kernel, CTRAJ_NW);
+    int N = 0;
+    if (nlbac_hold_intervals(H, m, n_stages, n, "nlbac_concat_rk_hold_bwd", &N)) return -1;
+    return ctraj_bwd(table, "nlbac_concat_rk_hold_bwd", 0.f, hs, hs_host, net, n, N, n_stages, beta, c_out, acts,
+                     acts_ls, acts_bits, norm, dout, dx0, dc, dK, dz, s, nullptr, m);
 }

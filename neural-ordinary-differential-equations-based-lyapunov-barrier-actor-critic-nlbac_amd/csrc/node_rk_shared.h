@@ -689,6 +689,11 @@ __device__ __forceinline__ void rk_bwd_outputs(const NodeRkBwdLaunch& L, const R
 // interval k in place of the interval's state; the backward forms interval k's d from sum_j theta_j dout[j] and adds
 // sum_j (1 - theta_j) dout[j] to the dy0 it hands to interval k-1 (resp. to dx0).  With every weight 1 these are the
 // GRID kernels' fp32 operations on the fine grid with zero dout at the unused points.
+// HOLD (with GRID, not SUB; nlbac_node_rk_hold_*: a rollout under step_size): the intervals are N = H m fine intervals,
+// i = k m + r: control interval k's actions u[k] held over its m fine steps hs[r] (the same schedule in every control
+// interval).  The forward replaces the actions in sU behind r = m-1 and writes out[k] there only; the backward takes
+// dout[k+1] at r = m-1 (d = 0 + the carried dy0 elsewhere, SUB's fine interval without an output), sums du inside a
+// control interval as GRID sums it over its grid (total = du_{m-1}; total = total + du_r) and writes du[k] at r = 0.
 // ---------------------------------------------------------------------------------------------------------------
 struct NodeRkTrajBwd {
     int H;
@@ -700,16 +705,19 @@ struct NodeRkTrajBwd {
 // forward, behind interval k's last stage: out[k] = y0 + h sum_j c_j K_j (rk_fwd_outputs_and_control's arithmetic) to
 // global and, as interval k+1's y0, to sY0; interval k+1's actions to sU.  One (row, component) per thread; ends with a
 // barrier (every thread must call it).
-template <int NTHR, bool GRID = false, bool SUB = false>
+template <int NTHR, bool GRID = false, bool SUB = false, bool HOLD = false>
 __device__ __forceinline__ void rk_traj_advance(const NodeRkLaunch& L, const RkFwdTile& T, int row0, int k, int H, int tid,
-                                                const NlbacSubGrid* sub = nullptr) {
+                                                const NlbacSubGrid* sub = nullptr, int hm = 1) {
     static_assert(NTHR >= NLBAC_MLP_TILE * RK_MAX_NS, "one (row, component) per thread");
     const int n = L.n, ns = L.n_s, nu = L.n_u;
-    const bool more = !GRID && k + 1 < H;      // (GRID: the actions in sU are every interval's)
+    const int kc = HOLD ? k / hm : k;          // (HOLD) the control interval, whose last fine step this is or is not
+    const bool last = !HOLD || k - kc * hm == hm - 1;
+    // (GRID: the actions in sU are every interval's; HOLD: the control interval's, replaced behind its last fine step)
+    const bool more = (HOLD ? last : !GRID) && k + 1 < H;
     float vu = 0.f;
     if (more && tid < NLBAC_MLP_TILE * RK_MAX_NU) {
         const int m = tid >> 2, c = tid & 3;
-        vu = L.u[(long)(k + 1) * n * nu + (long)min(row0 + m, n - 1) * nu + min(c, nu - 1)];
+        vu = L.u[(long)(kc + 1) * n * nu + (long)min(row0 + m, n - 1) * nu + min(c, nu - 1)];
     }
     if (tid < NLBAC_MLP_TILE * RK_MAX_NS) {
         const int m = tid >> 3, r = tid & 7, row = row0 + m;
@@ -724,7 +732,7 @@ __device__ __forceinline__ void rk_traj_advance(const NodeRkLaunch& L, const RkF
                 for (int j = sub->ofs[k]; j < j1; ++j)
                     L.out[(long)(j - 1) * n * ns + (long)row * ns + r] = nlbac_sub_point(y_old, a, sub->theta[j - 1]);
             } else {
-                L.out[(long)k * n * ns + (long)row * ns + r] = a;
+                if (last) L.out[(long)kc * n * ns + (long)row * ns + r] = a;
             }
             T.sY0[m * RK_MAX_NS + r] = a;
         }
@@ -739,22 +747,24 @@ __device__ __forceinline__ void rk_traj_advance(const NodeRkLaunch& L, const RkF
 // backward, before interval k's stages (kk = H-1-k intervals done): u_k -> sU, du = 0, and from
 // d = dout[k+1] (+ the dy0 of interval k+1, in sDY0 when kk > 0): dy0 = 0 + d, dK_j = 0 + (c_j h) d — what
 // nlbac_rk_stage_bwd leaves for the one-step backward (same arithmetic).  No barrier inside.
-template <int NTHR, bool GRID = false, bool SUB = false>
+template <int NTHR, bool GRID = false, bool SUB = false, bool HOLD = false>
 __device__ __forceinline__ void rk_traj_bwd_begin(const NodeRkBwdLaunch& L, const NodeRkTrajBwd& X, const RkBwdTile& T,
                                                   int row0, int k, int kk, int tid, const float* hs = nullptr,
-                                                  const NlbacSubGrid* sub = nullptr) {
+                                                  const NlbacSubGrid* sub = nullptr, int hm = 1) {
     static_assert(NTHR >= NLBAC_MLP_TILE * RK_MAX_NS, "one (row, component) per thread");
     const int n = L.n, ns = L.n_s, nu = L.n_u;
     float vu = 0.f, vd = 0.f;
-    const float vh = GRID ? hs[k] : L.h_val[0];          // (one problem: one step size for every row)
+    const int kc = HOLD ? k / hm : k, kr = k - kc * hm;  // (HOLD) control interval and fine step inside it
+    const float vh = GRID ? hs[HOLD ? kr : k] : L.h_val[0];          // (one problem: one step size for every row)
     if (tid < NLBAC_MLP_TILE * RK_MAX_NU) {
         const int m = tid >> 2, c = tid & 3;
-        vu = L.u[(long)(GRID ? 0 : k) * n * nu + (long)min(row0 + m, n - 1) * nu + min(c, nu - 1)];
+        vu = L.u[(long)(HOLD ? kc : (GRID ? 0 : k)) * n * nu + (long)min(row0 + m, n - 1) * nu + min(c, nu - 1)];
     }
     if (tid < NLBAC_MLP_TILE * RK_MAX_NS) {
         const int m = tid >> 3, c = tid & 7;
         if constexpr (SUB) vd = nlbac_sub_gather<true>(*sub, X.dout, (long)n * ns, (long)min(row0 + m, n - 1) * ns + min(c, ns - 1), k, 0.f);
-        else vd = X.dout[(long)(k + 1) * n * ns + (long)min(row0 + m, n - 1) * ns + min(c, ns - 1)];
+        else if (HOLD && kr != hm - 1) vd = 0.f;          // (no output behind this fine step)
+        else vd = X.dout[(long)(kc + 1) * n * ns + (long)min(row0 + m, n - 1) * ns + min(c, ns - 1)];
     }
     if (tid < NLBAC_MLP_TILE * RK_MAX_NU) {
         const int m = tid >> 2, c = tid & 3;
@@ -783,10 +793,10 @@ __device__ __forceinline__ void rk_traj_bwd_begin(const NodeRkBwdLaunch& L, cons
 
 // backward, behind interval k's stages: du_k (and dK when the weight gradients want it) to global; the dy0 stays in sDY0
 // for interval k-1, after interval 0 dx0 = dout[0] + dy0.  No barrier inside.
-template <int NTHR, bool GRID = false, bool SUB = false>
+template <int NTHR, bool GRID = false, bool SUB = false, bool HOLD = false>
 __device__ __forceinline__ void rk_traj_bwd_end(const NodeRkBwdLaunch& L, const NodeRkTrajBwd& X, const RkBwdWhere& w,
                                                 const RkBwdTile& T, int row0, int k, int tid,
-                                                const NlbacSubGrid* sub = nullptr) {
+                                                const NlbacSubGrid* sub = nullptr, int hm = 1) {
     const int n = L.n, ns = L.n_s, nu = L.n_u;
     if (w.gdK)
         for (int idx = tid; idx < L.st_hi * NLBAC_MLP_TILE * ns; idx += NTHR) {
@@ -796,7 +806,13 @@ __device__ __forceinline__ void rk_traj_bwd_end(const NodeRkBwdLaunch& L, const 
         }
     for (int idx = tid; idx < NLBAC_MLP_TILE * nu; idx += NTHR) {
         const int m = idx / nu, c = idx - m * nu, row = row0 + m;
-        if constexpr (GRID) {       // (the same thread holds (m, c) in every interval: no barrier between them)
+        if constexpr (HOLD) {       // (GRID's sum below, afresh in every control interval)
+            const int kc = k / hm, kr = k - kc * hm;
+            float a = T.sDU[m * RK_MAX_NU + c];
+            if (kr != hm - 1) a = T.sDYup[m * RK_MAX_NU + c] + a;
+            T.sDYup[m * RK_MAX_NU + c] = a;
+            if (kr == 0 && row < n) L.du[(long)kc * n * nu + (long)row * nu + c] = a;
+        } else if constexpr (GRID) {       // (the same thread holds (m, c) in every interval: no barrier between them)
             float a = T.sDU[m * RK_MAX_NU + c];
             if (k != X.H - 1) a = T.sDYup[m * RK_MAX_NU + c] + a;
             T.sDYup[m * RK_MAX_NU + c] = a;

@@ -64,11 +64,15 @@ __device__ long long g_bwd_stamps[2 * 256];      // (defined in the one translat
 // the interval, and the actions L.u [n][n_u] are the same for every interval (node_rk_shared.h).
 // SUB (with GRID; nlbac_node_rk_subgrid_fwd): the intervals are the fine intervals of a time grid under step_size; L.out
 // takes the output points read off them (node_rk_shared.h).
-template <int NB, int R, int BITS, int SPLIT, bool TRAJ = false, bool GRID = false, bool SUB = false>
+// HOLD (with GRID, not SUB; nlbac_node_rk_hold_fwd: a rollout under step_size): H = N fine intervals, hm of them per
+// control interval — interval k's step size is hs[k % hm], its actions L.u + (k / hm) n n_u, and L.out + (k / hm) n n_s
+// is written behind a control interval's last fine step only (node_rk_shared.h).
+template <int NB, int R, int BITS, int SPLIT, bool TRAJ = false, bool GRID = false, bool SUB = false, bool HOLD = false>
 __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 1, const float* hs = nullptr,
-                                                 const NlbacSubGrid* sub = nullptr) {
+                                                 const NlbacSubGrid* sub = nullptr, int hm = 1) {
     static_assert(TRAJ || !GRID, "a time grid is a trajectory");
     static_assert(GRID || !SUB, "sub-steps are a time grid's");
+    static_assert((GRID && !SUB) || !HOLD, "a held control's fine steps are a time grid's, its outputs their end points");
     static_assert(BITS != 2 || SPLIT == 0, "rows + words: the fit's forward is the unsplit one (same sums as mode 0)");
     constexpr bool WORDS = BITS != 0, ROWS = BITS != 1;
     using S = RRShape<NB, R>;
@@ -207,7 +211,7 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
     }
     // (GRID) this interval's step size: behind the barrier that ended the interval before, in front of the one behind
     // the first stage's input (which, at stage 0, uses no step size; nlbac_node_rk_grid_fwd requires stage_begin == 0)
-    if constexpr (GRID) { if (tid < NLBAC_MLP_TILE) T.sH[tid] = hs[k]; }
+    if constexpr (GRID) { if (tid < NLBAC_MLP_TILE) T.sH[tid] = hs[HOLD ? k % hm : k]; }
     for (int st = L.stage_begin; st < stage_end; ++st) {
         const int sb = 2 + 8 * (st - L.stage_begin);
         (void)sb;
@@ -495,7 +499,7 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
         __syncthreads();
         RSTAMP(sb + 7)
     }
-    if constexpr (TRAJ) rk_traj_advance<256, GRID, SUB>(L, T, row0, k, H, tid, sub);
+    if constexpr (TRAJ) rk_traj_advance<256, GRID, SUB, HOLD>(L, T, row0, k, H, tid, sub, hm);
     }
     if constexpr (TRAJ) return;
 #ifdef RR_TIMING
@@ -521,11 +525,15 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
 // [n][n_u] the sum of the intervals' du, formed in the tile's LDS in the order k = H-1 .. 0 (node_rk_shared.h).
 // SUB (with GRID; nlbac_node_rk_subgrid_bwd): X.dout [T][n][n_s] belongs to the output points, injected between the fine
 // intervals (node_rk_shared.h).
-template <int NB, int R, int BITS, int SPLIT, bool TRAJ = false, bool GRID = false, bool SUB = false>
+// HOLD (with GRID, not SUB; nlbac_node_rk_hold_bwd): X.H = N fine intervals, hm per control interval; X.dout [N/hm + 1]
+// and L.du [N/hm] belong to the control intervals (node_rk_shared.h).
+template <int NB, int R, int BITS, int SPLIT, bool TRAJ = false, bool GRID = false, bool SUB = false, bool HOLD = false>
 __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const NodeRkTrajBwd* X = nullptr,
-                                                 const float* hs = nullptr, const NlbacSubGrid* sub = nullptr) {
+                                                 const float* hs = nullptr, const NlbacSubGrid* sub = nullptr,
+                                                 int hm = 1) {
     static_assert(TRAJ || !GRID, "a time grid is a trajectory");
     static_assert(GRID || !SUB, "sub-steps are a time grid's");
+    static_assert((GRID && !SUB) || !HOLD, "a held control's fine steps are a time grid's, its outputs their end points");
     constexpr bool WORDS = BITS != 0;          // the gates come from the mask words (1, 2) or from the activation rows (0)
     constexpr bool DZ = BITS != 1;             // dz rows are stored when asked for (0; 2: the fit, words behind the rows)
     using S = RRShape<NB, R>;
@@ -636,7 +644,7 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
         w.gG = L.G + (long)kS * n * gout;
         w.gdG = L.dG ? L.dG + (long)kS * n * gout : nullptr;
         w.gdK = L.dK ? L.dK + (long)kS * n * ns : nullptr;
-        rk_traj_bwd_begin<256, GRID, SUB>(L, *X, T, row0, k, kk, tid, hs, sub);
+        rk_traj_bwd_begin<256, GRID, SUB, HOLD>(L, *X, T, row0, k, kk, tid, hs, sub, hm);
         __syncthreads();
     }
 #pragma unroll
@@ -925,7 +933,7 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
     __syncthreads();
     BWSTAMP(2 + 8 * 7)
     if constexpr (TRAJ) {
-        rk_traj_bwd_end<256, GRID, SUB>(L, *X, w, T, row0, k, tid, sub);
+        rk_traj_bwd_end<256, GRID, SUB, HOLD>(L, *X, w, T, row0, k, tid, sub, hm);
         __syncthreads();
     }
     }

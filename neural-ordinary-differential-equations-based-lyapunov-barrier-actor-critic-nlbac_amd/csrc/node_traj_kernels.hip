@@ -20,6 +20,10 @@
 // the T - 1 points read off them by linear interpolation (SUB in node_rr_body.h, NlbacSubGrid in common.h); the backward
 // takes the output points' gradients in between the fine intervals.  K / Y / G, mask words and activation rows per fine
 // stage, as the grid kernels keep them per interval.
+//
+// nlbac_node_rk_hold_*: a rollout under step_size — H control intervals of m fine steps each, the actions held through a
+// control interval (HOLD in node_rr_body.h): the grid kernels over the H m fine intervals with the step schedule hs [m]
+// repeated, the trajectory kernels' change of actions and outputs behind every m-th of them.
 #undef RR_TIMING          // (the ablation stamps belong to the one-step kernels)
 #include "node_rr_body.h"
 
@@ -58,6 +62,30 @@ struct NodeRkSubgridBwdLaunch {
     const float* hs;
     NlbacSubGrid sub;
 };
+
+struct NodeRkHoldFwdLaunch {
+    NodeRkLaunch L;
+    int H;                            // the N = (control intervals) * m fine intervals
+    const float* hs;                  // [m] the fine steps of a control interval (device)
+    int m;
+};
+
+struct NodeRkHoldBwdLaunch {
+    NodeRkBwdLaunch L;
+    NodeRkTrajBwd X;                  // (H: the N fine intervals; dout [N/m + 1][n][n_s])
+    const float* hs;
+    int m;
+};
+
+template <int NB, int R, int BITS, int SPLIT>
+__global__ __launch_bounds__(256) void node_hold_fwd_kernel(const NodeRkHoldFwdLaunch A) {
+    node_rr_fwd_body<NB, R, BITS, SPLIT, true, true, false, true>(A.L, A.H, A.hs, nullptr, A.m);
+}
+
+template <int NB, int R, int BITS, int SPLIT>
+__global__ __launch_bounds__(256) void node_hold_bwd_kernel(const NodeRkHoldBwdLaunch A) {
+    node_rr_bwd_body<NB, R, BITS, SPLIT, true, true, false, true>(A.L, &A.X, A.hs, nullptr, A.m);
+}
 
 template <int NB, int R, int BITS, int SPLIT>
 __global__ __launch_bounds__(256) void node_subgrid_fwd_kernel(const NodeRkSubgridFwdLaunch A) {
@@ -108,24 +136,31 @@ static int traj_check(const nlbac_mlp* f, const nlbac_mlp* g, int n, int H, int 
 template <typename Launch>
 constexpr bool traj_on_subgrid = std::is_same<Launch, NodeRkSubgridFwdLaunch>::value || std::is_same<Launch, NodeRkSubgridBwdLaunch>::value;
 
+// a held-control launch carries the m fine steps of a control interval; its intervals are the fine ones
+template <typename Launch>
+constexpr bool traj_on_hold = std::is_same<Launch, NodeRkHoldFwdLaunch>::value || std::is_same<Launch, NodeRkHoldBwdLaunch>::value;
+
 // a time-grid launch carries a step size per interval
 template <typename Launch>
 constexpr bool traj_on_grid = std::is_same<Launch, NodeRkGridFwdLaunch>::value ||
-                              std::is_same<Launch, NodeRkGridBwdLaunch>::value || traj_on_subgrid<Launch>;
+                              std::is_same<Launch, NodeRkGridBwdLaunch>::value || traj_on_subgrid<Launch> ||
+                              traj_on_hold<Launch>;
 
 // The forward launch of `who` (an entry point below) over H intervals: the instances of its kernel template in `table`
 // (chosen as the one-step launcher chooses, node_rr_body.h, so that the sums are the same), its step — h for every
 // interval, or (time grid) hs [H] on the device for the kernel with hs_host [H] beside it for the checks here — and
 // what the interval's one-step launch takes.  (Sub-stepped time grid) sg: the output points; out is [T-1][n][n_s].
+// (Held controls) H: the fine intervals, a multiple of m (nlbac_hold_intervals); hs / hs_host [m]; out is [H/m][n][n_s].
 template <typename Launch>
 static int traj_fwd(const NodeRrTable<Launch>& table, const char* who, float h, const float* hs, const float* hs_host,
                     const nlbac_mlp* f, const nlbac_mlp* g, const float* x0, const float* u, int n, int H, int n_stages,
                     const float* beta, const float* c_out, float* out, float* K, float* Y, float* G, float* acts_f,
                     long acts_f_ls, float* acts_g, long acts_g_ls, int acts_bits, nlbac_stream_t s,
-                    const NlbacSubGridArgs* sg = nullptr) {
+                    const NlbacSubGridArgs* sg = nullptr, int m = 1) {
     constexpr bool grid = traj_on_grid<Launch>;
+    const int n_hs = traj_on_hold<Launch> ? m : H;      // the step sizes the launch carries
     if (traj_check(f, g, n, H, n_stages, beta, c_out, grid ? 1.f : h, acts_bits, who)) return -1;
-    if (grid && nlbac_grid_steps_check(hs, hs_host, H, who)) return -1;
+    if (grid && nlbac_grid_steps_check(hs, hs_host, n_hs, who)) return -1;
     if (traj_on_subgrid<Launch> && nlbac_subgrid_check(sg, H, who)) return -1;
     Launch A;
     memset(&A, 0, sizeof(A));
@@ -152,6 +187,7 @@ static int traj_fwd(const NodeRrTable<Launch>& table, const char* who, float h, 
         A.hs = hs;
     }
     if constexpr (traj_on_subgrid<Launch>) { A.sub.ofs = sg->ofs; A.sub.theta = sg->theta; }
+    if constexpr (traj_on_hold<Launch>) A.m = m;
     node_rr_fwd_start(table, A, f->hid, n, acts_bits, (hipStream_t)s);
     NLBAC_CHECK_LAUNCH(who);
     return 0;
@@ -163,10 +199,11 @@ static int traj_bwd(const NodeRrTable<Launch>& table, const char* who, float h, 
                     const nlbac_mlp* f, const nlbac_mlp* g, const float* u, int n, int H, int n_stages, const float* beta,
                     const float* c_out, const float* G, const float* acts_f, long acts_f_ls, const float* acts_g,
                     long acts_g_ls, int acts_bits, const float* dout, float* dx0, float* du, float* dK, float* dG,
-                    float* dz_f, float* dz_g, nlbac_stream_t s, const NlbacSubGridArgs* sg = nullptr) {
+                    float* dz_f, float* dz_g, nlbac_stream_t s, const NlbacSubGridArgs* sg = nullptr, int m = 1) {
     constexpr bool grid = traj_on_grid<Launch>;
+    const int n_hs = traj_on_hold<Launch> ? m : H;
     if (traj_check(f, g, n, H, n_stages, beta, c_out, grid ? 1.f : h, acts_bits, who)) return -1;
-    if (grid && nlbac_grid_steps_check(hs, hs_host, H, who)) return -1;
+    if (grid && nlbac_grid_steps_check(hs, hs_host, n_hs, who)) return -1;
     if (traj_on_subgrid<Launch> && nlbac_subgrid_check(sg, H, who)) return -1;
     Launch A;
     memset(&A, 0, sizeof(A));
@@ -184,10 +221,11 @@ static int traj_bwd(const NodeRrTable<Launch>& table, const char* who, float h, 
     L.n = n; L.rpp = n; L.n_s = f->in_dim; L.n_u = g->out_dim / f->in_dim;
     L.S_total = n_stages; L.st_lo = 0; L.st_hi = n_stages; L.dx_stage0 = 1;
     nlbac_tableau_copy(L.beta, A.X.c_out, A.X.n_out, n_stages, beta, c_out);
-    L.h_val[0] = grid ? hs_host[H - 1] : h;
+    L.h_val[0] = grid ? hs_host[n_hs - 1] : h;
     A.X.H = H; A.X.dout = dout; A.X.dx0 = dx0;
     if constexpr (grid) A.hs = hs;
     if constexpr (traj_on_subgrid<Launch>) { A.sub.ofs = sg->ofs; A.sub.theta = sg->theta; }
+    if constexpr (traj_on_hold<Launch>) A.m = m;
     node_rr_bwd_start(table, A, f->hid, n, acts_bits, (hipStream_t)s);
     NLBAC_CHECK_LAUNCH(who);
     return 0;
@@ -261,4 +299,32 @@ extern "C" int nlbac_node_rk_subgrid_bwd(const nlbac_mlp* f, const nlbac_mlp* g,
     const NlbacSubGridArgs sg = {ofs, ofs_host, theta, theta_host, T};
     return traj_bwd(table, "nlbac_node_rk_subgrid_bwd", 0.f, hs, hs_host, f, g, u, n, H, n_stages, beta, c_out, G,
                     acts_f, acts_f_ls, acts_g, acts_g_ls, acts_bits, dout, dx0, du, dK, dG, dz_f, dz_g, s, &sg);
+}
+
+// ---- a rollout under step_size: H control intervals of m fine steps each, steps hs / hs_host [m] (the same schedule in
+//      every control interval; device array for the kernel, host copy for the checks here), the actions u [H][n][n_u] held
+//      through their control interval.  out [H][n][n_s], dout [H+1][n][n_s], du [H][n][n_u]; K / Y / G / acts / dK / dG /
+//      dz per fine stage, [H * m * n_stages][n][..]
+extern "C" int nlbac_node_rk_hold_fwd(const nlbac_mlp* f, const nlbac_mlp* g, const float* x0, const float* u, int n,
+                                      int H, int n_stages, const float* beta, const float* c_out, const float* hs,
+                                      const float* hs_host, int m, float* out, float* K, float* Y, float* G,
+                                      float* acts_f, long acts_f_ls, float* acts_g, long acts_g_ls, int acts_bits,
+                                      nlbac_stream_t s) {
+    static const NodeRrTable<NodeRkHoldFwdLaunch> table = NODE_RR_FWD_TABLE(node_hold_fwd_kernel);
+    int N = 0;
+    if (nlbac_hold_intervals(H, m, n_stages, n, "nlbac_node_rk_hold_fwd", &N)) return -1;
+    return traj_fwd(table, "nlbac_node_rk_hold_fwd", 0.f, hs, hs_host, f, g, x0, u, n, N, n_stages, beta, c_out, out, K,
+                    Y, G, acts_f, acts_f_ls, acts_g, acts_g_ls, acts_bits, s, nullptr, m);
+}
+
+extern "C" int nlbac_node_rk_hold_bwd(const nlbac_mlp* f, const nlbac_mlp* g, const float* u, int n, int H,
+                                      int n_stages, const float* beta, const float* c_out, const float* hs,
+                                      const float* hs_host, int m, const float* G, const float* acts_f, long acts_f_ls,
+                                      const float* acts_g, long acts_g_ls, int acts_bits, const float* dout, float* dx0,
+                                      float* du, float* dK, float* dG, float* dz_f, float* dz_g, nlbac_stream_t s) {
+    static const NodeRrTable<NodeRkHoldBwdLaunch> table = NODE_RR_BWD_TABLE(node_hold_bwd_kernel);
+    int N = 0;
+    if (nlbac_hold_intervals(H, m, n_stages, n, "nlbac_node_rk_hold_bwd", &N)) return -1;
+    return traj_bwd(table, "nlbac_node_rk_hold_bwd", 0.f, hs, hs_host, f, g, u, n, N, n_stages, beta, c_out, G, acts_f,
+                    acts_f_ls, acts_g, acts_g_ls, acts_bits, dout, dx0, du, dK, dG, dz_f, dz_g, s, nullptr, m);
 }

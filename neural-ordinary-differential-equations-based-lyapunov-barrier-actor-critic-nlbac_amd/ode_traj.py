@@ -2,7 +2,8 @@
 
   * the intervals (``EqualSteps``: one ``dt`` and a control per interval, ``rollout``; ``GridSteps``: a step per
     interval and one set of controls, ``odeint_grid``; ``SubGridSteps``: the fine intervals of ``odeint_grid`` under
-    ``step_size``, whose output points are interpolated): the entry points' infix, their step arguments, what the
+    ``step_size``, whose output points are interpolated; ``HeldSteps``: the fine intervals of ``rollout`` under
+    ``step_size``, a control held over each m of them): the entry points' infix, their step arguments, what the
     controls' gradient looks like, where the outputs and their gradients meet the intervals;
   * what a solve keeps and how its backward becomes gradients, one class per path — ``AffineTraj`` / ``ConcatTraj`` (one
     launch forward, one backward, + the weight-gradient launch over all H * stages * rows) and ``Chain`` (H one-interval
@@ -33,6 +34,10 @@ class _OutputPerInterval:
 
     @property
     def n_out(self):
+        return self.H
+
+    @property
+    def launch_H(self):                       # the entry points' H argument (the intervals their controls / outputs count)
         return self.H
 
     def emit(self, xs, k, x_old, x_new):      # interval k's result into the outputs; returns the next interval's state
@@ -161,6 +166,61 @@ class SubGridSteps(GridSteps):
         return per.sum(0)
 
 
+class HeldSteps(_OutputPerInterval):
+    """The N = H m fine intervals of a rollout solved under ``step_size``: every control interval is cut into the same m
+    fine steps ``hs`` (``ode_grid._sub_grid`` over [0, dt]), its control held through them — fine interval i = k m + r runs
+    under controls[k] with step hs[r].  One output per control interval (the fine-grid end point, weight 1: nothing is
+    interpolated), the controls' gradient summed inside a control interval and stacked per control interval.  The
+    one-launch kernels (``nlbac_*_rk_hold_*``) take ``m`` beside the steps; the chained path does the same with the torch
+    ops below — in the kernels' order."""
+    api, infix, solvers_key = "rollout", "hold", "_rollout_hold_solvers"
+
+    def __init__(self, hs, H, device):
+        self.hs, self.m, self.n_ctl, self.H, self.device, self.arrays = hs, len(hs), H, H * len(hs), device, None
+
+    @property
+    def n_out(self):
+        return self.n_ctl
+
+    @property
+    def launch_H(self):
+        return self.n_ctl
+
+    def step_args(self):
+        if self.arrays is None:      # the steps twice: on the device for the kernels, in host memory for the launcher's checks
+            self.arrays = (torch.tensor(self.hs, dtype=torch.float32, device=self.device), fptr(*self.hs))
+        return (self.arrays[0].data_ptr(), self.arrays[1], self.m)
+
+    def step(self, i):
+        return self.hs[i % self.m]
+
+    def control(self, u, i):
+        return u[i // self.m]
+
+    def du_shape(self, n, nc):
+        return (self.n_ctl, n, nc)
+
+    def emit(self, xs, i, x_old, x_new):      # out[k] behind the control interval's last fine step only
+        k, r = divmod(i, self.m)
+        return xs[k].copy_(x_new) if r == self.m - 1 else x_new.clone()
+
+    def grad_in(self, dout, i, carry):        # dout[k+1] comes in behind r = m-1; elsewhere d = 0 + what interval i+1 sends back
+        k, r = divmod(i, self.m)
+        if r == self.m - 1:
+            return dout[k + 1] if carry is None else (dout[k + 1] + carry)
+        return torch.zeros_like(carry) + carry
+
+    def add_du(self, acc, i, du):             # i = N-1 .. 0: total = du_{m-1}; total = total + du_r, per control interval
+        k, r = divmod(i, self.m)
+        if acc is None:
+            acc = torch.empty(self.n_ctl, *du.shape, dtype=torch.float32, device=du.device)
+        acc[k].copy_(du if r == self.m - 1 else acc[k] + du)
+        return acc
+
+    def slabs(self, arena, sv):
+        return arena.n_slabs
+
+
 def _tableau(method):
     tab = TABLEAU[method]
     S = len(tab["c_sol"])
@@ -220,12 +280,12 @@ class AffineTraj:
     def forward(self, x0, u, xs):
         self.u = u
         _lib.call("nlbac_node_rk_%s_fwd" % self.iv.infix, C.byref(self.f.desc), C.byref(self.g.desc), x0.data_ptr(),
-                  u.data_ptr(), self.n, self.H, self.S, self.beta, self.c_out, *self.iv.step_args(),
+                  u.data_ptr(), self.n, self.iv.launch_H, self.S, self.beta, self.c_out, *self.iv.step_args(),
                   xs.data_ptr(), self.K.data_ptr(), self.Y.data_ptr(), self.G.data_ptr(), _ptr(self.acts[0]), self.ls[0],
                   _ptr(self.acts[1]), self.ls[1], self.bits, stream_ptr())
 
     def backward(self, dout, need_p):
-        n, H, S, HS = self.n, self.H, self.S, self.H * self.S
+        n, H, S, HS = self.n, self.iv.launch_H, self.S, self.H * self.S      # (H: the launch's; HS: the stages kept)
         dev = dout.device
         z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         dx0, du = z(n, self.ns), z(*self.iv.du_shape(n, self.nu))
@@ -280,11 +340,11 @@ class ConcatTraj:
 
     def forward(self, x0, u, xs):
         _lib.call("nlbac_concat_rk_%s_fwd" % self.iv.infix, C.byref(self.net.desc), x0.data_ptr(), u.data_ptr(), self.n,
-                  self.H, self.S, self.beta, self.c_out, *self.iv.step_args(), xs.data_ptr(), _ptr(self.Xin),
+                  self.iv.launch_H, self.S, self.beta, self.c_out, *self.iv.step_args(), xs.data_ptr(), _ptr(self.Xin),
                   _ptr(self.acts), self.ls, self.bits, _ptr(self.norm), stream_ptr())
 
     def backward(self, dout, need_p):
-        n, H, S, HS = self.n, self.H, self.S, self.H * self.S
+        n, H, S, HS = self.n, self.iv.launch_H, self.S, self.H * self.S      # (H: the launch's; HS: the stages kept)
         dev = dout.device
         z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         dx0, du = z(n, self.ns), z(*self.iv.du_shape(n, self.nc))

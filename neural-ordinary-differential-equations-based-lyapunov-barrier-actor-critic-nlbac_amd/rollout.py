@@ -10,6 +10,11 @@ Two paths, same results:
   * chained (dopri5, nets wider than 128, shapes the register-resident kernels refuse): H single-interval solves on
     the existing solvers, one solver per interval, cached on the model apart from ``odeint``'s and the agent's.
 ``ONE_LAUNCH = False`` (env ``NLBAC_ROLLOUT_ONE_LAUNCH=0``) runs the chained path everywhere: the A/B baseline.
+
+``step_size=s`` (euler / rk4) solves every control interval in steps of ``s`` with its control held — the chain of
+``odeint(..., options=dict(step_size=s))`` calls, bit for bit: still one launch forward (``nlbac_node_rk_hold_fwd`` /
+``nlbac_concat_rk_hold_fwd``) and one backward (``*_hold_bwd``) over the H * m fine intervals, or chained fine interval
+by fine interval (``ode_traj.HeldSteps``).
 """
 import math
 import os
@@ -22,13 +27,18 @@ ONE_LAUNCH = os.environ.get("NLBAC_ROLLOUT_ONE_LAUNCH", "1") != "0"
 METHODS = ("euler", "rk4", "dopri5")
 
 
-def _check(func, x0, controls, dt, method):
+def _check(func, x0, controls, dt, method, step_size=None):
+    """Every argument check, before anything touches a device.  Returns ``dt`` rounded to float32 as ``odeint``'s time
+    grid rounds it and, with ``step_size``, the fine steps of a control interval (``ode_grid._sub_grid`` over [0, dt])."""
     from .sac_cbf_clf.model import NeuralODEModel
     if not isinstance(func, NeuralODEModel):
         raise TypeError("nlbac_amd.rollout integrates this build's NeuralODEModel (its field runs as HIP kernels); "
                         "got %s" % type(func).__name__)
     if method not in METHODS:
         raise ValueError("rollout: method is one of %s; got %r" % (", ".join(METHODS), method))
+    if step_size is not None and method == "dopri5":
+        raise ValueError("rollout: step_size goes with method='euler' or 'rk4'; torchdiffeq's dopri5 ignores it, "
+                         "which this build does not do silently")
     for name, t in (("x0", x0), ("controls", controls)):
         if not isinstance(t, torch.Tensor):
             raise TypeError("rollout: %s must be a tensor; got %s" % (name, type(t).__name__))
@@ -38,18 +48,31 @@ def _check(func, x0, controls, dt, method):
         raise TypeError("rollout: dt must be a Python float; got %s" % type(dt).__name__)
     if not (math.isfinite(dt) and dt > 0):
         raise ValueError("rollout: dt must be a finite positive number; got %r" % (dt,))
+    grid = torch.tensor([0.0, float(dt)], dtype=torch.float32)
+    dt, hs = float(grid[1]), None
+    if step_size is not None:
+        from .ode_grid import _sub_grid      # (the one place the step_size rule lives; it imports this module)
+        _, hs, _, theta = _sub_grid(grid, step_size)
+        assert theta == (1.0,), "the one output of a control interval is the fine grid's end point"
     ns = func.n_s
     nc = func.n_u if func.affine else func.n_carry
     if x0.dim() != 2 or x0.shape[1] != ns or x0.shape[0] < 1:
         raise ValueError("rollout: x0 must be (batch, %d); got %s" % (ns, tuple(x0.shape)))
     if controls.dim() != 3 or controls.shape[0] < 1 or controls.shape[1] != x0.shape[0] or controls.shape[2] != nc:
         raise ValueError("rollout: controls must be (H >= 1, %d, %d); got %s" % (x0.shape[0], nc, tuple(controls.shape)))
+    if hs is not None:
+        from .ode_consts import TABLEAU
+        H, m, S = controls.shape[0], len(hs), len(TABLEAU[method]["c_sol"])
+        if H * m * S * x0.shape[0] >= 2 ** 31:
+            raise ValueError("rollout: %d intervals x %d fine steps x %d stages x %d rows is 2^31 or more (the launch's "
+                             "limit); use a larger step_size, a shorter horizon or fewer rows" % (H, m, S, x0.shape[0]))
     if x0.device.type != "cuda" or controls.device != x0.device:
         raise ValueError("rollout: x0 and controls must be on the same CUDA device; got %s and %s"
                          % (x0.device, controls.device))
+    return dt, hs
 
 
-def rollout(func, x0, controls, dt, *, method="rk4", atol=1e-7, rtol=1e-5):
+def rollout(func, x0, controls, dt, *, method="rk4", atol=1e-7, rtol=1e-5, step_size=None):
     """Predict H intervals of ``dt`` ahead with the NODE ``func`` (either form; a model owned by an agent included),
     a new control per interval: returns ``out`` (H + 1, B, n_s) with ``out[0] = x0`` and
 
@@ -65,13 +88,25 @@ def rollout(func, x0, controls, dt, *, method="rk4", atol=1e-7, rtol=1e-5):
     nothing under ``torch.no_grad``, ReLU mask words for input gradients only, activation rows as well for parameter
     gradients — memory grows linearly with H.  The one-step kernels sum f_net's output layer in two parts when they
     keep mask words only, so a rollout differentiated w.r.t. its inputs only can differ from ``odeint``'s values in the
-    last bits; without gradients, or with parameter gradients, the values are ``odeint``'s."""
-    _check(func, x0, controls, dt, method)
-    dt = float(torch.tensor([0.0, float(dt)], dtype=torch.float32)[1])
+    last bits; without gradients, or with parameter gradients, the values are ``odeint``'s.
+
+    ``step_size=s`` (a positive finite Python number; euler / rk4 only — with dopri5 a ``ValueError``, as in ``odeint``):
+    every control interval is solved in steps of ``s`` on the fine grid ``odeint(..., options=dict(step_size=s))`` builds
+    for ``[0, dt]`` (``ode_grid._sub_grid``: m steps, the last one cut at ``dt``), its control — SimulatedCars' [u | t]
+    columns included — held through the interval:
+
+        out[k+1] = odeint(func, cat(out[k], controls[k]), tensor([0.0, dt]), method=..., options=dict(step_size=s))[-1][:, :n_s]
+
+    bit for bit, gradients w.r.t. ``x0`` and ``controls`` included.  The accuracy no longer hangs on the control rate;
+    the solve is still one launch forward and one backward, over H * m fine intervals, and one autograd node.  What is
+    kept grows with H * m; ``out`` and the gradients stay per control interval — the fine states and their gradients are
+    never stored.  ``step_size >= dt`` gives m = 1: the results without ``step_size``."""
+    dt, hs = _check(func, x0, controls, dt, method, step_size)
     params = tuple(func.parameters())
     mode = T.keep_mode(params, x0, controls)
     func.refresh_device_weights()
-    return _RolloutFunction.apply(func, method, dt, float(atol), float(rtol), mode, x0, controls, *params)
+    return _RolloutFunction.apply(func, method, dt if hs is None else hs, float(atol), float(rtol), mode, x0, controls,
+                                  *params)
 
 
 def _one_launch_ok(func, method):
@@ -81,6 +116,7 @@ def _one_launch_ok(func, method):
 class _RolloutFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, func, method, dt, atol, rtol, mode, x0, controls, *params):
+        # (dt: the interval, or with step_size the fine steps of a control interval)
         H, n, ns = controls.shape[0], x0.shape[0], func.n_s
         x0 = x0.detach().contiguous()
         u = controls.detach().contiguous()
@@ -89,8 +125,8 @@ class _RolloutFunction(torch.autograd.Function):
         ctx.func, ctx.mode, ctx.n_params = func, mode, len(params)
         one = _one_launch_ok(func, method)
         # (the one launch reads x0 where the caller's tensor is; the chain's first solver keeps a reference, to out[0])
-        ctx.kept = T.solve(func, T.EqualSteps(dt, H), method, mode, one, x0 if one else first, u, out.narrow(0, 1, H),
-                           atol, rtol)
+        iv = T.HeldSteps(dt, H, x0.device) if isinstance(dt, tuple) else T.EqualSteps(dt, H)
+        ctx.kept = T.solve(func, iv, method, mode, one, x0 if one else first, u, out.narrow(0, 1, H), atol, rtol)
         return out
 
     @staticmethod

@@ -918,6 +918,34 @@ int nlbac_gather_rows(const float *src, long src_rows, int ld, const long *idx, 
 int nlbac_sample_rows(const float *src, long src_rows, int ld, long n_rows, float *dst, float *eps, long n_eps,
                       unsigned long long seed, unsigned long long draw, nlbac_stream_t s);
 
+/* Trajectory windows from the replay ring (the multi-step NODE fit): n windows of H rows each out of the ring `src`
+ * (src_rows filled rows of ld floats, capacity cap, head = the ring's write position), idx[n] the start rows (int64, in
+ * [0, src_rows)), `stride` rows between consecutive steps of one window (1, or the lane count of a vectorised driver).
+ *   oldest = (src_rows == cap) ? head : 0;   a0 = (idx - oldest) mod cap   (the start row's rank in push order);
+ *   step k of a window = the row of rank a0 + k stride = row (oldest + a0 + k stride) mod cap.
+ * A window is valid iff (a) a0 + (H-1) stride < src_rows and (b) for every k < H-1 the obs_dim 32-bit words at column
+ * nobs_col of step k equal, compared as integers, the words at column obs_col of step k+1 (a reset or a termination
+ * breaks the chain; `mask` stays 1 at a time-limit reset and cannot tell).  Outputs: dst [H][n][ld] (rows of an invalid
+ * window are written too: step k = the row of rank min(a0 + k stride, src_rows - 1)), valid [n] (1.0f / 0.0f), counts
+ * [ceil(n / 256)] (int: valid windows per 256-window block; plain stores).  (Added without an ABI bump: new entry
+ * points only.) */
+int nlbac_gather_windows(const float *src, long src_rows, long cap, long head, int ld, const long *idx, long n, int H,
+                         long stride, int obs_col, int nobs_col, int obs_dim, float *dst, float *valid, int *counts,
+                         nlbac_stream_t s);
+/* The same with the start rows drawn on the device: uniform on [0, src_rows) with replacement, Philox4x32-10 keyed by
+ * `seed`, counter (draw, window, 0) — as nlbac_sample_rows draws its rows. */
+int nlbac_sample_windows(const float *src, long src_rows, long cap, long head, int ld, long n, int H, long stride,
+                         int obs_col, int nobs_col, int obs_dim, float *dst, float *valid, int *counts,
+                         unsigned long long seed, unsigned long long draw, nlbac_stream_t s);
+/* Masked MSE over a trajectory: pred / target / dpred [H][n][n_s] contiguous; valid [n] (or NULL: all ones, counts
+ * unused) and counts [n_counts = ceil(n / 256)] as nlbac_gather_windows leaves them.  V = max(1, sum of counts), summed
+ * by every workgroup itself (integers: no atomics, the same in any order);
+ *   L = sum_i valid_i sum_k sum_c (pred - target)^2 / (V H n_s),   dpred = 2 valid_i (pred - target) / (V H n_s).
+ * partials [min(256, ceil(n H n_s / 1024))]: every workgroup's share of L, already normalised — nlbac_sum_partials(
+ * partials, that many, 1, 1.0f, out) finishes the scalar.  H = 1 with every window valid is nn.MSELoss('mean'). */
+int nlbac_traj_mse_fwd_bwd(const float *pred, const float *target, const float *valid, const int *counts, int n_counts,
+                           long n, int H, int n_s, float *dpred, float *partials, nlbac_stream_t s);
+
 /* ------------------------------------------------------------------------
  * Batched device simulators (row f3): n independent environments advanced by one launch, one lane each, float64 like
  * the reference's numpy simulators — U/envs/unicycle_env.py:57-152 (+ barrier signal NU/envs/unicycle_env.py:116-144),

@@ -194,6 +194,10 @@ _PROTOS = {
     "nlbac_copy_blocks": [_P, _L, _P, _L, _L, _L, _P],
     "nlbac_gather_rows": [_P, _L, _I, _P, _L, _P, _P],
     "nlbac_sample_rows": [_P, _L, _I, _L, _P, _P, _L, C.c_uint64, C.c_uint64, _P],
+    # (new entry points of ABI 17: trajectory windows out of the replay ring and the loss over them)
+    "nlbac_gather_windows": [_P, _L, _L, _L, _I, _P, _L, _I, _L, _I, _I, _I, _P, _P, _P, _P],
+    "nlbac_sample_windows": [_P, _L, _L, _L, _I, _L, _I, _L, _I, _I, _I, _P, _P, _P, C.c_uint64, C.c_uint64, _P],
+    "nlbac_traj_mse_fwd_bwd": [_P, _P, _P, _P, _I, _L, _I, _I, _P, _P, _P],
     "nlbac_td_value": [_P, _P, _I, _P, _I, _P, _F, _I, _I, _P, _P, _P, _P, _F, _P, _P],
     "nlbac_unicycle_obs_fwd": [_P, _I, _F, _F, _P, _I, _P],
     "nlbac_unicycle_obs_bwd": [_P, _P, _I, _I, _F, _F, _P, _I, _P],

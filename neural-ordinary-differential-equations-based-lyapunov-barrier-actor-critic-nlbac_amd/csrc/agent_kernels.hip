@@ -522,6 +522,56 @@ __global__ __launch_bounds__(256) void mse_kernel(const float* pred, int pred_ld
     if (threadIdx.x == 0) partials[blockIdx.x] = v[0];
 }
 
+// Masked MSE over a trajectory: pred / target / dpred [H][n][n_s] (contiguous), window i counts iff valid[i] != 0
+// (valid NULL: every window).  V = sum(valid) is the integer sum of counts [n_counts] (nlbac_gather_windows: valid windows
+// per 256-window block), formed by every workgroup itself — integers: the same in any order, no atomics — and clamped to
+// >= 1;  L = sum_i v_i sum_k sum_c (pred - target)^2 / (V H n_s),  dpred = 2 v_i (pred - target) / (V H n_s).
+// The grid is min(TRAJ_MSE_MAX_BLOCKS, ceil(elements / TRAJ_MSE_ELEMS)) workgroups, each on one contiguous run of
+// elements (consecutive lanes on consecutive floats); partials[block] = its share of L, already normalised:
+// nlbac_sum_partials with mul 1 finishes the scalar (one thread adds them in block order: the cap keeps that short).
+// For H = 1 and every window valid dpred is mse_kernel's, bit for bit.
+#define TRAJ_MSE_ELEMS 1024
+#define TRAJ_MSE_MAX_BLOCKS 256
+static inline long traj_mse_blocks(long total) {
+    const long b = (total + TRAJ_MSE_ELEMS - 1) / TRAJ_MSE_ELEMS;
+    return b < TRAJ_MSE_MAX_BLOCKS ? b : TRAJ_MSE_MAX_BLOCKS;
+}
+__global__ __launch_bounds__(256) void traj_mse_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                       const float* __restrict__ valid, const int* __restrict__ counts,
+                                                       int n_counts, long n, int H, int n_s, float* __restrict__ dpred,
+                                                       float* __restrict__ partials) {
+    __shared__ float red[4];
+    __shared__ int s_cnt[4];
+    long V = n;
+    if (valid) {
+        int c = 0;
+        for (int j = threadIdx.x; j < n_counts; j += 256) c += counts[j];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+        if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = c;
+        __syncthreads();
+        V = (long)s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    }
+    if (V < 1) V = 1;
+    const double denom = (double)V * H * n_s;
+    const float norm = (float)(2.0 / denom), inv = (float)(1.0 / denom);
+    const long total = n * H * n_s;
+    float v[1] = {0.f};
+    // this workgroup's run: the elements split evenly over the grid, in whole strides of the 256 lanes
+    const long chunk = ((total + gridDim.x - 1) / gridDim.x + 255) / 256 * 256;
+    const long begin = (long)blockIdx.x * chunk;
+    const long end = begin + chunk < total ? begin + chunk : total;
+    for (long e = begin + threadIdx.x; e < end; e += 256) {
+        const long i = (e / n_s) % n;                      // the element's window
+        const bool on = !valid || valid[i] != 0.f;
+        const float d = pred[e] - target[e];
+        dpred[e] = on ? norm * d : 0.f;
+        if (on) v[0] += d * d;
+    }
+    block_sum_256<1>(v, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = v[0] * inv;
+}
+
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
@@ -690,6 +740,22 @@ extern "C" int nlbac_mse_fwd_bwd(const float* pred, int pred_ld, const float* ta
     NLBAC_REQUIRE(pred && target && dpred && partials, "nlbac_mse_fwd_bwd: null pointer");
     hipLaunchKernelGGL(mse_kernel, GRID1(n), pred, pred_ld, target, target_ld, n, n_norm, d, dpred, dpred_ld, partials);
     NLBAC_CHECK_LAUNCH("nlbac_mse_fwd_bwd");
+    return 0;
+}
+
+extern "C" int nlbac_traj_mse_fwd_bwd(const float* pred, const float* target, const float* valid, const int* counts,
+                                      int n_counts, long n, int H, int n_s, float* dpred, float* partials,
+                                      nlbac_stream_t s) {
+    NLBAC_REQUIRE(pred && target && dpred && partials, "nlbac_traj_mse_fwd_bwd: null pointer");
+    NLBAC_REQUIRE(n >= 1 && H >= 1 && n_s >= 1, "nlbac_traj_mse_fwd_bwd: bad sizes");
+    NLBAC_REQUIRE(!valid || (counts && n_counts == (n + 255) / 256),
+                  "nlbac_traj_mse_fwd_bwd: valid needs counts [ceil(n / 256)]");
+    const long total = n * H * n_s;
+    NLBAC_REQUIRE(n < (1L << 31) && total / n == (long)H * n_s && total < (1L << 46),
+                  "nlbac_traj_mse_fwd_bwd: too many elements");
+    hipLaunchKernelGGL(traj_mse_kernel, dim3((unsigned)traj_mse_blocks(total)), dim3(256), 0, (hipStream_t)s, pred,
+                       target, valid, counts, n_counts, n, H, n_s, dpred, partials);
+    NLBAC_CHECK_LAUNCH("nlbac_traj_mse_fwd_bwd");
     return 0;
 }
 

@@ -474,3 +474,134 @@ extern "C" int nlbac_gather_rows(const float* src, long src_rows, int ld, const 
     NLBAC_CHECK_LAUNCH("nlbac_gather_rows");
     return 0;
 }
+
+// ---------------------------------------------------------------------------
+// Trajectory windows from the replay ring (multi-step NODE fit): n windows of H rows each, `stride` rows between
+// consecutive steps of one window (1, or the lane count of a vectorised driver that pushes one row per lane per step).
+//   oldest = (src_rows == cap) ? head : 0          the oldest row (head: the ring's write position)
+//   a0     = (idx - oldest) mod cap                 the start row's rank in push order
+//   step k = the row of rank a0 + k stride, i.e. row (oldest + a0 + k stride) mod cap
+// A window is valid iff (a) a0 + (H-1) stride < src_rows — it neither runs past the newest row nor steps over the write
+// head — and (b) for every k < H-1 the obs_dim 32-bit words at nobs_col of step k equal, bit for bit (compared as
+// integers), the words at obs_col of step k+1: an episode's next observation IS its next row's observation, and a reset
+// or a termination — which `mask` cannot tell from a time-limit reset — breaks the chain.  Rows of an invalid window are
+// still written (nothing downstream reads garbage): step k is the row of rank min(a0 + k stride, src_rows - 1).
+// Outputs: dst [H][n][ld]; valid [n] 1.0f / 0.0f; counts [ceil(n / 256)] valid windows per 256-window block (plain
+// stores, no atomics).  Grid (ceil(n / 256), H + 1): workgroup (b, k < H) moves step k of block b's 256 windows, one lane
+// per float4, consecutive lanes on consecutive 16-byte pieces of a row; workgroup (b, H) checks the block's windows, one
+// lane per compared word (consecutive lanes on consecutive words of a step), so neither a window's H rows nor its
+// continuity compare run on one lane.  IDX false: the start rows are drawn here, uniform on [0, src_rows) with
+// replacement, Philox counter (draw, window, 0) as sample_rows_kernel draws its rows.
+// ---------------------------------------------------------------------------
+template <bool IDX>
+__global__ __launch_bounds__(256) void gather_windows_kernel(const float4* __restrict__ src, int ld4, long src_rows,
+                                                             long cap, long head, const long* __restrict__ idx, long n,
+                                                             int H, long stride, int obs_col, int nobs_col, int obs_dim,
+                                                             float4* __restrict__ dst, float* __restrict__ valid,
+                                                             int* __restrict__ counts, unsigned long long seed,
+                                                             unsigned long long draw) {
+    __shared__ long s_a0[256];
+    __shared__ int s_bad[256];
+    __shared__ float s_red[4];
+    const long w0 = (long)blockIdx.x * 256;
+    const int nw = (int)((n - w0) < 256 ? (n - w0) : 256);          // windows of this block
+    const long oldest = (src_rows == cap) ? head : 0;
+    const long last = src_rows - 1;
+    if ((int)threadIdx.x < nw) {
+        long j;
+        if (IDX) {
+            j = idx[w0 + threadIdx.x];
+            j = j < 0 ? 0 : (j > last ? last : j);                   // never read outside the buffer
+        } else {
+            const uint2 key = make_uint2((unsigned)seed, (unsigned)(seed >> 32));
+            const uint4 x = philox4x32_10(make_uint4((unsigned)draw, (unsigned)(draw >> 32), (unsigned)(w0 + threadIdx.x), 0u), key);
+            j = (long)(((unsigned long long)x.x * (unsigned long long)src_rows) >> 32);
+        }
+        long a0 = j - oldest;
+        if (a0 < 0) a0 += cap;
+        s_a0[threadIdx.x] = a0;
+        s_bad[threadIdx.x] = (a0 + (long)(H - 1) * stride < src_rows) ? 0 : 1;      // (a)
+    }
+    __syncthreads();
+    const int k = blockIdx.y;
+    if (k < H) {
+        const int items = nw * ld4;
+        for (int i = threadIdx.x; i < items; i += 256) {
+            const int w = i / ld4, c = i - w * ld4;
+            long rank = s_a0[w] + (long)k * stride;
+            rank = rank > last ? last : rank;
+            const long row = (oldest + rank) % cap;
+            dst[((long)k * n + w0 + w) * ld4 + c] = src[row * ld4 + c];
+        }
+        return;
+    }
+    // (b): word j of the link k -> k+1 of window w; a lane that sees a difference flags the window (every writer
+    // stores the same value)
+    const unsigned* words = reinterpret_cast<const unsigned*>(src);
+    const long ld = 4L * ld4;
+    const int per_w = (H - 1) * obs_dim;
+    const long items = (long)nw * per_w;
+    for (long i = threadIdx.x; i < items; i += 256) {
+        const int w = (int)(i / per_w), r = (int)(i - (long)w * per_w);
+        const int kk = r / obs_dim, j = r - kk * obs_dim;
+        long r0 = s_a0[w] + (long)kk * stride, r1 = r0 + stride;
+        r0 = r0 > last ? last : r0;
+        r1 = r1 > last ? last : r1;
+        const unsigned a = words[((oldest + r0) % cap) * ld + nobs_col + j];
+        const unsigned b = words[((oldest + r1) % cap) * ld + obs_col + j];
+        if (a != b) s_bad[w] = 1;
+    }
+    __syncthreads();
+    float v[1] = {0.f};
+    if ((int)threadIdx.x < nw) {
+        v[0] = s_bad[threadIdx.x] ? 0.f : 1.f;
+        valid[w0 + threadIdx.x] = v[0];
+    }
+    block_sum_256<1>(v, s_red);                                      // (<= 256 ones: exact)
+    if (threadIdx.x == 0) counts[blockIdx.x] = (int)v[0];
+}
+
+static int windows_check(const float* src, long src_rows, long cap, long head, int ld, long n, int H, long stride,
+                         int obs_col, int nobs_col, int obs_dim, const float* dst, const float* valid, const int* counts,
+                         const char* who) {
+    NLBAC_REQUIRE(src && dst && valid && counts, "%s: null pointer", who);
+    NLBAC_REQUIRE(cap >= 1 && src_rows >= 1 && src_rows <= cap && cap < (1L << 32) && head >= 0 && head < cap,
+                  "%s: bad ring (rows %ld, capacity %ld, head %ld)", who, src_rows, cap, head);
+    NLBAC_REQUIRE(n >= 1 && H >= 1 && H < 65535 && stride >= 1 && stride < (1L << 32) && (n + 255) / 256 < (1L << 31),
+                  "%s: bad window count / horizon / stride", who);
+    NLBAC_REQUIRE(ld >= 4 && ld % 4 == 0 && ((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0,
+                  "%s: rows must be whole float4s (ld %d)", who, ld);
+    NLBAC_REQUIRE(obs_dim >= 0 && obs_col >= 0 && nobs_col >= 0 && obs_col + obs_dim <= ld && nobs_col + obs_dim <= ld &&
+                      (long)(H - 1) * obs_dim < (1L << 22),
+                  "%s: the observation columns must lie inside a row", who);
+    return 0;
+}
+
+#define WINDOWS_GRID(n, H) dim3((unsigned)(((n) + 255) / 256), (unsigned)((H) + 1)), dim3(256), 0, (hipStream_t)s
+
+extern "C" int nlbac_gather_windows(const float* src, long src_rows, long cap, long head, int ld, const long* idx, long n,
+                                    int H, long stride, int obs_col, int nobs_col, int obs_dim, float* dst, float* valid,
+                                    int* counts, nlbac_stream_t s) {
+    if (windows_check(src, src_rows, cap, head, ld, n, H, stride, obs_col, nobs_col, obs_dim, dst, valid, counts,
+                      "nlbac_gather_windows"))
+        return 1;
+    NLBAC_REQUIRE(idx, "nlbac_gather_windows: null pointer");
+    hipLaunchKernelGGL(gather_windows_kernel<true>, WINDOWS_GRID(n, H), (const float4*)src, ld / 4, src_rows, cap, head,
+                       idx, n, H, stride, obs_col, nobs_col, obs_dim, (float4*)dst, valid, counts, 0ull, 0ull);
+    NLBAC_CHECK_LAUNCH("nlbac_gather_windows");
+    return 0;
+}
+
+extern "C" int nlbac_sample_windows(const float* src, long src_rows, long cap, long head, int ld, long n, int H,
+                                    long stride, int obs_col, int nobs_col, int obs_dim, float* dst, float* valid,
+                                    int* counts, unsigned long long seed, unsigned long long draw, nlbac_stream_t s) {
+    if (windows_check(src, src_rows, cap, head, ld, n, H, stride, obs_col, nobs_col, obs_dim, dst, valid, counts,
+                      "nlbac_sample_windows"))
+        return 1;
+    NLBAC_REQUIRE(n < (1L << 32), "nlbac_sample_windows: the Philox counter holds 2^32 windows per draw");
+    hipLaunchKernelGGL(gather_windows_kernel<false>, WINDOWS_GRID(n, H), (const float4*)src, ld / 4, src_rows, cap, head,
+                       (const long*)nullptr, n, H, stride, obs_col, nobs_col, obs_dim, (float4*)dst, valid, counts, seed,
+                       draw);
+    NLBAC_CHECK_LAUNCH("nlbac_sample_windows");
+    return 0;
+}

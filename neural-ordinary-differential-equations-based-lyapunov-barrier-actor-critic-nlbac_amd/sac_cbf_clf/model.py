@@ -301,3 +301,7 @@ def train_step(model, state, action, next_state, *rest) -> float:
     optimizer.step()
     model.refresh_device_weights()
     return float(loss.item()) / horizon
+
+
+# the multi-step form (the horizon the reference's ``train_step`` reads and never loops over): nlbac_amd/node_fit.py
+from ..node_fit import train_rollout_step  # noqa: E402,F401

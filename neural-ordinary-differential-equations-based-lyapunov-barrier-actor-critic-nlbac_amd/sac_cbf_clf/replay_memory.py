@@ -52,8 +52,52 @@ class ReplayMemory:
         idx = np.asarray(random.sample(range(self._len), batch_size), dtype=np.int64)
         return tuple(c[idx] for c in self._cols)
 
+    def sample_windows(self, batch_size, horizon, stride=1):
+        """``batch_size`` windows of ``horizon`` consecutive transitions (``stride`` rows apart): ``(fields, valid)`` —
+        the field arrays of ``sample`` with a leading (H, B, ...) and valid (B,) bool.  Start rows are drawn like
+        ``sample``'s; the validity rule and the rows of an invalid window are ``window_rows``'s (the device replay's
+        ``nlbac_gather_windows`` applies the same rule to its float32 rows)."""
+        check_windows(batch_size, horizon, stride, self._len, host_draw=True)
+        idx = np.asarray(random.sample(range(self._len), batch_size), dtype=np.int64)
+        nstate = len(self._cols) - 4          # (..., next_state, mask, t, next_t)
+        rows, valid = window_rows(idx, horizon, stride, self._len, self.capacity, self.position,
+                                  self._cols[0], self._cols[nstate])
+        return tuple(c[rows] for c in self._cols), valid
+
     def __len__(self):
         return self._len
+
+
+def check_windows(batch_size, horizon, stride, length, host_draw):
+    """The argument checks of ``sample_windows`` (host and device replay), before anything touches a device."""
+    for name, v in (("batch_size", batch_size), ("horizon", horizon), ("stride", stride)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError("sample_windows: %s must be an integer >= 1; got %r" % (name, v))
+    if host_draw and batch_size > length:
+        raise ValueError("sample_windows: %d start rows drawn without replacement from %d rows" % (batch_size, length))
+    if (horizon - 1) * stride >= length:
+        raise ValueError("sample_windows: a window of %d steps %d rows apart spans more than the %d rows held"
+                         % (horizon, stride, length))
+
+
+def window_rows(idx, horizon, stride, length, capacity, position, obs, next_obs):
+    """Ring rows (H, B) of the windows that start at rows ``idx`` and which of them are valid (B,).
+
+    ``oldest = position if length == capacity else 0``; ``a0 = (idx - oldest) mod capacity`` is the start row's rank in
+    push order, step k the row of rank ``a0 + k stride``.  Valid: (a) ``a0 + (H-1) stride < length`` — the window neither
+    runs past the newest row nor steps over the write head — and (b) every step's ``next_obs`` is, bit for bit, the next
+    step's ``obs``: a reset or a termination breaks that chain (``mask`` stays 1 at a time-limit reset and cannot tell).
+    An invalid window still gets rows: step k is the row of rank ``min(a0 + k stride, length - 1)``."""
+    idx = np.asarray(idx, dtype=np.int64)
+    oldest = position if length == capacity else 0
+    a0 = (idx - oldest) % capacity
+    ranks = a0[None, :] + stride * np.arange(horizon, dtype=np.int64)[:, None]
+    valid = ranks[-1] < length
+    rows = (oldest + np.minimum(ranks, length - 1)) % capacity
+    bits = lambda a: np.ascontiguousarray(a).view(np.int64 if a.dtype.itemsize == 8 else np.int32).reshape(len(a), -1)
+    for k in range(horizon - 1):
+        valid &= (bits(next_obs[rows[k]]) == bits(obs[rows[k + 1]])).all(axis=1)
+    return rows, valid
 
 
 
@@ -146,6 +190,43 @@ class DeviceReplayMemory:
         if eps_out is not None:
             eps_out.normal_()
         return out
+
+    def sample_windows(self, batch_size, horizon, stride=1, out=None, idx=None):
+        """``batch_size`` trajectory windows of ``horizon`` consecutive rows (``stride`` rows apart: 1, or the lane count
+        of a driver that pushes one row per lane per step): ``(rows (H, B, LD), valid (B,) float 1 / 0)`` on the device,
+        one ``nlbac_gather_windows`` launch (its header comment has the validity rule; ``window_rows`` above is the same
+        rule in numpy).  Start rows: ``random.sample`` on the host like ``sample_rows``; with ``device_rng`` drawn by the
+        launch itself (``nlbac_sample_windows``, with replacement); ``idx`` (int64 tensor, host or device): the caller's.
+        The launch's per-block counts of valid windows stay in ``self.window_counts`` for the loss that follows."""
+        import torch
+        from .. import _lib
+        from ..arena import stream_ptr
+        check_windows(batch_size, horizon, stride, self._len, host_draw=idx is None and not self.device_rng)
+        if idx is not None:
+            idx = torch.as_tensor(idx)
+            if idx.dtype != torch.int64 or idx.dim() != 1 or idx.numel() != batch_size:
+                raise ValueError("sample_windows: idx must be %d int64 start rows" % batch_size)
+        if out is not None and (tuple(out.shape) != (horizon, batch_size, self.lay.LD) or not out.is_contiguous()
+                                or out.dtype != torch.float32):
+            raise ValueError("sample_windows: out must be a contiguous float32 (%d, %d, %d) tensor"
+                             % (horizon, batch_size, self.lay.LD))
+        self.flush()
+        lay = self.lay
+        if out is None:
+            out = torch.empty(horizon, batch_size, lay.LD, dtype=torch.float32, device=self.device)
+        valid = torch.empty(batch_size, dtype=torch.float32, device=self.device)
+        self.window_counts = counts = torch.empty((batch_size + 255) // 256, dtype=torch.int32, device=self.device)
+        ring = (self.rows.data_ptr(), self._len, self.capacity, self.position, lay.LD)
+        tail = (horizon, stride, lay.obs, lay.nobs, lay.obs_dim, out.data_ptr(), valid.data_ptr(), counts.data_ptr())
+        if idx is None and self.device_rng:
+            self._draws += 1
+            _lib.call("nlbac_sample_windows", *ring, batch_size, *tail, self._seed, self._draws, stream_ptr())
+            return out, valid
+        if idx is None:
+            idx = torch.tensor(random.sample(range(self._len), batch_size), dtype=torch.int64)
+        idx = idx.to(self.device)
+        _lib.call("nlbac_gather_windows", *ring, idx.data_ptr(), batch_size, *tail, stream_ptr())
+        return out, valid
 
     def sample(self, batch_size):
         """Reference-shaped ``sample``: the 10 (11) stacked numpy arrays (device -> host; use ``sample_rows`` on the

@@ -33,6 +33,7 @@ import torch.nn as nn
 
 from .. import _lib
 from ..arena import Arena, bwd_weights, pack, stream_ptr
+from ..node_fit import loss_blocks, node_fit_options, traj_mse_launch, valid_counts
 from . import _layout as SC
 from .model import BarrierNetwork, GaussianPolicy, LyaNetwork, QNetwork
 from .scalars_readback import ScalarsReadback
@@ -86,6 +87,10 @@ class SAC_CBF_CLF(object):
         hidden = args.hidden_size
         n_act = action_space.shape[0]
         self.num_inputs, self.n_act, self.hidden = num_inputs, n_act, hidden
+        # NODE fit over trajectory windows of ``node_horizon`` consecutive transitions (fit_node_windows); 1: the
+        # reference's one-step fit, the path as it was.  ``node_stride``: replay rows between consecutive steps of one
+        # trajectory (the lane count of a driver that pushes one row per lane per step)
+        self.node_horizon, self.node_stride = node_fit_options(args)
         # gradient slabs of the actor / critic arenas (row ranges whose weight-gradient partials the optimiser sums).  8 for
         # the usual batches; 16 from batch 16384 on: a slab is then still >= 1024 rows and mlp_bwd_wide has twice the
         # workgroups (measured at B = 32768: 184 -> 159 us per launch; 128 x 128 output tiles instead — half the operand
@@ -190,6 +195,7 @@ class SAC_CBF_CLF(object):
         self._ws = {}
         self._noise = None
         self._fit_ws = {}
+        self._fit_win_ws = {}                 # fit_node_windows' buffers per (rows, horizon)
         self._fill = collections.deque()      # pieces of part 1 not yet queued (see _upd_part1)
         self._fill_first = True               # the next solver wait is the first of its update
         self._readback = ScalarsReadback(self.sc)
@@ -381,6 +387,8 @@ class SAC_CBF_CLF(object):
         #  wrapped reports 0 — the reference would then sample zero rows and fail — and the fit takes the filled size)
         nb = min(NODE_memory.position or len(NODE_memory), 32768) if fit else 0
         fit = fit and nb > 0
+        if fit and self.node_horizon > 1:            # multi-step fit on trajectory windows (same draw order: below)
+            return self._update_with_window_fit(memory, batch_size, updates, NODE_memory, nb)
         if hasattr(memory, "sample_rows"):           # replay resident in HBM: gather on the device
             ws = self._workspace(batch_size)
             eps_ready = self._noise is None and getattr(memory, "device_rng", False)
@@ -484,6 +492,89 @@ class SAC_CBF_CLF(object):
         used = self.task.fit_solver.accumulate_param_grads(
             self.ar_n, max(1, min(self.n_fit_slabs, self.ar_n.n_slabs // min(n_steps, self.ar_n.n_slabs))))
         self._adam(self.ar_n, 1e-3, used, extra=self.sc[SC.SC_NODE_LOSS:SC.SC_NODE_LOSS + 1])
+
+    # -- multi-step NODE fit on trajectory windows (node_horizon > 1) ------------------------
+    def _update_with_window_fit(self, memory, batch_size, updates, NODE_memory, nb):
+        """``update_parameters`` when a multi-step fit is due: minibatch draw, window draw (the reference's order:
+        minibatch first, then the NODE rows), the fit, the update."""
+        H, stride = self.node_horizon, self.node_stride
+        on_device = hasattr(memory, "sample_rows")
+        if on_device:
+            ws = self._workspace(batch_size)
+            eps_ready = self._noise is None and getattr(memory, "device_rng", False)
+            memory.sample_rows(batch_size, out=ws.mb, **({"eps_out": ws.eps} if eps_ready else {}))
+        else:
+            batch = memory.sample(batch_size=batch_size)
+        if (H - 1) * stride < len(NODE_memory):      # (a replay shorter than one window: nothing to fit on yet)
+            if hasattr(NODE_memory, "sample_windows") and hasattr(NODE_memory, "sample_rows"):
+                rows, valid = NODE_memory.sample_windows(nb, H, stride)
+                self.fit_node_windows(rows, valid, NODE_memory.window_counts)
+            else:                                    # host replay: its own rule, packed step by step
+                fields, valid = NODE_memory.sample_windows(nb, H, stride)
+                rows = torch.stack([self._rows_from_host(tuple(f[k] for f in fields)) for k in range(H)])
+                self.fit_node_windows(rows.to(self.device), torch.from_numpy(valid.astype(np.float32)))
+        if on_device:
+            return self.update_on_device(ws, updates, eps_ready=eps_ready)
+        return self.update_from_host(batch, updates, None)
+
+    def fit_node_windows(self, rows, valid=None, counts=None):
+        """One Adam step of the NODE regression over trajectory windows: ``rows`` (H, N, LD) minibatch-layout rows on
+        the device, step k of window i at ``rows[k, i]`` (``DeviceReplayMemory.sample_windows``); ``valid`` (N,): windows
+        with 0 do not count (None: all do); ``counts``: the int32 sums of ``valid`` per 256 windows where the caller has
+        them (``DeviceReplayMemory.window_counts``), else formed here.
+
+        x_0 = state(obs of step 0), target_k = state(next_obs of step k), the carried columns of step k as ``fit_inputs``
+        forms them; the H intervals are ONE solve (``ode_traj.solve``: one launch forward, one backward and one
+        weight-gradient pass for euler / rk4, chained interval by interval for dopri5), the loss ``nlbac_traj_mse_fwd_bwd``
+        (masked MSE, normalised by valid windows x H x n_s) lands in the scalars block where the one-step fit leaves
+        its own, and the agent's Adam kernel steps the NODE arena.  Runs eagerly (never captured into a hipGraph)."""
+        from .. import ode_traj as T
+        from ..rollout import _one_launch_ok
+        if self.world > 1:
+            raise RuntimeError("fit_node_windows: trajectory windows are not sharded over GPUs; use node_horizon = 1 "
+                               "under enable_data_parallel")
+        if rows.dim() != 3 or rows.shape[2] != self.lay.LD or rows.dtype != torch.float32 or not rows.is_cuda:
+            raise ValueError("fit_node_windows: rows must be a float32 device tensor (H, N, %d); got %s"
+                             % (self.lay.LD, tuple(rows.shape)))
+        rows = rows.contiguous()
+        H, N, LD = rows.shape
+        task, lay, model, ns = self.task, self.lay, self.neural_ode_model, self.task.n_s
+        self._fill.clear()      # (as _fit: pieces of an update that raised half-way must not run behind this fit)
+        w = self._fit_windows_ws(N, H)
+        if valid is not None and counts is None:
+            valid, counts = valid_counts(valid, N, self.device)
+        elif valid is not None:
+            valid = valid.to(self.device, torch.float32).contiguous()
+            assert valid.numel() == N and counts.numel() == (N + 255) // 256 and counts.dtype == torch.int32
+        # every step's rows as one (H N, LD) block: the task's hooks read them in place
+        flat = rows.view(H * N, LD)
+        p_obs, obs_ld, ctl, p_nobs, nobs_ld, _ = task.fit_inputs(flat)
+        task.state_rows(p_obs, obs_ld, N, w["x0"])                      # step 0's observation
+        task.state_rows(p_nobs, nobs_ld, H * N, w["target"])            # every step's next observation
+        w["u"].view(H * N, -1).copy_(ctl)                               # every step's carried columns
+        dt = float(torch.tensor([0.0, float(self.env.dt)], dtype=torch.float32)[1])      # (as odeint's time grid rounds it)
+        kept = T.solve(model, T.EqualSteps(dt, H), self.solver, "params", _one_launch_ok(model, self.solver),
+                       w["x0"], w["u"], w["xs"], self.atol, self.rtol)
+        dout = w["dout"]                                                # (H + 1, N, n_s); dout[0] stays zero
+        traj_mse_launch(w["xs"], w["target"], valid, counts, H, N, ns, dout[1:], w["part"],
+                        self.sc.data_ptr() + 4 * SC.SC_NODE_LOSS)
+        _, _, flat_grad = kept.backward(dout, need_p=True)
+        a = self.ar_n
+        used = a.n_slabs                  # one launch: the weight-gradient pass left its slab partials in the arena
+        if isinstance(kept, T.Chain):     # chained: every interval reduced its own slabs; their sum goes in as slab 0
+            a.grad[0].copy_(flat_grad)
+            used = 1
+        self._adam(a, 1e-3, used, extra=self.sc[SC.SC_NODE_LOSS:SC.SC_NODE_LOSS + 1])
+
+    def _fit_windows_ws(self, N, H):
+        if (N, H) not in self._fit_win_ws:
+            while len(self._fit_win_ws) >= 2:       # as _fit_ws: the fit batch grows with the replay
+                self._fit_win_ws.pop(next(iter(self._fit_win_ws)))
+            z, ns = self.task.z, self.task.n_s
+            nc = self.neural_ode_model.n_u if self.neural_ode_model.affine else self.neural_ode_model.n_carry
+            self._fit_win_ws[(N, H)] = dict(x0=z(N, ns), target=z(H, N, ns), u=z(H, N, nc), xs=z(H, N, ns),
+                                            dout=z(H + 1, N, ns), part=z(loss_blocks(H, N, ns)))
+        return self._fit_win_ws[(N, H)]
 
     # -- the update proper --------------------------------------------------------
     def _plan(self, ws, NP=None):

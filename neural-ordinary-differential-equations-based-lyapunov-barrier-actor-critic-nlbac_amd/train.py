@@ -36,6 +36,9 @@ def get_args(argv=None):
     p.add_argument('--target_update_interval', type=int, default=1)
     p.add_argument('--Lagrangian_multiplier_update_interval', type=int, default=8)
     p.add_argument('--NODE_model_update_interval', type=int, default=10)
+    p.add_argument('--node_horizon', type=int, default=1,
+                   help="H > 1: fit the NODE on trajectory windows of H consecutive transitions (multi-step rollout loss, "
+                        "SAC_CBF_CLF.fit_node_windows); 1: the reference's one-step fit")
     p.add_argument('--backup_update_interval', type=int, default=20)
     p.add_argument('--replay_size', type=int, default=10000000)
     p.add_argument('--cuda', action="store_true")
@@ -312,6 +315,7 @@ def train_vectorized(agent, env, args, n_steps, log=print, memory=None, check=No
     from .sac_cbf_clf.replay_memory import DeviceReplayMemory
     dev, lay, N = agent.device, agent.lay, env.n
     barrier = lay.sig is not None
+    agent.node_stride = N          # one row per lane per step: a lane's consecutive transitions lie N rows apart
     if memory is None:
         memory = DeviceReplayMemory(args.replay_size, args.seed, agent, device_rng=True)
     lo = torch.as_tensor(np.asarray(env.action_space.low), dtype=torch.float32, device=dev)

@@ -902,6 +902,38 @@ int nlbac_concat_adj_step(const nlbac_mlp *net, const float *c, int P, int rows_
                           float *acts, long acts_ls, float *dz, float *interp_out /* ABI 8, as nlbac_node_adj_step; or NULL */,
                           double t_end, nlbac_stream_t s);
 
+/* The continuous adjoint over a whole horizon in ONE launch (rollout / odeint_grid with adjoint=True; euler, rk4):
+ * torchdiffeq's OdeintAdjointMethod.backward on a grid.  A RUN of N fine intervals is walked last to first with the
+ * stage body of nlbac_node_adj_step / nlbac_concat_adj_step (their register-resident kernels; *_adj_traj_ok says whether
+ * the nets are served, other shapes are refused), z = [y | a_x | a_c] in LDS from the run's top to its end.  hs [N]: the
+ * fine steps (device) with hs_host [N] beside them for the checks; begin / begin_host [N]: fine interval i is the upper
+ * end of output interval begin[i] in [0, H), or -1 — there y is reset to out[k+1] ([H+1][n][out_ld], the state in the
+ * first n_s columns), a_x becomes dout[k+1] + a_x ([H+1][n][n_s]; just dout[k+1] when `top` and i = N-1: the horizon's
+ * end) and a_c starts at zero; begin[N-1] >= 0.  Behind an output interval's last fine step (the next lower marker, or
+ * i = 0) a_c goes to du + k du_stride (du_stride = n n_c: stacked, rollout) or is added to du (du_stride = 0: summed,
+ * odeint_grid; `top` assigns the first).  Controls of output interval k at u + k u_stride (n n_c, or 0: one set for
+ * all).  carry [n][W]: read at the run's top unless `top`, written at its end — z between two runs of a horizon cut
+ * into several launches, whose du / carry bits are those of the one launch; dx0 = dout[0] + carry[:, n_s:2 n_s] after
+ * the last run.  Refused without a launch: N, n, H < 1, a non-positive or non-finite step, N n_stages n >= 2^31.
+ * KEEP (all pointers or none): every stage's rows at block (i n_stages + st) of N n_stages n rows — ZS [.][W] the stage
+ * inputs (layer 0 reads the first n_s columns), acts_* / dz_* [layer][N S n][hid] (layer strides acts_*_ls), and the
+ * output cotangents dK [.][n_s] (f_net), dG [.][n_s n_u] (g_net); single-net form: Xin [.][in_dim], Ay [.][n_s], acts, dz.
+ * Every cotangent row (dK, dG, Ay, dz) is stored times h c_out[st], so that ONE nlbac_mlp_bwd_weights launch over the
+ * N n_stages n rows sums the run's share of the parameter adjoint. */
+int nlbac_node_adj_traj_ok(const nlbac_mlp *f, const nlbac_mlp *g);
+int nlbac_node_adj_traj(const nlbac_mlp *f, const nlbac_mlp *g, int n, int N, int H, int n_stages, const float *beta,
+                        const float *c_out, const float *hs, const float *hs_host, const int *begin,
+                        const int *begin_host, const float *out, int out_ld, const float *dout, const float *u,
+                        long u_stride, float *du, long du_stride, float *carry, int top, float *ZS, float *dK, float *dG,
+                        float *acts_f, long acts_f_ls, float *acts_g, long acts_g_ls, float *dz_f, float *dz_g,
+                        nlbac_stream_t s);
+int nlbac_concat_adj_traj_ok(const nlbac_mlp *net);
+int nlbac_concat_adj_traj(const nlbac_mlp *net, int n, int N, int H, int n_stages, const float *beta, const float *c_out,
+                          const float *hs, const float *hs_host, const int *begin, const int *begin_host,
+                          const float *out, int out_ld, const float *dout, const float *c, long c_stride, float *dc,
+                          long dc_stride, float *carry, int top, const float *norm, float *Xin, float *Ay, float *acts,
+                          long acts_ls, float *dz, nlbac_stream_t s);
+
 /* Strided block copy of 32-bit words: block b (block_len words) from src + b*src_stride to dst + b*dst_stride —
  * a row range of a stage-major solver buffer in one launch (hands a problem's first attempted dopri5 step to its
  * own solver when the problems of a joint solve stop agreeing on accept / done). */

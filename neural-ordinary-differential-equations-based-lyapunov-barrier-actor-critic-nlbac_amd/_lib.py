@@ -159,6 +159,15 @@ _PROTOS = {
     "nlbac_concat_adj_step": [C.POINTER(Mlp), _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P,
                               _P, _P, _P, _P, _L, _P, _P, _D, _P],
     "nlbac_node_adj_interp_ok": [C.POINTER(Mlp), C.POINTER(Mlp)],
+    # the adjoint over a run of fine intervals in one launch (rollout / odeint_grid with adjoint=True): nets, n, N, H,
+    # stages, beta, c_sol, steps (device, host), output-interval markers (device, host), out, out_ld, dout, controls and
+    # their stride, du and its stride, carry, top, then what KEEP writes
+    "nlbac_node_adj_traj_ok": [C.POINTER(Mlp), C.POINTER(Mlp)],
+    "nlbac_node_adj_traj": [C.POINTER(Mlp), C.POINTER(Mlp), _I, _I, _I, _I, c_float_p, c_float_p, _P, c_float_p, _P,
+                            C.POINTER(C.c_int), _P, _I, _P, _P, _L, _P, _L, _P, _I, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P],
+    "nlbac_concat_adj_traj_ok": [C.POINTER(Mlp)],
+    "nlbac_concat_adj_traj": [C.POINTER(Mlp), _I, _I, _I, _I, c_float_p, c_float_p, _P, c_float_p, _P,
+                              C.POINTER(C.c_int), _P, _I, _P, _P, _L, _P, _L, _P, _I, _P, _P, _P, _P, _L, _P, _P],
     "nlbac_reduce_slabs": [_P, _P, _I, _L, _L, _P],
     "nlbac_soft_update": [_P, _P, _L, _F, _P],
     "nlbac_gauss_sample_fwd": [_P, _I, _P, _P, _P, _I, _I, _P, _I, _P, _P],

@@ -207,6 +207,37 @@ class AffineAdjoint:
                       du.data_ptr() if du is not None else None, s)
         return du, dy0
 
+    # -- an output interval solved backwards in fine steps (rollout / odeint_grid with adjoint=True and step_size, chained) --
+    def adjoint_grid_begin(self, n, method, need_params, atol=1e-7, rtol=1e-5):
+        """Start a chained grid adjoint on ``n`` rows (``ode_traj.ChainSubAdjoint``): a solve state of its own — no
+        forward of this solver precedes it — and, with ``need_params``, the zeroed parameter adjoint."""
+        self._touch(n)
+        self.ctx = dict(P=1, rpp=n, n=n, method=method, t_end=0.0, atol=atol, rtol=rtol)
+        S = len(TABLEAU[method]["c_sol"])
+        w = self._adj_ws(n, S)
+        self._adj_par_cur = self._adj_params_begin(w, n, S) if need_params else None
+        return self._adj_par_cur
+
+    def adjoint_interval(self, y_end, a_end, u, method, hs, par):
+        """One output interval: z = [``y_end`` | ``a_end`` | 0] at its upper end carried through the fine steps ``hs``
+        (applied in that order, from the upper end down) — one nlbac_*_adj_step launch per fine step, Z0 <-> Z1 swapped
+        in between, no reset inside; with ``par`` the parameter adjoint goes on accumulating, th1 = th0 + h sum c_sol[j]
+        K_theta[j] (nlbac_adj_param_norm mode 2), th0 <-> th1 swapped likewise.  Returns (du, dy0) in the solver's buffers."""
+        n, ns, nu, s = self.ctx["n"], self.n_s, self.n_u, stream_ptr()
+        tab = TABLEAU[method]
+        S, c_sol = len(tab["c_sol"]), fptr(*tab["c_sol"])
+        w = self._adj_ws(n, S)
+        _lib.call("nlbac_adj_pack", y_end.data_ptr(), a_end.data_ptr(), ns, nu, n, w["Z0"].data_ptr(), s)
+        for h in hs:
+            self._adj_step(w, u, 1, n, method, 0, S, h_host=[h], c_out=c_sol, keep=par and par["keep"])
+            w["Z0"], w["Z1"] = w["Z1"], w["Z0"]
+            if par:
+                self._adj_params_norm(par, 2, None, h_host=h, c_sol=c_sol)
+                par["th0"], par["th1"] = par["th1"], par["th0"]
+        du, dy0 = self._buf("du", n, nu), self._buf("dy0_adj", n, ns)
+        _lib.call("nlbac_adj_unpack", w["Z0"].data_ptr(), ns, nu, n, dy0.data_ptr(), du.data_ptr(), s)
+        return du, dy0
+
     def _adj_dopri(self, w, u, P, rpp, par):
         ctx = self.ctx
         n, S, s = ctx["n"], 7, stream_ptr()

@@ -131,7 +131,17 @@ def _steps(func, y0, t, method, step_size=None):
     return hs
 
 
-def odeint_grid(func, y0, t, *, method="rk4", step_size=None):
+def _adjoint_steps(t, step_size):
+    """Per grid interval [t[j-1], t[j]] the fine steps of its backward solve under ``adjoint=True``, in the order they are
+    applied from the interval's upper end: the interval's one step (``_steps_of``), or with ``step_size`` the steps
+    ``_sub_grid`` gives for [0, length] — the interval's own fine grid, anchored at its upper end."""
+    if step_size is None:
+        return [(h,) for h in _steps_of(t)]
+    times = [float(v) for v in (t if isinstance(t, torch.Tensor) else torch.as_tensor(t, dtype=torch.float64)).detach().cpu()]
+    return [_sub_grid([0.0, b - a], step_size)[1] for a, b in zip(times, times[1:])]
+
+
+def odeint_grid(func, y0, t, *, method="rk4", step_size=None, adjoint=False, adjoint_chunk=None):
     """The solution of the NODE ``func`` (either form; a model owned by an agent included) at every point of the time
     grid ``t`` (1-D tensor or sequence, T >= 2 finite strictly increasing times): returns ``out`` (T, B, n_s + n_c) with
     ``out[0] = y0`` and
@@ -160,11 +170,22 @@ def odeint_grid(func, y0, t, *, method="rk4", step_size=None):
     ``torch.no_grad``, ReLU mask words for input gradients only, activation rows as well for parameter gradients
     (memory grows linearly with the number of steps — T - 1, or with ``step_size`` the N fine intervals, not T: the fine
     states themselves and their gradients are never stored; see ``rollout`` on the last bits of the values under input
-    gradients only)."""
+    gradients only).
+
+    ``adjoint=True``: the same ``out``, differentiated by the continuous adjoint on the grid — torchdiffeq's
+    ``OdeintAdjointMethod.backward``: the grid intervals are walked last to first, the state restarts at the stored
+    ``out[k+1]``, the output's gradient joins the adjoint there, and every stage is re-computed; without ``step_size`` the
+    autograd chain of ``odeint_adjoint`` calls over the grid intervals (bit for bit in the gradient w.r.t. ``y0``).
+    Nothing is kept but ``out``.  With ``step_size`` every grid interval is solved backwards on its own fine grid,
+    anchored at its upper end (``_sub_grid`` over [0, t[j] - t[j-1]]).  ``adjoint_chunk`` as in ``rollout``."""
+    T.check_adjoint_chunk("odeint_grid", adjoint, adjoint_chunk)
     hs = _steps(func, y0, t, method, step_size)
     params = tuple(func.parameters())
     mode = T.keep_mode(params, y0)
     func.refresh_device_weights()
+    if adjoint:
+        plan = T.AdjointPlan(_adjoint_steps(t, step_size), False, adjoint_chunk, step_size is not None)
+        return _GridAdjointFunction.apply(func, method, hs, mode, plan, y0, *params)
     return _GridFunction.apply(func, method, hs, mode, y0, *params)
 
 
@@ -201,3 +222,41 @@ class _GridFunction(torch.autograd.Function):
             gy0 = torch.cat([dx0, dout[0][:, ns:] + (dc + ctx.iv.sum_copied(dout[1:, :, ns:]))], dim=1)
         gp = T.param_grads(ctx.func, flat) if need_p else [None] * ctx.n_params
         return (None, None, None, None, gy0, *gp)
+
+
+class _GridAdjointFunction(torch.autograd.Function):
+    """``odeint_grid(adjoint=True)``: what is saved for the backward is ``out`` (as a saved tensor); the carried columns
+    are read from it."""
+
+    @staticmethod
+    def forward(ctx, func, method, hs, mode, plan, y0, *params):
+        n, ns = y0.shape[0], func.n_s
+        y0 = y0.detach().contiguous()
+        x0, c = y0[:, :ns].contiguous(), y0[:, ns:].contiguous()
+        dev = y0.device
+        iv = T.SubGridSteps(*hs[1:], dev) if isinstance(hs[0], tuple) else T.GridSteps(hs, dev)
+        H = iv.n_out
+        xs = torch.empty(H, n, ns, dtype=torch.float32, device=dev)
+        ctx.func, ctx.mode, ctx.n_params, ctx.iv = func, mode, len(params), iv
+        ctx.kept = T.solve_adjoint(func, iv, method, mode, rollout._one_launch_ok(func, method), plan, x0, c, xs)
+        out = torch.empty(H + 1, n, y0.shape[1], dtype=torch.float32, device=dev)
+        out[0].copy_(y0)
+        out[1:, :, :ns].copy_(xs)
+        out[1:, :, ns:].copy_(c)
+        if ctx.kept is not None:
+            ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        assert ctx.kept is not None, "odeint_grid: nothing was kept for a backward (the forward ran without gradients)"
+        out, = ctx.saved_tensors
+        ns = ctx.func.n_s
+        dout = dout.float()
+        need_p = ctx.mode == "params" and any(ctx.needs_input_grad[6:])
+        dx0, dc, flat = ctx.kept.backward(out, dout[:, :, :ns].contiguous(), need_p)
+        gy0 = None
+        if ctx.needs_input_grad[5]:
+            gy0 = torch.cat([dx0, dout[0][:, ns:] + (dc + ctx.iv.sum_copied(dout[1:, :, ns:]))], dim=1)
+        gp = T.param_grads(ctx.func, flat) if need_p else [None] * ctx.n_params
+        return (None, None, None, None, None, gy0, *gp)

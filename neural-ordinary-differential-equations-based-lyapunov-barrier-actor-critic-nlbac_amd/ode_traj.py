@@ -7,7 +7,11 @@
     controls' gradient looks like, where the outputs and their gradients meet the intervals;
   * what a solve keeps and how its backward becomes gradients, one class per path — ``AffineTraj`` / ``ConcatTraj`` (one
     launch forward, one backward, + the weight-gradient launch over all H * stages * rows) and ``Chain`` (H one-interval
-    solves on the existing solvers) — each with ``forward(x0, u, xs)`` and ``backward(dout, need_p)``; ``solve`` picks.
+    solves on the existing solvers) — each with ``forward(x0, u, xs)`` and ``backward(dout, need_p)``; ``solve`` picks;
+  * the same under ``adjoint=True`` (``solve_adjoint``): nothing kept but the outputs the caller holds and the controls —
+    ``AdjointPlan`` (per output interval the fine steps of its backward solve, the chunk), ``AffineAdjTraj`` /
+    ``ConcatAdjTraj`` (the continuous adjoint over the whole horizon in one ``nlbac_*_adj_traj`` launch per chunk),
+    ``ChainAdjoint`` / ``ChainSubAdjoint`` (chained), each with ``backward(out, dout, need_p)``.
 """
 import ctypes as C
 
@@ -378,12 +382,15 @@ class Chain:
     ``solvers_key`` (apart from ``odeint``'s and any agent task's): one solver per interval when a backward follows (each
     keeps its interval's state), one for all intervals otherwise."""
 
-    def __init__(self, func, n, iv, method, mode, atol, rtol):
+    def __init__(self, func, n, iv, method, mode, atol, rtol, adjoint=False):
+        # (adjoint: solvers of their own whose backward is the continuous adjoint of their interval — the chain of
+        #  one-interval ``odeint_adjoint`` calls; each keeps its interval's end state and controls, nothing else)
         self.func, self.n, self.iv, self.method, self.mode, self.tol = func, n, iv, method, mode, (atol, rtol)
-        lst = func.__dict__.setdefault(iv.solvers_key, {}).setdefault(mode, [])
+        lst = func.__dict__.setdefault(iv.solvers_key + ("_adj" if adjoint else ""), {}).setdefault(mode, [])
         for _ in range((1 if mode == "none" else iv.H) - len(lst)):
             sv = traj_class(func).Solver(func, func.device_handles()[0].arena.device)
-            sv.keep_acts = mode != "inputs"      # (no grad: the same kernels as odeint's solver; nothing is read back)
+            sv.keep_acts = adjoint or mode != "inputs"      # (no grad: the same kernels as odeint's solver; nothing is read back)
+            sv.adjoint = bool(adjoint)
             lst.append(sv)
         self.svs = lst[:iv.H]
 
@@ -410,6 +417,273 @@ class Chain:
                 fk = _reduce(arena, sv.accumulate_param_grads(arena, iv.slabs(arena, sv)))
                 flat = fk if flat is None else flat + fk
         return dout[0] + carry, du_all, flat
+
+
+def check_adjoint_chunk(api, adjoint, adjoint_chunk, chained=False):
+    """``adjoint_chunk`` is a positive int or None, goes with ``adjoint=True`` only, and not with a backward that has no
+    chunks (``chained``: rollout's dopri5)."""
+    if adjoint_chunk is None:
+        return
+    if isinstance(adjoint_chunk, bool) or not isinstance(adjoint_chunk, int) or adjoint_chunk < 1:
+        raise ValueError("%s: adjoint_chunk must be a positive int (output intervals per backward launch) or None; got %r"
+                         % (api, adjoint_chunk))
+    if not adjoint:
+        raise ValueError("%s: adjoint_chunk goes with adjoint=True (the direct backward is one launch over the whole "
+                         "horizon); got adjoint_chunk=%r with adjoint=False" % (api, adjoint_chunk))
+    if chained:
+        raise ValueError("%s: adjoint_chunk goes with method='euler' or 'rk4'; dopri5's backward is a chain of "
+                         "one-interval adjoint solves, which has no chunks" % api)
+
+
+class AdjointPlan:
+    """What ``adjoint=True`` adds to a solve: per OUTPUT interval (a control interval of ``rollout``, [t[j-1], t[j]] of
+    ``odeint_grid``) the fine steps of its backward solve, in the order they are applied from the interval's upper end
+    (one step without ``step_size``; else ``ode_grid._sub_grid`` over [0, length]: the cut step falls at the lower
+    end); whether the controls come one set per output interval with their gradient stacked (``rollout``) or one set
+    for all with the gradient summed (``odeint_grid``); and the caller's ``adjoint_chunk``."""
+
+    def __init__(self, steps, stacked, chunk=None, sub=False):
+        self.steps, self.stacked, self.chunk, self.sub = tuple(tuple(s) for s in steps), stacked, chunk, sub
+        self.H = len(self.steps)
+
+    def run(self, lo, hi):
+        """The fine intervals of the run over the output intervals lo <= k < hi, in ascending order (the launch walks
+        them last to first): their steps, and the output interval whose upper end each one is (-1: none)."""
+        hs, begin = [], []
+        for k in range(lo, hi):
+            hs += list(reversed(self.steps[k]))
+            begin += [-1] * (len(self.steps[k]) - 1) + [k]
+        return hs, begin
+
+    def runs(self, chunk):
+        """The runs of a backward in chunks of ``chunk`` output intervals, last run first: (lo, hi) each."""
+        return [(max(0, hi - chunk), hi) for hi in range(self.H, 0, -chunk)]
+
+    def pick_chunk(self, rows_limit, n, S):
+        """The largest chunk (whole output intervals) none of whose runs has ``rows_limit`` stage rows or more."""
+        if self.chunk is not None:
+            return min(self.chunk, self.H)
+        for chunk in range(self.H, 1, -1):
+            if all(sum(len(self.steps[k]) for k in range(lo, hi)) * S * n < rows_limit for lo, hi in self.runs(chunk)):
+                return chunk
+        return 1
+
+
+DW_ROWS_SLACK = 16 * 8      # per slab: the rows the weight-gradient ring requests past the end (mlp_dw16_kernels.hip)
+
+
+def _dw_rows_limit(hid, n_slabs):
+    """Rows one nlbac_mlp_bwd_weights launch takes for nets of width ``hid``: fewer than 2^29 elements per layer (up to
+    112 units the launch refuses more; wider nets would fall from their 64-row-staged kernel, 256-wide tiles, to the
+    older one)."""
+    return (2 ** 29 - 1) // (hid if hid <= 112 else 256) - DW_ROWS_SLACK * n_slabs - 4
+
+
+class _AdjTraj:
+    """The one-launch backward of ``adjoint=True``: nothing of the forward is kept but the outputs the caller holds and
+    the controls.  The forward is the direct path's in keep-mode "none" (its K / Y / G scratch dropped when it returns);
+    the backward walks the horizon last to first in runs of whole output intervals — one ``nlbac_*_adj_traj`` launch per
+    run, a carry row handing z = [y | a_x | a_c] from run to run — and, with parameter gradients, one
+    ``nlbac_mlp_bwd_weights`` + ``nlbac_reduce_slabs`` per run over what the launch kept of every stage, the runs'
+    flat gradients summed last run first.  Kept buffers are sized by the chunk, not by the horizon."""
+
+    def __init__(self, func, n, iv, method, plan, device):
+        self.func, self.n, self.iv, self.method, self.plan, self.device = func, n, iv, method, plan, device
+        self.S, self.beta, self.c_out = _tableau(method)
+        self.ns = func.n_s
+        self._arrays = {}
+
+    def forward(self, x0, u, xs):
+        self.u = u
+        self.Direct(self.func, self.n, self.iv, self.method, "none", self.device).forward(x0, u, xs)
+
+    def _run_arrays(self, lo, hi):
+        a = self._arrays.get((lo, hi))
+        if a is None:      # steps and markers twice: on the device for the kernel, in host memory for the launcher's checks
+            hs, begin = self.plan.run(lo, hi)
+            a = self._arrays[(lo, hi)] = (torch.tensor(hs, dtype=torch.float32, device=self.device), fptr(*hs),
+                                          torch.tensor(begin, dtype=torch.int32, device=self.device),
+                                          (C.c_int * len(begin))(*begin), len(hs))
+        return a
+
+    def backward(self, out, dout, need_p):
+        n, ns, nc, S, plan, dev = self.n, self.ns, self.nc, self.S, self.plan, self.device
+        W = 2 * ns + nc
+        z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        limit = min(self.rows_limit(), 2 ** 31) if need_p else 2 ** 31
+        chunk = self.chunk_used = plan.pick_chunk(limit, n, S)
+        runs = plan.runs(chunk)
+        carry = z(n, W)
+        du = z(plan.H, n, nc) if plan.stacked else z(n, nc)
+        stride = n * nc if plan.stacked else 0
+        rows_max = max(self._run_arrays(lo, hi)[4] for lo, hi in runs) * S * n
+        keep = self.keep_buffers(z, rows_max) if need_p else None
+        flat = None
+        for lo, hi in runs:
+            hs_d, hs_h, bg_d, bg_h, N = self._run_arrays(lo, hi)
+            self.launch(n, N, plan.H, hs_d.data_ptr(), hs_h, bg_d.data_ptr(), bg_h, out.data_ptr(), out.shape[2],
+                        dout.data_ptr(), self.u.data_ptr(), stride, du.data_ptr(), stride, carry.data_ptr(),
+                        1 if hi == plan.H else 0, keep, N * S * n)
+            if need_p:
+                fk = self.weight_grads(keep, N * S * n)
+                flat = fk if flat is None else flat + fk
+        return dout[0] + carry[:, ns:2 * ns], du, flat
+
+
+class AffineAdjTraj(_AdjTraj):
+    """``_AdjTraj`` of the control-affine NODE: ``nlbac_node_adj_traj``."""
+    Direct = AffineTraj
+
+    @staticmethod
+    def ok(func):
+        f, g = func.device_handles()
+        return _lib.load().nlbac_node_adj_traj_ok(C.byref(f.desc), C.byref(g.desc)) == 1
+
+    def __init__(self, func, n, iv, method, plan, device):
+        _AdjTraj.__init__(self, func, n, iv, method, plan, device)
+        self.f, self.g = func.device_handles()
+        self.nc = func.n_u
+
+    def rows_limit(self):
+        return _dw_rows_limit(max(self.f.hid, self.g.hid), self.f.arena.n_slabs)
+
+    def keep_buffers(self, z, rows):
+        f, g, ns, nu = self.f, self.g, self.ns, self.nc
+        return dict(ZS=z(rows, 2 * ns + nu), dK=z(rows, ns), dG=z(rows, ns * nu), acts_f=z((f.n_layers - 1) * rows * f.hid),
+                    acts_g=z((g.n_layers - 1) * rows * g.hid), dz_f=z((f.n_layers - 1) * rows * f.hid),
+                    dz_g=z((g.n_layers - 1) * rows * g.hid))
+
+    def launch(self, n, N, H, hs, hs_host, begin, begin_host, out, out_ld, dout, u, u_stride, du, du_stride, carry, top,
+               keep, rows):
+        k = keep or {}
+        _lib.call("nlbac_node_adj_traj", C.byref(self.f.desc), C.byref(self.g.desc), n, N, H, self.S, self.beta, self.c_out,
+                  hs, hs_host, begin, begin_host, out, out_ld, dout, u, u_stride, du, du_stride, carry, top,
+                  _ptr(k.get("ZS")), _ptr(k.get("dK")), _ptr(k.get("dG")), _ptr(k.get("acts_f")), rows * self.f.hid,
+                  _ptr(k.get("acts_g")), rows * self.g.hid, _ptr(k.get("dz_f")), _ptr(k.get("dz_g")), stream_ptr())
+
+    def weight_grads(self, k, rows):
+        arena, ns, nu = self.f.arena, self.ns, self.nc
+        io = io_array(2)
+        for i, (net, dy, ld, acts, dz) in enumerate(((self.f, k["dK"], ns, k["acts_f"], k["dz_f"]),
+                                                     (self.g, k["dG"], ns * nu, k["acts_g"], k["dz_g"]))):
+            io[i].x0, io[i].x0_dim, io[i].x0_ld = k["ZS"].data_ptr(), ns, 2 * ns + nu
+            io[i].dy, io[i].dy_ld = dy.data_ptr(), ld
+            io[i].acts, io[i].acts_ls = acts.data_ptr(), rows * net.hid
+            io[i].dz = dz.data_ptr()
+            io[i].grad = arena.grad.data_ptr()
+        bwd_weights(mlp_array([self.f.desc, self.g.desc]), io, 2, rows, arena.n_slabs, arena.n, self.device)
+        return _reduce(arena, arena.n_slabs)
+
+
+class ConcatAdjTraj(_AdjTraj):
+    """``_AdjTraj`` of the single-net NODE (normalised or not): ``nlbac_concat_adj_traj``."""
+    Direct = ConcatTraj
+
+    @staticmethod
+    def ok(func):
+        return _lib.load().nlbac_concat_adj_traj_ok(C.byref(func.device_handles()[0].desc)) == 1
+
+    def __init__(self, func, n, iv, method, plan, device):
+        _AdjTraj.__init__(self, func, n, iv, method, plan, device)
+        self.net = func.device_handles()[0]
+        self.nc = func.n_carry
+        self.norm = func.norm_device() if getattr(func, "normalized", False) else None
+
+    def rows_limit(self):
+        return _dw_rows_limit(self.net.hid, self.net.arena.n_slabs)
+
+    def keep_buffers(self, z, rows):
+        net = self.net
+        return dict(Xin=z(rows, net.in_dim), Ay=z(rows, self.ns), acts=z((net.n_layers - 1) * rows * net.hid),
+                    dz=z((net.n_layers - 1) * rows * net.hid))
+
+    def launch(self, n, N, H, hs, hs_host, begin, begin_host, out, out_ld, dout, u, u_stride, du, du_stride, carry, top,
+               keep, rows):
+        k = keep or {}
+        _lib.call("nlbac_concat_adj_traj", C.byref(self.net.desc), n, N, H, self.S, self.beta, self.c_out, hs, hs_host,
+                  begin, begin_host, out, out_ld, dout, u, u_stride, du, du_stride, carry, top, _ptr(self.norm),
+                  _ptr(k.get("Xin")), _ptr(k.get("Ay")), _ptr(k.get("acts")), rows * self.net.hid, _ptr(k.get("dz")),
+                  stream_ptr())
+
+    def weight_grads(self, k, rows):
+        net, arena = self.net, self.net.arena
+        io = io_array(1)
+        io[0].x0, io[0].x0_dim, io[0].x0_ld = k["Xin"].data_ptr(), net.in_dim, net.in_dim
+        io[0].dy, io[0].dy_ld = k["Ay"].data_ptr(), self.ns
+        io[0].acts, io[0].acts_ls = k["acts"].data_ptr(), rows * net.hid
+        io[0].dz = k["dz"].data_ptr()
+        io[0].grad = arena.grad.data_ptr()
+        bwd_weights(mlp_array([net.desc]), io, 1, rows, arena.n_slabs, arena.n, self.device)
+        return _reduce(arena, arena.n_slabs)
+
+
+def adj_traj_class(func):
+    return AffineAdjTraj if func.affine else ConcatAdjTraj
+
+
+class ChainAdjoint(Chain):
+    """The chained path of ``adjoint=True`` without ``step_size`` (dopri5, shapes the kernels refuse, ``ONE_LAUNCH =
+    False``): ``Chain`` with the continuous adjoint on its solvers — H one-interval ``odeint_adjoint`` solves."""
+
+    def __init__(self, func, n, iv, method, mode, atol, rtol):
+        Chain.__init__(self, func, n, iv, method, mode, atol, rtol, adjoint=True)
+
+    def backward(self, out, dout, need_p):
+        return Chain.backward(self, dout, need_p)
+
+
+class ChainSubAdjoint:
+    """The chained path of ``adjoint=True`` with ``step_size``: the forward is the chained forward without gradients;
+    the backward solves every output interval backwards on its own fine grid with one ``nlbac_*_adj_step`` launch per
+    fine step (``ode_adjoint.AffineAdjoint.adjoint_interval``) on one solver, cached on the model under a key of its
+    own.  Its dx0 and controls' gradient are the one-launch path's bit for bit."""
+
+    def __init__(self, func, n, iv, method, plan, atol, rtol):
+        self.func, self.n, self.iv, self.method, self.plan, self.tol = func, n, iv, method, plan, (atol, rtol)
+
+    def forward(self, x0, u, xs):
+        self.u = u
+        Chain(self.func, self.n, self.iv, self.method, "none", *self.tol).forward(x0, u, xs)
+
+    def backward(self, out, dout, need_p):
+        func, plan, ns = self.func, self.plan, self.func.n_s
+        sv = func.__dict__.get("_grid_adjoint_solver")
+        if sv is None:
+            sv = func.__dict__["_grid_adjoint_solver"] = traj_class(func).Solver(func, func.device_handles()[0].arena.device)
+            sv.adjoint = True
+        par = sv.adjoint_grid_begin(self.n, self.method, need_p, *self.tol)
+        carry, du_all = None, None
+        for k in range(plan.H - 1, -1, -1):
+            a = dout[k + 1] if carry is None else (dout[k + 1] + carry)
+            du, dy0 = sv.adjoint_interval(out[k + 1][:, :ns].contiguous(), a.contiguous(),
+                                          self.u[k] if plan.stacked else self.u, self.method, plan.steps[k], par)
+            if plan.stacked:
+                if du_all is None:
+                    du_all = torch.empty(plan.H, *du.shape, dtype=torch.float32, device=du.device)
+                du_all[k].copy_(du)
+            else:
+                du_all = du.clone() if du_all is None else du_all + du
+            carry = dy0.clone()
+        return dout[0] + carry, du_all, par["th0"].clone() if need_p else None
+
+
+def solve_adjoint(func, iv, method, mode, one_launch, plan, x0, u, xs, atol=1e-7, rtol=1e-5):
+    """``solve`` under ``adjoint=True``: the same forward values, nothing kept for the backward but what the caller
+    holds — returns an object whose ``backward(out, dout, need_p)`` takes the forward's stored outputs
+    (plan.H + 1, n, >= n_s: the state in the first n_s columns) and gives what ``solve``'s does, or None without
+    gradients.  ``one_launch``: the direct path's answer; the adjoint launch must serve the nets as well."""
+    n = x0.shape[0]
+    if mode == "none":
+        solve(func, iv, method, "none", one_launch, x0, u, xs, atol, rtol)
+        return None
+    if one_launch and adj_traj_class(func).ok(func):
+        kept = adj_traj_class(func)(func, n, iv, method, plan, x0.device)
+    elif plan.sub:
+        kept = ChainSubAdjoint(func, n, iv, method, plan, atol, rtol)
+    else:
+        kept = ChainAdjoint(func, n, iv, method, mode, atol, rtol)
+    kept.forward(x0, u, xs)
+    return kept
 
 
 def solve(func, iv, method, mode, one_launch, x0, u, xs, atol=1e-7, rtol=1e-5):

@@ -685,7 +685,7 @@ def _odeint(func, y0, t, method, atol, rtol, adjoint, options):
         if sub.get("step_size") is not None:
             if adjoint:
                 raise NotImplementedError("odeint_adjoint: step_size is not offered (the adjoint solve steps once over "
-                                          "[t0, t1]); use odeint")
+                                          "[t0, t1]); use odeint, or rollout / odeint_grid with adjoint=True and step_size")
             if method == "dopri5":
                 raise ValueError("odeint: step_size goes with method='euler' or 'rk4'; torchdiffeq's dopri5 ignores it, "
                                  "which this build does not do silently")
@@ -700,7 +700,8 @@ def _odeint(func, y0, t, method, atol, rtol, adjoint, options):
                         "got %s" % type(func).__name__)
     t = torch.as_tensor(t)
     if t.numel() != 2:
-        raise NotImplementedError("odeint: the reference only ever integrates over t = [0, dt]; got %d time points"
+        raise NotImplementedError("odeint: the reference only ever integrates over t = [0, dt]; got %d time points "
+                                  "(ode_grid.odeint_grid takes a longer grid, with adjoint=True the continuous adjoint on it)"
                                   % t.numel())
     dt = float(t[1]) - float(t[0])
     func.refresh_device_weights()

@@ -72,7 +72,8 @@ def _check(func, x0, controls, dt, method, step_size=None):
     return dt, hs
 
 
-def rollout(func, x0, controls, dt, *, method="rk4", atol=1e-7, rtol=1e-5, step_size=None):
+def rollout(func, x0, controls, dt, *, method="rk4", atol=1e-7, rtol=1e-5, step_size=None, adjoint=False,
+            adjoint_chunk=None):
     """Predict H intervals of ``dt`` ahead with the NODE ``func`` (either form; a model owned by an agent included),
     a new control per interval: returns ``out`` (H + 1, B, n_s) with ``out[0] = x0`` and
 
@@ -100,11 +101,30 @@ def rollout(func, x0, controls, dt, *, method="rk4", atol=1e-7, rtol=1e-5, step_
     bit for bit, gradients w.r.t. ``x0`` and ``controls`` included.  The accuracy no longer hangs on the control rate;
     the solve is still one launch forward and one backward, over H * m fine intervals, and one autograd node.  What is
     kept grows with H * m; ``out`` and the gradients stay per control interval — the fine states and their gradients are
-    never stored.  ``step_size >= dt`` gives m = 1: the results without ``step_size``."""
+    never stored.  ``step_size >= dt`` gives m = 1: the results without ``step_size``.
+
+    ``adjoint=True``: the same ``out``, differentiated by the continuous adjoint on the grid of control intervals —
+    torchdiffeq's ``OdeintAdjointMethod.backward``, the autograd chain of H one-interval ``odeint_adjoint`` calls (bit
+    for bit in the gradients w.r.t. ``x0`` and ``controls`` without ``step_size``; parameter gradients to summation
+    order).  Nothing of the forward is kept but ``out`` itself and the controls, whatever H and ``step_size`` are: the
+    backward walks the control intervals last to first, restarts the state at the stored ``out[k+1]``, and re-computes
+    every stage — one launch for the whole horizon with euler / rk4 at the register-resident kernels' shapes
+    (``nlbac_node_adj_traj`` / ``nlbac_concat_adj_traj``), else chained.  With ``step_size`` each control interval is
+    solved backwards on its own fine grid, anchored at its upper end: the steps ``_sub_grid`` gives for [0, dt], in
+    that order, so that the cut step falls at the interval's lower end.  As in ``odeint_adjoint`` the gradient equals
+    the direct one only to solver accuracy, and it costs more time: every stage is evaluated again.
+    ``adjoint_chunk`` (a positive int, with ``adjoint=True`` and euler / rk4 only; a ``ValueError`` otherwise): the
+    backward runs in launches of that many control intervals, which changes no bit of the input gradients; with
+    parameter gradients the weight-gradient batch is one chunk's stage rows, and ``None`` picks the largest chunk that
+    batch admits (2^29 elements per layer) — a horizon the direct backward refuses still gets its gradients."""
+    T.check_adjoint_chunk("rollout", adjoint, adjoint_chunk, chained=method == "dopri5")
     dt, hs = _check(func, x0, controls, dt, method, step_size)
     params = tuple(func.parameters())
     mode = T.keep_mode(params, x0, controls)
     func.refresh_device_weights()
+    if adjoint:
+        return _RolloutAdjointFunction.apply(func, method, dt if hs is None else hs, float(atol), float(rtol), mode,
+                                             adjoint_chunk, x0, controls, *params)
     return _RolloutFunction.apply(func, method, dt if hs is None else hs, float(atol), float(rtol), mode, x0, controls,
                                   *params)
 
@@ -137,3 +157,34 @@ class _RolloutFunction(torch.autograd.Function):
         gp = T.param_grads(ctx.func, flat) if need_p else [None] * ctx.n_params
         return (None, None, None, None, None, None, dx0 if ctx.needs_input_grad[6] else None,
                 du if ctx.needs_input_grad[7] else None, *gp)
+
+
+class _RolloutAdjointFunction(torch.autograd.Function):
+    """``rollout(adjoint=True)``: what is saved for the backward is ``out`` (as a saved tensor) and the controls."""
+
+    @staticmethod
+    def forward(ctx, func, method, dt, atol, rtol, mode, chunk, x0, controls, *params):
+        H, n, ns = controls.shape[0], x0.shape[0], func.n_s
+        x0 = x0.detach().contiguous()
+        u = controls.detach().contiguous()
+        out = torch.empty(H + 1, n, ns, dtype=torch.float32, device=x0.device)
+        first = out[0].copy_(x0)
+        ctx.func, ctx.mode, ctx.n_params = func, mode, len(params)
+        one = _one_launch_ok(func, method)
+        sub = isinstance(dt, tuple)
+        iv = T.HeldSteps(dt, H, x0.device) if sub else T.EqualSteps(dt, H)
+        plan = T.AdjointPlan([dt if sub else (dt,)] * H, True, chunk, sub)
+        ctx.kept = T.solve_adjoint(func, iv, method, mode, one, plan, x0 if one else first, u, out.narrow(0, 1, H), atol, rtol)
+        if ctx.kept is not None:
+            ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        assert ctx.kept is not None, "rollout: nothing was kept for a backward (the forward ran without gradients)"
+        out, = ctx.saved_tensors
+        need_p = ctx.mode == "params" and any(ctx.needs_input_grad[9:])
+        dx0, du, flat = ctx.kept.backward(out, dout.float().contiguous(), need_p)
+        gp = T.param_grads(ctx.func, flat) if need_p else [None] * ctx.n_params
+        return (None, None, None, None, None, None, None, dx0 if ctx.needs_input_grad[7] else None,
+                du if ctx.needs_input_grad[8] else None, *gp)

@@ -808,6 +808,27 @@ int nlbac_dopri_interp_bwd(const float *dout, const float *h_host, const float *
                            long slot_floats, const nlbac_out_map *map /* or NULL */, nlbac_stream_t s);
 /* (slot_floats != 0: y1 / K resp. dy0 / dy1 / dK are slot 0's pointers of a device-driven chain and the step
  * interpolated is the one in slot ctl[12]; its y0 is the predecessor slot's y1.) */
+/* dopri5 on a time grid (new entry points of ABI 17): ONE adaptive solve of ONE problem (the device-driven chain, run to
+ * t_end without nlbac_rk_chain::interp_*), read at n_out solver times tau[0] < .. < tau[n_out-1] <= t_end (device
+ * doubles, measured from the solve's start).  y1 / K resp. dy0 / dy1 / dK are slot 0's pointers as above, ctl the
+ * problem's control block, hslots [n_slots] the accepted steps' sizes.  The slots 0 .. ctl[12] are walked once with
+ * t_i accumulated in double as the controller accumulates it; output j is the interpolant of the FIRST step with
+ * t_i + h_i >= tau[j], at x = (float)((tau[j] - t_i) / h_i) with h = (float)h_i (what is left at slot ctl[12] is that
+ * slot's): the arithmetic of nlbac_dopri_interp_fwd, so tau = {t_end} gives its bits.  One thread per (row, component).
+ *   fwd: out [n_out][n][n_s].
+ *   bwd: dout [n_out][n][n_s] -> dy0, dy1, dK[0..6] of EVERY slot 0 .. ctl[12]: the sum over the slot's outputs in
+ *        increasing j, zeros for a slot without one — plain stores, no fill needed, no atomics.
+ *   carry: dy1[i] += dy0_next[i], dK6[i] += dK0_next[i] for i < count (= n * n_s): what step i+1 sends back to step i
+ *        (its initial state is step i's y1, its first stage step i's last: FSAL) before step i's nlbac_node_rk_bwd /
+ *        nlbac_concat_rk_bwd launch without a chain. */
+int nlbac_dopri_dense_fwd(const float *y0, const float *y1, const float *K, long slot_floats, const double *ctl,
+                          const double *hslots, int n_slots, const double *tau, int n_out, int n, int n_s, float *out,
+                          nlbac_stream_t s);
+int nlbac_dopri_dense_bwd(const float *dout, long slot_floats, const double *ctl, const double *hslots, int n_slots,
+                          const double *tau, int n_out, int n, int n_s, float *dy0, float *dy1, float *dK,
+                          nlbac_stream_t s);
+int nlbac_dopri_dense_carry(const float *dy0_next, const float *dK0_next, long count, float *dy1, float *dK6,
+                            nlbac_stream_t s);
 
 /* ------------------------------------------------------------------------
  * odeint_adjoint (torchdiffeq 0.2.3 OdeintAdjointMethod, torchdiffeq/_impl/adjoint.py; pinned by the reference at

@@ -272,6 +272,10 @@ _PROTOS = {
     "nlbac_dopri_control_tiles": [C.POINTER(RkChain), _I, _I, _I, _I, _P],
     "nlbac_dopri_interp_fwd": [_P, _P, _P, c_float_p, c_float_p, _P, _I, _I, _I, _P, _L, C.POINTER(OutMap), _P],
     "nlbac_dopri_interp_bwd": [_P, c_float_p, c_float_p, _P, _I, _I, _I, _P, _P, _P, _L, C.POINTER(OutMap), _P],
+    # (new entry points of ABI 17: one dopri5 solve read at every point of a time grid, ode_dense.py)
+    "nlbac_dopri_dense_fwd": [_P, _P, _P, _L, _P, _P, _I, _P, _I, _I, _I, _P, _P],
+    "nlbac_dopri_dense_bwd": [_P, _L, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P],
+    "nlbac_dopri_dense_carry": [_P, _P, _L, _P, _P, _P],
     "nlbac_unicycle_env_step": [_I, c_double_p, _I] + [_P, _I] + [_P] * 13,
     "nlbac_pvtol_env_step": [_I, c_double_p, _I] + [_P, _I] + [_P] * 11,
     "nlbac_cars_env_step": [_I, c_double_p, _I] + [_P] * 12,

@@ -526,6 +526,139 @@ extern "C" int nlbac_dopri_interp_bwd(const float* dout, const float* h_host, co
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// dopri5 on a time grid (ode_dense.py): ONE adaptive solve of one problem, read at n_out abscissae tau[0] < tau[1] < ..
+// after the device-driven chain has finished.  The accepted steps sit in the step slots 0 .. C_NACC (slot i's y0 is slot
+// i-1's last stage input, slot 0's the caller's), their sizes in hslots.  A thread owns one (row, component) — the
+// K[(j n + row) n_s + r] loads of a wave are consecutive floats — and walks the slots once, with t_i accumulated in
+// double in the controller's order (C_T = t + h); output j belongs to the FIRST step with t_i + h_i >= tau_j and is
+// evaluated at x = (float)((tau_j - t_i) / h_i), h = (float)h_i: how the controller forms C_X and interp_hx reads
+// C_HUSED.  Whatever is left when the walk reaches slot C_NACC belongs to it (the step that passed t_end).  The walk
+// depends on ctl / hslots / tau only: uniform over the launch.
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int dense_last_slot(const double* ctl, int n_slots) {
+    const int s = (int)ctl[C_NACC];
+    return s < 0 ? 0 : (s >= n_slots ? n_slots - 1 : s);
+}
+
+__global__ __launch_bounds__(256) void dopri_dense_fwd_kernel(const float* y0, const float* y1, const float* K,
+                                                              long slot_floats, const double* ctl, const double* hslots,
+                                                              int n_slots, const double* tau, int n_out, int n, int n_s,
+                                                              float* out) {
+    const long total = (long)n * n_s;
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int last = dense_last_slot(ctl, n_slots);
+    double t = 0.0;
+    int j = 0;
+    float a0 = y0[idx];
+    for (int i = 0; i <= last && j < n_out; ++i) {
+        const double hd = hslots[i], tn = t + hd;
+        const float a1 = (y1 + (long)i * slot_floats)[idx];
+        if (i == last || tn >= tau[j]) {
+            const float* Ks = K + (long)i * slot_floats;
+            float k[7];
+#pragma unroll
+            for (int s = 0; s < 7; ++s) k[s] = Ks[(long)s * total + idx];
+            const float h = (float)hd;
+            while (j < n_out && (i == last || tn >= tau[j])) {
+                const float x = (float)((tau[j] - t) / hd);
+                out[(long)j * total + idx] = dopri_interp_value(a0, a1, k, h, x);
+                ++j;
+            }
+        }
+        a0 = a1;
+        t = tn;
+    }
+}
+
+// its backward: dout (n_out, n, n_s) -> dy0, dy1, dK[0..6] of EVERY slot 0 .. C_NACC: per slot the sum of
+// dopri_interp_grad over the outputs that fall in it, in increasing j, in registers; zeros where none does.  Plain
+// stores: the buffers need no fill and nothing depends on an order of arrival.
+__global__ __launch_bounds__(256) void dopri_dense_bwd_kernel(const float* dout, long slot_floats, const double* ctl,
+                                                              const double* hslots, int n_slots, const double* tau,
+                                                              int n_out, int n, int n_s, float* dy0, float* dy1,
+                                                              float* dK) {
+    const long total = (long)n * n_s;
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int last = dense_last_slot(ctl, n_slots);
+    double t = 0.0;
+    int j = 0;
+    for (int i = 0; i <= last; ++i) {
+        const double hd = hslots[i], tn = t + hd;
+        const float h = (float)hd;
+        float g0 = 0.f, g1 = 0.f, gk[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        while (j < n_out && (i == last || tn >= tau[j])) {
+            const float x = (float)((tau[j] - t) / hd);
+            float d0, d1, dk[7];
+            dopri_interp_grad(dout[(long)j * total + idx], h, x, d0, d1, dk);
+            g0 += d0; g1 += d1;
+#pragma unroll
+            for (int s = 0; s < 7; ++s) gk[s] += dk[s];
+            ++j;
+        }
+        const long off = (long)i * slot_floats;
+        (dy0 + off)[idx] = g0;
+        (dy1 + off)[idx] = g1;
+#pragma unroll
+        for (int s = 0; s < 7; ++s) (dK + off)[(long)s * total + idx] = gk[s];
+        t = tn;
+    }
+}
+
+// what step i+1 sends back to step i before step i's backward launch: dy1 += the next step's dy0, dK[6] += its dK[0] (FSAL)
+__global__ __launch_bounds__(256) void dopri_dense_carry_kernel(const float* dy0_next, const float* dK0_next, long count,
+                                                                float* dy1, float* dK6) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= count) return;
+    dy1[idx] = dy1[idx] + dy0_next[idx];
+    dK6[idx] = dK6[idx] + dK0_next[idx];
+}
+
+// (a slot holds at least K [7][n][n_s]: a slot stride below that cannot be one of these n rows)
+static int dense_args_ok(const char* who, const void* ctl, const void* hslots, const void* tau, int n_slots, int n_out,
+                         int n, int n_s, long slot_floats) {
+    NLBAC_REQUIRE(ctl && hslots && tau, "%s: null pointer", who);
+    NLBAC_REQUIRE(n_out >= 1, "%s: n_out %d < 1", who, n_out);
+    NLBAC_REQUIRE(n_s >= 1, "%s: n_s %d < 1", who, n_s);      // (a thread per (row, component): no per-row array, no MAX_NS)
+    NLBAC_REQUIRE(n_slots >= 1, "%s: n_slots %d < 1", who, n_slots);
+    NLBAC_REQUIRE(n >= 1 && (long)n * n_s * 7 <= slot_floats, "%s: a slot of %ld floats does not hold the stages of %d rows",
+                  who, slot_floats, n);
+    return 0;
+}
+
+extern "C" int nlbac_dopri_dense_fwd(const float* y0, const float* y1, const float* K, long slot_floats,
+                                     const double* ctl, const double* hslots, int n_slots, const double* tau, int n_out,
+                                     int n, int n_s, float* out, nlbac_stream_t s) {
+    NLBAC_REQUIRE(y0 && y1 && K && out, "nlbac_dopri_dense_fwd: null pointer");
+    if (dense_args_ok("nlbac_dopri_dense_fwd", ctl, hslots, tau, n_slots, n_out, n, n_s, slot_floats)) return -1;
+    hipLaunchKernelGGL(dopri_dense_fwd_kernel, GRID1((long)n * n_s), y0, y1, K, slot_floats, ctl, hslots, n_slots, tau,
+                       n_out, n, n_s, out);
+    NLBAC_CHECK_LAUNCH("nlbac_dopri_dense_fwd");
+    return 0;
+}
+
+extern "C" int nlbac_dopri_dense_bwd(const float* dout, long slot_floats, const double* ctl, const double* hslots,
+                                     int n_slots, const double* tau, int n_out, int n, int n_s, float* dy0, float* dy1,
+                                     float* dK, nlbac_stream_t s) {
+    NLBAC_REQUIRE(dout && dy0 && dy1 && dK, "nlbac_dopri_dense_bwd: null pointer");
+    if (dense_args_ok("nlbac_dopri_dense_bwd", ctl, hslots, tau, n_slots, n_out, n, n_s, slot_floats)) return -1;
+    hipLaunchKernelGGL(dopri_dense_bwd_kernel, GRID1((long)n * n_s), dout, slot_floats, ctl, hslots, n_slots, tau, n_out,
+                       n, n_s, dy0, dy1, dK);
+    NLBAC_CHECK_LAUNCH("nlbac_dopri_dense_bwd");
+    return 0;
+}
+
+extern "C" int nlbac_dopri_dense_carry(const float* dy0_next, const float* dK0_next, long count, float* dy1, float* dK6,
+                                       nlbac_stream_t s) {
+    NLBAC_REQUIRE(dy0_next && dK0_next && dy1 && dK6, "nlbac_dopri_dense_carry: null pointer");
+    NLBAC_REQUIRE(count >= 1, "nlbac_dopri_dense_carry: count %ld < 1", count);
+    hipLaunchKernelGGL(dopri_dense_carry_kernel, GRID1(count), dy0_next, dK0_next, count, dy1, dK6);
+    NLBAC_CHECK_LAUNCH("nlbac_dopri_dense_carry");
+    return 0;
+}
+
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The adjoint of the single-net NODE  dx/dt = out_mu + out_sig * net(([x | c] - in_mu) * in_isig)  (c: carried inputs;

@@ -1,0 +1,199 @@
+"""``odeint_dense``: ONE adaptive dopri5 solve of this build's NODE models, read at every point of a time grid —
+``torchdiffeq.odeint(func, y0, t)`` with ``len(t) >= 2`` on its adaptive path (0.2.3, as the oracle restates dopri5):
+the initial-step selection runs once, the error norm is taken over the whole batch tensor (one problem), steps are not
+clipped at the output times, and ``out[j]`` is the 4th-order interpolant of the first accepted step that reaches
+``t[j]``.  (``odeint`` serves exactly two time points; ``ode_grid.odeint_grid`` is the fixed-grid rule, euler / rk4.
+A chain of ``odeint`` calls restarted at every grid point is another solution: the initial-step selection runs again at
+every point and steps are cut there.)
+
+How it runs.  The solver's device-driven chain (``ode_dopri``) is run to ``t[-1] - t[0]`` as it is; it leaves every
+accepted step in a step slot — the stage derivatives ``K[0..6]``, the stage inputs ``Y`` — and the step sizes in
+``hslots``.  One launch, ``nlbac_dopri_dense_fwd``, then walks the slots and writes all T - 1 output states.  The
+backward starts with one launch, ``nlbac_dopri_dense_bwd``, that leaves in EVERY slot the gradient its outputs send to
+the step's ``y0`` / ``y1`` / ``K``; then the accepted steps are differentiated last to first by the solver's step
+backward WITHOUT a chain description (``nlbac_node_rk_bwd`` / ``nlbac_concat_rk_bwd`` add onto what a slot already
+holds; the chain's own carry mode ignores a slot's ``dK`` / ``dy0``), with one small ``nlbac_dopri_dense_carry`` launch
+between two steps for what step i + 1 sends back to step i.  That is one backward launch per accepted step, as in
+``odeint``, plus one carry launch per step boundary.
+
+Not served: decreasing ``t``, the continuous adjoint, hipGraph capture (the solve needs the host's look at the control
+block), and nets or settings the device-driven chain refuses — each raises, none runs some other way.
+"""
+import math
+
+import torch
+
+from . import _lib
+from . import ode_traj as T
+from .arena import stream_ptr
+from .ode_grid import _steps_of
+
+SOLVERS_KEY = "_odeint_dense_solvers"      # on the model: {keep mode: solver}, apart from odeint's, rollout's and the grid's
+
+
+def _taus(t):
+    """The grid's checks (``ode_grid._steps_of``'s); returns the output times 1 .. T-1 in solver time — the field is
+    autonomous, the solve runs over [0, t[-1] - t[0]] — each ``float(t[j]) - float(t[0])``, as ``odeint`` forms its dt."""
+    try:
+        _steps_of(t)
+    except (ValueError, TypeError) as e:
+        raise type(e)(str(e).replace("odeint_grid:", "odeint_dense:")) from None
+    times = [float(v) for v in torch.as_tensor(t).detach().cpu()]
+    return tuple(v - times[0] for v in times[1:])
+
+
+def _check(func, y0, t, atol, rtol, adjoint):
+    """Every argument check, before anything touches a device; returns the output times (``_taus``)."""
+    from .sac_cbf_clf.model import NeuralODEModel
+    if adjoint:
+        raise NotImplementedError("odeint_dense: the continuous adjoint on a dense dopri5 solve is not offered; the "
+                                  "backward goes through the accepted steps")
+    if not isinstance(func, NeuralODEModel):
+        raise TypeError("nlbac_amd.ode_dense.odeint_dense integrates this build's NeuralODEModel (its field runs as HIP "
+                        "kernels); got %s" % type(func).__name__)
+    taus = _taus(t)
+    for name, v in (("atol", atol), ("rtol", rtol)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise TypeError("odeint_dense: %s must be a Python number; got %s" % (name, type(v).__name__))
+        if not (math.isfinite(v) and v > 0):
+            raise ValueError("odeint_dense: %s must be positive and finite; got %r" % (name, v))
+    if not isinstance(y0, torch.Tensor):
+        raise TypeError("odeint_dense: y0 must be a tensor; got %s" % type(y0).__name__)
+    if y0.dtype != torch.float32:
+        raise TypeError("odeint_dense: y0 must be float32; got %s" % y0.dtype)
+    width = func.n_s + (func.n_u if func.affine else func.n_carry)
+    if y0.dim() != 2 or y0.shape[1] != width or y0.shape[0] < 1:
+        raise ValueError("odeint_dense: y0 must be (batch, %d) = [x | carried columns]; got %s" % (width, tuple(y0.shape)))
+    if y0.device.type != "cuda":
+        raise ValueError("odeint_dense: y0 must be on a CUDA device; got %s" % y0.device)
+    return taus
+
+
+def solver_of(func, mode):
+    """The (cached) solver of ``func``'s dense solves that keep ``mode`` (``ode_traj.keep_mode``): a solver of its own, so
+    that what a long solve teaches it (``_chain_len``, the slot pool's size) stays out of ``odeint``'s."""
+    svs = func.__dict__.setdefault(SOLVERS_KEY, {})
+    sv = svs.get(mode)
+    if sv is None:
+        sv = T.traj_class(func).Solver(func, func.device_handles()[0].arena.device)
+        sv.keep_acts = mode != "inputs"      # (no grad: the same kernels as odeint's solver; nothing is read back)
+        sv.interp_fold = False               # the attempt launches interpolate nothing: every output is read off the slots
+        svs[mode] = sv
+    return sv
+
+
+def odeint_dense(func, y0, t, *, atol=1e-7, rtol=1e-5, adjoint=False):
+    """The dopri5 solution of the NODE ``func`` (either form; a model owned by an agent included) at every point of the
+    time grid ``t`` (1-D tensor or sequence, T >= 2 finite strictly increasing times): returns ``out`` (T, B, n_s + n_c)
+    with ``out[0] = y0``, from ONE adaptive solve over ``[t[0], t[-1]]``.  ``y0`` (B, n_s + n_c) is CUDA float32,
+    ``[x | carried columns]`` as ``odeint`` takes it; the carried columns are copied through to every ``out[j]``.
+
+    The initial-step selection runs once, the error norm is the RMS over the whole batch tensor, steps are not cut at the
+    output times; for j >= 1, ``out[j]`` is the 4th-order interpolant of the FIRST accepted step ``[t_i, t_i + h_i]``
+    with ``t_i + h_i >= tau_j``, at ``x = (tau_j - t_i) / h_i``, where ``tau_j = float(t[j]) - float(t[0])`` (the field
+    is autonomous in solver time).  ``odeint_dense(func, y0, [t0, t1])`` equals ``odeint(func, y0, [t0, t1],
+    method="dopri5")`` in the values bit for bit.
+
+    Differentiable w.r.t. ``y0`` (state and carried columns) and ``func.parameters()`` through one autograd node; ``t``
+    is a constant and step sizes carry no gradient, as everywhere in this build.  The weight copies are refreshed first.
+    What is kept follows what needs a gradient, as in ``rollout``; under ``torch.no_grad`` nothing beyond the solver's
+    step slots.  Memory grows with the number of accepted steps, not with T.
+
+    Raises instead of running some other way: decreasing ``t`` (``ValueError``), ``adjoint=True`` (``NotImplementedError``),
+    a call inside a hipGraph capture (``RuntimeError``: the solve needs the host's look at the control block), and a
+    solver whose device-driven chain is not available — nets the fused step kernels refuse, or ``device_loop`` off
+    (``NotImplementedError``)."""
+    taus = _check(func, y0, t, atol, rtol, adjoint)
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("odeint_dense: not inside a hipGraph capture — the adaptive solve needs the host's look at the "
+                           "control block to know how many steps were accepted")
+    params = tuple(func.parameters())
+    mode = T.keep_mode(params, y0)
+    sv = solver_of(func, mode)
+    if not sv._chain_ok(1, y0.shape[0]):
+        raise NotImplementedError(
+            "odeint_dense: needs the device-driven dopri5 chain (_chain_ok(1, %d) is false: fused=%s — the fused step "
+            "kernels refuse these nets — device_loop=%s); the host-driven and stage-by-stage paths emit no interior "
+            "points" % (y0.shape[0], sv.fused, sv.device_loop))
+    func.refresh_device_weights()
+    return _DenseFunction.apply(func, sv, taus, float(atol), float(rtol), mode, y0, *params)
+
+
+class _DenseSolve:
+    """What one dense solve keeps: the solver (whose step slots hold the accepted steps), the output times on the device
+    and the carried columns."""
+
+    def __init__(self, sv, taus, x0, c, atol, rtol, xs):
+        n, ns = x0.shape[0], sv.n_s
+        self.sv, self.n, self.n_out, self.c = sv, n, len(taus), c
+        sv.forward(x0, c, 1, n, "dopri5", taus[-1], atol, rtol)
+        st = sv.ctx["chain"]
+        assert not st["ip"] and not sv.ctx.get("out_mapped"), "a dense solve interpolates nothing inside its attempts"
+        self.solve_id = sv.stats["solves"]
+        self.pool, self.hslots = st["pool"], st["ch"].hslots
+        self.tau = torch.tensor(taus, dtype=torch.float64, device=x0.device)
+        ws0 = self.pool.ws(n, 0)
+        _lib.call("nlbac_dopri_dense_fwd", x0.data_ptr(), ws0.Y[6].data_ptr(), ws0.K.data_ptr(), self.pool.slot_floats,
+                  sv._ctl(1).data_ptr(), self.hslots, self.pool.n_slots, self.tau.data_ptr(), self.n_out, n, ns,
+                  xs.data_ptr(), stream_ptr())
+
+    def backward(self, dxs, need_p):
+        """dxs (T - 1, n, n_s): d loss / d out[1:] on the state columns.  Returns (dx0, dc, flat parameter gradient or
+        None); dc is the solve's own share of the carried columns' gradient."""
+        sv, n, pool = self.sv, self.n, self.pool
+        assert sv.stats["solves"] == self.solve_id, \
+            "odeint_dense: backward must run before the next odeint_dense with the same model and what it keeps"
+        ctx, ns, s = sv.ctx, sv.n_s, stream_ptr()
+        nacc = ctx["nacc"][0]
+        wss = [pool.ws(n, i).bwd(sv) for i in range(nacc + 1)]
+        ws0 = wss[0]
+        _lib.call("nlbac_dopri_dense_bwd", dxs.data_ptr(), pool.slot_floats, sv._ctl(1).data_ptr(), self.hslots,
+                  pool.n_slots, self.tau.data_ptr(), self.n_out, n, ns, ws0.dy0.data_ptr(), ws0.dy1.data_ptr(),
+                  ws0.dK.data_ptr(), s)
+        du = sv._buf("du", n, sv.n_u)
+        for i in range(nacc, -1, -1):
+            ws = wss[i]
+            if i < nacc:
+                # (a launch of the library's, not ATen ops: see the loop in AffineNodeSolver.backward)
+                nxt = wss[i + 1]
+                _lib.call("nlbac_dopri_dense_carry", nxt.dy0.data_ptr(), nxt.dK[0].data_ptr(), n * ns, ws.dy1.data_ptr(),
+                          ws.dK[6].data_ptr(), s)
+            sv._rk_fused_bwd(ws, self.c, 1, n, "dopri5", i == 0, True, need_p, None, self.hslots + 8 * i, pool.n_slots,
+                             ws.dy1, du, i == nacc)
+        flat = None
+        if need_p:
+            arena = sv.node.device_handles()[0].arena
+            used = sv.accumulate_param_grads(arena, max(1, arena.n_slabs // len(ctx["steps"])))
+            flat = T._reduce(arena, used)
+        return ws0.dy0, du, flat
+
+
+class _DenseFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, func, sv, taus, atol, rtol, mode, y0, *params):
+        n, ns = y0.shape[0], func.n_s
+        y0 = y0.detach().contiguous()
+        x0, c = y0[:, :ns].contiguous(), y0[:, ns:].contiguous()
+        xs = torch.empty(len(taus), n, ns, dtype=torch.float32, device=y0.device)
+        solve = _DenseSolve(sv, taus, x0, c, atol, rtol, xs)
+        ctx.func, ctx.mode, ctx.n_params = func, mode, len(params)
+        ctx.kept = solve if mode != "none" else None
+        out = torch.empty(len(taus) + 1, n, y0.shape[1], dtype=torch.float32, device=y0.device)
+        out[0].copy_(y0)
+        out[1:, :, :ns].copy_(xs)
+        out[1:, :, ns:].copy_(c)          # (the carried columns, the same at every output point)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        assert ctx.kept is not None, "odeint_dense: nothing was kept for a backward (the forward ran without gradients)"
+        ns = ctx.func.n_s
+        dout = dout.float()
+        need_p = ctx.mode == "params" and any(ctx.needs_input_grad[7:])
+        dx0, dc, flat = ctx.kept.backward(dout[1:, :, :ns].contiguous(), need_p)
+        gy0 = None
+        if ctx.needs_input_grad[6]:
+            # d/d carried columns: the solve's own, and the share of every output point they were copied to
+            gy0 = dout[0] + torch.cat([dx0, dc + dout[1:, :, ns:].sum(0)], dim=1)
+        gp = T.param_grads(ctx.func, flat) if need_p else [None] * ctx.n_params
+        return (None, None, None, None, None, None, gy0, *gp)

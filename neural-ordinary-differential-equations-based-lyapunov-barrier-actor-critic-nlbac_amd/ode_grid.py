@@ -111,8 +111,8 @@ def _steps(func, y0, t, method, step_size=None):
     if method == "dopri5":
         raise NotImplementedError(
             "odeint_grid: dopri5 on a time grid is ONE adaptive solve over [t[0], t[-1]] whose interior points are "
-            "interpolated from the accepted steps, not a chain of solves restarted at every grid point; the step driver "
-            "(ode_dopri.py) does not emit interior points yet.  Use method='euler' or 'rk4', or odeint per interval")
+            "interpolated from the accepted steps, not a chain of solves restarted at every grid point: that is "
+            "ode_dense.odeint_dense.  Here, use method='euler' or 'rk4'")
     if method not in METHODS:
         raise ValueError("odeint_grid: method is one of %s; got %r" % (", ".join(METHODS), method))
     hs = _steps_of(t) if step_size is None else _sub_grid(t, step_size)
@@ -161,8 +161,8 @@ def odeint_grid(func, y0, t, *, method="rk4", step_size=None, adjoint=False, adj
     ``(t[j] - tau_i) / (tau_i+1 - tau_i)``.
 
     ``'dopri5'`` raises ``NotImplementedError`` (with or without ``step_size``): on a grid it is one adaptive solve
-    interpolated at the interior points, which the step driver does not offer yet; it is not approximated by restarting
-    at every grid point.
+    interpolated at the interior points — ``ode_dense.odeint_dense`` — and is not approximated here by restarting at
+    every grid point.
 
     Differentiable w.r.t. ``y0`` (state and carried columns) and ``func.parameters()`` through one autograd node for the
     whole grid; ``t`` is a constant (no gradient w.r.t. the times).  The weight copies are refreshed first, as in

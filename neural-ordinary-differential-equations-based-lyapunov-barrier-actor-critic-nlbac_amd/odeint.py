@@ -701,7 +701,8 @@ def _odeint(func, y0, t, method, atol, rtol, adjoint, options):
     t = torch.as_tensor(t)
     if t.numel() != 2:
         raise NotImplementedError("odeint: the reference only ever integrates over t = [0, dt]; got %d time points "
-                                  "(ode_grid.odeint_grid takes a longer grid, with adjoint=True the continuous adjoint on it)"
+                                  "(ode_grid.odeint_grid takes a longer grid, with adjoint=True the continuous adjoint on it; "
+                                  "ode_dense.odeint_dense reads one dopri5 solve at every point of one)"
                                   % t.numel())
     dt = float(t[1]) - float(t[0])
     func.refresh_device_weights()
@@ -716,8 +717,8 @@ def odeint(func, y0, t, *, method="dopri5", atol=1e-7, rtol=1e-5, **options):
     or ``'dopri5'`` (which refuses ``step_size``; no other option is served).
     The packed MFMA copies of the weights are refreshed first, so a ``torch.optim`` step on ``func.parameters()``
     between calls is picked up.  For several intervals ahead with a new control each, differentiated as a whole, use
-    ``nlbac_amd.rollout.rollout``; for the solution at every point of a longer time grid (euler / rk4), use
-    ``nlbac_amd.ode_grid.odeint_grid``."""
+    ``nlbac_amd.rollout.rollout``; for the solution at every point of a longer time grid, use
+    ``nlbac_amd.ode_grid.odeint_grid`` (euler / rk4) or ``nlbac_amd.ode_dense.odeint_dense`` (one dopri5 solve)."""
     return _odeint(func, y0, t, method, atol, rtol, False, options)
 
 

@@ -861,6 +861,13 @@ int nlbac_node_adj_interp_ok(const nlbac_mlp *f, const nlbac_mlp *g);
 /* Z[row] = [y | a_x | 0]  and  (dy0, du) = (Z[:, n_s:2n_s], Z[:, 2n_s:])  (either output may be NULL) */
 int nlbac_adj_pack(const float *y, const float *a_x, int n_s, int n_u, int n, float *Z, nlbac_stream_t s);
 int nlbac_adj_unpack(const float *Z, int n_s, int n_u, int n, float *dy0, float *du, nlbac_stream_t s);
+/* The hand-over at a grid point of a dense solve's adjoint:
+ *   Z0[row] = [ y[row, :n_s] | Zprev[row, n_s:2n_s] + dout[row, :n_s] | Zprev[row, 2n_s:] ]
+ * y / dout are read in place from rows of leading dimension y_ld / dout_ld (>= n_s); Zprev [n][2 n_s + n_u] is the
+ * augmented state the interval above ended with, or NULL at the last grid point: the middle block is then a copy of
+ * dout and the last block zeros (nlbac_adj_pack's result).  Z0 must not be Zprev. */
+int nlbac_adj_dense_restart(const float *y, long y_ld, const float *dout, long dout_ld, const float *Zprev, int n_s,
+                            int n_u, int n, float *Z0, nlbac_stream_t s);
 /* Step control of the adjoint solve: torchdiffeq's default adjoint norm (handle_adjoint_norm_) — the maximum of the
  * RMS norms of the y part [x | u], the adj_y part [a_x | a_u] and, when pnorm is given, pnorm[0] (pnorm[1] for the
  * second norm of mode 0): the largest per-tensor RMS of the parameter adjoint, from nlbac_adj_param_norm.

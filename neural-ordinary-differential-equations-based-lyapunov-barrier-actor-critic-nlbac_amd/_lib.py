@@ -260,6 +260,7 @@ _PROTOS = {
     "nlbac_node_adj_step": [C.POINTER(Mlp), C.POINTER(Mlp), _P, _I, _I, _I, _I, _I, c_float_p, c_float_p, _I, c_float_p,
                             _I, c_float_p, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _D, _P],
     "nlbac_adj_pack": [_P, _P, _I, _I, _I, _P, _P],
+    "nlbac_adj_dense_restart": [_P, _L, _P, _L, _P, _I, _I, _I, _P, _P],
     "nlbac_adj_unpack": [_P, _I, _I, _I, _P, _P, _P],
     "nlbac_adj_norm_control": [_P, _P, _P, _P, _P, _I, _F, _F, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _D, _P],
     "nlbac_adj_control": [_P, _I, _I, _I, _I, _I, _I, _D, _P, _P, _P],

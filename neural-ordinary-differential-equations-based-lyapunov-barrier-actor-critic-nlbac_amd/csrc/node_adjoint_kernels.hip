@@ -333,6 +333,37 @@ __global__ __launch_bounds__(256) void adj_unpack_kernel(const float* Z, int ns,
     if (du) for (int c = 0; c < nu; ++c) du[(long)i * nu + c] = Z[(long)i * W + 2 * ns + c];
 }
 
+// The hand-over of the augmented state at a grid point of a dense solve's adjoint (ode_adjoint.backward_adjoint_dense):
+// Z0[row] = [ y | a_x + dout | a_u ] with y and dout read in place from rows of leading dimension y_ld / dout_ld and
+// a_x, a_u from the interval above (Zprev; NULL at the last grid point: a_x = 0 is not added, a_u = 0 — adj_pack's
+// row).  One lane per (row, column of Z0), consecutive lanes on consecutive floats.
+__global__ __launch_bounds__(256) void adj_dense_restart_kernel(const float* y, long y_ld, const float* dout, long dout_ld,
+                                                                const float* Zprev, int ns, int nu, long total, float* Z0) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int W = 2 * ns + nu;
+    const long row = i / W;
+    const int c = (int)(i - row * W);
+    float v;
+    if (c < ns) v = y[row * y_ld + c];
+    else if (c < 2 * ns) v = Zprev ? Zprev[i] + dout[row * dout_ld + (c - ns)] : dout[row * dout_ld + (c - ns)];
+    else v = Zprev ? Zprev[i] : 0.f;
+    Z0[i] = v;
+}
+
+extern "C" int nlbac_adj_dense_restart(const float* y, long y_ld, const float* dout, long dout_ld, const float* Zprev,
+                                       int n_s, int n_u, int n, float* Z0, nlbac_stream_t s) {
+    NLBAC_REQUIRE(y && dout && Z0 && n >= 1 && n_s >= 1 && n_u >= 0 && y_ld >= n_s && dout_ld >= n_s && Z0 != Zprev,
+                  "nlbac_adj_dense_restart: bad arguments");
+    const long total = (long)n * (2 * n_s + n_u);
+    const long blocks = (total + 255) / 256;
+    NLBAC_REQUIRE(blocks <= 0x7fffffffL, "nlbac_adj_dense_restart: too many rows");
+    hipLaunchKernelGGL(adj_dense_restart_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)s,
+                       y, y_ld, dout, dout_ld, Zprev, n_s, n_u, total, Z0);
+    NLBAC_CHECK_LAUNCH("nlbac_adj_dense_restart");
+    return 0;
+}
+
 extern "C" int nlbac_adj_pack(const float* y, const float* a_x, int n_s, int n_u, int n, float* Z, nlbac_stream_t s) {
     NLBAC_REQUIRE(y && a_x && Z && n >= 1, "nlbac_adj_pack: bad arguments");
     hipLaunchKernelGGL(adj_pack_kernel, dim3(nlbac_ceil_div(n, 256)), dim3(256), 0, (hipStream_t)s, y, a_x, n_s, n_u, n, Z);

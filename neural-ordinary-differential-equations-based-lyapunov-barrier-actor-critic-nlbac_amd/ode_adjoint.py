@@ -207,6 +207,46 @@ class AffineAdjoint:
                       du.data_ptr() if du is not None else None, s)
         return du, dy0
 
+    # -- the adjoint of a dense dopri5 solve (ode_dense.odeint_dense_adjoint) -----------------------------------------------
+    def backward_adjoint_dense(self, out, dout, c, lengths, need_params):
+        """torchdiffeq 0.2.3 ``OdeintAdjointMethod.backward`` on a time grid, after this solver's dense forward: ``out`` /
+        ``dout`` (T, n, n_s + n_c) contiguous — the stored outputs and their gradient, read in place — ``c`` (n, n_c) the
+        carried columns, ``lengths[j - 1]`` the length of [t[j-1], t[j]].  The intervals are solved last to first, each a
+        fresh adaptive solve over [0, length] (``_adj_dopri``: its own f0, Hairer step, probe and attempts).  At an
+        interval's upper end nlbac_adj_dense_restart RESETS the state part of z to the stored ``out[j]`` and adds
+        ``dout[j]``'s state columns to a_x; a_x, a_c and the parameter adjoint are CARRIED from the interval above (the
+        parameter adjoint by a buffer swap: what the interpolation at the lower end wrote is the next interval's th0) and
+        take part in the mixed norm.  ``dout``'s carried columns stay out of the solve: the caller adds them.
+        Returns (a_x, a_c) at t[0] in the solver's buffers and the parameter adjoint (``par["out"]``) or None;
+        ``ctx["adjoint_info"]`` lists what ``_adj_dopri`` records per interval, last interval first.  One host wait on the
+        control block per chain of attempts, so at least one per interval."""
+        ctx = self.ctx
+        n, ns, nu, s = ctx["n"], self.n_s, self.n_u, stream_ptr()
+        if self.comm is not None and self.comm.world > 1:
+            raise NotImplementedError("odeint_dense_adjoint: not offered on a sample-sharded solve (comm.world = %d)"
+                                      % self.comm.world)
+        assert ctx["P"] == 1 and ctx["method"] == "dopri5", "the dense adjoint follows a single-problem dopri5 solve"
+        ld = ns + nu
+        for t in (out, dout):
+            assert t.shape == (len(lengths) + 1, n, ld) and t.is_contiguous() and t.dtype == torch.float32
+        assert c.shape == (n, nu) and c.is_contiguous()
+        self._cur_n = n
+        w = self._adj_ws(n, 7)
+        par = self._adj_par_cur = self._adj_params_begin(w, n, 7) if need_params else None
+        infos, prev = [], None
+        for j in range(len(lengths), 0, -1):
+            ctx["t_end"] = lengths[j - 1]
+            _lib.call("nlbac_adj_dense_restart", out[j].data_ptr(), ld, dout[j].data_ptr(), ld, prev, ns, nu, n,
+                      w["Z0"].data_ptr(), s)
+            if par and prev is not None:
+                par["th0"], par["out"] = par["out"], par["th0"]
+            prev = self._adj_dopri(w, c, 1, n, par).data_ptr()
+            infos.append(ctx["adjoint_info"])
+        ctx["adjoint_info"] = infos
+        a_x, a_c = self._buf("dy0_adj", n, ns), self._buf("du", n, nu)
+        _lib.call("nlbac_adj_unpack", prev, ns, nu, n, a_x.data_ptr(), a_c.data_ptr(), s)
+        return a_x, a_c, (par["out"] if par else None)
+
     # -- an output interval solved backwards in fine steps (rollout / odeint_grid with adjoint=True and step_size, chained) --
     def adjoint_grid_begin(self, n, method, need_params, atol=1e-7, rtol=1e-5):
         """Start a chained grid adjoint on ``n`` rows (``ode_traj.ChainSubAdjoint``): a solve state of its own — no

@@ -16,8 +16,13 @@ holds; the chain's own carry mode ignores a slot's ``dK`` / ``dy0``), with one s
 between two steps for what step i + 1 sends back to step i.  That is one backward launch per accepted step, as in
 ``odeint``, plus one carry launch per step boundary.
 
-Not served: decreasing ``t``, the continuous adjoint, hipGraph capture (the solve needs the host's look at the control
-block), and nets or settings the device-driven chain refuses — each raises, none runs some other way.
+``odeint_dense_adjoint`` is the same solve with the continuous adjoint as its backward (torchdiffeq's ``odeint_adjoint``
+on a time grid): nothing of the forward is kept but the outputs, the carried columns and the interval lengths; the
+backward walks the grid's intervals last to first, one adaptive adjoint solve each
+(``ode_adjoint.AffineAdjoint.backward_adjoint_dense``), with one ``nlbac_adj_dense_restart`` launch at every grid point.
+
+Not served: decreasing ``t``, hipGraph capture (the solve needs the host's look at the control block), and nets or
+settings the device-driven chain refuses — each raises, none runs some other way.
 """
 import math
 
@@ -29,6 +34,7 @@ from .arena import stream_ptr
 from .ode_grid import _steps_of
 
 SOLVERS_KEY = "_odeint_dense_solvers"      # on the model: {keep mode: solver}, apart from odeint's, rollout's and the grid's
+ADJOINT = "adjoint"                        # the key of odeint_dense_adjoint's solver beside the keep modes
 
 
 def _taus(t):
@@ -46,8 +52,8 @@ def _check(func, y0, t, atol, rtol, adjoint):
     """Every argument check, before anything touches a device; returns the output times (``_taus``)."""
     from .sac_cbf_clf.model import NeuralODEModel
     if adjoint:
-        raise NotImplementedError("odeint_dense: the continuous adjoint on a dense dopri5 solve is not offered; the "
-                                  "backward goes through the accepted steps")
+        raise NotImplementedError("odeint_dense: the backward goes through the accepted steps; the continuous adjoint on "
+                                  "a dense dopri5 solve is an entry of its own, odeint_dense_adjoint")
     if not isinstance(func, NeuralODEModel):
         raise TypeError("nlbac_amd.ode_dense.odeint_dense integrates this build's NeuralODEModel (its field runs as HIP "
                         "kernels); got %s" % type(func).__name__)
@@ -76,8 +82,12 @@ def solver_of(func, mode):
     sv = svs.get(mode)
     if sv is None:
         sv = T.traj_class(func).Solver(func, func.device_handles()[0].arena.device)
-        sv.keep_acts = mode != "inputs"      # (no grad: the same kernels as odeint's solver; nothing is read back)
+        sv.keep_acts = mode not in ("inputs", ADJOINT)      # (no grad: the same kernels as odeint's solver; nothing is read back)
         sv.interp_fold = False               # the attempt launches interpolate nothing: every output is read off the slots
+        if mode == ADJOINT:
+            # nothing of a step is kept (the slots are the smallest there are: no activation rows, no dz), and the values
+            # are still those of the solvers that keep rows
+            sv.adjoint = sv.rows_sums = True
         svs[mode] = sv
     return sv
 
@@ -168,20 +178,26 @@ class _DenseSolve:
         return ws0.dy0, du, flat
 
 
+def _solve(sv, taus, atol, rtol, y0):
+    """One dense solve on ``sv`` from ``y0`` (B, n_s + n_c): returns (out (T, B, n_s + n_c), the ``_DenseSolve``)."""
+    n, ns = y0.shape[0], sv.n_s
+    y0 = y0.detach().contiguous()
+    x0, c = y0[:, :ns].contiguous(), y0[:, ns:].contiguous()
+    xs = torch.empty(len(taus), n, ns, dtype=torch.float32, device=y0.device)
+    solve = _DenseSolve(sv, taus, x0, c, atol, rtol, xs)
+    out = torch.empty(len(taus) + 1, n, y0.shape[1], dtype=torch.float32, device=y0.device)
+    out[0].copy_(y0)
+    out[1:, :, :ns].copy_(xs)
+    out[1:, :, ns:].copy_(c)          # (the carried columns, the same at every output point)
+    return out, solve
+
+
 class _DenseFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, func, sv, taus, atol, rtol, mode, y0, *params):
-        n, ns = y0.shape[0], func.n_s
-        y0 = y0.detach().contiguous()
-        x0, c = y0[:, :ns].contiguous(), y0[:, ns:].contiguous()
-        xs = torch.empty(len(taus), n, ns, dtype=torch.float32, device=y0.device)
-        solve = _DenseSolve(sv, taus, x0, c, atol, rtol, xs)
+        out, solve = _solve(sv, taus, atol, rtol, y0)
         ctx.func, ctx.mode, ctx.n_params = func, mode, len(params)
         ctx.kept = solve if mode != "none" else None
-        out = torch.empty(len(taus) + 1, n, y0.shape[1], dtype=torch.float32, device=y0.device)
-        out[0].copy_(y0)
-        out[1:, :, :ns].copy_(xs)
-        out[1:, :, ns:].copy_(c)          # (the carried columns, the same at every output point)
         return out
 
     @staticmethod
@@ -197,3 +213,84 @@ class _DenseFunction(torch.autograd.Function):
             gy0 = dout[0] + torch.cat([dx0, dc + dout[1:, :, ns:].sum(0)], dim=1)
         gp = T.param_grads(ctx.func, flat) if need_p else [None] * ctx.n_params
         return (None, None, None, None, None, None, gy0, *gp)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The continuous adjoint on a dense solve: torchdiffeq.odeint_adjoint(func, y0, t) with default arguments on a time grid
+# ---------------------------------------------------------------------------------------------------------------------
+def _lengths(t):
+    """The lengths of the grid's intervals, ``float(t[j]) - float(t[j-1])`` of the entries as ``_taus`` reads them (a
+    Python sequence rounded to float32 first); with two points the one length is ``_taus``'s one output time."""
+    times = [float(v) for v in torch.as_tensor(t).detach().cpu()]
+    return tuple(times[j] - times[j - 1] for j in range(1, len(times)))
+
+
+def odeint_dense_adjoint(func, y0, t, *, atol=1e-7, rtol=1e-5, adjoint_params=None):
+    """``torchdiffeq.odeint_adjoint(func, y0, t)`` (0.2.3, default arguments: dopri5, the adjoint's method and tolerances
+    the forward's, the mixed adjoint norm) on a time grid: ``odeint_dense``'s arguments, checks, refusals and VALUES — the
+    same single dense solve, ``out`` (T, B, n_s + n_c) bit for bit — with the backward as a second solve that keeps
+    nothing of the forward but ``out`` (which the caller holds), the carried columns and the interval lengths.  Step
+    slots are the solver's pool, as under ``torch.no_grad``; memory does not grow with the number of accepted steps.
+
+    Differentiable as one autograd node w.r.t. ``y0`` and, with ``adjoint_params=None`` (every parameter of ``func``,
+    torchdiffeq's default), ``func.parameters()``; ``adjoint_params=()`` leaves the parameter adjoint out of the
+    augmented state and of the step-size norm.  Anything else raises ``NotImplementedError``.
+
+    The backward is ``OdeintAdjointMethod.backward`` on the grid: the intervals [t[j-1], t[j]] are solved from j = T-1
+    down to 1, each a fresh adaptive solve over its length (own initial-step selection; steps are not cut, the lower end
+    is the interpolant of the last accepted step).  At a grid point the state part of the augmented state is RESET to the
+    stored ``out[j]`` and ``dout[j]``'s state columns are added to the state adjoint; the state adjoint, the carried
+    columns' adjoint and the parameter adjoint are CARRIED from the interval above and take part in the mixed norm, as in
+    torchdiffeq.  The one deviation from torchdiffeq: the output gradients on the CARRIED columns (whose derivative is
+    zero, so they pass through every interval unchanged) are added outside the solve — ``gy0[:, n_s:] = dout[0][:, n_s:] +
+    a_c + sum_j dout[j][:, n_s:]`` — and stay out of the norm, as ``odeint_adjoint`` does for two points.  With two time
+    points gradients and values are ``odeint_adjoint(..., method="dopri5")``'s bit for bit.  The gradient equals
+    ``odeint_dense``'s direct back-propagation to solver tolerance only, and every interval costs at least one host wait
+    on the control block.
+
+    Raises as ``odeint_dense`` does (decreasing ``t``, hipGraph capture, nets the device-driven chain refuses).  Not
+    offered: several problems in one solve, a sample-sharded solve, adjoint tolerances or method other than the
+    forward's."""
+    with_params = adjoint_params is None
+    if not with_params and len(tuple(adjoint_params)) != 0:
+        raise NotImplementedError("odeint_dense_adjoint: adjoint_params is None (all of func's parameters) or ()")
+    taus = _check(func, y0, t, atol, rtol, False)
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("odeint_dense_adjoint: not inside a hipGraph capture — the adaptive solves need the host's look "
+                           "at the control block to know how many steps were accepted")
+    sv = solver_of(func, ADJOINT)
+    if not sv._chain_ok(1, y0.shape[0]):
+        raise NotImplementedError(
+            "odeint_dense_adjoint: needs the device-driven dopri5 chain (_chain_ok(1, %d) is false: fused=%s — the fused "
+            "step kernels refuse these nets — device_loop=%s); the host-driven and stage-by-stage paths emit no interior "
+            "points" % (y0.shape[0], sv.fused, sv.device_loop))
+    func.refresh_device_weights()
+    return _DenseAdjointFunction.apply(func, sv, taus, _lengths(t), float(atol), float(rtol), with_params, y0,
+                                       *func.parameters())
+
+
+class _DenseAdjointFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, func, sv, taus, lengths, atol, rtol, with_params, y0, *params):
+        out, solve = _solve(sv, taus, atol, rtol, y0)
+        # kept: the carried columns and the lengths; the step slots stay the pool's, the output times go with `solve`
+        ctx.func, ctx.sv, ctx.c, ctx.lengths, ctx.solve_id = func, sv, solve.c, lengths, solve.solve_id
+        ctx.with_params, ctx.n_params = with_params, len(params)
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        sv, ns = ctx.sv, ctx.func.n_s
+        assert sv.stats["solves"] == ctx.solve_id, \
+            "odeint_dense_adjoint: backward must run before the next odeint_dense_adjoint with the same model"
+        out, = ctx.saved_tensors
+        dout = dout.float().contiguous()
+        need_p = ctx.with_params and any(ctx.needs_input_grad[8:])
+        a_x, a_c, theta = sv.backward_adjoint_dense(out, dout, ctx.c, ctx.lengths, need_p)
+        gy0 = None
+        if ctx.needs_input_grad[7]:
+            # the carried columns' output gradients never entered the solve: added here, as odeint_adjoint adds them
+            gy0 = dout[0] + torch.cat([a_x, a_c + dout[1:, :, ns:].sum(0)], dim=1)
+        gp = T.param_grads(ctx.func, theta.clone()) if need_p else [None] * ctx.n_params
+        return (None, None, None, None, None, None, None, gy0, *gp)

@@ -72,6 +72,10 @@ class AffineNodeSolver(SolverWorkspaces, DopriDriver, AffineAdjoint):
         # (SAC_CBF_CLF.enable_data_parallel(step_control="shard")) computes on that many ranks, on one device
         self.row_groups = 1
         self.adjoint = False   # True: ``backward`` is the continuous adjoint (odeint_adjoint); the forward keeps nothing
+        # True: a launch that keeps nothing runs the kernel instance of a solver that keeps activation rows (acts_bits 0)
+        # although this solver's slots hold mask words only (keep_acts False) — that instance's sums, bit for bit, in
+        # slots without rows (ode_dense.odeint_dense_adjoint)
+        self.rows_sums = False
         self.device_loop = True   # dopri5 attempts as a device-driven chain (no host decision per attempt)
         self._chain_len = 1    # attempts the last chain solve needed = launches enqueued before the host first looks
         self._in_map, self._in_map_armed = None, False      # ``set_in_map``
@@ -201,7 +205,8 @@ class AffineNodeSolver(SolverWorkspaces, DopriDriver, AffineAdjoint):
                   fptr(*h_host) if h_host is not None else None, h_dev, _lib.DOPRI_CTL if h_dev else 0,
                   ws.K.data_ptr(), ws.Y.data_ptr(), ws.gout.data_ptr(),
                   ws.acts_f.data_ptr() if save_acts else None, ws.S * n * ws.wf,
-                  ws.acts_g.data_ptr() if save_acts else None, ws.S * n * ws.wg, ws.acts_bits if save_acts else int(ws.bits),
+                  ws.acts_g.data_ptr() if save_acts else None, ws.S * n * ws.wg,
+                  ws.acts_bits if save_acts else int(ws.bits and not self.rows_sums),
                   out.data_ptr() if out is not None else None, err.data_ptr() if err is not None else None,
                   C.byref(chain) if chain is not None else None, C.byref(im) if im is not None else None, stream_ptr())
         self.nfe += st1 - st0
@@ -515,7 +520,8 @@ class ConcatNodeSolver(ConcatAdjoint, AffineNodeSolver):
                   c_out, len(c_out) if c_out is not None else 0, c_err, len(c_err) if c_err is not None else 0,
                   fptr(*h_host) if h_host is not None else None, h_dev, _lib.DOPRI_CTL if h_dev else 0,
                   ws.K.data_ptr(), ws.Y.data_ptr(), ws.acts.data_ptr() if save_acts else None,
-                  ws.S * P * rpp * ws.wa, 1 if ws.bits else 0, out.data_ptr() if out is not None else None,
+                  ws.S * P * rpp * ws.wa, 1 if (ws.bits and (save_acts or not self.rows_sums)) else 0,
+                  out.data_ptr() if out is not None else None,
                   err.data_ptr() if err is not None else None,
                   self.norm.data_ptr() if self.norm is not None else None,
                   ws.Xn.data_ptr() if (self.norm is not None and save_acts and self.keep_acts) else None,
@@ -702,7 +708,8 @@ def _odeint(func, y0, t, method, atol, rtol, adjoint, options):
     if t.numel() != 2:
         raise NotImplementedError("odeint: the reference only ever integrates over t = [0, dt]; got %d time points "
                                   "(ode_grid.odeint_grid takes a longer grid, with adjoint=True the continuous adjoint on it; "
-                                  "ode_dense.odeint_dense reads one dopri5 solve at every point of one)"
+                                  "ode_dense.odeint_dense reads one dopri5 solve at every point of one, "
+                                  "ode_dense.odeint_dense_adjoint with the continuous adjoint as its backward)"
                                   % t.numel())
     dt = float(t[1]) - float(t[0])
     func.refresh_device_weights()
@@ -730,7 +737,8 @@ def odeint_adjoint(func, y0, t, *, method="dopri5", atol=1e-7, rtol=1e-5, adjoin
     steps, and the gradient equals direct back-propagation only to solver tolerance.  ``adjoint_params``: ``None`` —
     every parameter of ``func`` (torchdiffeq's default, ``find_parameters``); ``()`` — no parameter adjoint (it then
     also stays out of the step-size norm).  The reference never calls this; semantics follow the
-    published algorithm."""
+    published algorithm.  On a time grid (more than two points, dopri5) the same call is
+    ``nlbac_amd.ode_dense.odeint_dense_adjoint``: one dense forward solve, the adjoint walked over the grid's intervals."""
     if adjoint_params is not None and len(tuple(adjoint_params)) != 0:
         raise NotImplementedError("odeint_adjoint: adjoint_params is None (all of func's parameters) or ()")
     return _odeint(func, y0, t, method, atol, rtol, "no-params" if adjoint_params is not None else "params", options)

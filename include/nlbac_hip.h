@@ -601,6 +601,36 @@ int nlbac_node_rk_traj_bwd(const nlbac_mlp *f, const nlbac_mlp *g, const float *
                            const float *beta, const float *c_out, float h, const float *G, const float *acts_f,
                            long acts_f_ls, const float *acts_g, long acts_g_ls, int acts_bits, const float *dout,
                            float *dx0, float *du, float *dK, float *dG, float *dz_f, float *dz_g, nlbac_stream_t s);
+/* dopri5 rollouts of the control-affine NODE under TILE-LOCAL step control (ABI 17, additions): every 32-row tile of
+ * the n rows is an adaptive solve of its own — its own error norm over its rows' [x | u] entries, step sizes and accept
+ * decisions — so the whole horizon of H control intervals is one launch (csrc/node_tile_kernels.hip).  The rows of tile j
+ * are what the chained dopri5 solves (nlbac_node_rk_fwd with an nlbac_rk_chain) give for a batch of those rows alone.
+ * Only where nlbac_node_dopri_tile_ok(f, g) is 1 (the register-resident kernels' shapes), else 0.
+ * fwd: x0 [n][n_s], u [H][n][n_u], out [H][n][n_s]; beta [7][7] and c_err [7]: dopri5's table and error weights; dt the
+ * interval, rtol / atol the tolerances.  accepted / attempts [tiles][H] and status [tiles] (int, ZERO on entry; tiles =
+ * ceil(n / 32)) receive the accepted and attempted steps per interval and 0 (ok), 1 (no slot left), 2 (more than 1000
+ * attempts in an interval); a tile that stops writes NaN into its rows of out from that interval on.  G NULL: nothing is
+ * kept (Y, acts_*, hslots, iv_first, iv_x NULL too; acts_bits picks the kernel instance).  G given: a backward follows —
+ * every ACCEPTED step of a tile is kept in a slot, max_slots (>= H) per tile for the whole horizon, stage (slot, st) at
+ * index slot*7 + st of max_slots*7 stages: G [max_slots*7][n][n_s*n_u], acts_* as nlbac_node_rk_traj_fwd lays them out for
+ * max_slots*7 stages, Y [max_slots*7][n][n_s] (the stage inputs; weight gradients only, else NULL) — all ZERO on entry,
+ * a stage nobody evaluated reads as zero — hslots [tiles][max_slots] (double: the kept steps' sizes), iv_first (int) and
+ * iv_x (float) [tiles][H]: an interval's first slot and the abscissa of its output inside its last step. */
+int nlbac_node_dopri_tile_ok(const nlbac_mlp *f, const nlbac_mlp *g);
+int nlbac_node_dopri_tile_fwd(const nlbac_mlp *f, const nlbac_mlp *g, const float *x0, const float *u, int n, int H,
+                              const float *beta, const float *c_err, double dt, float rtol, float atol, float *out,
+                              int max_slots, float *Y, float *G, float *acts_f, long acts_f_ls, float *acts_g,
+                              long acts_g_ls, int acts_bits, double *hslots, int *iv_first, float *iv_x, int *accepted,
+                              int *attempts, int *status, nlbac_stream_t s);
+/* Its backward, one launch: every tile walks its intervals H-1 .. 0 and inside each its kept steps last to first
+ * (iv_nacc: the forward's `accepted`; only where every status is 0).  dout [H+1][n][n_s] -> dx0 [n][n_s], du [H][n][n_u].
+ * dK, dG, dz_f, dz_g (together, or all NULL; not with acts_bits 1; ZERO on entry): per (slot, stage, row) as in the
+ * forward — with Y and the activation rows what nlbac_mlp_bwd_weights takes as one batch over the used slots. */
+int nlbac_node_dopri_tile_bwd(const nlbac_mlp *f, const nlbac_mlp *g, const float *u, int n, int H, const float *beta,
+                              int max_slots, const double *hslots, const int *iv_first, const int *iv_nacc,
+                              const float *iv_x, const float *G, const float *acts_f, long acts_f_ls,
+                              const float *acts_g, long acts_g_ls, int acts_bits, const float *dout, float *dx0,
+                              float *du, float *dK, float *dG, float *dz_f, float *dz_g, nlbac_stream_t s);
 /* One-launch fixed-grid rollout of the single-net NODE dx/dt = net([x | c]) (euler: n_stages 1, rk4: 4, with that
  * method's beta [n_stages][n_stages] and c_out [n_stages]): H intervals of step h, interval k integrating from out[k-1]
  * (x0 for k = 0) with the carried columns c[k] — what H nlbac_concat_rk_fwd launches compute, bit for bit, in one launch

@@ -833,3 +833,279 @@ __device__ __forceinline__ void rk_traj_bwd_end(const NodeRkBwdLaunch& L, const 
             }
         }
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// dopri5 under tile-local step control (node_tile_kernels.hip): every 32-row tile is an adaptive solve of its own — its
+// own error norm, step sizes and accept decisions — so a tile never waits for another workgroup and a whole horizon of
+// H control intervals is ONE launch.  Per interval the tile does what the chained solve's launches do for a batch of
+// its rows, in their order: stage 0, the norm of mode 0 and its controller; the probe stage f(y0 + h0 f0), mode 1;
+// attempts of stages 1-6 (stage 0 = the accepted step before: FSAL) with the error norm and the controller behind each,
+// until an accepted step reaches dt; the interpolant there.  The control block lives in LDS; one lane runs the
+// controller (fp64, one pow) in a function of its own, outside the stage loop's live ranges.
+// What a backward needs is kept per (slot, stage, row), a slot per ACCEPTED step, counted per tile over the whole
+// horizon (a rejected attempt overwrites its slot): G, mask words / activation rows, stage inputs Y — the [k][stage][row]
+// layout of the fixed-grid kernels with the slot in place of k — and per tile the slots' step sizes, per interval its
+// first slot, its accepted count and the interpolation abscissa.
+// Every loop has a bound from the launch's arguments: H intervals, NODE_TILE_MAX_ATTEMPTS attempts per interval,
+// max_slots slots.  A tile that hits one stops: status, NaN into its rows of the outputs from that interval on.
+// ---------------------------------------------------------------------------------------------------------------
+#define NODE_TILE_MAX_ATTEMPTS 1000      /* per interval: the chained solve's own cap (ode_dopri.py) */
+enum { TILE_OK = 0, TILE_NO_SLOT = 1, TILE_MAX_ATTEMPTS = 2 };
+
+struct NodeTileFwd {
+    int H;
+    int keep;                         // a backward follows: accepted steps are kept in slots
+    int max_slots;                    // (keep) slots a tile has for the whole horizon
+    double* hslots;                   // (keep) [tile][max_slots] the kept steps' sizes
+    int* iv_first;                    // (keep) [tile][H] interval k's first slot
+    float* iv_x;                      // (keep) [tile][H] the abscissa of out[k+1] in interval k's last step
+    int* accepted;                    // [tile][H] accepted steps of interval k
+    int* attempts;                    // [tile][H] attempted steps of interval k
+    int* status;                      // [tile] TILE_*
+};
+
+struct NodeTileBwd {
+    int H, max_slots;
+    const double* hslots; const int* iv_first; const int* iv_nacc; const float* iv_x;
+    const float* dout;                // [H+1][n][n_s]
+    float* dx0;                       // [n][n_s]
+};
+
+// the tile's ints in LDS
+enum { TI_SLOT = 0, TI_COUNT = 4 };
+
+// the controller on the tile's finished squared-norm sums (a batch of `cnt` entries), on the block in LDS
+static __device__ __attribute__((noinline)) void rk_tile_controller(double s0, double s1, double cnt, int mode,
+                                                                    double t_end, double* ctl) {
+    dopri_control_vals(sqrt(s0 / cnt), sqrt(s1 / cnt), 0, mode, t_end, ctl);
+}
+
+// the first stage's input of a phase (rk_fwd_first_input's arithmetic; probe: the table row is (1, 0, ...)), to sYin
+// and, when the slot keeps its stage inputs, to gY
+__device__ __forceinline__ void rk_tile_first_input(const NodeRkLaunch& L, const RkFwdTile& T, int row0, int st, bool probe,
+                                                    float* gY, float* in, int t, int nthr) {
+    const int n = L.n, ns = L.n_s;
+    for (int idx = t; idx < NLBAC_MLP_TILE * 8; idx += nthr) {
+        const int m = idx >> 3, c = idx & 7;
+        float a = 0.f;
+        if (c < ns) {
+            a = T.sY0[m * RK_MAX_NS + c];
+            const float h = T.sH[m];
+            for (int j = 0; j < st; ++j) {
+                const float b = probe ? (j == 0 ? 1.f : 0.f) : L.beta[st][j];
+                if (b != 0.f) a = a + T.sK[(j * NLBAC_MLP_TILE + m) * RK_MAX_NS + c] * (b * h);
+            }
+            if (gY && row0 + m < n) gY[((long)st * n + row0 + m) * ns + c] = a;
+        }
+        in[m * 8 + c] = a;
+    }
+}
+
+// the tile stops in interval k: NaN into its rows of out[k ..], its status.  No barrier inside.
+template <int NTHR>
+__device__ __forceinline__ void rk_tile_stop(const NodeRkLaunch& L, const NodeTileFwd& X, int row0, int k, int status, int tid) {
+    const int n = L.n, ns = L.n_s;
+    const float nanv = __int_as_float(0x7fc00000);
+    for (int kk = k; kk < X.H; ++kk)
+        for (int idx = tid; idx < NLBAC_MLP_TILE * ns; idx += NTHR) {
+            const int m = idx / ns, r = idx - m * ns;
+            if (row0 + m < n) L.out[(long)kk * n * ns + (long)(row0 + m) * ns + r] = nanv;
+        }
+    if (tid == 0) X.status[row0 / NLBAC_MLP_TILE] = status;
+}
+
+// behind a phase's stages (ph 0: stage 0; 1: the probe; >= 2: an attempt): the tile's norm of that mode (the per-entry
+// arithmetic of rk_fwd_outputs_and_control, summed as rk_fwd_norm_pre sums one tile), the controller, and what its
+// decision asks for — the next phase's step size in sH; an accepted step's size into its slot; behind an accepted
+// step that stops short of dt the next step's y0 = y1 (the last stage's input, sYin) and K_0 = K_6 (FSAL); behind one
+// that reaches dt out[k] = the interpolant there, the next interval's state and actions.  Returns 0: go on, 1: the
+// interval is done, 2 / 3: no slot is left for the next step of this interval / for interval k + 1 (the tile stops).
+// Every thread calls it; contains barriers, ends with one.
+template <int NTHR>
+__device__ __forceinline__ int rk_tile_after_phase(const NodeRkLaunch& L, const NodeTileFwd& X, const RkFwdTile& T,
+                                                   const float* sYin, double* sCtl, int* sInt, int row0, int n_rows,
+                                                   int k, int ph, int slot, int tid) {
+    static_assert(NTHR == NLBAC_MLP_TILE * RK_MAX_NS, "one (row, component) per thread");
+    const int n = L.n, ns = L.n_s, nu = L.n_u, tile = row0 / NLBAC_MLP_TILE;
+    const int mode = ph < 2 ? ph : 2;
+    const float *sK = T.sK, *sY0 = T.sY0, *sU = T.sU, *sH = T.sH;
+    const int m8 = tid >> 3, r8 = tid & 7, row8 = row0 + m8;
+    float o = 0.f;
+    if (mode == 2) {      // the error estimate's term of this (row, component) and, if the step reaches dt, the interpolant there
+        const double t = sCtl[C_T], hd = sCtl[C_H];
+        const bool ip = t + hd >= L.t_end;
+        const float ipx = (float)((L.t_end - t) / hd);
+        if (r8 < ns) {
+            const int sl = L.S_total - 1;
+            const float h = sH[m8];
+            float a = 0.f;
+            for (int j = 0; j < L.n_err; ++j)
+                if (L.c_err[j] != 0.f) a = a + sK[(j * NLBAC_MLP_TILE + m8) * RK_MAX_NS + r8] * (L.c_err[j] * h);
+            const float y = sY0[m8 * RK_MAX_NS + r8];
+            float y1 = y;
+            for (int j = 0; j < sl; ++j)
+                if (L.beta[sl][j] != 0.f) y1 = y1 + sK[(j * NLBAC_MLP_TILE + m8) * RK_MAX_NS + r8] * (L.beta[sl][j] * h);
+            const float tol = L.atol + L.rtol * fmaxf(fabsf(y), fabsf(y1));
+            const float q = a / tol;
+            T.sG[m8 * RK_MAX_NS + r8] = q * q;
+            if (ip) {      // (uniform)
+                float kk[7], bl[RK_MAX_STAGES];
+#pragma unroll
+                for (int j = 0; j < 7; ++j) kk[j] = sK[(j * NLBAC_MLP_TILE + m8) * RK_MAX_NS + r8];
+#pragma unroll
+                for (int j = 0; j < RK_MAX_STAGES; ++j) bl[j] = L.beta[sl][j];
+                float a1 = y;
+#pragma unroll
+                for (int j = 0; j < 6; ++j) {
+                    const float tt = a1 + kk[j] * (bl[j] * h);
+                    a1 = (j < sl && bl[j] != 0.f) ? tt : a1;
+                }
+                o = dopri_interp_value(y, a1, kk, h, ipx);
+            }
+        }
+        __syncthreads();
+    }
+    if (tid < 64) {
+        const int m = tid;
+        float v0 = 0.f, v1 = 0.f;
+        if (m < n_rows) {
+            for (int r = 0; r < ns; ++r) {
+                const float y = sY0[m * RK_MAX_NS + r];
+                if (mode == 2) {
+                    v0 += T.sG[m * RK_MAX_NS + r];
+                } else {
+                    const float sc = L.atol + fabsf(y) * L.rtol;
+                    if (mode == 0) {
+                        const float q0 = y / sc, q1 = sK[m * RK_MAX_NS + r] / sc;
+                        v0 += q0 * q0; v1 += q1 * q1;
+                    } else {
+                        const float q = (sK[(NLBAC_MLP_TILE + m) * RK_MAX_NS + r] - sK[m * RK_MAX_NS + r]) / sc;
+                        v0 += q * q;
+                    }
+                }
+            }
+            if (mode == 0)
+                for (int c = 0; c < nu; ++c) {
+                    const float y = sU[m * RK_MAX_NU + c];
+                    const float q = y / (L.atol + fabsf(y) * L.rtol);
+                    v0 += q * q;
+                }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { v0 += __shfl_down(v0, off, 64); v1 += __shfl_down(v1, off, 64); }
+        if (tid == 0) {
+            rk_tile_controller((double)v0, (double)v1, (double)n_rows * (double)(ns + nu), mode, L.t_end, sCtl);
+            if (mode == 0 && X.keep) X.iv_first[(long)tile * X.H + k] = slot;
+        }
+    }
+    __syncthreads();
+    if (mode < 2) {
+        if (tid < NLBAC_MLP_TILE) T.sH[tid] = (float)sCtl[mode == 0 ? C_H0 : C_H];
+        __syncthreads();
+        return 0;
+    }
+    const bool accept = sCtl[C_ACCEPT] > 0.0, done = sCtl[C_DONE] > 0.0;      // (uniform)
+    int ret = done ? 1 : 0;
+    if (accept && tid == 0 && X.keep) X.hslots[(long)tile * X.max_slots + slot] = sCtl[C_HUSED];
+    if (done) {
+        // out[k] and the next interval's state; its actions
+        const bool more = k + 1 < X.H;
+        float vu = 0.f;
+        if (more && tid < NLBAC_MLP_TILE * RK_MAX_NU) {
+            const int m = tid >> 2, c = tid & 3;
+            vu = L.u[(long)(k + 1) * n * nu + (long)min(row0 + m, n - 1) * nu + min(c, nu - 1)];
+        }
+        if (r8 < ns && row8 < n) {
+            L.out[(long)k * n * ns + (long)row8 * ns + r8] = o;
+            T.sY0[m8 * RK_MAX_NS + r8] = o;
+        }
+        if (more && tid < NLBAC_MLP_TILE * RK_MAX_NU) {
+            const int m = tid >> 2, c = tid & 3;
+            T.sU[tid] = (row0 + m < n && c < nu) ? vu : 0.f;
+        }
+        if (tid == 0) {
+            X.accepted[(long)tile * X.H + k] = (int)sCtl[C_NACC] + 1;
+            X.attempts[(long)tile * X.H + k] = (int)sCtl[C_NSTEPS];
+            if (X.keep) X.iv_x[(long)tile * X.H + k] = (float)sCtl[C_X];
+        }
+    } else {
+        if (accept && r8 < ns && row8 < n) {      // the next step starts where this one ended; its stage 0 is this one's last (FSAL)
+            T.sY0[m8 * RK_MAX_NS + r8] = sYin[m8 * 8 + r8];
+            T.sK[m8 * RK_MAX_NS + r8] = sK[((L.S_total - 1) * NLBAC_MLP_TILE + m8) * RK_MAX_NS + r8];
+        }
+        if (tid < NLBAC_MLP_TILE) T.sH[tid] = (float)sCtl[C_H];
+    }
+    if (accept && X.keep) {      // the slot is taken; the next step — of this interval or of the next — needs one more
+        const bool need = !done || k + 1 < X.H;
+        if (need && slot + 1 >= X.max_slots) ret = done ? 3 : 2;
+        if (tid == 0) sInt[TI_SLOT] = slot + 1;
+    }
+    __syncthreads();
+    return ret;
+}
+
+// backward of a tile's kept steps (node_rr_bwd_body with TILE), before the stages of interval k's step sj (slot =
+// first + sj; of nacc): the step size; at the interval's LAST step (the first one walked) the actions, du = 0 and, from
+// d = dout[k+1] (+ the dy0 of interval k+1 in sDY0 when kk > 0), the interpolant's backward: dy0, dy1 (sDYup), dK_0..6
+// (rk_bwd_tile_constants' ip branch); at an earlier step the hand-over of the chained launches (back_idx > 0): dYup =
+// the later step's dy0, dK_6 = its dK_0 (FSAL), every other dK and dy0 zero; du goes on accumulating.  No barrier inside.
+template <int NTHR>
+__device__ __forceinline__ void rk_tile_bwd_begin(const NodeRkBwdLaunch& L, const NodeTileBwd& X, const RkBwdTile& T,
+                                                  int row0, int k, int kk, bool last, float h, float x, int tid) {
+    static_assert(NTHR == NLBAC_MLP_TILE * RK_MAX_NS, "one (row, component) per thread");
+    const int n = L.n, ns = L.n_s, nu = L.n_u;
+    const int m = tid >> 3, c = tid & 7;
+    const bool ok = row0 + m < n && c < ns;
+    if (tid < NLBAC_MLP_TILE) T.sH[tid] = h;
+    if (last) {
+        float vu = 0.f;
+        if (tid < NLBAC_MLP_TILE * RK_MAX_NU) {
+            const int mu = tid >> 2, cu = tid & 3;
+            vu = L.u[(long)k * n * nu + (long)min(row0 + mu, n - 1) * nu + min(cu, nu - 1)];
+        }
+        float d = X.dout[(long)(k + 1) * n * ns + (long)min(row0 + m, n - 1) * ns + min(c, ns - 1)];
+        if (kk > 0) d = d + T.sDY0[tid];
+        float d0v, d1v, dk[7];
+        dopri_interp_grad(d, h, x, d0v, d1v, dk);
+        if (tid < NLBAC_MLP_TILE * RK_MAX_NU) {
+            const int mu = tid >> 2, cu = tid & 3;
+            T.sU[tid] = (row0 + mu < n && cu < nu) ? vu : 0.f;
+            T.sDU[tid] = 0.f;
+        }
+        T.sDY0[tid] = ok ? d0v : 0.f;
+        T.sDYup[tid] = ok ? d1v : 0.f;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) T.sDK[j * NLBAC_MLP_TILE * RK_MAX_NS + tid] = ok ? dk[j] : 0.f;
+    } else {
+        const float dy = T.sDY0[tid], dk0 = T.sDK[tid];
+        T.sDYup[tid] = ok ? dy : 0.f;
+        T.sDY0[tid] = 0.f;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) T.sDK[j * NLBAC_MLP_TILE * RK_MAX_NS + tid] = (j == 6 && ok) ? dk0 : 0.f;
+    }
+}
+
+// behind the stages of interval k's step sj: dK of the evaluated stages to global when the weight gradients want it (an
+// FSAL step's stage 0 belongs to the step before: its row stays zero); behind the interval's first step du[k], behind
+// interval 0's dx0 = dout[0] + dy0.  No barrier inside.
+template <int NTHR>
+__device__ __forceinline__ void rk_tile_bwd_end(const NodeRkBwdLaunch& L, const NodeTileBwd& X, const RkBwdWhere& w,
+                                                const RkBwdTile& T, int row0, int k, int sj, int tid) {
+    const int n = L.n, ns = L.n_s, nu = L.n_u;
+    if (w.gdK)
+        for (int idx = tid; idx < L.st_hi * NLBAC_MLP_TILE * ns; idx += NTHR) {
+            const int j = idx / (NLBAC_MLP_TILE * ns), rem = idx - j * NLBAC_MLP_TILE * ns;
+            const int m = rem / ns, c = rem - m * ns, row = row0 + m;
+            if (row < n && j >= w.st_lo) w.gdK[((long)j * n + row) * ns + c] = T.sDK[(j * NLBAC_MLP_TILE + m) * RK_MAX_NS + c];
+        }
+    if (sj != 0) return;
+    for (int idx = tid; idx < NLBAC_MLP_TILE * nu; idx += NTHR) {
+        const int m = idx / nu, c = idx - m * nu, row = row0 + m;
+        if (row < n) L.du[(long)k * n * nu + (long)row * nu + c] = T.sDU[m * RK_MAX_NU + c];
+    }
+    if (k == 0)
+        for (int idx = tid; idx < NLBAC_MLP_TILE * ns; idx += NTHR) {
+            const int m = idx / ns, c = idx - m * ns, row = row0 + m;
+            if (row < n) X.dx0[(long)row * ns + c] = X.dout[(long)row * ns + c] + T.sDY0[m * RK_MAX_NS + c];
+        }
+}

@@ -42,6 +42,17 @@ __device__ __forceinline__ int rr_out_row(int grp, int hu, int ns, int nu) {
 
 #define RR_MAX_W 4        /* layer 0 + up to three hid x hid layers (n_layers <= 5: the reference's f_net) */
 
+// dynamic LDS of the forward / backward bodies, in floats (the carve at the top of each); both are even, so the
+// tile-local step control's doubles (TILE: NLBAC_DOPRI_CTL of them and TI_COUNT ints) sit aligned behind them
+__host__ __device__ constexpr int node_rr_fwd_lds_floats() {
+    return RkFwdTile::floats() + NLBAC_MLP_TILE * 8 + 2 * 3 * 8 * 64 + 2 * 32 * 64 + NLBAC_MLP_TILE * RK_MAX_NS + 2 * 2 * 64 + 4;
+}
+__host__ __device__ constexpr int node_rr_bwd_lds_floats() {
+    return RkBwdTile::floats() + 2 * 4 * 8 * 64 + 2 * 32 * 64 + 2 * 16 * 64 + 4;
+}
+static_assert(node_rr_fwd_lds_floats() % 2 == 0, "the tile's control block is 8-byte aligned");
+__host__ __device__ constexpr int node_tile_fwd_lds_floats() { return node_rr_fwd_lds_floats() + 2 * NLBAC_DOPRI_CTL + TI_COUNT; }
+
 #ifdef RR_TIMING      // ablation build only: the backward's stamps go to a device symbol (nlbac_debug_bwd_stamps reads it back)
 __device__ long long g_bwd_stamps[2 * 256];      // (defined in the one translation unit that includes this with RR_TIMING)
 #define BWSTAMP(slot_) if (blockIdx.x == 0 && lane == 0 && half == 0) g_bwd_stamps[grp * 256 + (slot_)] = (long long)__builtin_readcyclecounter();
@@ -67,10 +78,17 @@ __device__ long long g_bwd_stamps[2 * 256];      // (defined in the one translat
 // HOLD (with GRID, not SUB; nlbac_node_rk_hold_fwd: a rollout under step_size): H = N fine intervals, hm of them per
 // control interval — interval k's step size is hs[k % hm], its actions L.u + (k / hm) n n_u, and L.out + (k / hm) n n_s
 // is written behind a control interval's last fine step only (node_rk_shared.h).
-template <int NB, int R, int BITS, int SPLIT, bool TRAJ = false, bool GRID = false, bool SUB = false, bool HOLD = false>
+// TILE (not TRAJ; nlbac_node_dopri_tile_fwd, node_tile_kernels.hip): H intervals of dopri5 under tile-local step control
+// (node_rk_shared.h).  The stage loop runs in PHASES per interval — stage 0; the probe stage (index 1, quiet, the table
+// row (1, 0, ..)); attempts of stages 1 .. S-1 — with rk_tile_after_phase behind each; what is kept goes to the tile's
+// current slot (stage index slot S + st), nothing when tile->keep is 0.
+template <int NB, int R, int BITS, int SPLIT, bool TRAJ = false, bool GRID = false, bool SUB = false, bool HOLD = false,
+          bool TILE = false>
 __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 1, const float* hs = nullptr,
-                                                 const NlbacSubGrid* sub = nullptr, int hm = 1) {
+                                                 const NlbacSubGrid* sub = nullptr, int hm = 1,
+                                                 const NodeTileFwd* tile = nullptr) {
     static_assert(TRAJ || !GRID, "a time grid is a trajectory");
+    static_assert(!(TILE && TRAJ), "tile-local step control walks its intervals itself");
     static_assert(GRID || !SUB, "sub-steps are a time grid's");
     static_assert((GRID && !SUB) || !HOLD, "a held control's fine steps are a time grid's, its outputs their end points");
     static_assert(BITS != 2 || SPLIT == 0, "rows + words: the fit's forward is the unsplit one (same sums as mode 0)");
@@ -99,6 +117,9 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
     float* const sF2 = sX + 2 * KS * 64;                 // [32][8] the g_net wave's part of f(x)
     unsigned* const sMw = reinterpret_cast<unsigned*>(sF2 + NLBAC_MLP_TILE * RK_MAX_NS);      // [half][f, g][lane] mask-word parts
     int* const sFlag = reinterpret_cast<int*>(sMw + 2 * 2 * 64);                               // [half] stage + 1 once sX is there
+    // (TILE) the tile's control block and ints, behind everything else (node_tile_fwd_lds_floats)
+    double* const sCtl = reinterpret_cast<double*>(smem + node_rr_fwd_lds_floats());
+    int* const sInt = reinterpret_cast<int*>(sCtl + NLBAC_DOPRI_CTL);
     const nlbac_mlp& net = L.net[grp];
     const int nw = net.n_layers - 1;                     // layer 0 + (nw - 1) hid x hid layers, then the output layer
     const int n_rows = min(NLBAC_MLP_TILE, n - row0);
@@ -118,12 +139,13 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
     // the mask words: in place of the rows (BITS 1, layer stride acts_ls), or behind the net's nw layers of rows (BITS 2,
     // [layer][S_total * n][4])
     unsigned* const words = !acts ? nullptr : reinterpret_cast<unsigned*>(BITS == 2 ? acts + (long)nw * acts_ls : acts);
-    const long words_ls = (BITS == 2) ? (long)(TRAJ ? H : 1) * L.S_total * n * 4 : acts_ls;
+    const long words_ls = (BITS == 2) ? (long)(TRAJ ? H : (TILE ? tile->max_slots : 1)) * L.S_total * n * 4 : acts_ls;
     const int stage_end = L.stage_end, S_last = L.S_total - 1;
     // the initial-step probe with its norm fused into this launch (norm_mode 1): nothing it would leave in memory — the
     // probe point, its derivative, g there — is read by anyone (the norm comes from LDS, the step's stage 1 overwrites
     // them), and stores in front of the epilogue's atomics are waited for there (vmcnt is in order)
-    const bool quiet = L.norm_mode == 1;
+    // (TILE: the probe phase, and every phase of a solve that keeps nothing)
+    const bool quiet_launch = L.norm_mode == 1;
 
     // ---- the wave's weight stream: hid x hid layers 1 .. nw-1, then layer 1 again (next stage)
     const __amdgpu_buffer_rsrc_t rs = rr_rsrc(net.packed, net.packed_floats);
@@ -199,24 +221,50 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
     }
 
     RSTAMP(0)
+    if constexpr (TILE) { if (tid == 0) sInt[TI_SLOT] = 0; }
     rk_fwd_tile_constants<256>(L, w, T, row0, tid);
     RSTAMP(1)
 
-    for (int k = 0; k < (TRAJ ? H : 1); ++k) {
-    const int kS = TRAJ ? k * L.S_total : 0;             // interval k's first stage in the [k][stage][row] layout
+    [[maybe_unused]] unsigned tile_seq = 0u;             // (TILE) stages run so far: what the SPLIT hand-over's flags count
+    for (int k = 0; k < ((TRAJ || TILE) ? H : 1); ++k) {
+    const int kS_iv = TRAJ ? k * L.S_total : 0;          // interval k's first stage in the [k][stage][row] layout
     if constexpr (TRAJ) {
-        w.gK = L.K + (long)kS * n * ns;
-        w.gY = L.Y + (long)kS * n * ns;
-        w.gG = L.G + (long)kS * n * gout;
+        w.gK = L.K + (long)kS_iv * n * ns;
+        w.gY = L.Y + (long)kS_iv * n * ns;
+        w.gG = L.G + (long)kS_iv * n * gout;
     }
     // (GRID) this interval's step size: behind the barrier that ended the interval before, in front of the one behind
     // the first stage's input (which, at stage 0, uses no step size; nlbac_node_rk_grid_fwd requires stage_begin == 0)
     if constexpr (GRID) { if (tid < NLBAC_MLP_TILE) T.sH[tid] = hs[HOLD ? k % hm : k]; }
-    for (int st = L.stage_begin; st < stage_end; ++st) {
-        const int sb = 2 + 8 * (st - L.stage_begin);
+    // (TILE) the phases of the interval come back to this label (a jump, not a loop: the instances that are not TILE
+    // have to come out of the compiler as they did before there were phases); ph counts them
+    int ph = 0;
+    [[maybe_unused]] tile_phase:;
+    // (TILE) the phase's stages, and the slot it keeps them in: stage index slot S + st of max_slots S stages
+    int slot = 0, tile_b = 0, tile_e = 0;
+    bool tile_quiet = false;
+    if constexpr (TILE) {
+        if (tile->keep) slot = __builtin_amdgcn_readfirstlane(sInt[TI_SLOT]);
+        tile_b = ph == 0 ? 0 : 1;
+        tile_e = ph == 0 ? 1 : (ph == 1 ? 2 : L.S_total);
+        tile_quiet = ph == 1 || !tile->keep;
+    }
+#define RR_ST_B (TILE ? tile_b : L.stage_begin)
+#define RR_ST_E (TILE ? tile_e : stage_end)
+#define RR_FKEY (TILE ? (int)tile_seq : kS + st + 1)      /* (SPLIT) the stage the hand-over's flag names */
+    const int kS = TILE ? slot * L.S_total : kS_iv;
+    const bool quiet = TILE ? tile_quiet : quiet_launch;
+    if constexpr (TILE) {
+        w.gG = L.G ? L.G + (long)kS * n * gout : nullptr;
+        w.gY = (L.Y && !quiet) ? L.Y + (long)kS * n * ns : nullptr;
+    }
+    for (int st = RR_ST_B; st < RR_ST_E; ++st) {
+        const int sb = 2 + 8 * (st - RR_ST_B);
         (void)sb;
-        if (st == L.stage_begin) {
-            rk_fwd_first_input(L, w, T, row0, st, 8, sYin, 8, !quiet, tid, 256);
+        if constexpr (TILE) ++tile_seq;
+        if (st == RR_ST_B) {
+            if constexpr (TILE) rk_tile_first_input(L, T, row0, st, ph == 1, w.gY, sYin, tid, 256);
+            else rk_fwd_first_input(L, w, T, row0, st, 8, sYin, 8, !quiet, tid, 256);
             __syncthreads();
         }
         RSTAMP(sb + 0)
@@ -253,7 +301,7 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
         // loads' in-order vmcnt queue: issued one by one between the fragment loads, each made the MFMAs behind it wait
         // for its own trip to HBM; as a burst the trips overlap and the stream stalls once per layer.
         auto save_layer = [&](int l, const float (&H)[KS]) __attribute__((always_inline)) {
-            if (!ROWS || !acts || !row_ok) return;
+            if (!ROWS || !acts || !row_ok || (TILE && quiet)) return;
             float* rowp = acts + (long)l * acts_ls + srow * HID;
 #pragma unroll
             for (int jo = 0; jo < NB; ++jo) {
@@ -264,7 +312,7 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
             }
         };
         auto save_word = [&](int l, unsigned word) __attribute__((always_inline)) {
-            if (WORDS && words && row_ok) words[(long)l * words_ls + srow * 4 + q] = word;
+            if (WORDS && words && row_ok && !(TILE && quiet)) words[(long)l * words_ls + srow * 4 + q] = word;
         };
         // layer 0's value ks (no bias: folded into the product), finished just before layer 1's k-step ks reads it
         auto pre_l0 = [&](int ks) __attribute__((always_inline)) {
@@ -403,7 +451,7 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) sX[(half * KS + ks) * 64 + lane] = Ha[ks];
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __hip_atomic_store(sFlag + half, kS + st + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_store(sFlag + half, RR_FKEY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 #pragma unroll
                 for (int jo = 0; jo < NB; ++jo) bv[jo] = rr_bias<S>(params + boff[3], jo, q);
                 auto fin3 = [&](int jo, int r) __attribute__((always_inline)) {
@@ -423,7 +471,7 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
             } else {
                 outl(I3{}, Ha);
                 // f_net's layer-2 activations of the same rows, once its wave has put them there
-                while (__hip_atomic_load(sFlag + half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != kS + st + 1) __builtin_amdgcn_s_sleep(1);
+                while (__hip_atomic_load(sFlag + half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != RR_FKEY) __builtin_amdgcn_s_sleep(1);
                 asm volatile("" ::: "memory");
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) Hb[ks] = sX[(half * KS + ks) * 64 + lane];
@@ -455,7 +503,7 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
         //      thread, every LDS operand requested up front, no data-dependent branch
         {
             const int mm = tid >> 3, c = tid & 7;
-            const bool more = st + 1 < stage_end, cv = c < ns, rv = row0 + mm < n;
+            const bool more = st + 1 < RR_ST_E, cv = c < ns, rv = row0 + mm < n;
             float a = T.sF[mm * RK_MAX_NS + c];
             if constexpr (SPLIT != 0) a += sF2[mm * RK_MAX_NS + c];
             float gv[RK_MAX_NU], uv[RK_MAX_NU], kj[RK_MAX_STAGES - 1];
@@ -486,22 +534,33 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
             }
             if (cv) {
                 T.sK[(st * NLBAC_MLP_TILE + mm) * RK_MAX_NS + c] = a;
-                if (rv && !quiet) w.gK[((long)st * n + row0 + mm) * ns + c] = a;
-                if (more && rv) w.gY[((long)(st + 1) * n + row0 + mm) * ns + c] = y;
+                if (rv && !quiet && !TILE) w.gK[((long)st * n + row0 + mm) * ns + c] = a;      // (TILE: K_0..6 stay in LDS)
+                if (more && rv && (!TILE || w.gY)) w.gY[((long)(st + 1) * n + row0 + mm) * ns + c] = y;
             }
             if (more) sYin[mm * 8 + c] = cv ? y : 0.f;
         }
         if constexpr (SPLIT != 0 && BITS != 0) {      // layer 3's mask word: the two waves' parts, stored by the f_net wave
-            if (grp == 0 && L.acts[0] && row_ok)
+            if (grp == 0 && L.acts[0] && row_ok && !(TILE && quiet))
                 reinterpret_cast<unsigned*>(L.acts[0] + w.soff + 3 * L.acts_ls[0])[srow * 4 + q] =
                     sMw[(half * 2 + 0) * 64 + lane] | sMw[(half * 2 + 1) * 64 + lane];
         }
         __syncthreads();
         RSTAMP(sb + 7)
     }
+#undef RR_ST_B
+#undef RR_ST_E
+#undef RR_FKEY
+    if constexpr (TILE) {
+        const int act = rk_tile_after_phase<256>(L, *tile, T, sYin, sCtl, sInt, row0, n_rows, k, ph, slot, tid);
+        if (act >= 2) { rk_tile_stop<256>(L, *tile, row0, act == 3 ? k + 1 : k, TILE_NO_SLOT, tid); return; }
+        if (act == 0) {      // the next phase — at most NODE_TILE_MAX_ATTEMPTS attempts behind the two that open the interval
+            if (++ph >= 2 + NODE_TILE_MAX_ATTEMPTS) { rk_tile_stop<256>(L, *tile, row0, k, TILE_MAX_ATTEMPTS, tid); return; }
+            goto tile_phase;
+        }
+    }
     if constexpr (TRAJ) rk_traj_advance<256, GRID, SUB, HOLD>(L, T, row0, k, H, tid, sub, hm);
     }
-    if constexpr (TRAJ) return;
+    if constexpr (TRAJ || TILE) return;
 #ifdef RR_TIMING
     if (L.err) return;
 #endif
@@ -527,11 +586,17 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
 // intervals (node_rk_shared.h).
 // HOLD (with GRID, not SUB; nlbac_node_rk_hold_bwd): X.H = N fine intervals, hm per control interval; X.dout [N/hm + 1]
 // and L.du [N/hm] belong to the control intervals (node_rk_shared.h).
-template <int NB, int R, int BITS, int SPLIT, bool TRAJ = false, bool GRID = false, bool SUB = false, bool HOLD = false>
+// TILE (not TRAJ; nlbac_node_dopri_tile_bwd, node_tile_kernels.hip): the backward of a dopri5 horizon under tile-local
+// step control — intervals k = H-1 .. 0 and, inside each, the tile's kept steps last to first (slot = first + sj; rows /
+// words / G / dK / dG / dz at stage index slot S + st); rk_tile_bwd_begin / _end (node_rk_shared.h) around each step's
+// stages; a step that is not its interval's first leaves out stage 0 (its predecessor's last: FSAL).
+template <int NB, int R, int BITS, int SPLIT, bool TRAJ = false, bool GRID = false, bool SUB = false, bool HOLD = false,
+          bool TILE = false>
 __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const NodeRkTrajBwd* X = nullptr,
                                                  const float* hs = nullptr, const NlbacSubGrid* sub = nullptr,
-                                                 int hm = 1) {
+                                                 int hm = 1, const NodeTileBwd* tile = nullptr) {
     static_assert(TRAJ || !GRID, "a time grid is a trajectory");
+    static_assert(!(TILE && TRAJ), "tile-local step control walks its intervals itself");
     static_assert(GRID || !SUB, "sub-steps are a time grid's");
     static_assert((GRID && !SUB) || !HOLD, "a held control's fine steps are a time grid's, its outputs their end points");
     constexpr bool WORDS = BITS != 0;          // the gates come from the mask words (1, 2) or from the activation rows (0)
@@ -573,8 +638,9 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
     const long acts_ls = L.acts_ls[grp];
     // (WORDS) where the forward left the words: in place of the rows (1), or behind the net's nw layers of rows (2)
     const unsigned* const words = reinterpret_cast<const unsigned*>(BITS == 2 ? acts + (long)nw * acts_ls : acts);
-    const int H = TRAJ ? X->H : 1;
-    const long words_ls = (BITS == 2) ? (long)H * L.S_total * n * 4 : acts_ls;
+    const int H = TRAJ ? X->H : (TILE ? tile->H : 1);
+    // (the stages the buffers hold: H S of a trajectory, max_slots S under TILE)
+    const long words_ls = (BITS == 2) ? (long)(TILE ? tile->max_slots : H) * L.S_total * n * 4 : acts_ls;
     const int dx_stage0 = L.dx_stage0;
 
     // ---- weight stream: backward fragments of layers nw-1 .. 1, then nw-1 again (next stage)
@@ -619,7 +685,8 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
     }
 
     BWSTAMP(0)
-    if constexpr (!TRAJ) rk_bwd_tile_constants<256>(L, w, T, row0, tid);
+    if constexpr (!TRAJ && !TILE) rk_bwd_tile_constants<256>(L, w, T, row0, tid);
+    if constexpr (TILE) w.ip = true;      // (dL/dy1 of every step comes from sDYup: rk_tile_bwd_begin)
     __syncthreads();
     BWSTAMP(1)
 
@@ -638,13 +705,33 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
 #pragma unroll
         for (int r = 0; r < RK_MAX_NS; ++r) gnext[r] = gp[min(r, ns - 1) * nu];
     };
+    [[maybe_unused]] unsigned tile_seq = 0u;                      // (TILE) stages walked so far: what the SPLIT flags count
     for (int kk = 0; kk < H; ++kk) {
-    const int k = H - 1 - kk, kS = TRAJ ? k * L.S_total : 0;      // interval k's first stage in the [k][stage][row] layout
-    if constexpr (TRAJ) {
+    const int k = H - 1 - kk, kS_iv = TRAJ ? k * L.S_total : 0;   // interval k's first stage in the [k][stage][row] layout
+    // (TILE) the interval's kept steps: clamped to the tile's slots, whatever the arrays hold
+    int t_first = 0, t_nacc = 1;
+    float t_x = 0.f;
+    if constexpr (TILE) {
+        const long ti = (long)blockIdx.x * H + k;
+        t_first = min(max(tile->iv_first[ti], 0), tile->max_slots - 1);
+        t_nacc = min(max(tile->iv_nacc[ti], 1), tile->max_slots - t_first);
+        t_x = tile->iv_x[ti];
+    }
+    // (TILE) the interval's steps come back to this label, last to first (a jump, not a loop: see the forward)
+    int sj = TILE ? t_nacc - 1 : 0;
+    [[maybe_unused]] tile_step:;
+    const int kS = TILE ? (t_first + sj) * L.S_total : kS_iv;
+    if constexpr (TRAJ || TILE) {
         w.gG = L.G + (long)kS * n * gout;
         w.gdG = L.dG ? L.dG + (long)kS * n * gout : nullptr;
         w.gdK = L.dK ? L.dK + (long)kS * n * ns : nullptr;
-        rk_traj_bwd_begin<256, GRID, SUB, HOLD>(L, *X, T, row0, k, kk, tid, hs, sub, hm);
+        if constexpr (TILE) {
+            w.st_lo = sj == 0 ? 0 : 1;
+            const float h = (float)tile->hslots[(long)blockIdx.x * tile->max_slots + t_first + sj];
+            rk_tile_bwd_begin<256>(L, *tile, T, row0, k, kk, sj == t_nacc - 1, h, t_x, tid);
+        } else {
+            rk_traj_bwd_begin<256, GRID, SUB, HOLD>(L, *X, T, row0, k, kk, tid, hs, sub, hm);
+        }
         __syncthreads();
     }
 #pragma unroll
@@ -820,7 +907,7 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
             if (grp == 0) { prod(I3{}, Za, Zb, avB, avA); dxl(Zb); }
             else dxl(Za);
         } else {
-            const int key = kk * L.S_total + L.st_hi - st;    // (1, 2, ...: what the flags count)
+            const int key = TILE ? (int)(++tile_seq) : kk * L.S_total + L.st_hi - st;    // (1, 2, ...: what the flags count)
             const float* const actsF = L.acts[0] + w.soff;
             if (grp == 0) {
                 // dz_3 complete (the top product is not deferred here), handed over; then the upper groups of dz_2's blocks
@@ -861,7 +948,7 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
                 if (WORDS) {
                     const unsigned* const wordsF = reinterpret_cast<const unsigned*>(
                         BITS == 2 ? actsF + (long)(netF.n_layers - 1) * L.acts_ls[0] : actsF);
-                    mwF = wordsF[2 * (BITS == 2 ? (long)H * L.S_total * n * 4 : L.acts_ls[0]) + srow * 4 + q];
+                    mwF = wordsF[2 * (BITS == 2 ? (long)(TILE ? tile->max_slots : H) * L.S_total * n * 4 : L.acts_ls[0]) + srow * 4 + q];
                     mwF = row_ok ? mwF : 0u;
                 } else {
                     const float* arow = actsF + 2 * L.acts_ls[0] + srow * HID;
@@ -936,8 +1023,13 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
         rk_traj_bwd_end<256, GRID, SUB, HOLD>(L, *X, w, T, row0, k, tid, sub, hm);
         __syncthreads();
     }
+    if constexpr (TILE) {
+        rk_tile_bwd_end<256>(L, *tile, w, T, row0, k, sj, tid);
+        __syncthreads();
+        if (--sj >= 0) goto tile_step;
     }
-    if constexpr (!TRAJ) rk_bwd_outputs<256>(L, w, T, row0, tid);
+    }
+    if constexpr (!TRAJ && !TILE) rk_bwd_outputs<256>(L, w, T, row0, tid);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -972,12 +1064,10 @@ static void node_rr_start(const NodeRrTable<Launch>& t, const Launch& A, int hid
 
 template <typename Launch>
 static void node_rr_fwd_start(const NodeRrTable<Launch>& t, const Launch& A, int hid, int n, int acts_bits, hipStream_t s) {
-    node_rr_start(t, A, hid, n, acts_bits,
-                  RkFwdTile::floats() + NLBAC_MLP_TILE * 8 + 2 * 3 * 8 * 64 + 2 * 32 * 64 + NLBAC_MLP_TILE * RK_MAX_NS +
-                      2 * 2 * 64 + 4, s);
+    node_rr_start(t, A, hid, n, acts_bits, node_rr_fwd_lds_floats(), s);
 }
 
 template <typename Launch>
 static void node_rr_bwd_start(const NodeRrTable<Launch>& t, const Launch& A, int hid, int n, int acts_bits, hipStream_t s) {
-    node_rr_start(t, A, hid, n, acts_bits, RkBwdTile::floats() + 2 * 4 * 8 * 64 + 2 * 32 * 64 + 2 * 16 * 64 + 4, s);
+    node_rr_start(t, A, hid, n, acts_bits, node_rr_bwd_lds_floats(), s);
 }

@@ -8,6 +8,8 @@
   * what a solve keeps and how its backward becomes gradients, one class per path — ``AffineTraj`` / ``ConcatTraj`` (one
     launch forward, one backward, + the weight-gradient launch over all H * stages * rows) and ``Chain`` (H one-interval
     solves on the existing solvers) — each with ``forward(x0, u, xs)`` and ``backward(dout, need_p)``; ``solve`` picks;
+    ``AffineTileDopri`` beside them for ``TileSteps`` — ``EqualSteps`` solved by dopri5 under tile-local step control, one
+    launch each way over step slots (``rollout(step_control="tile")``);
   * the same under ``adjoint=True`` (``solve_adjoint``): nothing kept but the outputs the caller holds and the controls —
     ``AdjointPlan`` (per output interval the fine steps of its backward solve, the chunk), ``AffineAdjTraj`` /
     ``ConcatAdjTraj`` (the continuous adjoint over the whole horizon in one ``nlbac_*_adj_traj`` launch per chunk),
@@ -372,6 +374,133 @@ class ConcatTraj:
         return dx0, du, _reduce(arena, arena.n_slabs)
 
 
+class TileSteps(EqualSteps):
+    """``EqualSteps`` solved by dopri5 under tile-local step control (``rollout(step_control="tile")``): every 32-row tile
+    an adaptive solve of its own, ``max_steps`` step slots per tile for the whole horizon when a backward follows;
+    ``info`` (a dict or None) receives the solve's device tensors."""
+
+    def __init__(self, dt, H, max_steps, info=None):
+        EqualSteps.__init__(self, dt, H)
+        self.max_steps, self.info = max_steps, info
+
+
+class AffineTileDopri:
+    """Device buffers of one dopri5 solve of the control-affine NODE under tile-local step control: one
+    ``nlbac_node_dopri_tile_fwd`` launch for the whole horizon, one ``nlbac_node_dopri_tile_bwd`` for its backward (+ the
+    weight-gradient launch over the used slots).  Slot-major [slot][stage][row] over max_steps * 7 stages, a slot per
+    accepted step of a tile — ``AffineTraj``'s layout with the slot in place of the interval; zero-filled, so that a
+    stage nobody evaluated (a slot a tile did not use, stage 0 of a step that took it from the step before) adds
+    nothing to the weight gradients."""
+    S = 7
+
+    @staticmethod
+    def shapes_ok(func):
+        """What the library's ``nlbac_node_dopri_tile_ok`` asks of the nets, from their shapes alone (no device, no
+        library: ``rollout._check`` runs before either)."""
+        if not func.affine:
+            return False
+        lin = lambda net: [m for m in net.modules() if isinstance(m, torch.nn.Linear)]
+        f, g = lin(func.f_net), lin(func.g_net)
+        hid = f[0].out_features
+        return (len(f) == 5 and len(g) == 4 and hid in (64, 100, 128) and g[0].out_features == hid and
+                1 <= func.n_s <= 8 and 1 <= func.n_u <= 4 and ((func.n_s + 3) // 4) * func.n_u <= 4)
+
+    @staticmethod
+    def ok(func):
+        if not func.affine:
+            return False
+        f, g = func.device_handles()
+        return _lib.load().nlbac_node_dopri_tile_ok(C.byref(f.desc), C.byref(g.desc)) == 1
+
+    def __init__(self, func, n, iv, mode, atol, rtol, device):
+        from .ode_consts import DP_C_ERR
+        if not self.ok(func):
+            raise NotImplementedError("rollout: step_control='tile' needs nets the register-resident kernels serve "
+                                      "(nlbac_node_dopri_tile_ok); there is no chained fallback")
+        f, g = func.device_handles()
+        self.f, self.g, self.iv, self.mode, self.tol = f, g, iv, mode, (rtol, atol)
+        self.ns, self.nu, self.n, self.H = func.n_s, func.n_u, n, iv.H
+        beta = [0.0] * (self.S * self.S)
+        for i, r in enumerate(TABLEAU["dopri5"]["beta"]):
+            for j, v in enumerate(r):
+                beta[(i + 1) * self.S + j] = v
+        self.beta, self.c_err = fptr(*beta), fptr(*DP_C_ERR)
+        self.tiles = (n + _lib.MLP_TILE - 1) // _lib.MLP_TILE
+        z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=device)
+        self.accepted, self.attempts = z(self.tiles, iv.H, dtype=torch.int32), z(self.tiles, iv.H, dtype=torch.int32)
+        self.status = z(self.tiles, dtype=torch.int32)
+        self.M = iv.max_steps if mode != "none" else 0
+        MS = self.M * self.S
+        words = mode == "inputs" or (mode == "params" and env_switch("fit_words"))
+        self.bits = 0 if mode == "none" else (1 if mode == "inputs" else (2 if words else 0))
+        self.G = self.Y = self.hslots = self.iv_first = self.iv_x = None
+        self.acts, self.ls = [None, None], [0, 0]
+        if mode != "none":
+            self.G = z(MS, n, self.ns * self.nu)
+            self.Y = z(MS, n, self.ns) if mode == "params" else None
+            self.hslots = z(self.tiles, self.M, dtype=torch.float64)
+            self.iv_first, self.iv_x = z(self.tiles, iv.H, dtype=torch.int32), z(self.tiles, iv.H)
+            for i, net in enumerate((f, g)):      # (AffineTraj's layouts over MS stages)
+                nw = net.n_layers - 1
+                if mode == "inputs":
+                    self.acts[i], self.ls[i] = z(nw * MS * n * 4, dtype=torch.int32), MS * n * 4
+                else:
+                    self.acts[i] = z(nw * MS * n * (net.hid + (4 if words else 0)))
+                    self.ls[i] = MS * n * net.hid
+
+    def forward(self, x0, u, xs):
+        self.u = u
+        rtol, atol = self.tol
+        _lib.call("nlbac_node_dopri_tile_fwd", C.byref(self.f.desc), C.byref(self.g.desc), x0.data_ptr(), u.data_ptr(),
+                  self.n, self.H, self.beta, self.c_err, self.iv.dt, rtol, atol, xs.data_ptr(), self.M, _ptr(self.Y),
+                  _ptr(self.G), _ptr(self.acts[0]), self.ls[0], _ptr(self.acts[1]), self.ls[1], self.bits,
+                  _ptr(self.hslots), _ptr(self.iv_first), _ptr(self.iv_x), self.accepted.data_ptr(),
+                  self.attempts.data_ptr(), self.status.data_ptr(), stream_ptr())
+        if self.iv.info is not None:
+            self.iv.info.update(accepted=self.accepted, attempts=self.attempts, status=self.status)
+
+    def backward(self, dout, need_p):
+        n, H, M, dev = self.n, self.H, self.M, dout.device
+        # the one look at the solve: every tile's status and step count, long after the launch has finished
+        seen = torch.stack((self.status, self.accepted.sum(1, dtype=torch.int32))).cpu()
+        used = int(seen[1].max())
+        bad = seen[0].nonzero().flatten().tolist()
+        if bad:
+            why = {1: "ran out of step slots", 2: "took more than 1000 attempts in one interval"}
+            raise _lib.NlbacError(
+                "rollout(step_control='tile'): tile %d %s (status %d; %d of %d tiles stopped), so the solve has no "
+                "backward: max_steps = %d slots per tile, the largest count of accepted steps a tile had kept when it "
+                "stopped or finished is %d — raise max_steps (its default is 8 H)"
+                % (bad[0], why.get(int(seen[0][bad[0]]), "stopped"), int(seen[0][bad[0]]), len(bad), self.tiles, M, used))
+        z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        zero = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+        dx0, du = z(n, self.ns), z(H, n, self.nu)
+        MS = M * self.S
+        dK = dG = dz_f = dz_g = None
+        if need_p:
+            dK, dG = zero(MS, n, self.ns), zero(MS, n, self.ns * self.nu)
+            dz_f, dz_g = zero(self.f.n_layers - 1, MS * n, self.f.hid), zero(self.g.n_layers - 1, MS * n, self.g.hid)
+        _lib.call("nlbac_node_dopri_tile_bwd", C.byref(self.f.desc), C.byref(self.g.desc), self.u.data_ptr(), n, H,
+                  self.beta, M, self.hslots.data_ptr(), self.iv_first.data_ptr(), self.accepted.data_ptr(),
+                  self.iv_x.data_ptr(), self.G.data_ptr(), _ptr(self.acts[0]), self.ls[0], _ptr(self.acts[1]), self.ls[1],
+                  self.bits, dout.data_ptr(), dx0.data_ptr(), du.data_ptr(), _ptr(dK), _ptr(dG), _ptr(dz_f), _ptr(dz_g),
+                  stream_ptr())
+        if not need_p:
+            return dx0, du, None
+        # every stage of the USED slots as one batch through the weight-gradient launch: the slots are the leading
+        # index, so the first used * 7 * n rows of every buffer hold them (the layers' stride stays that of all slots)
+        arena = self.f.arena
+        io = io_array(2)
+        for i, (dy, ld, dz) in enumerate(((dK, self.ns, dz_f), (dG, self.ns * self.nu, dz_g))):
+            io[i].x0, io[i].x0_dim, io[i].x0_ld = self.Y.data_ptr(), self.ns, self.ns
+            io[i].dy, io[i].dy_ld = dy.data_ptr(), ld
+            io[i].acts, io[i].acts_ls = _ptr(self.acts[i]), self.ls[i]
+            io[i].dz = dz.data_ptr()
+            io[i].grad = arena.grad.data_ptr()
+        bwd_weights(mlp_array([self.f.desc, self.g.desc]), io, 2, used * self.S * n, arena.n_slabs, arena.n, dev)
+        return dx0, du, _reduce(arena, arena.n_slabs)
+
+
 def traj_class(func):
     """The one-launch path of ``func``'s NODE form (the one place that asks which form it is)."""
     return AffineTraj if func.affine else ConcatTraj
@@ -693,6 +822,9 @@ def solve(func, iv, method, mode, one_launch, x0, u, xs, atol=1e-7, rtol=1e-5):
     ``backward(dout (iv.n_out + 1, n, n_s), need_p)`` gives (dx0, the controls' gradient, the flat parameter gradient or None),
     or None without gradients."""
     n = x0.shape[0]
-    kept = traj_class(func)(func, n, iv, method, mode, x0.device) if one_launch else Chain(func, n, iv, method, mode, atol, rtol)
+    if isinstance(iv, TileSteps):      # (dopri5 under tile-local step control: one launch, no chained form)
+        kept = AffineTileDopri(func, n, iv, mode, atol, rtol, x0.device)
+    else:
+        kept = traj_class(func)(func, n, iv, method, mode, x0.device) if one_launch else Chain(func, n, iv, method, mode, atol, rtol)
     kept.forward(x0, u, xs)
     return kept if mode != "none" else None

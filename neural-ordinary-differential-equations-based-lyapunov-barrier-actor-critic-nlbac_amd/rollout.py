@@ -9,6 +9,8 @@ Two paths, same results:
     weight-gradient launch over all H * stages * rows when parameter gradients are wanted);
   * chained (dopri5, nets wider than 128, shapes the register-resident kernels refuse): H single-interval solves on
     the existing solvers, one solver per interval, cached on the model apart from ``odeint``'s and the agent's.
+dopri5 with ``step_control="tile"`` is a third: every 32-row tile under a step control of its own, the whole horizon in
+one ``nlbac_node_dopri_tile_fwd`` launch and one ``nlbac_node_dopri_tile_bwd`` (``ode_traj.AffineTileDopri``).
 ``ONE_LAUNCH = False`` (env ``NLBAC_ROLLOUT_ONE_LAUNCH=0``) runs the chained path everywhere: the A/B baseline.
 
 ``step_size=s`` (euler / rk4) solves every control interval in steps of ``s`` with its control held — the chain of
@@ -25,9 +27,46 @@ from . import ode_traj as T
 
 ONE_LAUNCH = os.environ.get("NLBAC_ROLLOUT_ONE_LAUNCH", "1") != "0"
 METHODS = ("euler", "rk4", "dopri5")
+STEP_CONTROLS = ("batch", "tile")
 
 
-def _check(func, x0, controls, dt, method, step_size=None):
+def _check_device(x0, controls):
+    if x0.device.type != "cuda" or controls.device != x0.device:
+        raise ValueError("rollout: x0 and controls must be on the same CUDA device; got %s and %s"
+                         % (x0.device, controls.device))
+
+
+def _check_tile(func, H, method, adjoint, step_control, max_steps, info):
+    """The checks of ``step_control`` / ``max_steps`` / ``info``; returns the slots a tile gets (``max_steps``, or 8 H)."""
+    if step_control not in STEP_CONTROLS:
+        raise ValueError("rollout: step_control is one of %s; got %r" % (", ".join(STEP_CONTROLS), step_control))
+    if step_control == "batch":
+        if max_steps is not None or info is not None:
+            raise ValueError("rollout: max_steps and info go with step_control='tile' (the batch-wide control keeps its "
+                             "steps per interval and reports through the solvers)")
+        return None
+    if method != "dopri5":
+        raise ValueError("rollout: step_control='tile' goes with method='dopri5'; %s runs on a fixed grid, which has no "
+                         "step control" % method)
+    if adjoint:
+        raise NotImplementedError("rollout: step_control='tile' with adjoint=True is not built (the continuous adjoint "
+                                  "of a tile-local solve is left open)")
+    if info is not None and not isinstance(info, dict):
+        raise ValueError("rollout: info is a dict (it receives the device tensors accepted / attempts / status) or None; "
+                         "got %s" % type(info).__name__)
+    if max_steps is None:
+        max_steps = 8 * H
+    if isinstance(max_steps, bool) or not isinstance(max_steps, int) or max_steps < H:
+        raise ValueError("rollout: max_steps must be an int >= H = %d (every interval keeps at least one step); got %r"
+                         % (H, max_steps))
+    if not func.affine:
+        raise NotImplementedError("rollout: step_control='tile' serves the control-affine NODE only "
+                                  "(nlbac_node_dopri_tile_ok); the single-net form is left open")
+    return max_steps
+
+
+def _check(func, x0, controls, dt, method, step_size=None, *, adjoint=False, step_control="batch", max_steps=None,
+           info=None):
     """Every argument check, before anything touches a device.  Returns ``dt`` rounded to float32 as ``odeint``'s time
     grid rounds it and, with ``step_size``, the fine steps of a control interval (``ode_grid._sub_grid`` over [0, dt])."""
     from .sac_cbf_clf.model import NeuralODEModel
@@ -66,14 +105,21 @@ def _check(func, x0, controls, dt, method, step_size=None):
         if H * m * S * x0.shape[0] >= 2 ** 31:
             raise ValueError("rollout: %d intervals x %d fine steps x %d stages x %d rows is 2^31 or more (the launch's "
                              "limit); use a larger step_size, a shorter horizon or fewer rows" % (H, m, S, x0.shape[0]))
-    if x0.device.type != "cuda" or controls.device != x0.device:
-        raise ValueError("rollout: x0 and controls must be on the same CUDA device; got %s and %s"
-                         % (x0.device, controls.device))
+    slots = _check_tile(func, controls.shape[0], method, adjoint, step_control, max_steps, info)
+    if slots is not None:
+        if slots * 7 * x0.shape[0] >= 2 ** 31:
+            raise ValueError("rollout: max_steps * 7 stages * %d rows is 2^31 or more (the launch's limit: %d * 7 * %d); "
+                             "use a smaller max_steps or fewer rows" % (x0.shape[0], slots, x0.shape[0]))
+        if not T.AffineTileDopri.shapes_ok(func):
+            raise NotImplementedError("rollout: step_control='tile' needs nets the register-resident kernels serve "
+                                      "(nlbac_node_dopri_tile_ok: both nets 64, 100 or 128 wide, f_net five layers, "
+                                      "g_net four); there is no chained fallback")
+    _check_device(x0, controls)
     return dt, hs
 
 
 def rollout(func, x0, controls, dt, *, method="rk4", atol=1e-7, rtol=1e-5, step_size=None, adjoint=False,
-            adjoint_chunk=None):
+            adjoint_chunk=None, step_control="batch", max_steps=None, info=None):
     """Predict H intervals of ``dt`` ahead with the NODE ``func`` (either form; a model owned by an agent included),
     a new control per interval: returns ``out`` (H + 1, B, n_s) with ``out[0] = x0`` and
 
@@ -116,12 +162,49 @@ def rollout(func, x0, controls, dt, *, method="rk4", atol=1e-7, rtol=1e-5, step_
     ``adjoint_chunk`` (a positive int, with ``adjoint=True`` and euler / rk4 only; a ``ValueError`` otherwise): the
     backward runs in launches of that many control intervals, which changes no bit of the input gradients; with
     parameter gradients the weight-gradient batch is one chunk's stage rows, and ``None`` picks the largest chunk that
-    batch admits (2^29 elements per layer) — a horizon the direct backward refuses still gets its gradients."""
+    batch admits (2^29 elements per layer) — a horizon the direct backward refuses still gets its gradients.
+
+    ``step_control`` (dopri5's step-size control): ``"batch"``, the default, is torchdiffeq's — one RMS error norm over
+    all rows, so every row takes the steps the stiffest row needs, and every attempt ends in a reduction over the batch:
+    H chained solves, each a row of launches and a look by the host.  ``"tile"`` (``method="dopri5"`` on the
+    control-affine NODE only) gives every 32 rows a step control of their own — the per-sample control of batched ODE
+    libraries at the granularity of the kernels.  With R_j the rows [32 j, min(32 j + 32, B)):
+
+        out[:, R_j] == rollout(func, x0[R_j], controls[:, R_j], dt, method="dopri5", atol=..., rtol=...)
+
+    — each tile is the chain of H ``odeint`` calls on its own rows: a fresh initial-step selection per interval, norms
+    over the tile's [x | u] entries (a last partial tile is a smaller batch), steps not clipped at ``dt``, ``out[k+1]``
+    the interpolant at ``dt``, step sizes without a gradient.  The results differ from ``"batch"``'s within the
+    tolerances.  No tile waits for another, so the whole horizon is ONE launch (``nlbac_node_dopri_tile_fwd``) that the
+    host never looks into, its backward one more (``nlbac_node_dopri_tile_bwd``, + the weight-gradient launch for
+    parameter gradients): one autograd node, differentiable w.r.t. ``x0``, ``controls`` and the parameters, with the
+    keep modes above.  It needs nets the register-resident kernels serve (``nlbac_node_dopri_tile_ok``; a
+    ``NotImplementedError`` otherwise): there is no chained fallback, and ``ONE_LAUNCH`` does not apply.
+    ``max_steps`` (an int >= H, or None: 8 H; with ``"tile"`` only): the accepted steps a tile may KEEP over the whole
+    horizon when a backward follows — slots are counted per tile across the intervals, not per interval.  The kept
+    buffers are max_steps x 7 stages x B rows of what the grid kernels keep per stage; per row and slot, with n_g = n_s
+    n_u: input gradients 7 (4 n_g + 112) bytes (g(x) and the seven layers' mask words); parameter gradients
+    7 (4 n_g + 4 n_s + 28 hid + 112) bytes forward (g(x), the stage inputs, seven layers of activation rows, the words)
+    and 7 (4 n_g + 4 n_s + 28 hid) more in the backward; nothing under ``torch.no_grad``, where ``max_steps`` is no
+    limit either.  ``max_steps * 7 * B >= 2**31`` is a ``ValueError``.
+    ``info`` (a dict or None; with ``"tile"`` only) receives device tensors, without a synchronisation: ``accepted`` and
+    ``attempts`` (n_tiles, H) int32 — the steps of every tile in every interval — and ``status`` (n_tiles,) int32: 0 ok,
+    1 out of step slots, 2 more than 1000 attempts in an interval (the chained solve's own cap).  A tile that stops
+    writes NaN into its rows of ``out`` from that interval on; the forward never synchronises, and the backward — which
+    reads ``status`` first, one small copy to the host — raises ``NlbacError`` naming ``max_steps`` and the largest
+    count seen."""
     T.check_adjoint_chunk("rollout", adjoint, adjoint_chunk, chained=method == "dopri5")
-    dt, hs = _check(func, x0, controls, dt, method, step_size)
+    # (the default call is the call as it was; the step-control arguments go along only where one of them is given)
+    tile_args = {} if (step_control == "batch" and max_steps is None and info is None) else dict(
+        adjoint=adjoint, step_control=step_control, max_steps=max_steps, info=info)
+    dt, hs = _check(func, x0, controls, dt, method, step_size, **tile_args)
+    slots = None if step_control == "batch" else (8 * controls.shape[0] if max_steps is None else max_steps)
     params = tuple(func.parameters())
     mode = T.keep_mode(params, x0, controls)
     func.refresh_device_weights()
+    if slots is not None:
+        iv = T.TileSteps(dt, controls.shape[0], slots, info)
+        return _RolloutFunction.apply(func, method, iv, float(atol), float(rtol), mode, x0, controls, *params)
     if adjoint:
         return _RolloutAdjointFunction.apply(func, method, dt if hs is None else hs, float(atol), float(rtol), mode,
                                              adjoint_chunk, x0, controls, *params)
@@ -143,9 +226,10 @@ class _RolloutFunction(torch.autograd.Function):
         out = torch.empty(H + 1, n, ns, dtype=torch.float32, device=x0.device)
         first = out[0].copy_(x0)
         ctx.func, ctx.mode, ctx.n_params = func, mode, len(params)
-        one = _one_launch_ok(func, method)
+        tile = isinstance(dt, T.TileSteps)      # (the intervals under tile-local step control: always one launch)
+        one = tile or _one_launch_ok(func, method)
         # (the one launch reads x0 where the caller's tensor is; the chain's first solver keeps a reference, to out[0])
-        iv = T.HeldSteps(dt, H, x0.device) if isinstance(dt, tuple) else T.EqualSteps(dt, H)
+        iv = dt if tile else (T.HeldSteps(dt, H, x0.device) if isinstance(dt, tuple) else T.EqualSteps(dt, H))
         ctx.kept = T.solve(func, iv, method, mode, one, x0 if one else first, u, out.narrow(0, 1, H), atol, rtol)
         return out
 

@@ -631,6 +631,33 @@ int nlbac_node_dopri_tile_bwd(const nlbac_mlp *f, const nlbac_mlp *g, const floa
                               const float *iv_x, const float *G, const float *acts_f, long acts_f_ls,
                               const float *acts_g, long acts_g_ls, int acts_bits, const float *dout, float *dx0,
                               float *du, float *dK, float *dG, float *dz_f, float *dz_g, nlbac_stream_t s);
+/* A dense dopri5 solve of the control-affine NODE under tile-local step control (ABI 17, additions;
+ * csrc/node_tile_dense_kernels.hip): every 32-row tile runs ONE adaptive solve over [0, t_end] and writes its
+ * interpolant at the n_out output times tau (DEVICE doubles, increasing, tau[n_out - 1] == t_end) behind the accepted
+ * steps — the rows of tile j are what the device-driven chain + nlbac_dopri_dense_fwd give for a batch of those rows
+ * alone.  Where nlbac_node_dopri_tile_ok(f, g) is 1.  x0 [n][n_s], u [n][n_u], out [n_out][n][n_s]; accepted /
+ * attempts / status [tiles] (int, ZERO on entry): a tile's counts and 0 / 1 (no slot left) / 2 (more than 1000
+ * attempts); a tile that stops writes NaN into its rows of the outputs it has not emitted.  G NULL: nothing is kept (Y,
+ * acts_*, hslots, ov_slot, ov_x NULL too) and no slot runs out.  G given: the kept buffers of
+ * nlbac_node_dopri_tile_fwd, max_slots (>= 1) slots per tile, ZERO on entry, and ov_slot (int) / ov_x (float)
+ * [tiles][n_out]: the slot that emitted output j, and its abscissa inside that step. */
+int nlbac_node_dopri_tile_dense_fwd(const nlbac_mlp *f, const nlbac_mlp *g, const float *x0, const float *u, int n,
+                                    const float *beta, const float *c_err, const double *tau, int n_out, double t_end,
+                                    float rtol, float atol, float *out, int max_slots, float *Y, float *G,
+                                    float *acts_f, long acts_f_ls, float *acts_g, long acts_g_ls, int acts_bits,
+                                    double *hslots, int *ov_slot, float *ov_x, int *accepted, int *attempts,
+                                    int *status, nlbac_stream_t s);
+/* Its backward, one launch: every tile walks its slots last to first (nacc [tiles]: the forward's `accepted`; only
+ * where every status is 0; what is read of nacc / ov_slot is clamped).  A slot takes the gradients of the outputs that
+ * fell in it (summed in increasing j), then the later step's hand-over as adds, then its own backward.  dout
+ * [n_out][n][n_s]: the gradients of the outputs 1 .. n_out -> dx0 [n][n_s] (the first step's dy0: the gradient of
+ * out[0] is the caller's to add), du [n][n_u].  dK, dG, dz_f, dz_g as in nlbac_node_dopri_tile_bwd. */
+int nlbac_node_dopri_tile_dense_bwd(const nlbac_mlp *f, const nlbac_mlp *g, const float *u, int n, const float *beta,
+                                    int n_out, int max_slots, const double *hslots, const int *ov_slot,
+                                    const float *ov_x, const int *nacc, const float *G, const float *acts_f,
+                                    long acts_f_ls, const float *acts_g, long acts_g_ls, int acts_bits,
+                                    const float *dout, float *dx0, float *du, float *dK, float *dG, float *dz_f,
+                                    float *dz_g, nlbac_stream_t s);
 /* One-launch fixed-grid rollout of the single-net NODE dx/dt = net([x | c]) (euler: n_stages 1, rk4: 4, with that
  * method's beta [n_stages][n_stages] and c_out [n_stages]): H intervals of step h, interval k integrating from out[k-1]
  * (x0 for k = 0) with the carried columns c[k] — what H nlbac_concat_rk_fwd launches compute, bit for bit, in one launch

@@ -871,8 +871,25 @@ struct NodeTileBwd {
     float* dx0;                       // [n][n_s]
 };
 
-// the tile's ints in LDS
-enum { TI_SLOT = 0, TI_COUNT = 4 };
+// DENSE (node_tile_dense_kernels.hip: odeint_dense under tile-local step control): the tile runs ONE interval of length
+// tau[n_out - 1] and reads it at the n_out output times tau (device doubles, increasing) — behind every ACCEPTED attempt
+// it emits the pending outputs the step reaches, out[j] = the step's interpolant at x = (float)((tau_j - t) / h) with
+// t the controller's C_T before it moved (dopri_dense_fwd_kernel's walk, ode_kernels.hip).  When a backward follows,
+// ov_slot / ov_x [tile][n_out] record the slot that emitted output j and its abscissa.
+struct NodeTileDenseFwd {
+    const double* tau;                // [n_out]
+    int n_out;
+    int* ov_slot;                     // (keep) [tile][n_out]
+    float* ov_x;                      // (keep) [tile][n_out]
+};
+
+struct NodeTileDenseBwd {
+    int n_out;
+    const int* ov_slot; const float* ov_x;
+};
+
+// the tile's ints in LDS (TI_OUT: DENSE, the outputs emitted so far)
+enum { TI_SLOT = 0, TI_OUT = 1, TI_COUNT = 4 };
 
 // the controller on the tile's finished squared-norm sums (a batch of `cnt` entries), on the block in LDS
 static __device__ __attribute__((noinline)) void rk_tile_controller(double s0, double s1, double cnt, int mode,
@@ -914,27 +931,55 @@ __device__ __forceinline__ void rk_tile_stop(const NodeRkLaunch& L, const NodeTi
     if (tid == 0) X.status[row0 / NLBAC_MLP_TILE] = status;
 }
 
+// (DENSE) the tile stops: NaN into its rows of every output it has not emitted (j0 = sInt[TI_OUT], read behind the
+// barrier that ends rk_tile_after_phase), its status and the counts so far.  No barrier inside.
+template <int NTHR>
+__device__ __forceinline__ void rk_tile_dense_stop(const NodeRkLaunch& L, const NodeTileFwd& X, const NodeTileDenseFwd& D,
+                                                   const double* sCtl, int row0, int j0, int status, int tid) {
+    const int n = L.n, ns = L.n_s;
+    const float nanv = __int_as_float(0x7fc00000);
+    for (int j = max(j0, 0); j < D.n_out; ++j)
+        for (int idx = tid; idx < NLBAC_MLP_TILE * ns; idx += NTHR) {
+            const int m = idx / ns, r = idx - m * ns;
+            if (row0 + m < n) L.out[(long)j * n * ns + (long)(row0 + m) * ns + r] = nanv;
+        }
+    if (tid == 0) {
+        const int tile = row0 / NLBAC_MLP_TILE;
+        X.status[tile] = status;
+        X.accepted[tile] = (int)sCtl[C_NACC];
+        X.attempts[tile] = (int)sCtl[C_NSTEPS];
+    }
+}
+
 // behind a phase's stages (ph 0: stage 0; 1: the probe; >= 2: an attempt): the tile's norm of that mode (the per-entry
 // arithmetic of rk_fwd_outputs_and_control, summed as rk_fwd_norm_pre sums one tile), the controller, and what its
 // decision asks for — the next phase's step size in sH; an accepted step's size into its slot; behind an accepted
 // step that stops short of dt the next step's y0 = y1 (the last stage's input, sYin) and K_0 = K_6 (FSAL); behind one
 // that reaches dt out[k] = the interpolant there, the next interval's state and actions.  Returns 0: go on, 1: the
 // interval is done, 2 / 3: no slot is left for the next step of this interval / for interval k + 1 (the tile stops).
+// DENSE (H = 1, D the output times): nothing is interpolated at dt; behind an ACCEPTED attempt, before the hand-over,
+// every (row, component) thread writes the pending outputs the step reaches (the walk over tau is uniform), and the
+// interval is done when an accepted step reaches dt = tau[n_out - 1] — by then every output is out.
 // Every thread calls it; contains barriers, ends with one.
-template <int NTHR>
+template <int NTHR, bool DENSE = false>
 __device__ __forceinline__ int rk_tile_after_phase(const NodeRkLaunch& L, const NodeTileFwd& X, const RkFwdTile& T,
                                                    const float* sYin, double* sCtl, int* sInt, int row0, int n_rows,
-                                                   int k, int ph, int slot, int tid) {
+                                                   int k, int ph, int slot, int tid,
+                                                   const NodeTileDenseFwd* D = nullptr) {
     static_assert(NTHR == NLBAC_MLP_TILE * RK_MAX_NS, "one (row, component) per thread");
     const int n = L.n, ns = L.n_s, nu = L.n_u, tile = row0 / NLBAC_MLP_TILE;
     const int mode = ph < 2 ? ph : 2;
     const float *sK = T.sK, *sY0 = T.sY0, *sU = T.sU, *sH = T.sH;
     const int m8 = tid >> 3, r8 = tid & 7, row8 = row0 + m8;
     float o = 0.f;
+    // (DENSE) the step's start and size before the controller moves them, the outputs emitted so far
+    [[maybe_unused]] double d_t = 0.0, d_hd = 0.0;
+    [[maybe_unused]] int d_j = 0;
     if (mode == 2) {      // the error estimate's term of this (row, component) and, if the step reaches dt, the interpolant there
         const double t = sCtl[C_T], hd = sCtl[C_H];
-        const bool ip = t + hd >= L.t_end;
+        const bool ip = !DENSE && t + hd >= L.t_end;
         const float ipx = (float)((L.t_end - t) / hd);
+        if constexpr (DENSE) { d_t = t; d_hd = hd; d_j = sInt[TI_OUT]; }
         if (r8 < ns) {
             const int sl = L.S_total - 1;
             const float h = sH[m8];
@@ -995,7 +1040,7 @@ __device__ __forceinline__ int rk_tile_after_phase(const NodeRkLaunch& L, const 
         for (int off = 32; off > 0; off >>= 1) { v0 += __shfl_down(v0, off, 64); v1 += __shfl_down(v1, off, 64); }
         if (tid == 0) {
             rk_tile_controller((double)v0, (double)v1, (double)n_rows * (double)(ns + nu), mode, L.t_end, sCtl);
-            if (mode == 0 && X.keep) X.iv_first[(long)tile * X.H + k] = slot;
+            if (!DENSE && mode == 0 && X.keep) X.iv_first[(long)tile * X.H + k] = slot;
         }
     }
     __syncthreads();
@@ -1007,7 +1052,34 @@ __device__ __forceinline__ int rk_tile_after_phase(const NodeRkLaunch& L, const 
     const bool accept = sCtl[C_ACCEPT] > 0.0, done = sCtl[C_DONE] > 0.0;      // (uniform)
     int ret = done ? 1 : 0;
     if (accept && tid == 0 && X.keep) X.hslots[(long)tile * X.max_slots + slot] = sCtl[C_HUSED];
-    if (done) {
+    if constexpr (DENSE) {
+        if (accept) {      // (uniform) the outputs this step reaches: a0 = y0, a1 = the last stage's input, K_0..6 as the slots hold them
+            const double tn = d_t + d_hd;
+            int j = min(max(d_j, 0), D->n_out);
+            if (j < D->n_out && tn >= D->tau[j]) {
+                const float h = (float)d_hd, a0 = sY0[m8 * RK_MAX_NS + r8], a1 = sYin[m8 * 8 + r8];
+                float kk[7];
+#pragma unroll
+                for (int s = 0; s < 7; ++s) kk[s] = sK[(s * NLBAC_MLP_TILE + m8) * RK_MAX_NS + r8];
+                do {
+                    const float x = (float)((D->tau[j] - d_t) / d_hd);
+                    const float v = dopri_interp_value(a0, a1, kk, h, x);
+                    if (r8 < ns && row8 < n) L.out[(long)j * n * ns + (long)row8 * ns + r8] = v;
+                    if (tid == 0 && X.keep) {
+                        D->ov_slot[(long)tile * D->n_out + j] = slot;
+                        D->ov_x[(long)tile * D->n_out + j] = x;
+                    }
+                    ++j;
+                } while (j < D->n_out && tn >= D->tau[j]);
+            }
+            if (tid == 0) sInt[TI_OUT] = j;
+        }
+        if (done && tid == 0) {
+            X.accepted[tile] = (int)sCtl[C_NACC] + 1;
+            X.attempts[tile] = (int)sCtl[C_NSTEPS];
+        }
+    }
+    if (!DENSE && done) {
         // out[k] and the next interval's state; its actions
         const bool more = k + 1 < X.H;
         float vu = 0.f;
@@ -1085,10 +1157,57 @@ __device__ __forceinline__ void rk_tile_bwd_begin(const NodeRkBwdLaunch& L, cons
     }
 }
 
+// (DENSE) before the stages of the step in `slot` (the tile's steps last to first): what the outputs that fell in the
+// step send to its y0 / y1 / K — the sum of dopri_interp_grad over them in increasing j, from 0.f
+// (dopri_dense_bwd_kernel's order; [jb, je) are the outputs ov_slot names this slot, je the ones not yet taken, both
+// inside [0, n_out] whatever the arrays hold) — and the hand-over of the chained launches as ADDS onto it
+// (nlbac_dopri_dense_carry): dy1 = g1 + the later step's dy0, dK_6 = gk_6 + its dK_0; the step's own backward adds
+// onto dy0 = g0 and dK = gk.  dout [n_out][n][n_s]: the gradients of the outputs 1 .. n_out.  No barrier inside.
+template <int NTHR>
+__device__ __forceinline__ void rk_tile_dense_bwd_begin(const NodeRkBwdLaunch& L, const NodeTileBwd& X,
+                                                        const NodeTileDenseBwd& D, const RkBwdTile& T, int row0, int slot,
+                                                        bool last, float h, int& je, int tid) {
+    static_assert(NTHR == NLBAC_MLP_TILE * RK_MAX_NS, "one (row, component) per thread");
+    const int n = L.n, ns = L.n_s, nu = L.n_u;
+    const int m = tid >> 3, c = tid & 7;
+    const bool ok = row0 + m < n && c < ns;
+    const long tb = (long)(row0 / NLBAC_MLP_TILE) * D.n_out;
+    if (tid < NLBAC_MLP_TILE) T.sH[tid] = h;
+    int jb = je;
+    while (jb > 0 && D.ov_slot[tb + jb - 1] >= slot) --jb;      // (uniform; at most n_out looks over the whole walk)
+    float g0 = 0.f, g1 = 0.f, gk[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int j = jb; j < je; ++j) {
+        const float x = D.ov_x[tb + j];
+        const float d = X.dout[(long)j * n * ns + (long)min(row0 + m, n - 1) * ns + min(c, ns - 1)];
+        float d0v, d1v, dk[7];
+        dopri_interp_grad(d, h, x, d0v, d1v, dk);
+        g0 += d0v; g1 += d1v;
+#pragma unroll
+        for (int s = 0; s < 7; ++s) gk[s] += dk[s];
+    }
+    je = jb;
+    if (last) {
+        if (tid < NLBAC_MLP_TILE * RK_MAX_NU) {
+            const int mu = tid >> 2, cu = tid & 3;
+            const float vu = L.u[(long)min(row0 + mu, n - 1) * nu + min(cu, nu - 1)];
+            T.sU[tid] = (row0 + mu < n && cu < nu) ? vu : 0.f;
+            T.sDU[tid] = 0.f;
+        }
+        T.sDYup[tid] = ok ? g1 : 0.f;
+    } else {
+        const float dy = T.sDY0[tid], dk0 = T.sDK[tid];
+        T.sDYup[tid] = ok ? g1 + dy : 0.f;
+        gk[6] = gk[6] + dk0;
+    }
+    T.sDY0[tid] = ok ? g0 : 0.f;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) T.sDK[j * NLBAC_MLP_TILE * RK_MAX_NS + tid] = ok ? gk[j] : 0.f;
+}
+
 // behind the stages of interval k's step sj: dK of the evaluated stages to global when the weight gradients want it (an
 // FSAL step's stage 0 belongs to the step before: its row stays zero); behind the interval's first step du[k], behind
-// interval 0's dx0 = dout[0] + dy0.  No barrier inside.
-template <int NTHR>
+// interval 0's dx0 = dout[0] + dy0 (DENSE: dx0 = slot 0's dy0; dout holds no gradient of y0).  No barrier inside.
+template <int NTHR, bool DENSE = false>
 __device__ __forceinline__ void rk_tile_bwd_end(const NodeRkBwdLaunch& L, const NodeTileBwd& X, const RkBwdWhere& w,
                                                 const RkBwdTile& T, int row0, int k, int sj, int tid) {
     const int n = L.n, ns = L.n_s, nu = L.n_u;
@@ -1106,6 +1225,7 @@ __device__ __forceinline__ void rk_tile_bwd_end(const NodeRkBwdLaunch& L, const 
     if (k == 0)
         for (int idx = tid; idx < NLBAC_MLP_TILE * ns; idx += NTHR) {
             const int m = idx / ns, c = idx - m * ns, row = row0 + m;
-            if (row < n) X.dx0[(long)row * ns + c] = X.dout[(long)row * ns + c] + T.sDY0[m * RK_MAX_NS + c];
+            if constexpr (DENSE) { if (row < n) X.dx0[(long)row * ns + c] = T.sDY0[m * RK_MAX_NS + c]; }
+            else if (row < n) X.dx0[(long)row * ns + c] = X.dout[(long)row * ns + c] + T.sDY0[m * RK_MAX_NS + c];
         }
 }

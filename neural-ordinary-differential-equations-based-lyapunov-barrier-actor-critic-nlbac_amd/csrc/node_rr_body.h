@@ -82,13 +82,17 @@ __device__ long long g_bwd_stamps[2 * 256];      // (defined in the one translat
 // (node_rk_shared.h).  The stage loop runs in PHASES per interval — stage 0; the probe stage (index 1, quiet, the table
 // row (1, 0, ..)); attempts of stages 1 .. S-1 — with rk_tile_after_phase behind each; what is kept goes to the tile's
 // current slot (stage index slot S + st), nothing when tile->keep is 0.
+// DENSE (with TILE, H = 1; nlbac_node_dopri_tile_dense_fwd, node_tile_dense_kernels.hip): one dense solve per tile, read
+// at the output times of `dense` behind every accepted attempt (node_rk_shared.h).
 template <int NB, int R, int BITS, int SPLIT, bool TRAJ = false, bool GRID = false, bool SUB = false, bool HOLD = false,
-          bool TILE = false>
+          bool TILE = false, bool DENSE = false>
 __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 1, const float* hs = nullptr,
                                                  const NlbacSubGrid* sub = nullptr, int hm = 1,
-                                                 const NodeTileFwd* tile = nullptr) {
+                                                 const NodeTileFwd* tile = nullptr,
+                                                 const NodeTileDenseFwd* dense = nullptr) {
     static_assert(TRAJ || !GRID, "a time grid is a trajectory");
     static_assert(!(TILE && TRAJ), "tile-local step control walks its intervals itself");
+    static_assert(TILE || !DENSE, "a dense solve is a tile's");
     static_assert(GRID || !SUB, "sub-steps are a time grid's");
     static_assert((GRID && !SUB) || !HOLD, "a held control's fine steps are a time grid's, its outputs their end points");
     static_assert(BITS != 2 || SPLIT == 0, "rows + words: the fit's forward is the unsplit one (same sums as mode 0)");
@@ -222,6 +226,7 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
 
     RSTAMP(0)
     if constexpr (TILE) { if (tid == 0) sInt[TI_SLOT] = 0; }
+    if constexpr (DENSE) { if (tid == 0) sInt[TI_OUT] = 0; }
     rk_fwd_tile_constants<256>(L, w, T, row0, tid);
     RSTAMP(1)
 
@@ -551,10 +556,18 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
 #undef RR_ST_E
 #undef RR_FKEY
     if constexpr (TILE) {
-        const int act = rk_tile_after_phase<256>(L, *tile, T, sYin, sCtl, sInt, row0, n_rows, k, ph, slot, tid);
-        if (act >= 2) { rk_tile_stop<256>(L, *tile, row0, act == 3 ? k + 1 : k, TILE_NO_SLOT, tid); return; }
+        const int act = rk_tile_after_phase<256, DENSE>(L, *tile, T, sYin, sCtl, sInt, row0, n_rows, k, ph, slot, tid, dense);
+        if (act >= 2) {
+            if constexpr (DENSE) rk_tile_dense_stop<256>(L, *tile, *dense, sCtl, row0, sInt[TI_OUT], TILE_NO_SLOT, tid);
+            else rk_tile_stop<256>(L, *tile, row0, act == 3 ? k + 1 : k, TILE_NO_SLOT, tid);
+            return;
+        }
         if (act == 0) {      // the next phase — at most NODE_TILE_MAX_ATTEMPTS attempts behind the two that open the interval
-            if (++ph >= 2 + NODE_TILE_MAX_ATTEMPTS) { rk_tile_stop<256>(L, *tile, row0, k, TILE_MAX_ATTEMPTS, tid); return; }
+            if (++ph >= 2 + NODE_TILE_MAX_ATTEMPTS) {
+                if constexpr (DENSE) rk_tile_dense_stop<256>(L, *tile, *dense, sCtl, row0, sInt[TI_OUT], TILE_MAX_ATTEMPTS, tid);
+                else rk_tile_stop<256>(L, *tile, row0, k, TILE_MAX_ATTEMPTS, tid);
+                return;
+            }
             goto tile_phase;
         }
     }
@@ -590,11 +603,15 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
 // step control — intervals k = H-1 .. 0 and, inside each, the tile's kept steps last to first (slot = first + sj; rows /
 // words / G / dK / dG / dz at stage index slot S + st); rk_tile_bwd_begin / _end (node_rk_shared.h) around each step's
 // stages; a step that is not its interval's first leaves out stage 0 (its predecessor's last: FSAL).
+// DENSE (with TILE, H = 1; nlbac_node_dopri_tile_dense_bwd): the backward of a tile's dense solve — every step takes the
+// gradients of the outputs that fell in it before the hand-over (rk_tile_dense_bwd_begin, node_rk_shared.h).
 template <int NB, int R, int BITS, int SPLIT, bool TRAJ = false, bool GRID = false, bool SUB = false, bool HOLD = false,
-          bool TILE = false>
+          bool TILE = false, bool DENSE = false>
 __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const NodeRkTrajBwd* X = nullptr,
                                                  const float* hs = nullptr, const NlbacSubGrid* sub = nullptr,
-                                                 int hm = 1, const NodeTileBwd* tile = nullptr) {
+                                                 int hm = 1, const NodeTileBwd* tile = nullptr,
+                                                 const NodeTileDenseBwd* dense = nullptr) {
+    static_assert(TILE || !DENSE, "a dense solve is a tile's");
     static_assert(TRAJ || !GRID, "a time grid is a trajectory");
     static_assert(!(TILE && TRAJ), "tile-local step control walks its intervals itself");
     static_assert(GRID || !SUB, "sub-steps are a time grid's");
@@ -711,11 +728,17 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
     // (TILE) the interval's kept steps: clamped to the tile's slots, whatever the arrays hold
     int t_first = 0, t_nacc = 1;
     float t_x = 0.f;
-    if constexpr (TILE) {
+    if constexpr (TILE && !DENSE) {
         const long ti = (long)blockIdx.x * H + k;
         t_first = min(max(tile->iv_first[ti], 0), tile->max_slots - 1);
         t_nacc = min(max(tile->iv_nacc[ti], 1), tile->max_slots - t_first);
         t_x = tile->iv_x[ti];
+    }
+    // (DENSE) the one interval's steps are the slots 0 .. accepted - 1; d_je: the outputs no later step has taken
+    [[maybe_unused]] int d_je = 0;
+    if constexpr (DENSE) {
+        t_nacc = min(max(tile->iv_nacc[blockIdx.x], 1), tile->max_slots);
+        d_je = max(dense->n_out, 0);
     }
     // (TILE) the interval's steps come back to this label, last to first (a jump, not a loop: see the forward)
     int sj = TILE ? t_nacc - 1 : 0;
@@ -728,7 +751,8 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
         if constexpr (TILE) {
             w.st_lo = sj == 0 ? 0 : 1;
             const float h = (float)tile->hslots[(long)blockIdx.x * tile->max_slots + t_first + sj];
-            rk_tile_bwd_begin<256>(L, *tile, T, row0, k, kk, sj == t_nacc - 1, h, t_x, tid);
+            if constexpr (DENSE) rk_tile_dense_bwd_begin<256>(L, *tile, *dense, T, row0, sj, sj == t_nacc - 1, h, d_je, tid);
+            else rk_tile_bwd_begin<256>(L, *tile, T, row0, k, kk, sj == t_nacc - 1, h, t_x, tid);
         } else {
             rk_traj_bwd_begin<256, GRID, SUB, HOLD>(L, *X, T, row0, k, kk, tid, hs, sub, hm);
         }
@@ -1024,7 +1048,7 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
         __syncthreads();
     }
     if constexpr (TILE) {
-        rk_tile_bwd_end<256>(L, *tile, w, T, row0, k, sj, tid);
+        rk_tile_bwd_end<256, DENSE>(L, *tile, w, T, row0, k, sj, tid);
         __syncthreads();
         if (--sj >= 0) goto tile_step;
     }

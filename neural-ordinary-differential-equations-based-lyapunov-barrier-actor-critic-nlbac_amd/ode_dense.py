@@ -21,8 +21,14 @@ on a time grid): nothing of the forward is kept but the outputs, the carried col
 backward walks the grid's intervals last to first, one adaptive adjoint solve each
 (``ode_adjoint.AffineAdjoint.backward_adjoint_dense``), with one ``nlbac_adj_dense_restart`` launch at every grid point.
 
-Not served: decreasing ``t``, hipGraph capture (the solve needs the host's look at the control block), and nets or
-settings the device-driven chain refuses — each raises, none runs some other way.
+``odeint_dense(..., step_control="tile")`` is the same call with every 32-row tile of the batch an adaptive solve of its
+own (the control-affine NODE at the register-resident kernels' shapes; ``ode_traj.AffineTileDense``): the rows of tile j
+are ``odeint_dense`` of those rows alone.  No tile waits for another and the host never looks into the solve, so the whole
+time series is ONE launch (``nlbac_node_dopri_tile_dense_fwd``: the tile emits every output behind the accepted step
+that reaches it) and its backward one more (``nlbac_node_dopri_tile_dense_bwd``, + the weight-gradient launch).
+
+Not served: decreasing ``t``, hipGraph capture of the batch-wide control (the solve needs the host's look at the control
+block), and nets or settings the device-driven chain refuses — each raises, none runs some other way.
 """
 import math
 
@@ -33,6 +39,8 @@ from . import ode_traj as T
 from .arena import stream_ptr
 from .ode_grid import _steps_of
 
+STEP_CONTROLS = ("batch", "tile")
+TILE_MAX_STEPS = 32                        # the slots a tile gets when max_steps is None
 SOLVERS_KEY = "_odeint_dense_solvers"      # on the model: {keep mode: solver}, apart from odeint's, rollout's and the grid's
 ADJOINT = "adjoint"                        # the key of odeint_dense_adjoint's solver beside the keep modes
 
@@ -48,8 +56,51 @@ def _taus(t):
     return tuple(v - times[0] for v in times[1:])
 
 
+def _check_tile(func, n, step_control, max_steps, info):
+    """The checks of ``step_control`` / ``max_steps`` / ``info`` (``func`` is a NeuralODEModel, ``n`` its rows); returns
+    the slots a tile gets (``max_steps``, or 32), None under the batch-wide control."""
+    if step_control not in STEP_CONTROLS:
+        raise ValueError("odeint_dense: step_control is one of %s; got %r" % (", ".join(STEP_CONTROLS), step_control))
+    if step_control == "batch":
+        if max_steps is not None or info is not None:
+            raise ValueError("odeint_dense: max_steps and info go with step_control='tile' (the batch-wide control keeps "
+                             "its steps in the solver's slot pool and reports through the solver)")
+        return None
+    if info is not None and not isinstance(info, dict):
+        raise ValueError("odeint_dense: info is a dict (it receives the device tensors accepted / attempts / status) or "
+                         "None; got %s" % type(info).__name__)
+    if max_steps is None:
+        max_steps = TILE_MAX_STEPS
+    if isinstance(max_steps, bool) or not isinstance(max_steps, int) or max_steps < 1:
+        raise ValueError("odeint_dense: max_steps must be an int >= 1 (the accepted steps a tile may keep) or None (%d); "
+                         "got %r" % (TILE_MAX_STEPS, max_steps))
+    if max_steps * 7 * n >= 2 ** 31:
+        raise ValueError("odeint_dense: max_steps * 7 stages * %d rows is 2^31 or more (the launch's limit: %d * 7 * %d); "
+                         "use a smaller max_steps or fewer rows" % (n, max_steps, n))
+    if not func.affine:
+        raise NotImplementedError("odeint_dense: step_control='tile' serves the control-affine NODE only "
+                                  "(nlbac_node_dopri_tile_ok); the single-net form is left open")
+    if not T.AffineTileDopri.shapes_ok(func):
+        raise NotImplementedError("odeint_dense: step_control='tile' needs nets the register-resident kernels serve "
+                                  "(nlbac_node_dopri_tile_ok: both nets 64, 100 or 128 wide, f_net five layers, g_net "
+                                  "four); there is no other path under tile-local control")
+    return max_steps
+
+
+def _check_device(y0):
+    if y0.device.type != "cuda":
+        raise ValueError("odeint_dense: y0 must be on a CUDA device; got %s" % y0.device)
+
+
 def _check(func, y0, t, atol, rtol, adjoint):
     """Every argument check, before anything touches a device; returns the output times (``_taus``)."""
+    taus = _check_args(func, y0, t, atol, rtol, adjoint)
+    _check_device(y0)
+    return taus
+
+
+def _check_args(func, y0, t, atol, rtol, adjoint):
+    """``_check`` without its last one, the device of ``y0`` (``odeint_dense`` puts the step control's checks between)."""
     from .sac_cbf_clf.model import NeuralODEModel
     if adjoint:
         raise NotImplementedError("odeint_dense: the backward goes through the accepted steps; the continuous adjoint on "
@@ -70,8 +121,6 @@ def _check(func, y0, t, atol, rtol, adjoint):
     width = func.n_s + (func.n_u if func.affine else func.n_carry)
     if y0.dim() != 2 or y0.shape[1] != width or y0.shape[0] < 1:
         raise ValueError("odeint_dense: y0 must be (batch, %d) = [x | carried columns]; got %s" % (width, tuple(y0.shape)))
-    if y0.device.type != "cuda":
-        raise ValueError("odeint_dense: y0 must be on a CUDA device; got %s" % y0.device)
     return taus
 
 
@@ -92,7 +141,7 @@ def solver_of(func, mode):
     return sv
 
 
-def odeint_dense(func, y0, t, *, atol=1e-7, rtol=1e-5, adjoint=False):
+def odeint_dense(func, y0, t, *, atol=1e-7, rtol=1e-5, adjoint=False, step_control="batch", max_steps=None, info=None):
     """The dopri5 solution of the NODE ``func`` (either form; a model owned by an agent included) at every point of the
     time grid ``t`` (1-D tensor or sequence, T >= 2 finite strictly increasing times): returns ``out`` (T, B, n_s + n_c)
     with ``out[0] = y0``, from ONE adaptive solve over ``[t[0], t[-1]]``.  ``y0`` (B, n_s + n_c) is CUDA float32,
@@ -109,11 +158,36 @@ def odeint_dense(func, y0, t, *, atol=1e-7, rtol=1e-5, adjoint=False):
     What is kept follows what needs a gradient, as in ``rollout``; under ``torch.no_grad`` nothing beyond the solver's
     step slots.  Memory grows with the number of accepted steps, not with T.
 
+    ``step_control="tile"`` (the control-affine NODE; ``"batch"``, the default, is everything above): every 32-row tile
+    ``R_j = [32 j, min(32 j + 32, B))`` is a dense solve of its own —
+
+        out[:, R_j] == odeint_dense(func, y0[R_j], t, atol=..., rtol=...)
+
+    with its own initial-step selection, norms over its rows' ``[x | u]`` entries (a partial last tile is a smaller
+    batch), step sizes and accept decisions.  No tile waits for another, so the whole time series is ONE launch that the
+    host never looks into, its backward one more (+ the weight-gradient launch for parameter gradients), with the keep
+    modes above.  When a backward follows, a tile KEEPS at most ``max_steps`` accepted steps (an int >= 1; None: 32;
+    ``max_steps * 7 * B`` stays below 2^31); under ``torch.no_grad`` it is no limit.  A tile that runs out of slots, or
+    takes more than 1000 attempts, writes NaN into its rows of every output it has not yet emitted and sets its status;
+    the other tiles are unaffected, nothing synchronises, and ``backward()`` — which reads status and counts first, in one
+    small copy — raises ``NlbacError`` naming ``max_steps`` and the largest count seen.  ``info`` (a dict) receives
+    device tensors without a synchronisation: ``accepted`` and ``attempts`` (n_tiles,) int32 and ``status`` (n_tiles,)
+    int32 — 0 ok, 1 no slot left, 2 attempt cap.  ``max_steps`` / ``info`` with ``"batch"`` are a ``ValueError``.
+
     Raises instead of running some other way: decreasing ``t`` (``ValueError``), ``adjoint=True`` (``NotImplementedError``),
-    a call inside a hipGraph capture (``RuntimeError``: the solve needs the host's look at the control block), and a
-    solver whose device-driven chain is not available — nets the fused step kernels refuse, or ``device_loop`` off
-    (``NotImplementedError``)."""
-    taus = _check(func, y0, t, atol, rtol, adjoint)
+    under ``"batch"`` a call inside a hipGraph capture (``RuntimeError``: the solve needs the host's look at the control
+    block; the tile-local solve needs no look) and a solver whose device-driven chain is not available — nets the fused
+    step kernels refuse, or ``device_loop`` off (``NotImplementedError``); under ``"tile"`` the single-net form and nets
+    the register-resident kernels refuse (``NotImplementedError`` naming ``nlbac_node_dopri_tile_ok``)."""
+    taus = _check_args(func, y0, t, atol, rtol, adjoint)
+    slots = _check_tile(func, y0.shape[0], step_control, max_steps, info)
+    _check_device(y0)
+    if slots is not None:
+        # the tile-local solve: no solver, no chain — the cached solvers of the batch-wide control are not touched
+        params = tuple(func.parameters())
+        func.refresh_device_weights()
+        return _DenseTileFunction.apply(func, taus, float(atol), float(rtol), T.keep_mode(params, y0), slots, info, y0,
+                                        *params)
     if torch.cuda.is_current_stream_capturing():
         raise RuntimeError("odeint_dense: not inside a hipGraph capture — the adaptive solve needs the host's look at the "
                            "control block to know how many steps were accepted")
@@ -213,6 +287,42 @@ class _DenseFunction(torch.autograd.Function):
             gy0 = dout[0] + torch.cat([dx0, dc + dout[1:, :, ns:].sum(0)], dim=1)
         gp = T.param_grads(ctx.func, flat) if need_p else [None] * ctx.n_params
         return (None, None, None, None, None, None, gy0, *gp)
+
+
+class _DenseTileFunction(torch.autograd.Function):
+    """``odeint_dense(step_control="tile")`` as one autograd node over ``ode_traj.AffineTileDense``."""
+
+    @staticmethod
+    def forward(ctx, func, taus, atol, rtol, mode, slots, info, y0, *params):
+        n, ns = y0.shape[0], func.n_s
+        y0 = y0.detach().contiguous()
+        x0, c = y0[:, :ns].contiguous(), y0[:, ns:].contiguous()
+        xs = torch.empty(len(taus), n, ns, dtype=torch.float32, device=y0.device)
+        solve = T.AffineTileDense(func, n, taus, slots, info, mode, atol, rtol, y0.device)
+        solve.forward(x0, c, xs)
+        out = torch.empty(len(taus) + 1, n, y0.shape[1], dtype=torch.float32, device=y0.device)
+        out[0].copy_(y0)
+        out[1:, :, :ns].copy_(xs)
+        # the carried columns, the same at every output point; NaN with the state where a stopped tile emitted nothing
+        nan = torch.isnan(xs[:, :, :1])
+        out[1:, :, ns:].copy_(torch.where(nan, xs[:, :, :1], c))
+        ctx.func, ctx.mode, ctx.n_params = func, mode, len(params)
+        ctx.kept = solve if mode != "none" else None
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        assert ctx.kept is not None, "odeint_dense: nothing was kept for a backward (the forward ran without gradients)"
+        ns = ctx.func.n_s
+        dout = dout.float()
+        need_p = ctx.mode == "params" and any(ctx.needs_input_grad[8:])
+        dx0, dc, flat = ctx.kept.backward(dout[1:, :, :ns].contiguous(), need_p)
+        gy0 = None
+        if ctx.needs_input_grad[7]:
+            # (_DenseFunction.backward's expression: the solve's own, and the share of every output point)
+            gy0 = dout[0] + torch.cat([dx0, dc + dout[1:, :, ns:].sum(0)], dim=1)
+        gp = T.param_grads(ctx.func, flat) if need_p else [None] * ctx.n_params
+        return (None, None, None, None, None, None, None, gy0, *gp)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

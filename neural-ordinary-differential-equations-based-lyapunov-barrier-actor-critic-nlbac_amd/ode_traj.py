@@ -9,7 +9,8 @@
     launch forward, one backward, + the weight-gradient launch over all H * stages * rows) and ``Chain`` (H one-interval
     solves on the existing solvers) — each with ``forward(x0, u, xs)`` and ``backward(dout, need_p)``; ``solve`` picks;
     ``AffineTileDopri`` beside them for ``TileSteps`` — ``EqualSteps`` solved by dopri5 under tile-local step control, one
-    launch each way over step slots (``rollout(step_control="tile")``);
+    launch each way over step slots (``rollout(step_control="tile")``) — and its sibling ``AffineTileDense``, one dense
+    solve per tile read at every point of a time grid (``ode_dense.odeint_dense(step_control="tile")``);
   * the same under ``adjoint=True`` (``solve_adjoint``): nothing kept but the outputs the caller holds and the controls —
     ``AdjointPlan`` (per output interval the fine steps of its backward solve, the chunk), ``AffineAdjTraj`` /
     ``ConcatAdjTraj`` (the continuous adjoint over the whole horizon in one ``nlbac_*_adj_traj`` launch per chunk),
@@ -392,6 +393,7 @@ class AffineTileDopri:
     stage nobody evaluated (a slot a tile did not use, stage 0 of a step that took it from the step before) adds
     nothing to the weight gradients."""
     S = 7
+    api = "rollout"
 
     @staticmethod
     def shapes_ok(func):
@@ -415,8 +417,8 @@ class AffineTileDopri:
     def __init__(self, func, n, iv, mode, atol, rtol, device):
         from .ode_consts import DP_C_ERR
         if not self.ok(func):
-            raise NotImplementedError("rollout: step_control='tile' needs nets the register-resident kernels serve "
-                                      "(nlbac_node_dopri_tile_ok); there is no chained fallback")
+            raise NotImplementedError("%s: step_control='tile' needs nets the register-resident kernels serve "
+                                      "(nlbac_node_dopri_tile_ok); there is no chained fallback" % self.api)
         f, g = func.device_handles()
         self.f, self.g, self.iv, self.mode, self.tol = f, g, iv, mode, (rtol, atol)
         self.ns, self.nu, self.n, self.H = func.n_s, func.n_u, n, iv.H
@@ -473,13 +475,8 @@ class AffineTileDopri:
                 "stopped or finished is %d — raise max_steps (its default is 8 H)"
                 % (bad[0], why.get(int(seen[0][bad[0]]), "stopped"), int(seen[0][bad[0]]), len(bad), self.tiles, M, used))
         z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-        zero = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
         dx0, du = z(n, self.ns), z(H, n, self.nu)
-        MS = M * self.S
-        dK = dG = dz_f = dz_g = None
-        if need_p:
-            dK, dG = zero(MS, n, self.ns), zero(MS, n, self.ns * self.nu)
-            dz_f, dz_g = zero(self.f.n_layers - 1, MS * n, self.f.hid), zero(self.g.n_layers - 1, MS * n, self.g.hid)
+        dK, dG, dz_f, dz_g = self._weight_rows(need_p, dev)
         _lib.call("nlbac_node_dopri_tile_bwd", C.byref(self.f.desc), C.byref(self.g.desc), self.u.data_ptr(), n, H,
                   self.beta, M, self.hslots.data_ptr(), self.iv_first.data_ptr(), self.accepted.data_ptr(),
                   self.iv_x.data_ptr(), self.G.data_ptr(), _ptr(self.acts[0]), self.ls[0], _ptr(self.acts[1]), self.ls[1],
@@ -487,8 +484,20 @@ class AffineTileDopri:
                   stream_ptr())
         if not need_p:
             return dx0, du, None
-        # every stage of the USED slots as one batch through the weight-gradient launch: the slots are the leading
-        # index, so the first used * 7 * n rows of every buffer hold them (the layers' stride stays that of all slots)
+        return dx0, du, self._weight_grads(dK, dG, dz_f, dz_g, used, dev)
+
+    def _weight_rows(self, need_p, dev):
+        """dK, dG, dz_f, dz_g per (slot, stage, row) for the weight gradients (zero-filled), or four times None."""
+        if not need_p:
+            return None, None, None, None
+        n, MS = self.n, self.M * self.S
+        zero = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+        return (zero(MS, n, self.ns), zero(MS, n, self.ns * self.nu), zero(self.f.n_layers - 1, MS * n, self.f.hid),
+                zero(self.g.n_layers - 1, MS * n, self.g.hid))
+
+    def _weight_grads(self, dK, dG, dz_f, dz_g, used, dev):
+        """Every stage of the USED slots as one batch through the weight-gradient launch: the slots are the leading
+        index, so the first used * 7 * n rows of every buffer hold them (the layers' stride stays that of all slots)."""
         arena = self.f.arena
         io = io_array(2)
         for i, (dy, ld, dz) in enumerate(((dK, self.ns, dz_f), (dG, self.ns * self.nu, dz_g))):
@@ -497,8 +506,66 @@ class AffineTileDopri:
             io[i].acts, io[i].acts_ls = _ptr(self.acts[i]), self.ls[i]
             io[i].dz = dz.data_ptr()
             io[i].grad = arena.grad.data_ptr()
-        bwd_weights(mlp_array([self.f.desc, self.g.desc]), io, 2, used * self.S * n, arena.n_slabs, arena.n, dev)
-        return dx0, du, _reduce(arena, arena.n_slabs)
+        bwd_weights(mlp_array([self.f.desc, self.g.desc]), io, 2, used * self.S * self.n, arena.n_slabs, arena.n, dev)
+        return _reduce(arena, arena.n_slabs)
+
+
+class AffineTileDense(AffineTileDopri):
+    """Device buffers of one DENSE dopri5 solve under tile-local step control (``odeint_dense(step_control="tile")``):
+    every 32-row tile runs one adaptive solve over ``[0, taus[-1]]`` and writes its interpolant at every output time
+    behind the accepted steps — one ``nlbac_node_dopri_tile_dense_fwd`` launch, one ``nlbac_node_dopri_tile_dense_bwd``
+    for its backward (+ the weight-gradient launch over the used slots).  ``AffineTileDopri``'s kept buffers with H = 1
+    (``max_steps`` slots per tile), and per tile and output the slot that emitted it and its abscissa (``ov_slot`` /
+    ``ov_x``) in place of the intervals' arrays."""
+    api = "odeint_dense"
+
+    def __init__(self, func, n, taus, max_steps, info, mode, atol, rtol, device):
+        AffineTileDopri.__init__(self, func, n, TileSteps(taus[-1], 1, max_steps, info), mode, atol, rtol, device)
+        self.n_out = len(taus)
+        self.tau = torch.tensor(taus, dtype=torch.float64, device=device)
+        self.accepted, self.attempts = self.accepted.view(self.tiles), self.attempts.view(self.tiles)
+        self.iv_first = self.iv_x = self.ov_slot = self.ov_x = None
+        if mode != "none":
+            self.ov_slot = torch.zeros(self.tiles, self.n_out, dtype=torch.int32, device=device)
+            self.ov_x = torch.zeros(self.tiles, self.n_out, dtype=torch.float32, device=device)
+
+    def forward(self, x0, u, xs):
+        self.u = u
+        rtol, atol = self.tol
+        _lib.call("nlbac_node_dopri_tile_dense_fwd", C.byref(self.f.desc), C.byref(self.g.desc), x0.data_ptr(),
+                  u.data_ptr(), self.n, self.beta, self.c_err, self.tau.data_ptr(), self.n_out, self.iv.dt, rtol, atol,
+                  xs.data_ptr(), self.M, _ptr(self.Y), _ptr(self.G), _ptr(self.acts[0]), self.ls[0], _ptr(self.acts[1]),
+                  self.ls[1], self.bits, _ptr(self.hslots), _ptr(self.ov_slot), _ptr(self.ov_x),
+                  self.accepted.data_ptr(), self.attempts.data_ptr(), self.status.data_ptr(), stream_ptr())
+        if self.iv.info is not None:
+            self.iv.info.update(accepted=self.accepted, attempts=self.attempts, status=self.status)
+
+    def backward(self, dxs, need_p):
+        """dxs (T - 1, n, n_s): d loss / d out[1:] on the state columns.  Returns (the first step's dy0, du, flat
+        parameter gradient or None)."""
+        n, M, dev = self.n, self.M, dxs.device
+        # the one look at the solve: every tile's status and step count, long after the launch has finished
+        seen = torch.stack((self.status, self.accepted)).cpu()
+        used = int(seen[1].max())
+        bad = seen[0].nonzero().flatten().tolist()
+        if bad:
+            why = {1: "ran out of step slots", 2: "took more than 1000 attempts"}
+            raise _lib.NlbacError(
+                "odeint_dense(step_control='tile'): tile %d %s (status %d; %d of %d tiles stopped), so the solve has no "
+                "backward: max_steps = %d slots per tile, the largest count of accepted steps a tile had kept when it "
+                "stopped or finished is %d — raise max_steps (its default is 32)"
+                % (bad[0], why.get(int(seen[0][bad[0]]), "stopped"), int(seen[0][bad[0]]), len(bad), self.tiles, M, used))
+        z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        dx0, du = z(n, self.ns), z(n, self.nu)
+        dK, dG, dz_f, dz_g = self._weight_rows(need_p, dev)
+        _lib.call("nlbac_node_dopri_tile_dense_bwd", C.byref(self.f.desc), C.byref(self.g.desc), self.u.data_ptr(), n,
+                  self.beta, self.n_out, M, self.hslots.data_ptr(), self.ov_slot.data_ptr(), self.ov_x.data_ptr(),
+                  self.accepted.data_ptr(), self.G.data_ptr(), _ptr(self.acts[0]), self.ls[0], _ptr(self.acts[1]),
+                  self.ls[1], self.bits, dxs.data_ptr(), dx0.data_ptr(), du.data_ptr(), _ptr(dK), _ptr(dG), _ptr(dz_f),
+                  _ptr(dz_g), stream_ptr())
+        if not need_p:
+            return dx0, du, None
+        return dx0, du, self._weight_grads(dK, dG, dz_f, dz_g, used, dev)
 
 
 def traj_class(func):

@@ -15,6 +15,7 @@
 // off the accepted steps), the call of U/sac_cbf_clf/model.py:252 on a time series, on a batch of one tile's rows.
 #undef RR_TIMING          // (the ablation stamps belong to the one-step kernels)
 #include "node_rr_body.h"
+#include "node_tile_launch.h"      // what a tile launch checks and carries, shared with node_tile_kernels.hip
 
 struct NodeTileDenseFwdLaunch {
     NodeRkLaunch L;
@@ -38,18 +39,6 @@ __global__ __launch_bounds__(256) void node_tile_dense_bwd_kernel(const NodeTile
     node_rr_bwd_body<NB, R, BITS, SPLIT, false, false, false, false, true, true>(A.L, nullptr, nullptr, nullptr, 1, &A.X, &A.D);
 }
 
-static int tile_dense_check(const nlbac_mlp* f, const nlbac_mlp* g, int n, int n_out, const float* beta, int max_slots,
-                            bool keep, int acts_bits, const char* who) {
-    NLBAC_REQUIRE(f && g && beta, "%s: null pointer", who);
-    NLBAC_REQUIRE(nlbac_node_dopri_tile_ok(f, g), "%s: these nets do not run on the register-resident kernels (nlbac_node_dopri_tile_ok)", who);
-    NLBAC_REQUIRE(n >= 1 && n_out >= 1 && (long)n_out * n < (1L << 31), "%s: bad rows / output times", who);
-    NLBAC_REQUIRE(acts_bits >= 0 && acts_bits <= 2, "%s: acts_bits is 0, 1 or 2", who);
-    if (keep)
-        NLBAC_REQUIRE(max_slots >= 1 && (long)max_slots * 7 * n < (1L << 31),
-                      "%s: max_slots must be at least 1, and max_slots * 7 * n below 2^31", who);
-    return 0;
-}
-
 // One launch: a dense dopri5 solve of every 32-row tile of the n rows over [0, t_end], read at tau [n_out] (DEVICE
 // doubles, increasing, tau[n_out - 1] == t_end).  x0 [n][n_s], u [n][n_u], out [n_out][n][n_s].  accepted / attempts /
 // status [tiles] (zero on entry) receive each tile's counts and TILE_* status; a tile that stops writes NaN into its rows
@@ -64,33 +53,13 @@ extern "C" int nlbac_node_dopri_tile_dense_fwd(const nlbac_mlp* f, const nlbac_m
                                                int* attempts, int* status, nlbac_stream_t s) {
     static const NodeRrTable<NodeTileDenseFwdLaunch> table = NODE_RR_FWD_TABLE(node_tile_dense_fwd_kernel);
     const char* who = "nlbac_node_dopri_tile_dense_fwd";
-    const bool keep = G != nullptr;
-    if (tile_dense_check(f, g, n, n_out, beta, max_slots, keep, acts_bits, who)) return -1;
-    NLBAC_REQUIRE(x0 && u && out && c_err && tau && accepted && attempts && status, "%s: null pointer", who);
-    NLBAC_REQUIRE(t_end > 0.0 && t_end <= 3.0e38 && rtol >= 0.f && atol >= 0.f && rtol + atol > 0.f, "%s: bad interval / tolerances", who);
-    NLBAC_REQUIRE((acts_f == nullptr) == (acts_g == nullptr), "%s: acts_f and acts_g go together", who);
-    NLBAC_REQUIRE(keep ? (acts_f && hslots && ov_slot && ov_x) : (!acts_f && !Y), "%s: G, the acts and the slot arrays go together", who);
     NodeTileDenseFwdLaunch A;
     memset(&A, 0, sizeof(A));
-    NodeRkLaunch& L = A.L;
-    L.net[0] = *f; L.net[1] = *g;
-    L.y0 = x0; L.u = u;
-    L.n = n; L.rpp = n; L.n_s = f->in_dim; L.n_u = g->out_dim / f->in_dim;
-    L.stage_begin = 0; L.stage_end = 7; L.S_total = 7;
-    for (int i = 0; i < 7; ++i) {
-        for (int j = 0; j < 7; ++j) L.beta[i][j] = beta[i * 7 + j];
-        L.c_err[i] = c_err[i];
-    }
-    L.n_err = 7;
-    L.Y = Y; L.G = G;
-    L.acts[0] = acts_f; L.acts[1] = acts_g; L.acts_ls[0] = acts_f_ls; L.acts_ls[1] = acts_g_ls;
-    L.acts_bits = acts_bits;
-    L.out = out;
-    L.norm_mode = -1;
-    L.rtol = rtol; L.atol = atol; L.t_end = t_end;
-    A.X.H = 1; A.X.keep = keep ? 1 : 0; A.X.max_slots = keep ? max_slots : 1;
-    A.X.hslots = hslots;
-    A.X.accepted = accepted; A.X.attempts = attempts; A.X.status = status;
+    if (tile_fill_fwd(A.L, A.X, who, 1, n_out, "output times", "1", f, g, x0, u, n, beta, c_err, t_end, rtol, atol, out,
+                      max_slots, Y, G, acts_f, acts_f_ls, acts_g, acts_g_ls, acts_bits, hslots, accepted, attempts, status))
+        return -1;
+    NLBAC_REQUIRE(tau, "%s: null pointer", who);
+    NLBAC_REQUIRE(!G || (ov_slot && ov_x), "%s: G, the acts and the slot arrays go together", who);
     A.D.tau = tau; A.D.n_out = n_out; A.D.ov_slot = ov_slot; A.D.ov_x = ov_x;
     node_rr_start(table, A, f->hid, n, acts_bits, node_tile_fwd_lds_floats(), (hipStream_t)s);
     NLBAC_CHECK_LAUNCH(who);
@@ -110,27 +79,12 @@ extern "C" int nlbac_node_dopri_tile_dense_bwd(const nlbac_mlp* f, const nlbac_m
                                                float* dG, float* dz_f, float* dz_g, nlbac_stream_t s) {
     static const NodeRrTable<NodeTileDenseBwdLaunch> table = NODE_RR_BWD_TABLE(node_tile_dense_bwd_kernel);
     const char* who = "nlbac_node_dopri_tile_dense_bwd";
-    if (tile_dense_check(f, g, n, n_out, beta, max_slots, true, acts_bits, who)) return -1;
-    NLBAC_REQUIRE(u && hslots && ov_slot && ov_x && nacc && G && acts_f && acts_g && dout && dx0 && du, "%s: null pointer", who);
-    NLBAC_REQUIRE((dz_f == nullptr) == (dz_g == nullptr) && (dz_f == nullptr) == (dG == nullptr) &&
-                      (dz_f == nullptr) == (dK == nullptr), "%s: dz_f, dz_g, dG and dK go together", who);
-    NLBAC_REQUIRE(!(acts_bits == 1 && dz_f), "%s: weight gradients need the activations, not bit masks", who);
     NodeTileDenseBwdLaunch A;
     memset(&A, 0, sizeof(A));
-    NodeRkBwdLaunch& L = A.L;
-    L.net[0] = *f; L.net[1] = *g;
-    L.u = u; L.G = G;
-    L.acts[0] = acts_f; L.acts[1] = acts_g; L.acts_ls[0] = acts_f_ls; L.acts_ls[1] = acts_g_ls;
-    L.acts_bits = acts_bits;
-    L.dz[0] = dz_f; L.dz[1] = dz_g; L.dG = dG; L.dK = dK;
-    L.du = du;
-    L.n = n; L.rpp = n; L.n_s = f->in_dim; L.n_u = g->out_dim / f->in_dim;
-    L.S_total = 7; L.st_lo = 0; L.st_hi = 7; L.dx_stage0 = 1;
-    for (int i = 0; i < 7; ++i)
-        for (int j = 0; j < 7; ++j) L.beta[i][j] = beta[i * 7 + j];
-    A.X.H = 1; A.X.max_slots = max_slots;
-    A.X.hslots = hslots; A.X.iv_nacc = nacc;
-    A.X.dout = dout; A.X.dx0 = dx0;
+    if (tile_fill_bwd(A.L, A.X, who, 1, n_out, "output times", "1", f, g, u, n, beta, max_slots, hslots, nacc, G, acts_f,
+                      acts_f_ls, acts_g, acts_g_ls, acts_bits, dout, dx0, du, dK, dG, dz_f, dz_g))
+        return -1;
+    NLBAC_REQUIRE(ov_slot && ov_x, "%s: null pointer", who);
     A.D.n_out = n_out; A.D.ov_slot = ov_slot; A.D.ov_x = ov_x;
     node_rr_start(table, A, f->hid, n, acts_bits, node_rr_bwd_lds_floats(), (hipStream_t)s);
     NLBAC_CHECK_LAUNCH(who);

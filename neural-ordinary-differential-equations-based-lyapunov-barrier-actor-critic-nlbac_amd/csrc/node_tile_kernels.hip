@@ -16,6 +16,7 @@
 // (odeint(model, [x_k | u_k], [0, dt], method="dopri5")[-1], one interval per call), on a batch of one tile's rows.
 #undef RR_TIMING          // (the ablation stamps belong to the one-step kernels)
 #include "node_rr_body.h"
+#include "node_tile_launch.h"      // what a tile launch checks and carries, shared with node_tile_dense_kernels.hip
 
 struct NodeTileFwdLaunch {
     NodeRkLaunch L;
@@ -41,18 +42,6 @@ extern "C" int nlbac_node_dopri_tile_ok(const nlbac_mlp* f, const nlbac_mlp* g) 
     return (f && g && nlbac_node_rr_eligible(f, g)) ? 1 : 0;
 }
 
-static int tile_check(const nlbac_mlp* f, const nlbac_mlp* g, int n, int H, const float* beta, int max_slots, bool keep,
-                      int acts_bits, const char* who) {
-    NLBAC_REQUIRE(f && g && beta, "%s: null pointer", who);
-    NLBAC_REQUIRE(nlbac_node_dopri_tile_ok(f, g), "%s: these nets do not run on the register-resident kernels (nlbac_node_dopri_tile_ok)", who);
-    NLBAC_REQUIRE(n >= 1 && H >= 1 && (long)H * n < (1L << 31), "%s: bad rows / intervals", who);
-    NLBAC_REQUIRE(acts_bits >= 0 && acts_bits <= 2, "%s: acts_bits is 0, 1 or 2", who);
-    if (keep)
-        NLBAC_REQUIRE(max_slots >= H && (long)max_slots * 7 * n < (1L << 31),
-                      "%s: max_slots must be at least H, and max_slots * 7 * n below 2^31", who);
-    return 0;
-}
-
 // One launch: H intervals of dopri5 for every 32-row tile of the n rows.  x0 [n][n_s], u [H][n][n_u], out [H][n][n_s]
 // (the state behind every interval), beta [7][7] / c_err [7]: dopri5's table and error weights.  accepted / attempts
 // [tiles][H] and status [tiles] (zero on entry) receive the counts and the tiles' TILE_* status.
@@ -67,33 +56,13 @@ extern "C" int nlbac_node_dopri_tile_fwd(const nlbac_mlp* f, const nlbac_mlp* g,
                                          float* iv_x, int* accepted, int* attempts, int* status, nlbac_stream_t s) {
     static const NodeRrTable<NodeTileFwdLaunch> table = NODE_RR_FWD_TABLE(node_tile_fwd_kernel);
     const char* who = "nlbac_node_dopri_tile_fwd";
-    const bool keep = G != nullptr;
-    if (tile_check(f, g, n, H, beta, max_slots, keep, acts_bits, who)) return -1;
-    NLBAC_REQUIRE(x0 && u && out && c_err && accepted && attempts && status, "%s: null pointer", who);
-    NLBAC_REQUIRE(dt > 0.0 && dt <= 3.0e38 && rtol >= 0.f && atol >= 0.f && rtol + atol > 0.f, "%s: bad interval / tolerances", who);
-    NLBAC_REQUIRE((acts_f == nullptr) == (acts_g == nullptr), "%s: acts_f and acts_g go together", who);
-    NLBAC_REQUIRE(keep ? (acts_f && hslots && iv_first && iv_x) : (!acts_f && !Y), "%s: G, the acts and the slot arrays go together", who);
     NodeTileFwdLaunch A;
     memset(&A, 0, sizeof(A));
-    NodeRkLaunch& L = A.L;
-    L.net[0] = *f; L.net[1] = *g;
-    L.y0 = x0; L.u = u;
-    L.n = n; L.rpp = n; L.n_s = f->in_dim; L.n_u = g->out_dim / f->in_dim;
-    L.stage_begin = 0; L.stage_end = 7; L.S_total = 7;
-    for (int i = 0; i < 7; ++i) {
-        for (int j = 0; j < 7; ++j) L.beta[i][j] = beta[i * 7 + j];
-        L.c_err[i] = c_err[i];
-    }
-    L.n_err = 7;
-    L.Y = Y; L.G = G;
-    L.acts[0] = acts_f; L.acts[1] = acts_g; L.acts_ls[0] = acts_f_ls; L.acts_ls[1] = acts_g_ls;
-    L.acts_bits = acts_bits;
-    L.out = out;
-    L.norm_mode = -1;
-    L.rtol = rtol; L.atol = atol; L.t_end = dt;
-    A.X.H = H; A.X.keep = keep ? 1 : 0; A.X.max_slots = keep ? max_slots : 1;
-    A.X.hslots = hslots; A.X.iv_first = iv_first; A.X.iv_x = iv_x;
-    A.X.accepted = accepted; A.X.attempts = attempts; A.X.status = status;
+    if (tile_fill_fwd(A.L, A.X, who, H, H, "intervals", "H", f, g, x0, u, n, beta, c_err, dt, rtol, atol, out, max_slots, Y,
+                      G, acts_f, acts_f_ls, acts_g, acts_g_ls, acts_bits, hslots, accepted, attempts, status))
+        return -1;
+    NLBAC_REQUIRE(!G || (iv_first && iv_x), "%s: G, the acts and the slot arrays go together", who);
+    A.X.iv_first = iv_first; A.X.iv_x = iv_x;
     node_rr_start(table, A, f->hid, n, acts_bits, node_tile_fwd_lds_floats(), (hipStream_t)s);
     NLBAC_CHECK_LAUNCH(who);
     return 0;
@@ -111,27 +80,13 @@ extern "C" int nlbac_node_dopri_tile_bwd(const nlbac_mlp* f, const nlbac_mlp* g,
                                          float* dz_g, nlbac_stream_t s) {
     static const NodeRrTable<NodeTileBwdLaunch> table = NODE_RR_BWD_TABLE(node_tile_bwd_kernel);
     const char* who = "nlbac_node_dopri_tile_bwd";
-    if (tile_check(f, g, n, H, beta, max_slots, true, acts_bits, who)) return -1;
-    NLBAC_REQUIRE(u && hslots && iv_first && iv_nacc && iv_x && G && acts_f && acts_g && dout && dx0 && du, "%s: null pointer", who);
-    NLBAC_REQUIRE((dz_f == nullptr) == (dz_g == nullptr) && (dz_f == nullptr) == (dG == nullptr) &&
-                      (dz_f == nullptr) == (dK == nullptr), "%s: dz_f, dz_g, dG and dK go together", who);
-    NLBAC_REQUIRE(!(acts_bits == 1 && dz_f), "%s: weight gradients need the activations, not bit masks", who);
     NodeTileBwdLaunch A;
     memset(&A, 0, sizeof(A));
-    NodeRkBwdLaunch& L = A.L;
-    L.net[0] = *f; L.net[1] = *g;
-    L.u = u; L.G = G;
-    L.acts[0] = acts_f; L.acts[1] = acts_g; L.acts_ls[0] = acts_f_ls; L.acts_ls[1] = acts_g_ls;
-    L.acts_bits = acts_bits;
-    L.dz[0] = dz_f; L.dz[1] = dz_g; L.dG = dG; L.dK = dK;
-    L.du = du;
-    L.n = n; L.rpp = n; L.n_s = f->in_dim; L.n_u = g->out_dim / f->in_dim;
-    L.S_total = 7; L.st_lo = 0; L.st_hi = 7; L.dx_stage0 = 1;
-    for (int i = 0; i < 7; ++i)
-        for (int j = 0; j < 7; ++j) L.beta[i][j] = beta[i * 7 + j];
-    A.X.H = H; A.X.max_slots = max_slots;
-    A.X.hslots = hslots; A.X.iv_first = iv_first; A.X.iv_nacc = iv_nacc; A.X.iv_x = iv_x;
-    A.X.dout = dout; A.X.dx0 = dx0;
+    if (tile_fill_bwd(A.L, A.X, who, H, H, "intervals", "H", f, g, u, n, beta, max_slots, hslots, iv_nacc, G, acts_f,
+                      acts_f_ls, acts_g, acts_g_ls, acts_bits, dout, dx0, du, dK, dG, dz_f, dz_g))
+        return -1;
+    NLBAC_REQUIRE(iv_first && iv_x, "%s: null pointer", who);
+    A.X.iv_first = iv_first; A.X.iv_x = iv_x;
     node_rr_start(table, A, f->hid, n, acts_bits, node_rr_bwd_lds_floats(), (hipStream_t)s);
     NLBAC_CHECK_LAUNCH(who);
     return 0;

@@ -80,7 +80,7 @@ def _check_tile(func, n, step_control, max_steps, info):
     if not func.affine:
         raise NotImplementedError("odeint_dense: step_control='tile' serves the control-affine NODE only "
                                   "(nlbac_node_dopri_tile_ok); the single-net form is left open")
-    if not T.AffineTileDopri.shapes_ok(func):
+    if not T.AffineTile.shapes_ok(func):
         raise NotImplementedError("odeint_dense: step_control='tile' needs nets the register-resident kernels serve "
                                   "(nlbac_node_dopri_tile_ok: both nets 64, 100 or 128 wide, f_net five layers, g_net "
                                   "four); there is no other path under tile-local control")

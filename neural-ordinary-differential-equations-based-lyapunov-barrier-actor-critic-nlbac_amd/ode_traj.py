@@ -8,9 +8,11 @@
   * what a solve keeps and how its backward becomes gradients, one class per path — ``AffineTraj`` / ``ConcatTraj`` (one
     launch forward, one backward, + the weight-gradient launch over all H * stages * rows) and ``Chain`` (H one-interval
     solves on the existing solvers) — each with ``forward(x0, u, xs)`` and ``backward(dout, need_p)``; ``solve`` picks;
-    ``AffineTileDopri`` beside them for ``TileSteps`` — ``EqualSteps`` solved by dopri5 under tile-local step control, one
-    launch each way over step slots (``rollout(step_control="tile")``) — and its sibling ``AffineTileDense``, one dense
-    solve per tile read at every point of a time grid (``ode_dense.odeint_dense(step_control="tile")``);
+    beside them dopri5 under tile-local step control, one launch each way over step slots: ``AffineTile`` owns what such
+    a solve keeps, the look at its status in front of a backward and its weight gradients; its leaves their own arrays
+    and launches — ``AffineTileDopri`` for ``TileSteps`` (``rollout(step_control="tile")``), ``AffineTileDense`` for one
+    dense solve per tile read at every point of a time grid (``ode_dense.odeint_dense(step_control="tile")``); every
+    class of a form shares ``_kept_acts`` and ``_affine_weight_grads`` / ``_concat_weight_grads``;
   * the same under ``adjoint=True`` (``solve_adjoint``): nothing kept but the outputs the caller holds and the controls —
     ``AdjointPlan`` (per output interval the fine steps of its backward solve, the chunk), ``AffineAdjTraj`` /
     ``ConcatAdjTraj`` (the continuous adjoint over the whole horizon in one ``nlbac_*_adj_traj`` launch per chunk),
@@ -23,7 +25,7 @@ import torch
 from . import _lib
 from ._lib import fptr
 from .arena import bwd_weights, io_array, mlp_array, stream_ptr
-from .ode_consts import TABLEAU, env_switch
+from .ode_consts import DP_C_ERR, TABLEAU, env_switch
 from .odeint import AffineNodeSolver, ConcatNodeSolver
 
 
@@ -229,13 +231,15 @@ class HeldSteps(_OutputPerInterval):
 
 
 def _tableau(method):
+    """(S, beta, c_out) as the launchers take them: a stage per row of the table and the one in place, the table flat
+    [S][S] with its row i as row i + 1, and the solution weights (None where the method has none: dopri5)."""
     tab = TABLEAU[method]
-    S = len(tab["c_sol"])
+    S = len(tab["beta"]) + 1
     beta = [0.0] * (S * S)
     for i, r in enumerate(tab["beta"]):
         for j, v in enumerate(r):
             beta[(i + 1) * S + j] = v
-    return S, fptr(*beta), fptr(*tab["c_sol"])
+    return S, fptr(*beta), fptr(*tab["c_sol"]) if tab["c_sol"] is not None else None
 
 
 def _ptr(t):
@@ -246,6 +250,53 @@ def _reduce(arena, used):
     flat = torch.empty(arena.n, dtype=torch.float32, device=arena.device)
     _lib.call("nlbac_reduce_slabs", flat.data_ptr(), arena.grad.data_ptr(), used, arena.n, arena.n, stream_ptr())
     return flat
+
+
+def _kept_acts(f, g, rows, mode, alloc):
+    """What the control-affine form keeps of the hidden layers over ``rows`` stage rows (stages * n), from ``alloc``:
+    (acts_bits, the two nets' buffers, their layer strides)."""
+    words = mode == "inputs" or (mode == "params" and env_switch("fit_words"))
+    bits = 0 if mode == "none" else (1 if mode == "inputs" else (2 if words else 0))
+    acts, ls = [None, None], [0, 0]
+    if mode != "none":
+        for i, net in enumerate((f, g)):
+            nw = net.n_layers - 1
+            if mode == "inputs":                       # words in place of the rows
+                acts[i], ls[i] = alloc(nw * rows * 4, dtype=torch.int32), rows * 4
+            else:                                      # rows [layer][rows][hid], then (bits 2) words [layer][rows][4]
+                acts[i] = alloc(nw * rows * (net.hid + (4 if words else 0)))
+                ls[i] = rows * net.hid
+    return bits, acts, ls
+
+
+def _affine_weight_grads(f, g, x0, x0_ld, dys, acts, acts_ls, dzs, rows, dev):
+    """The control-affine form's weight gradients: ``rows`` stage rows as ONE batch through the weight-gradient launch,
+    then the slabs' sum.  ``x0`` / ``x0_ld``: where layer 0's input rows (n_s columns) lie and their leading dimension;
+    per net (f, g) the output gradients ``dys`` = (dK, dG), the ``acts`` pointers with their layer strides, ``dzs``."""
+    arena = f.arena
+    io = io_array(2)
+    for i in range(2):
+        io[i].x0, io[i].x0_dim, io[i].x0_ld = x0, dys[0].shape[-1], x0_ld
+        io[i].dy, io[i].dy_ld = dys[i].data_ptr(), dys[i].shape[-1]
+        io[i].acts, io[i].acts_ls = acts[i], acts_ls[i]
+        io[i].dz = dzs[i].data_ptr()
+        io[i].grad = arena.grad.data_ptr()
+    bwd_weights(mlp_array([f.desc, g.desc]), io, 2, rows, arena.n_slabs, arena.n, dev)
+    return _reduce(arena, arena.n_slabs)
+
+
+def _concat_weight_grads(net, xin, in_dim, dy, acts, acts_ls, dz, rows, dev):
+    """The single-net form's weight gradients, as ``_affine_weight_grads``: layer 0's input is the kept row at ``xin``
+    (``in_dim`` columns)."""
+    arena = net.arena
+    io = io_array(1)
+    io[0].x0, io[0].x0_dim, io[0].x0_ld = xin, in_dim, in_dim
+    io[0].dy, io[0].dy_ld = dy.data_ptr(), dy.shape[-1]
+    io[0].acts, io[0].acts_ls = acts, acts_ls
+    io[0].dz = dz.data_ptr()
+    io[0].grad = arena.grad.data_ptr()
+    bwd_weights(mlp_array([net.desc]), io, 1, rows, arena.n_slabs, arena.n, dev)
+    return _reduce(arena, arena.n_slabs)
 
 
 def param_grads(func, flat):
@@ -272,17 +323,7 @@ class AffineTraj:
         HS = iv.H * self.S
         z = lambda *s, dtype=torch.float32: torch.empty(*s, dtype=dtype, device=device)
         self.K, self.Y, self.G = z(HS, n, self.ns), z(HS, n, self.ns), z(HS, n, self.ns * self.nu)
-        words = mode == "inputs" or (mode == "params" and env_switch("fit_words"))
-        self.bits = 0 if mode == "none" else (1 if mode == "inputs" else (2 if words else 0))
-        self.acts, self.ls = [None, None], [0, 0]
-        if mode != "none":
-            for i, net in enumerate((f, g)):
-                nw = net.n_layers - 1
-                if mode == "inputs":                       # words in place of the rows
-                    self.acts[i], self.ls[i] = z(nw * HS * n * 4, dtype=torch.int32), HS * n * 4
-                else:                                      # rows [layer][HS n][hid], then (bits 2) words [layer][HS n][4]
-                    self.acts[i] = z(nw * HS * n * (net.hid + (4 if words else 0)))
-                    self.ls[i] = HS * n * net.hid
+        self.bits, self.acts, self.ls = _kept_acts(f, g, HS * n, mode, z)
 
     def forward(self, x0, u, xs):
         self.u = u
@@ -307,16 +348,8 @@ class AffineTraj:
         if not need_p:
             return dx0, du, None
         # every stage of every interval as ONE batch of H * S * n rows through the weight-gradient launch
-        arena = self.f.arena
-        io = io_array(2)
-        for i, (dy, ld, dz) in enumerate(((dK, self.ns, dz_f), (dG, self.ns * self.nu, dz_g))):
-            io[i].x0, io[i].x0_dim, io[i].x0_ld = self.Y.data_ptr(), self.ns, self.ns
-            io[i].dy, io[i].dy_ld = dy.data_ptr(), ld
-            io[i].acts, io[i].acts_ls = _ptr(self.acts[i]), self.ls[i]
-            io[i].dz = dz.data_ptr()
-            io[i].grad = arena.grad.data_ptr()
-        bwd_weights(mlp_array([self.f.desc, self.g.desc]), io, 2, HS * n, arena.n_slabs, arena.n, dev)
-        return dx0, du, _reduce(arena, arena.n_slabs)
+        return dx0, du, _affine_weight_grads(self.f, self.g, self.Y.data_ptr(), self.ns, (dK, dG),
+                                             [_ptr(a) for a in self.acts], self.ls, (dz_f, dz_g), HS * n, dev)
 
 
 class ConcatTraj:
@@ -364,15 +397,8 @@ class ConcatTraj:
         if not need_p:
             return dx0, du, None
         # every stage of every interval as ONE batch of H * S * n rows: layer 0's input is the kept Xin row
-        arena = self.net.arena
-        io = io_array(1)
-        io[0].x0, io[0].x0_dim, io[0].x0_ld = self.Xin.data_ptr(), self.net.in_dim, self.net.in_dim
-        io[0].dy, io[0].dy_ld = dK.data_ptr(), self.ns
-        io[0].acts, io[0].acts_ls = self.acts.data_ptr(), self.ls
-        io[0].dz = dz.data_ptr()
-        io[0].grad = arena.grad.data_ptr()
-        bwd_weights(mlp_array([self.net.desc]), io, 1, HS * n, arena.n_slabs, arena.n, dev)
-        return dx0, du, _reduce(arena, arena.n_slabs)
+        return dx0, du, _concat_weight_grads(self.net, self.Xin.data_ptr(), self.net.in_dim, dK, self.acts.data_ptr(),
+                                             self.ls, dz, HS * n, dev)
 
 
 class TileSteps(EqualSteps):
@@ -385,15 +411,15 @@ class TileSteps(EqualSteps):
         self.max_steps, self.info = max_steps, info
 
 
-class AffineTileDopri:
-    """Device buffers of one dopri5 solve of the control-affine NODE under tile-local step control: one
-    ``nlbac_node_dopri_tile_fwd`` launch for the whole horizon, one ``nlbac_node_dopri_tile_bwd`` for its backward (+ the
-    weight-gradient launch over the used slots).  Slot-major [slot][stage][row] over max_steps * 7 stages, a slot per
-    accepted step of a tile — ``AffineTraj``'s layout with the slot in place of the interval; zero-filled, so that a
-    stage nobody evaluated (a slot a tile did not use, stage 0 of a step that took it from the step before) adds
-    nothing to the weight gradients."""
+class AffineTile:
+    """What a dopri5 solve of the control-affine NODE under tile-local step control keeps, whichever way its outputs are
+    read (``AffineTileDopri``, ``AffineTileDense``): the nets, tolerances and dopri5's table, every tile's counts and
+    status, and — when a backward follows — the kept buffers, slot-major [slot][stage][row] over max_steps * 7 stages, a
+    slot per accepted step of a tile: ``AffineTraj``'s layout with the slot in place of the interval; zero-filled, so
+    that a stage nobody evaluated (a slot a tile did not use, stage 0 of a step that took it from the step before) adds
+    nothing to the weight gradients.  A leaf has ``api`` and ``words`` (what differs in the stopped-tile message),
+    ``du_shape``, ``_nacc()``, the arrays that say where its outputs lie in the slots, and its launches ``_fwd`` / ``_bwd``."""
     S = 7
-    api = "rollout"
 
     @staticmethod
     def shapes_ok(func):
@@ -414,82 +440,67 @@ class AffineTileDopri:
         f, g = func.device_handles()
         return _lib.load().nlbac_node_dopri_tile_ok(C.byref(f.desc), C.byref(g.desc)) == 1
 
-    def __init__(self, func, n, iv, mode, atol, rtol, device):
-        from .ode_consts import DP_C_ERR
+    def __init__(self, func, n, counts, max_steps, info, mode, atol, rtol, device):
+        """``counts``: the shape of a tile's ``accepted`` / ``attempts`` (a count per interval; one for a dense solve)."""
         if not self.ok(func):
             raise NotImplementedError("%s: step_control='tile' needs nets the register-resident kernels serve "
                                       "(nlbac_node_dopri_tile_ok); there is no chained fallback" % self.api)
         f, g = func.device_handles()
-        self.f, self.g, self.iv, self.mode, self.tol = f, g, iv, mode, (rtol, atol)
-        self.ns, self.nu, self.n, self.H = func.n_s, func.n_u, n, iv.H
-        beta = [0.0] * (self.S * self.S)
-        for i, r in enumerate(TABLEAU["dopri5"]["beta"]):
-            for j, v in enumerate(r):
-                beta[(i + 1) * self.S + j] = v
-        self.beta, self.c_err = fptr(*beta), fptr(*DP_C_ERR)
+        self.f, self.g, self.info, self.mode, self.tol = f, g, info, mode, (rtol, atol)
+        self.ns, self.nu, self.n = func.n_s, func.n_u, n
+        self.beta, self.c_err = _tableau("dopri5")[1], fptr(*DP_C_ERR)
         self.tiles = (n + _lib.MLP_TILE - 1) // _lib.MLP_TILE
         z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=device)
-        self.accepted, self.attempts = z(self.tiles, iv.H, dtype=torch.int32), z(self.tiles, iv.H, dtype=torch.int32)
+        self.accepted, self.attempts = z(self.tiles, *counts, dtype=torch.int32), z(self.tiles, *counts, dtype=torch.int32)
         self.status = z(self.tiles, dtype=torch.int32)
-        self.M = iv.max_steps if mode != "none" else 0
+        self.M = max_steps if mode != "none" else 0
         MS = self.M * self.S
-        words = mode == "inputs" or (mode == "params" and env_switch("fit_words"))
-        self.bits = 0 if mode == "none" else (1 if mode == "inputs" else (2 if words else 0))
-        self.G = self.Y = self.hslots = self.iv_first = self.iv_x = None
-        self.acts, self.ls = [None, None], [0, 0]
+        self.G = self.Y = self.hslots = None
         if mode != "none":
             self.G = z(MS, n, self.ns * self.nu)
             self.Y = z(MS, n, self.ns) if mode == "params" else None
             self.hslots = z(self.tiles, self.M, dtype=torch.float64)
-            self.iv_first, self.iv_x = z(self.tiles, iv.H, dtype=torch.int32), z(self.tiles, iv.H)
-            for i, net in enumerate((f, g)):      # (AffineTraj's layouts over MS stages)
-                nw = net.n_layers - 1
-                if mode == "inputs":
-                    self.acts[i], self.ls[i] = z(nw * MS * n * 4, dtype=torch.int32), MS * n * 4
-                else:
-                    self.acts[i] = z(nw * MS * n * (net.hid + (4 if words else 0)))
-                    self.ls[i] = MS * n * net.hid
+            self._interval_arrays(z)
+        self.bits, self.acts, self.ls = _kept_acts(f, g, MS * n, mode, z)
+
+    def _interval_arrays(self, z):
+        """A leaf's kept arrays that come between ``hslots`` and the activations in the order of allocation."""
 
     def forward(self, x0, u, xs):
         self.u = u
-        rtol, atol = self.tol
-        _lib.call("nlbac_node_dopri_tile_fwd", C.byref(self.f.desc), C.byref(self.g.desc), x0.data_ptr(), u.data_ptr(),
-                  self.n, self.H, self.beta, self.c_err, self.iv.dt, rtol, atol, xs.data_ptr(), self.M, _ptr(self.Y),
-                  _ptr(self.G), _ptr(self.acts[0]), self.ls[0], _ptr(self.acts[1]), self.ls[1], self.bits,
-                  _ptr(self.hslots), _ptr(self.iv_first), _ptr(self.iv_x), self.accepted.data_ptr(),
-                  self.attempts.data_ptr(), self.status.data_ptr(), stream_ptr())
-        if self.iv.info is not None:
-            self.iv.info.update(accepted=self.accepted, attempts=self.attempts, status=self.status)
+        self._fwd(x0, u, xs, *self.tol)
+        if self.info is not None:
+            self.info.update(accepted=self.accepted, attempts=self.attempts, status=self.status)
 
     def backward(self, dout, need_p):
-        n, H, M, dev = self.n, self.H, self.M, dout.device
-        # the one look at the solve: every tile's status and step count, long after the launch has finished
-        seen = torch.stack((self.status, self.accepted.sum(1, dtype=torch.int32))).cpu()
+        """``dout``: the outputs' gradients as the leaf's launch takes them.  Returns (dx0: the first step's dy0, the
+        controls' gradient, the flat parameter gradient or None)."""
+        dev = dout.device
+        used = self._look()
+        z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        dx0, du = z(self.n, self.ns), z(*self.du_shape)
+        rows = self._weight_rows(dev) if need_p else (None, None, None, None)
+        self._bwd(dout, dx0, du, *[_ptr(r) for r in rows])
+        return dx0, du, self._weight_grads(*rows, used, dev) if need_p else None
+
+    def _look(self):
+        """The one look at the solve, long after its launch has finished: every tile's status and count of accepted steps
+        (the leaf's ``_nacc()``) come to the host.  Returns the largest count, the slots in use; raises if a tile stopped."""
+        seen = torch.stack((self.status, self._nacc())).cpu()
         used = int(seen[1].max())
         bad = seen[0].nonzero().flatten().tolist()
         if bad:
-            why = {1: "ran out of step slots", 2: "took more than 1000 attempts in one interval"}
+            why = {1: "ran out of step slots", 2: "took more than 1000 attempts" + self.words[0]}
             raise _lib.NlbacError(
-                "rollout(step_control='tile'): tile %d %s (status %d; %d of %d tiles stopped), so the solve has no "
+                "%s(step_control='tile'): tile %d %s (status %d; %d of %d tiles stopped), so the solve has no "
                 "backward: max_steps = %d slots per tile, the largest count of accepted steps a tile had kept when it "
-                "stopped or finished is %d — raise max_steps (its default is 8 H)"
-                % (bad[0], why.get(int(seen[0][bad[0]]), "stopped"), int(seen[0][bad[0]]), len(bad), self.tiles, M, used))
-        z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-        dx0, du = z(n, self.ns), z(H, n, self.nu)
-        dK, dG, dz_f, dz_g = self._weight_rows(need_p, dev)
-        _lib.call("nlbac_node_dopri_tile_bwd", C.byref(self.f.desc), C.byref(self.g.desc), self.u.data_ptr(), n, H,
-                  self.beta, M, self.hslots.data_ptr(), self.iv_first.data_ptr(), self.accepted.data_ptr(),
-                  self.iv_x.data_ptr(), self.G.data_ptr(), _ptr(self.acts[0]), self.ls[0], _ptr(self.acts[1]), self.ls[1],
-                  self.bits, dout.data_ptr(), dx0.data_ptr(), du.data_ptr(), _ptr(dK), _ptr(dG), _ptr(dz_f), _ptr(dz_g),
-                  stream_ptr())
-        if not need_p:
-            return dx0, du, None
-        return dx0, du, self._weight_grads(dK, dG, dz_f, dz_g, used, dev)
+                "stopped or finished is %d — raise max_steps (its default is %s)"
+                % (self.api, bad[0], why.get(int(seen[0][bad[0]]), "stopped"), int(seen[0][bad[0]]), len(bad), self.tiles,
+                   self.M, used, self.words[1]))
+        return used
 
-    def _weight_rows(self, need_p, dev):
-        """dK, dG, dz_f, dz_g per (slot, stage, row) for the weight gradients (zero-filled), or four times None."""
-        if not need_p:
-            return None, None, None, None
+    def _weight_rows(self, dev):
+        """dK, dG, dz_f, dz_g per (slot, stage, row) for the weight gradients (zero-filled)."""
         n, MS = self.n, self.M * self.S
         zero = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
         return (zero(MS, n, self.ns), zero(MS, n, self.ns * self.nu), zero(self.f.n_layers - 1, MS * n, self.f.hid),
@@ -498,74 +509,76 @@ class AffineTileDopri:
     def _weight_grads(self, dK, dG, dz_f, dz_g, used, dev):
         """Every stage of the USED slots as one batch through the weight-gradient launch: the slots are the leading
         index, so the first used * 7 * n rows of every buffer hold them (the layers' stride stays that of all slots)."""
-        arena = self.f.arena
-        io = io_array(2)
-        for i, (dy, ld, dz) in enumerate(((dK, self.ns, dz_f), (dG, self.ns * self.nu, dz_g))):
-            io[i].x0, io[i].x0_dim, io[i].x0_ld = self.Y.data_ptr(), self.ns, self.ns
-            io[i].dy, io[i].dy_ld = dy.data_ptr(), ld
-            io[i].acts, io[i].acts_ls = _ptr(self.acts[i]), self.ls[i]
-            io[i].dz = dz.data_ptr()
-            io[i].grad = arena.grad.data_ptr()
-        bwd_weights(mlp_array([self.f.desc, self.g.desc]), io, 2, used * self.S * self.n, arena.n_slabs, arena.n, dev)
-        return _reduce(arena, arena.n_slabs)
+        return _affine_weight_grads(self.f, self.g, self.Y.data_ptr(), self.ns, (dK, dG), [_ptr(a) for a in self.acts],
+                                    self.ls, (dz_f, dz_g), used * self.S * self.n, dev)
 
 
-class AffineTileDense(AffineTileDopri):
-    """Device buffers of one DENSE dopri5 solve under tile-local step control (``odeint_dense(step_control="tile")``):
-    every 32-row tile runs one adaptive solve over ``[0, taus[-1]]`` and writes its interpolant at every output time
-    behind the accepted steps — one ``nlbac_node_dopri_tile_dense_fwd`` launch, one ``nlbac_node_dopri_tile_dense_bwd``
-    for its backward (+ the weight-gradient launch over the used slots).  ``AffineTileDopri``'s kept buffers with H = 1
-    (``max_steps`` slots per tile), and per tile and output the slot that emitted it and its abscissa (``ov_slot`` /
-    ``ov_x``) in place of the intervals' arrays."""
-    api = "odeint_dense"
+class AffineTileDopri(AffineTile):
+    """``AffineTile`` of a rollout (``TileSteps``): one ``nlbac_node_dopri_tile_fwd`` launch for the whole horizon, one
+    ``nlbac_node_dopri_tile_bwd`` for its backward (+ the weight-gradient launch over the used slots).  Counts per tile
+    and interval; per tile and interval its first slot and the abscissa of its output in its last step (``iv_first`` /
+    ``iv_x``)."""
+    api, words = "rollout", (" in one interval", "8 H")
+
+    def __init__(self, func, n, iv, mode, atol, rtol, device):
+        self.iv, self.H, self.du_shape = iv, iv.H, (iv.H, n, func.n_u)
+        self.iv_first = self.iv_x = None
+        AffineTile.__init__(self, func, n, (iv.H,), iv.max_steps, iv.info, mode, atol, rtol, device)
+
+    def _interval_arrays(self, z):
+        self.iv_first, self.iv_x = z(self.tiles, self.H, dtype=torch.int32), z(self.tiles, self.H)
+
+    def _nacc(self):
+        return self.accepted.sum(1, dtype=torch.int32)
+
+    def _fwd(self, x0, u, xs, rtol, atol):
+        _lib.call("nlbac_node_dopri_tile_fwd", C.byref(self.f.desc), C.byref(self.g.desc), x0.data_ptr(), u.data_ptr(),
+                  self.n, self.H, self.beta, self.c_err, self.iv.dt, rtol, atol, xs.data_ptr(), self.M, _ptr(self.Y),
+                  _ptr(self.G), _ptr(self.acts[0]), self.ls[0], _ptr(self.acts[1]), self.ls[1], self.bits,
+                  _ptr(self.hslots), _ptr(self.iv_first), _ptr(self.iv_x), self.accepted.data_ptr(),
+                  self.attempts.data_ptr(), self.status.data_ptr(), stream_ptr())
+
+    def _bwd(self, dout, dx0, du, dK, dG, dz_f, dz_g):
+        _lib.call("nlbac_node_dopri_tile_bwd", C.byref(self.f.desc), C.byref(self.g.desc), self.u.data_ptr(), self.n,
+                  self.H, self.beta, self.M, self.hslots.data_ptr(), self.iv_first.data_ptr(), self.accepted.data_ptr(),
+                  self.iv_x.data_ptr(), self.G.data_ptr(), _ptr(self.acts[0]), self.ls[0], _ptr(self.acts[1]), self.ls[1],
+                  self.bits, dout.data_ptr(), dx0.data_ptr(), du.data_ptr(), dK, dG, dz_f, dz_g, stream_ptr())
+
+
+class AffineTileDense(AffineTile):
+    """``AffineTile`` of one DENSE solve (``odeint_dense(step_control="tile")``): every 32-row tile runs one adaptive
+    solve over ``[0, taus[-1]]`` and writes its interpolant at every output time behind the accepted steps — one
+    ``nlbac_node_dopri_tile_dense_fwd`` launch, one ``nlbac_node_dopri_tile_dense_bwd`` for its backward (+ the
+    weight-gradient launch over the used slots).  One count per tile; per tile and output the slot that emitted it and
+    its abscissa (``ov_slot`` / ``ov_x``).  ``backward`` takes dxs (T - 1, n, n_s): d loss / d out[1:] on the state
+    columns."""
+    api, words = "odeint_dense", ("", "32")
 
     def __init__(self, func, n, taus, max_steps, info, mode, atol, rtol, device):
-        AffineTileDopri.__init__(self, func, n, TileSteps(taus[-1], 1, max_steps, info), mode, atol, rtol, device)
-        self.n_out = len(taus)
+        AffineTile.__init__(self, func, n, (), max_steps, info, mode, atol, rtol, device)
+        self.n_out, self.t_end, self.du_shape = len(taus), taus[-1], (n, func.n_u)
         self.tau = torch.tensor(taus, dtype=torch.float64, device=device)
-        self.accepted, self.attempts = self.accepted.view(self.tiles), self.attempts.view(self.tiles)
-        self.iv_first = self.iv_x = self.ov_slot = self.ov_x = None
+        self.ov_slot = self.ov_x = None
         if mode != "none":
             self.ov_slot = torch.zeros(self.tiles, self.n_out, dtype=torch.int32, device=device)
             self.ov_x = torch.zeros(self.tiles, self.n_out, dtype=torch.float32, device=device)
 
-    def forward(self, x0, u, xs):
-        self.u = u
-        rtol, atol = self.tol
+    def _nacc(self):
+        return self.accepted
+
+    def _fwd(self, x0, u, xs, rtol, atol):
         _lib.call("nlbac_node_dopri_tile_dense_fwd", C.byref(self.f.desc), C.byref(self.g.desc), x0.data_ptr(),
-                  u.data_ptr(), self.n, self.beta, self.c_err, self.tau.data_ptr(), self.n_out, self.iv.dt, rtol, atol,
+                  u.data_ptr(), self.n, self.beta, self.c_err, self.tau.data_ptr(), self.n_out, self.t_end, rtol, atol,
                   xs.data_ptr(), self.M, _ptr(self.Y), _ptr(self.G), _ptr(self.acts[0]), self.ls[0], _ptr(self.acts[1]),
                   self.ls[1], self.bits, _ptr(self.hslots), _ptr(self.ov_slot), _ptr(self.ov_x),
                   self.accepted.data_ptr(), self.attempts.data_ptr(), self.status.data_ptr(), stream_ptr())
-        if self.iv.info is not None:
-            self.iv.info.update(accepted=self.accepted, attempts=self.attempts, status=self.status)
 
-    def backward(self, dxs, need_p):
-        """dxs (T - 1, n, n_s): d loss / d out[1:] on the state columns.  Returns (the first step's dy0, du, flat
-        parameter gradient or None)."""
-        n, M, dev = self.n, self.M, dxs.device
-        # the one look at the solve: every tile's status and step count, long after the launch has finished
-        seen = torch.stack((self.status, self.accepted)).cpu()
-        used = int(seen[1].max())
-        bad = seen[0].nonzero().flatten().tolist()
-        if bad:
-            why = {1: "ran out of step slots", 2: "took more than 1000 attempts"}
-            raise _lib.NlbacError(
-                "odeint_dense(step_control='tile'): tile %d %s (status %d; %d of %d tiles stopped), so the solve has no "
-                "backward: max_steps = %d slots per tile, the largest count of accepted steps a tile had kept when it "
-                "stopped or finished is %d — raise max_steps (its default is 32)"
-                % (bad[0], why.get(int(seen[0][bad[0]]), "stopped"), int(seen[0][bad[0]]), len(bad), self.tiles, M, used))
-        z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-        dx0, du = z(n, self.ns), z(n, self.nu)
-        dK, dG, dz_f, dz_g = self._weight_rows(need_p, dev)
-        _lib.call("nlbac_node_dopri_tile_dense_bwd", C.byref(self.f.desc), C.byref(self.g.desc), self.u.data_ptr(), n,
-                  self.beta, self.n_out, M, self.hslots.data_ptr(), self.ov_slot.data_ptr(), self.ov_x.data_ptr(),
-                  self.accepted.data_ptr(), self.G.data_ptr(), _ptr(self.acts[0]), self.ls[0], _ptr(self.acts[1]),
-                  self.ls[1], self.bits, dxs.data_ptr(), dx0.data_ptr(), du.data_ptr(), _ptr(dK), _ptr(dG), _ptr(dz_f),
-                  _ptr(dz_g), stream_ptr())
-        if not need_p:
-            return dx0, du, None
-        return dx0, du, self._weight_grads(dK, dG, dz_f, dz_g, used, dev)
+    def _bwd(self, dxs, dx0, du, dK, dG, dz_f, dz_g):
+        _lib.call("nlbac_node_dopri_tile_dense_bwd", C.byref(self.f.desc), C.byref(self.g.desc), self.u.data_ptr(),
+                  self.n, self.beta, self.n_out, self.M, self.hslots.data_ptr(), self.ov_slot.data_ptr(),
+                  self.ov_x.data_ptr(), self.accepted.data_ptr(), self.G.data_ptr(), _ptr(self.acts[0]), self.ls[0],
+                  _ptr(self.acts[1]), self.ls[1], self.bits, dxs.data_ptr(), dx0.data_ptr(), du.data_ptr(), dK, dG, dz_f,
+                  dz_g, stream_ptr())
 
 
 def traj_class(func):
@@ -758,17 +771,10 @@ class AffineAdjTraj(_AdjTraj):
                   _ptr(k.get("acts_g")), rows * self.g.hid, _ptr(k.get("dz_f")), _ptr(k.get("dz_g")), stream_ptr())
 
     def weight_grads(self, k, rows):
-        arena, ns, nu = self.f.arena, self.ns, self.nc
-        io = io_array(2)
-        for i, (net, dy, ld, acts, dz) in enumerate(((self.f, k["dK"], ns, k["acts_f"], k["dz_f"]),
-                                                     (self.g, k["dG"], ns * nu, k["acts_g"], k["dz_g"]))):
-            io[i].x0, io[i].x0_dim, io[i].x0_ld = k["ZS"].data_ptr(), ns, 2 * ns + nu
-            io[i].dy, io[i].dy_ld = dy.data_ptr(), ld
-            io[i].acts, io[i].acts_ls = acts.data_ptr(), rows * net.hid
-            io[i].dz = dz.data_ptr()
-            io[i].grad = arena.grad.data_ptr()
-        bwd_weights(mlp_array([self.f.desc, self.g.desc]), io, 2, rows, arena.n_slabs, arena.n, self.device)
-        return _reduce(arena, arena.n_slabs)
+        # layer 0's input rows are the y columns of the kept z = [y | a_x | a_c] rows
+        return _affine_weight_grads(self.f, self.g, k["ZS"].data_ptr(), 2 * self.ns + self.nc, (k["dK"], k["dG"]),
+                                    (k["acts_f"].data_ptr(), k["acts_g"].data_ptr()),
+                                    (rows * self.f.hid, rows * self.g.hid), (k["dz_f"], k["dz_g"]), rows, self.device)
 
 
 class ConcatAdjTraj(_AdjTraj):
@@ -802,15 +808,8 @@ class ConcatAdjTraj(_AdjTraj):
                   stream_ptr())
 
     def weight_grads(self, k, rows):
-        net, arena = self.net, self.net.arena
-        io = io_array(1)
-        io[0].x0, io[0].x0_dim, io[0].x0_ld = k["Xin"].data_ptr(), net.in_dim, net.in_dim
-        io[0].dy, io[0].dy_ld = k["Ay"].data_ptr(), self.ns
-        io[0].acts, io[0].acts_ls = k["acts"].data_ptr(), rows * net.hid
-        io[0].dz = k["dz"].data_ptr()
-        io[0].grad = arena.grad.data_ptr()
-        bwd_weights(mlp_array([net.desc]), io, 1, rows, arena.n_slabs, arena.n, self.device)
-        return _reduce(arena, arena.n_slabs)
+        return _concat_weight_grads(self.net, k["Xin"].data_ptr(), self.net.in_dim, k["Ay"], k["acts"].data_ptr(),
+                                    rows * self.net.hid, k["dz"], rows, self.device)
 
 
 def adj_traj_class(func):

@@ -1,11 +1,15 @@
 """Host-side checks of ``odeint_dense(..., step_control=, max_steps=, info=)`` (no GPU needed): every refusal comes
 before anything touches a device — with every device entry patched to fail, as ``test_odeint_dense_host`` patches them —
-``step_control="batch"`` is the call as it was, and the two ``nlbac_node_dopri_tile_dense_*`` entry points are declared."""
+``step_control="batch"`` is the call as it was, the two ``nlbac_node_dopri_tile_dense_*`` entry points are declared,
+and they refuse bad arguments with a message before anything is launched."""
 import os
 import re
 
 import pytest
 import torch
+
+from test_rollout_concat_host import lib, refused      # noqa: F401  (lib: the fixture that builds and loads)
+from test_rollout_tile_host import backward_refusals, forward_refusals, tile_args
 
 GRID = [0.0, 0.01, 0.02, 0.05, 0.3]
 
@@ -197,3 +201,19 @@ def test_entry_points_are_declared():
             assert arg.replace("const ", "") in proto.replace("const ", ""), (name, arg)
     src = os.path.join(os.path.dirname(_lib.__file__), "csrc")
     assert "node_tile_dense_kernels.hip" in open(os.path.join(src, "Makefile")).read()
+
+
+def test_forward_refuses_before_launching(lib):
+    name = "nlbac_node_dopri_tile_dense_fwd"
+    forward_refusals(lib, name)
+    kw, keep = tile_args(lib, name)
+    assert "bad rows / output times" in refused(lib, name, dict(kw, n_out=0), "n_out = 0")
+    assert "max_slots must be at least 1" in refused(lib, name, dict(kw, max_slots=0), "no slot")
+    assert "null pointer" in refused(lib, name, dict(kw, tau=None), "a null tau")
+
+
+def test_backward_refuses_before_launching(lib):
+    name = "nlbac_node_dopri_tile_dense_bwd"
+    backward_refusals(lib, name)
+    kw, keep = tile_args(lib, name)
+    assert "max_slots must be at least 1" in refused(lib, name, dict(kw, max_slots=0), "no slot")

@@ -37,7 +37,8 @@ import torch
 from . import _lib
 from . import ode_traj as T
 from .arena import stream_ptr
-from .ode_grid import _steps_of
+from .ode_grid import _check_y0, _steps_of
+from .ode_node import PackedSolve, SolveNode, _reduce
 
 STEP_CONTROLS = ("batch", "tile")
 TILE_MAX_STEPS = 32                        # the slots a tile gets when max_steps is None
@@ -48,10 +49,7 @@ ADJOINT = "adjoint"                        # the key of odeint_dense_adjoint's s
 def _taus(t):
     """The grid's checks (``ode_grid._steps_of``'s); returns the output times 1 .. T-1 in solver time — the field is
     autonomous, the solve runs over [0, t[-1] - t[0]] — each ``float(t[j]) - float(t[0])``, as ``odeint`` forms its dt."""
-    try:
-        _steps_of(t)
-    except (ValueError, TypeError) as e:
-        raise type(e)(str(e).replace("odeint_grid:", "odeint_dense:")) from None
+    _steps_of(t, "odeint_dense")
     times = [float(v) for v in torch.as_tensor(t).detach().cpu()]
     return tuple(v - times[0] for v in times[1:])
 
@@ -114,13 +112,7 @@ def _check_args(func, y0, t, atol, rtol, adjoint):
             raise TypeError("odeint_dense: %s must be a Python number; got %s" % (name, type(v).__name__))
         if not (math.isfinite(v) and v > 0):
             raise ValueError("odeint_dense: %s must be positive and finite; got %r" % (name, v))
-    if not isinstance(y0, torch.Tensor):
-        raise TypeError("odeint_dense: y0 must be a tensor; got %s" % type(y0).__name__)
-    if y0.dtype != torch.float32:
-        raise TypeError("odeint_dense: y0 must be float32; got %s" % y0.dtype)
-    width = func.n_s + (func.n_u if func.affine else func.n_carry)
-    if y0.dim() != 2 or y0.shape[1] != width or y0.shape[0] < 1:
-        raise ValueError("odeint_dense: y0 must be (batch, %d) = [x | carried columns]; got %s" % (width, tuple(y0.shape)))
+    _check_y0("odeint_dense", func, y0)
     return taus
 
 
@@ -186,8 +178,8 @@ def odeint_dense(func, y0, t, *, atol=1e-7, rtol=1e-5, adjoint=False, step_contr
         # the tile-local solve: no solver, no chain — the cached solvers of the batch-wide control are not touched
         params = tuple(func.parameters())
         func.refresh_device_weights()
-        return _DenseTileFunction.apply(func, taus, float(atol), float(rtol), T.keep_mode(params, y0), slots, info, y0,
-                                        *params)
+        solve = _DenseTileSolve(func, taus, float(atol), float(rtol), T.keep_mode(params, y0), slots, info)
+        return SolveNode.apply(solve, 1, y0, *params)
     if torch.cuda.is_current_stream_capturing():
         raise RuntimeError("odeint_dense: not inside a hipGraph capture — the adaptive solve needs the host's look at the "
                            "control block to know how many steps were accepted")
@@ -200,34 +192,48 @@ def odeint_dense(func, y0, t, *, atol=1e-7, rtol=1e-5, adjoint=False, step_contr
             "kernels refuse these nets — device_loop=%s); the host-driven and stage-by-stage paths emit no interior "
             "points" % (y0.shape[0], sv.fused, sv.device_loop))
     func.refresh_device_weights()
-    return _DenseFunction.apply(func, sv, taus, float(atol), float(rtol), mode, y0, *params)
+    return SolveNode.apply(_DenseSolve(func, sv, taus, float(atol), float(rtol), mode), 1, y0, *params)
 
 
-class _DenseSolve:
-    """What one dense solve keeps: the solver (whose step slots hold the accepted steps), the output times on the device
-    and the carried columns."""
+def _dense_fwd(sv, taus, x0, c, atol, rtol, xs):
+    """One dense solve on ``sv`` from ``x0`` under the carried columns ``c`` into ``xs`` (T - 1, n, n_s): the chain to
+    ``taus[-1]``, then the launch that reads every output off the step slots.  Returns (the solve's id, the slot pool,
+    the steps' sizes, the output times on the device)."""
+    n = x0.shape[0]
+    sv.forward(x0, c, 1, n, "dopri5", taus[-1], atol, rtol)
+    st = sv.ctx["chain"]
+    assert not st["ip"] and not sv.ctx.get("out_mapped"), "a dense solve interpolates nothing inside its attempts"
+    pool, hslots = st["pool"], st["ch"].hslots
+    tau = torch.tensor(taus, dtype=torch.float64, device=x0.device)
+    ws0 = pool.ws(n, 0)
+    _lib.call("nlbac_dopri_dense_fwd", x0.data_ptr(), ws0.Y[6].data_ptr(), ws0.K.data_ptr(), pool.slot_floats,
+              sv._ctl(1).data_ptr(), hslots, pool.n_slots, tau.data_ptr(), len(taus), n, sv.n_s, xs.data_ptr(),
+              stream_ptr())
+    return sv.stats["solves"], pool, hslots, tau
 
-    def __init__(self, sv, taus, x0, c, atol, rtol, xs):
-        n, ns = x0.shape[0], sv.n_s
-        self.sv, self.n, self.n_out, self.c = sv, n, len(taus), c
-        sv.forward(x0, c, 1, n, "dopri5", taus[-1], atol, rtol)
-        st = sv.ctx["chain"]
-        assert not st["ip"] and not sv.ctx.get("out_mapped"), "a dense solve interpolates nothing inside its attempts"
-        self.solve_id = sv.stats["solves"]
-        self.pool, self.hslots = st["pool"], st["ch"].hslots
-        self.tau = torch.tensor(taus, dtype=torch.float64, device=x0.device)
-        ws0 = self.pool.ws(n, 0)
-        _lib.call("nlbac_dopri_dense_fwd", x0.data_ptr(), ws0.Y[6].data_ptr(), ws0.K.data_ptr(), self.pool.slot_floats,
-                  sv._ctl(1).data_ptr(), self.hslots, self.pool.n_slots, self.tau.data_ptr(), self.n_out, n, ns,
-                  xs.data_ptr(), stream_ptr())
 
-    def backward(self, dxs, need_p):
-        """dxs (T - 1, n, n_s): d loss / d out[1:] on the state columns.  Returns (dx0, dc, flat parameter gradient or
-        None); dc is the solve's own share of the carried columns' gradient."""
-        sv, n, pool = self.sv, self.n, self.pool
+class _DenseSolve(PackedSolve):
+    """One dense solve as ``ode_node.SolveNode``'s solve.  What it keeps: the solver (whose step slots hold the accepted
+    steps), the output times on the device and the carried columns."""
+    api = "odeint_dense"
+
+    def __init__(self, func, sv, taus, atol, rtol, mode):
+        PackedSolve.__init__(self, func)
+        self.sv, self.taus, self.tol, self.mode = sv, taus, (atol, rtol), mode
+        self.n_out, self.with_params = len(taus), mode == "params"
+
+    def solve(self, x0, c, xs):
+        self.n, self.c = x0.shape[0], c
+        self.solve_id, self.pool, self.hslots, self.tau = _dense_fwd(self.sv, self.taus, x0, c, *self.tol, xs)
+        self.kept = self.sv if self.mode != "none" else None
+
+    def backward(self, dout, need_in, need_p):
+        """Returns (d/dy0 or None, the flat parameter gradient or None)."""
+        sv, n, pool, ns = self.sv, self.n, self.pool, self.ns
         assert sv.stats["solves"] == self.solve_id, \
             "odeint_dense: backward must run before the next odeint_dense with the same model and what it keeps"
-        ctx, ns, s = sv.ctx, sv.n_s, stream_ptr()
+        dxs = dout[1:, :, :ns].contiguous()      # d loss / d out[1:] on the state columns
+        ctx, s = sv.ctx, stream_ptr()
         nacc = ctx["nacc"][0]
         wss = [pool.ws(n, i).bwd(sv) for i in range(nacc + 1)]
         ws0 = wss[0]
@@ -247,82 +253,39 @@ class _DenseSolve:
         flat = None
         if need_p:
             arena = sv.node.device_handles()[0].arena
-            used = sv.accumulate_param_grads(arena, max(1, arena.n_slabs // len(ctx["steps"])))
-            flat = T._reduce(arena, used)
-        return ws0.dy0, du, flat
+            flat = _reduce(arena, sv.accumulate_param_grads(arena, max(1, arena.n_slabs // len(ctx["steps"]))))
+        if not need_in[0]:
+            return None, flat
+        # d/d carried columns: the solve's own (du), and the share of every output point they were copied to
+        return self.grad_y0(dout, ws0.dy0, du, dout[1:, :, ns:].sum(0), self), flat
 
 
-def _solve(sv, taus, atol, rtol, y0):
-    """One dense solve on ``sv`` from ``y0`` (B, n_s + n_c): returns (out (T, B, n_s + n_c), the ``_DenseSolve``)."""
-    n, ns = y0.shape[0], sv.n_s
-    y0 = y0.detach().contiguous()
-    x0, c = y0[:, :ns].contiguous(), y0[:, ns:].contiguous()
-    xs = torch.empty(len(taus), n, ns, dtype=torch.float32, device=y0.device)
-    solve = _DenseSolve(sv, taus, x0, c, atol, rtol, xs)
-    out = torch.empty(len(taus) + 1, n, y0.shape[1], dtype=torch.float32, device=y0.device)
-    out[0].copy_(y0)
-    out[1:, :, :ns].copy_(xs)
-    out[1:, :, ns:].copy_(c)          # (the carried columns, the same at every output point)
-    return out, solve
+class _DenseTileSolve(PackedSolve):
+    """``odeint_dense(step_control="tile")`` as ``ode_node.SolveNode``'s solve: ``ode_traj.AffineTileDense`` behind the
+    packed layout."""
+    api = "odeint_dense"
 
+    def __init__(self, func, taus, atol, rtol, mode, slots, info):
+        PackedSolve.__init__(self, func)
+        self.taus, self.tol, self.mode, self.slots, self.info = taus, (atol, rtol), mode, slots, info
+        self.n_out, self.with_params = len(taus), mode == "params"
 
-class _DenseFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, func, sv, taus, atol, rtol, mode, y0, *params):
-        out, solve = _solve(sv, taus, atol, rtol, y0)
-        ctx.func, ctx.mode, ctx.n_params = func, mode, len(params)
-        ctx.kept = solve if mode != "none" else None
-        return out
+    def solve(self, x0, c, xs):
+        tile = T.AffineTileDense(self.func, x0.shape[0], self.taus, self.slots, self.info, self.mode, *self.tol, x0.device)
+        tile.forward(x0, c, xs)
+        self.kept = tile if self.mode != "none" else None
 
-    @staticmethod
-    def backward(ctx, dout):
-        assert ctx.kept is not None, "odeint_dense: nothing was kept for a backward (the forward ran without gradients)"
-        ns = ctx.func.n_s
-        dout = dout.float()
-        need_p = ctx.mode == "params" and any(ctx.needs_input_grad[7:])
-        dx0, dc, flat = ctx.kept.backward(dout[1:, :, :ns].contiguous(), need_p)
-        gy0 = None
-        if ctx.needs_input_grad[6]:
-            # d/d carried columns: the solve's own, and the share of every output point they were copied to
-            gy0 = dout[0] + torch.cat([dx0, dc + dout[1:, :, ns:].sum(0)], dim=1)
-        gp = T.param_grads(ctx.func, flat) if need_p else [None] * ctx.n_params
-        return (None, None, None, None, None, None, gy0, *gp)
-
-
-class _DenseTileFunction(torch.autograd.Function):
-    """``odeint_dense(step_control="tile")`` as one autograd node over ``ode_traj.AffineTileDense``."""
-
-    @staticmethod
-    def forward(ctx, func, taus, atol, rtol, mode, slots, info, y0, *params):
-        n, ns = y0.shape[0], func.n_s
-        y0 = y0.detach().contiguous()
-        x0, c = y0[:, :ns].contiguous(), y0[:, ns:].contiguous()
-        xs = torch.empty(len(taus), n, ns, dtype=torch.float32, device=y0.device)
-        solve = T.AffineTileDense(func, n, taus, slots, info, mode, atol, rtol, y0.device)
-        solve.forward(x0, c, xs)
-        out = torch.empty(len(taus) + 1, n, y0.shape[1], dtype=torch.float32, device=y0.device)
-        out[0].copy_(y0)
-        out[1:, :, :ns].copy_(xs)
-        # the carried columns, the same at every output point; NaN with the state where a stopped tile emitted nothing
+    def carried(self, xs, c):
+        # the same at every output point; NaN with the state where a stopped tile emitted nothing
         nan = torch.isnan(xs[:, :, :1])
-        out[1:, :, ns:].copy_(torch.where(nan, xs[:, :, :1], c))
-        ctx.func, ctx.mode, ctx.n_params = func, mode, len(params)
-        ctx.kept = solve if mode != "none" else None
-        return out
+        return torch.where(nan, xs[:, :, :1], c)
 
-    @staticmethod
-    def backward(ctx, dout):
-        assert ctx.kept is not None, "odeint_dense: nothing was kept for a backward (the forward ran without gradients)"
-        ns = ctx.func.n_s
-        dout = dout.float()
-        need_p = ctx.mode == "params" and any(ctx.needs_input_grad[8:])
-        dx0, dc, flat = ctx.kept.backward(dout[1:, :, :ns].contiguous(), need_p)
-        gy0 = None
-        if ctx.needs_input_grad[7]:
-            # (_DenseFunction.backward's expression: the solve's own, and the share of every output point)
-            gy0 = dout[0] + torch.cat([dx0, dc + dout[1:, :, ns:].sum(0)], dim=1)
-        gp = T.param_grads(ctx.func, flat) if need_p else [None] * ctx.n_params
-        return (None, None, None, None, None, None, None, gy0, *gp)
+    def backward(self, dout, need_in, need_p):
+        ns = self.ns
+        dx0, dc, flat = self.kept.backward(dout[1:, :, :ns].contiguous(), need_p)
+        if not need_in[0]:
+            return None, flat
+        return self.grad_y0(dout, dx0, dc, dout[1:, :, ns:].sum(0), self.kept), flat
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -375,32 +338,30 @@ def odeint_dense_adjoint(func, y0, t, *, atol=1e-7, rtol=1e-5, adjoint_params=No
             "step kernels refuse these nets — device_loop=%s); the host-driven and stage-by-stage paths emit no interior "
             "points" % (y0.shape[0], sv.fused, sv.device_loop))
     func.refresh_device_weights()
-    return _DenseAdjointFunction.apply(func, sv, taus, _lengths(t), float(atol), float(rtol), with_params, y0,
-                                       *func.parameters())
+    solve = _DenseAdjointSolve(func, sv, taus, _lengths(t), float(atol), float(rtol), with_params)
+    return SolveNode.apply(solve, 1, y0, *func.parameters())
 
 
-class _DenseAdjointFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, func, sv, taus, lengths, atol, rtol, with_params, y0, *params):
-        out, solve = _solve(sv, taus, atol, rtol, y0)
-        # kept: the carried columns and the lengths; the step slots stay the pool's, the output times go with `solve`
-        ctx.func, ctx.sv, ctx.c, ctx.lengths, ctx.solve_id = func, sv, solve.c, lengths, solve.solve_id
-        ctx.with_params, ctx.n_params = with_params, len(params)
-        ctx.save_for_backward(out)
-        return out
+class _DenseAdjointSolve(PackedSolve):
+    """``odeint_dense_adjoint`` as ``ode_node.SolveNode``'s solve: ``odeint_dense``'s forward; kept are the carried
+    columns and the lengths — the step slots stay the pool's, the output times go with the forward."""
+    api, saves_out = "odeint_dense_adjoint", True
 
-    @staticmethod
-    def backward(ctx, dout):
-        sv, ns = ctx.sv, ctx.func.n_s
-        assert sv.stats["solves"] == ctx.solve_id, \
+    def __init__(self, func, sv, taus, lengths, atol, rtol, with_params):
+        PackedSolve.__init__(self, func)
+        self.sv, self.taus, self.lengths, self.tol, self.with_params = sv, taus, lengths, (atol, rtol), with_params
+        self.n_out = len(taus)
+
+    def solve(self, x0, c, xs):
+        self.solve_id = _dense_fwd(self.sv, self.taus, x0, c, *self.tol, xs)[0]
+        self.kept = self.c = c
+
+    def backward(self, dout, need_in, need_p, out):
+        sv, ns = self.sv, self.ns
+        assert sv.stats["solves"] == self.solve_id, \
             "odeint_dense_adjoint: backward must run before the next odeint_dense_adjoint with the same model"
-        out, = ctx.saved_tensors
-        dout = dout.float().contiguous()
-        need_p = ctx.with_params and any(ctx.needs_input_grad[8:])
-        a_x, a_c, theta = sv.backward_adjoint_dense(out, dout, ctx.c, ctx.lengths, need_p)
-        gy0 = None
-        if ctx.needs_input_grad[7]:
-            # the carried columns' output gradients never entered the solve: added here, as odeint_adjoint adds them
-            gy0 = dout[0] + torch.cat([a_x, a_c + dout[1:, :, ns:].sum(0)], dim=1)
-        gp = T.param_grads(ctx.func, theta.clone()) if need_p else [None] * ctx.n_params
-        return (None, None, None, None, None, None, None, gy0, *gp)
+        dout = dout.contiguous()
+        a_x, a_c, theta = sv.backward_adjoint_dense(out, dout, self.c, self.lengths, need_p)
+        # the carried columns' output gradients never entered the solve: added here, as odeint_adjoint adds them
+        gy0 = self.grad_y0(dout, a_x, a_c, dout[1:, :, ns:].sum(0), self) if need_in[0] else None
+        return gy0, theta.clone() if need_p else None

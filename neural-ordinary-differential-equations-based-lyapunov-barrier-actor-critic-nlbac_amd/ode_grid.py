@@ -25,30 +25,32 @@ import torch
 
 from . import ode_traj as T
 from . import rollout
+from .ode_node import PackedSolve, SolveNode
 from .ode_consts import TABLEAU
 
 METHODS = ("euler", "rk4")
 
 
-def _steps_of(t):
-    """The grid's checks; returns the intervals' step sizes as float32 values, each formed exactly as ``odeint`` forms
-    its own: the difference of the two Python floats, then the C float argument."""
+def _steps_of(t, api="odeint_grid"):
+    """The grid's checks, their messages under the entry's name ``api``; returns the intervals' step sizes as float32
+    values, each formed exactly as ``odeint`` forms its own: the difference of the two Python floats, then the C float
+    argument."""
     tt = torch.as_tensor(t).detach()
     if tt.dim() != 1 or tt.numel() < 2:
-        raise ValueError("odeint_grid: t must be 1-D with at least two time points; got shape %s" % (tuple(tt.shape),))
+        raise ValueError("%s: t must be 1-D with at least two time points; got shape %s" % (api, tuple(tt.shape)))
     if tt.is_complex() or tt.dtype == torch.bool:
-        raise TypeError("odeint_grid: t must hold real numbers; got %s" % tt.dtype)
+        raise TypeError("%s: t must hold real numbers; got %s" % (api, tt.dtype))
     times = [float(v) for v in tt.cpu()]
     if not all(math.isfinite(v) for v in times):
-        raise ValueError("odeint_grid: t must be finite; got %r" % (times,))
+        raise ValueError("%s: t must be finite; got %r" % (api, times))
     if all(b < a for a, b in zip(times, times[1:])):
-        raise ValueError("odeint_grid: t is decreasing; integrating backwards in time is out of scope here "
-                         "(t must be strictly increasing)")
+        raise ValueError("%s: t is decreasing; integrating backwards in time is out of scope here "
+                         "(t must be strictly increasing)" % api)
     if not all(b > a for a, b in zip(times, times[1:])):
-        raise ValueError("odeint_grid: t must be strictly increasing (no repeated points); got %r" % (times,))
+        raise ValueError("%s: t must be strictly increasing (no repeated points); got %r" % (api, times))
     hs = [C.c_float(b - a).value for a, b in zip(times, times[1:])]
     if not all(math.isfinite(h) and h > 0.0 for h in hs):
-        raise ValueError("odeint_grid: every grid interval must be a positive finite float32; got %r" % (hs,))
+        raise ValueError("%s: every grid interval must be a positive finite float32; got %r" % (api, hs))
     return tuple(hs)
 
 
@@ -101,6 +103,17 @@ def _sub_grid(t, step_size):
     return tuple(taus), tuple(hs), tuple(ofs), tuple(theta)
 
 
+def _check_y0(api, func, y0):
+    """``y0`` is a float32 tensor (batch, n_s + n_c) = [x | carried columns] (``odeint_grid``'s and ``odeint_dense``'s)."""
+    if not isinstance(y0, torch.Tensor):
+        raise TypeError("%s: y0 must be a tensor; got %s" % (api, type(y0).__name__))
+    if y0.dtype != torch.float32:
+        raise TypeError("%s: y0 must be float32; got %s" % (api, y0.dtype))
+    width = func.n_s + (func.n_u if func.affine else func.n_carry)
+    if y0.dim() != 2 or y0.shape[1] != width or y0.shape[0] < 1:
+        raise ValueError("%s: y0 must be (batch, %d) = [x | carried columns]; got %s" % (api, width, tuple(y0.shape)))
+
+
 def _steps(func, y0, t, method, step_size=None):
     """Every argument check, before anything touches a device; returns the intervals: their step sizes (``_steps_of``),
     or with ``step_size`` what ``_sub_grid`` returns."""
@@ -116,13 +129,7 @@ def _steps(func, y0, t, method, step_size=None):
     if method not in METHODS:
         raise ValueError("odeint_grid: method is one of %s; got %r" % (", ".join(METHODS), method))
     hs = _steps_of(t) if step_size is None else _sub_grid(t, step_size)
-    if not isinstance(y0, torch.Tensor):
-        raise TypeError("odeint_grid: y0 must be a tensor; got %s" % type(y0).__name__)
-    if y0.dtype != torch.float32:
-        raise TypeError("odeint_grid: y0 must be float32; got %s" % y0.dtype)
-    width = func.n_s + (func.n_u if func.affine else func.n_carry)
-    if y0.dim() != 2 or y0.shape[1] != width or y0.shape[0] < 1:
-        raise ValueError("odeint_grid: y0 must be (batch, %d) = [x | carried columns]; got %s" % (width, tuple(y0.shape)))
+    _check_y0("odeint_grid", func, y0)
     if step_size is not None and len(hs[1]) * len(TABLEAU[method]["c_sol"]) * y0.shape[0] >= 2 ** 31:
         raise ValueError("odeint_grid: %d fine intervals x %d stages x %d rows is 2^31 or more (the launch's limit); "
                          "use a larger step_size or fewer rows" % (len(hs[1]), len(TABLEAU[method]["c_sol"]), y0.shape[0]))
@@ -183,80 +190,34 @@ def odeint_grid(func, y0, t, *, method="rk4", step_size=None, adjoint=False, adj
     params = tuple(func.parameters())
     mode = T.keep_mode(params, y0)
     func.refresh_device_weights()
-    if adjoint:
-        plan = T.AdjointPlan(_adjoint_steps(t, step_size), False, adjoint_chunk, step_size is not None)
-        return _GridAdjointFunction.apply(func, method, hs, mode, plan, y0, *params)
-    return _GridFunction.apply(func, method, hs, mode, y0, *params)
+    plan = T.AdjointPlan(_adjoint_steps(t, step_size), False, adjoint_chunk, step_size is not None) if adjoint else None
+    return SolveNode.apply(_GridSolve(func, method, hs, mode, plan, y0.device), 1, y0, *params)
 
 
-class _GridFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, func, method, hs, mode, y0, *params):
-        n, ns = y0.shape[0], func.n_s
-        y0 = y0.detach().contiguous()
-        x0, c = y0[:, :ns].contiguous(), y0[:, ns:].contiguous()
-        dev = y0.device
+class _GridSolve(PackedSolve):
+    """One solve on a time grid as ``ode_node.SolveNode``'s solve: direct, or with an ``AdjointPlan`` the continuous
+    adjoint — what is saved for the backward is then ``out`` (as a saved tensor); the carried columns are read from it."""
+    api = "odeint_grid"
+
+    def __init__(self, func, method, hs, mode, plan, device):
+        PackedSolve.__init__(self, func)
         # (hs: the intervals' steps, or with step_size _sub_grid's (fine times, steps, offsets, weights))
-        iv = T.SubGridSteps(*hs[1:], dev) if isinstance(hs[0], tuple) else T.GridSteps(hs, dev)
-        H = iv.n_out
-        xs = torch.empty(H, n, ns, dtype=torch.float32, device=dev)        # the states at the output points 1 .. H
-        ctx.func, ctx.mode, ctx.n_params, ctx.iv = func, mode, len(params), iv
-        ctx.kept = T.solve(func, iv, method, mode, rollout._one_launch_ok(func, method), x0, c, xs)
-        out = torch.empty(H + 1, n, y0.shape[1], dtype=torch.float32, device=dev)
-        out[0].copy_(y0)
-        out[1:, :, :ns].copy_(xs)
-        out[1:, :, ns:].copy_(c)          # (the carried columns, the same at every grid point)
-        return out
+        self.iv = T.SubGridSteps(*hs[1:], device) if isinstance(hs[0], tuple) else T.GridSteps(hs, device)
+        self.n_out, self.method, self.mode, self.plan = self.iv.n_out, method, mode, plan
+        self.with_params, self.saves_out = mode == "params", plan is not None
 
-    @staticmethod
-    def backward(ctx, dout):
-        assert ctx.kept is not None, "odeint_grid: nothing was kept for a backward (the forward ran without gradients)"
-        ns = ctx.func.n_s
-        dout = dout.float()
-        need_p = ctx.mode == "params" and any(ctx.needs_input_grad[5:])
-        dx0, dc, flat = ctx.kept.backward(dout[:, :, :ns].contiguous(), need_p)
-        gy0 = None
-        if ctx.needs_input_grad[4]:
-            # d/d carried columns: out[0]'s share, then per interval its control gradient (summed k = H-1 .. 0 by the
-            # backward) and every later output point's share
-            gy0 = torch.cat([dx0, dout[0][:, ns:] + (dc + ctx.iv.sum_copied(dout[1:, :, ns:]))], dim=1)
-        gp = T.param_grads(ctx.func, flat) if need_p else [None] * ctx.n_params
-        return (None, None, None, None, gy0, *gp)
+    def solve(self, x0, c, xs):
+        func, one = self.func, rollout._one_launch_ok(self.func, self.method)
+        if self.plan is None:
+            self.kept = T.solve(func, self.iv, self.method, self.mode, one, x0, c, xs)
+        else:
+            self.kept = T.solve_adjoint(func, self.iv, self.method, self.mode, one, self.plan, x0, c, xs)
 
-
-class _GridAdjointFunction(torch.autograd.Function):
-    """``odeint_grid(adjoint=True)``: what is saved for the backward is ``out`` (as a saved tensor); the carried columns
-    are read from it."""
-
-    @staticmethod
-    def forward(ctx, func, method, hs, mode, plan, y0, *params):
-        n, ns = y0.shape[0], func.n_s
-        y0 = y0.detach().contiguous()
-        x0, c = y0[:, :ns].contiguous(), y0[:, ns:].contiguous()
-        dev = y0.device
-        iv = T.SubGridSteps(*hs[1:], dev) if isinstance(hs[0], tuple) else T.GridSteps(hs, dev)
-        H = iv.n_out
-        xs = torch.empty(H, n, ns, dtype=torch.float32, device=dev)
-        ctx.func, ctx.mode, ctx.n_params, ctx.iv = func, mode, len(params), iv
-        ctx.kept = T.solve_adjoint(func, iv, method, mode, rollout._one_launch_ok(func, method), plan, x0, c, xs)
-        out = torch.empty(H + 1, n, y0.shape[1], dtype=torch.float32, device=dev)
-        out[0].copy_(y0)
-        out[1:, :, :ns].copy_(xs)
-        out[1:, :, ns:].copy_(c)
-        if ctx.kept is not None:
-            ctx.save_for_backward(out)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        assert ctx.kept is not None, "odeint_grid: nothing was kept for a backward (the forward ran without gradients)"
-        out, = ctx.saved_tensors
-        ns = ctx.func.n_s
-        dout = dout.float()
-        need_p = ctx.mode == "params" and any(ctx.needs_input_grad[6:])
-        dx0, dc, flat = ctx.kept.backward(out, dout[:, :, :ns].contiguous(), need_p)
-        gy0 = None
-        if ctx.needs_input_grad[5]:
-            gy0 = torch.cat([dx0, dout[0][:, ns:] + (dc + ctx.iv.sum_copied(dout[1:, :, ns:]))], dim=1)
-        gp = T.param_grads(ctx.func, flat) if need_p else [None] * ctx.n_params
-        return (None, None, None, None, None, gy0, *gp)
+    def backward(self, dout, need_in, need_p, out=None):
+        ns = self.ns
+        dx0, dc, flat = self.kept.backward(dout[:, :, :ns].contiguous(), need_p, out=out)
+        if not need_in[0]:
+            return None, flat
+        # d/d carried columns: out[0]'s share, then per interval its control gradient (summed k = H-1 .. 0 by the
+        # backward) and every later output point's share
+        return self.grad_y0(dout, dx0, dc, self.iv.sum_copied(dout[1:, :, ns:]), self.kept), flat

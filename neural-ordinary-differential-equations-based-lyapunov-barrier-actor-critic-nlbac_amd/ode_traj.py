@@ -7,8 +7,8 @@
     controls' gradient looks like, where the outputs and their gradients meet the intervals;
   * what a solve keeps and how its backward becomes gradients, one class per path — ``AffineTraj`` / ``ConcatTraj`` (one
     launch forward, one backward, + the weight-gradient launch over all H * stages * rows) and ``Chain`` (H one-interval
-    solves on the existing solvers) — each with ``forward(x0, u, xs)`` and ``backward(dout, need_p)``; ``solve`` picks;
-    beside them dopri5 under tile-local step control, one launch each way over step slots: ``AffineTile`` owns what such
+    solves on the existing solvers) — each with ``forward(x0, u, xs)`` and ``backward(dout, need_p, out=None)``;
+    ``solve`` picks; beside them dopri5 under tile-local step control, one launch each way over step slots: ``AffineTile`` owns what such
     a solve keeps, the look at its status in front of a backward and its weight gradients; its leaves their own arrays
     and launches — ``AffineTileDopri`` for ``TileSteps`` (``rollout(step_control="tile")``), ``AffineTileDense`` for one
     dense solve per tile read at every point of a time grid (``ode_dense.odeint_dense(step_control="tile")``); every
@@ -16,7 +16,7 @@
   * the same under ``adjoint=True`` (``solve_adjoint``): nothing kept but the outputs the caller holds and the controls —
     ``AdjointPlan`` (per output interval the fine steps of its backward solve, the chunk), ``AffineAdjTraj`` /
     ``ConcatAdjTraj`` (the continuous adjoint over the whole horizon in one ``nlbac_*_adj_traj`` launch per chunk),
-    ``ChainAdjoint`` / ``ChainSubAdjoint`` (chained), each with ``backward(out, dout, need_p)``.
+    ``Chain(adjoint=True)`` / ``ChainSubAdjoint`` (chained); the same ``backward``, which here needs ``out``.
 """
 import ctypes as C
 
@@ -26,6 +26,7 @@ from . import _lib
 from ._lib import fptr
 from .arena import bwd_weights, io_array, mlp_array, stream_ptr
 from .ode_consts import DP_C_ERR, TABLEAU, env_switch
+from .ode_node import _reduce
 from .odeint import AffineNodeSolver, ConcatNodeSolver
 
 
@@ -246,12 +247,6 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
-def _reduce(arena, used):
-    flat = torch.empty(arena.n, dtype=torch.float32, device=arena.device)
-    _lib.call("nlbac_reduce_slabs", flat.data_ptr(), arena.grad.data_ptr(), used, arena.n, arena.n, stream_ptr())
-    return flat
-
-
 def _kept_acts(f, g, rows, mode, alloc):
     """What the control-affine form keeps of the hidden layers over ``rows`` stage rows (stages * n), from ``alloc``:
     (acts_bits, the two nets' buffers, their layer strides)."""
@@ -299,15 +294,10 @@ def _concat_weight_grads(net, xin, in_dim, dy, acts, acts_ls, dz, rows, dev):
     return _reduce(arena, arena.n_slabs)
 
 
-def param_grads(func, flat):
-    """The flat arena gradient as one view per parameter, in ``func.parameters()``'s order."""
-    arena = func.device_handles()[0].arena
-    return [flat[arena.offset_of[id(p)]:arena.offset_of[id(p)] + p.numel()].view(p.shape) for p in func.parameters()]
-
-
 class AffineTraj:
     """Device buffers of one one-launch solve of the control-affine NODE: step-major [k][stage][row] over H * S stages."""
     Solver = AffineNodeSolver
+    dx0_total = True      # ``backward`` takes all of dout and returns dx0 with dout[0] inside (``ode_node.PackedSolve.grad_y0``)
 
     @staticmethod
     def ok(func):
@@ -332,7 +322,7 @@ class AffineTraj:
                   xs.data_ptr(), self.K.data_ptr(), self.Y.data_ptr(), self.G.data_ptr(), _ptr(self.acts[0]), self.ls[0],
                   _ptr(self.acts[1]), self.ls[1], self.bits, stream_ptr())
 
-    def backward(self, dout, need_p):
+    def backward(self, dout, need_p, out=None):
         n, H, S, HS = self.n, self.iv.launch_H, self.S, self.H * self.S      # (H: the launch's; HS: the stages kept)
         dev = dout.device
         z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
@@ -357,6 +347,7 @@ class ConcatTraj:
     nothing without gradients, the three layers' mask words for input gradients, activation rows and the stage-input
     rows layer 0 saw ([Y_st | c_k], normalised when the net is) for parameter gradients."""
     Solver = ConcatNodeSolver
+    dx0_total = True
 
     @staticmethod
     def ok(func):
@@ -383,7 +374,7 @@ class ConcatTraj:
                   self.iv.launch_H, self.S, self.beta, self.c_out, *self.iv.step_args(), xs.data_ptr(), _ptr(self.Xin),
                   _ptr(self.acts), self.ls, self.bits, _ptr(self.norm), stream_ptr())
 
-    def backward(self, dout, need_p):
+    def backward(self, dout, need_p, out=None):
         n, H, S, HS = self.n, self.iv.launch_H, self.S, self.H * self.S      # (H: the launch's; HS: the stages kept)
         dev = dout.device
         z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
@@ -472,7 +463,7 @@ class AffineTile:
         if self.info is not None:
             self.info.update(accepted=self.accepted, attempts=self.attempts, status=self.status)
 
-    def backward(self, dout, need_p):
+    def backward(self, dout, need_p, out=None):
         """``dout``: the outputs' gradients as the leaf's launch takes them.  Returns (dx0: the first step's dy0, the
         controls' gradient, the flat parameter gradient or None)."""
         dev = dout.device
@@ -553,6 +544,7 @@ class AffineTileDense(AffineTile):
     its abscissa (``ov_slot`` / ``ov_x``).  ``backward`` takes dxs (T - 1, n, n_s): d loss / d out[1:] on the state
     columns."""
     api, words = "odeint_dense", ("", "32")
+    dx0_total = False     # (``backward`` takes dout[1:]: dout[0] is added behind it)
 
     def __init__(self, func, n, taus, max_steps, info, mode, atol, rtol, device):
         AffineTile.__init__(self, func, n, (), max_steps, info, mode, atol, rtol, device)
@@ -590,6 +582,7 @@ class Chain:
     """The chained path: H one-interval solves on the existing solvers, cached on the model under the intervals'
     ``solvers_key`` (apart from ``odeint``'s and any agent task's): one solver per interval when a backward follows (each
     keeps its interval's state), one for all intervals otherwise."""
+    dx0_total = True
 
     def __init__(self, func, n, iv, method, mode, atol, rtol, adjoint=False):
         # (adjoint: solvers of their own whose backward is the continuous adjoint of their interval — the chain of
@@ -610,7 +603,7 @@ class Chain:
             x = iv.emit(xs, k, x, sv.forward(x, iv.control(u, k), 1, self.n, self.method, iv.step(k), *self.tol))
         self.solve_ids = [sv.stats["solves"] for sv in self.svs]
 
-    def backward(self, dout, need_p):
+    def backward(self, dout, need_p, out=None):
         iv, svs = self.iv, self.svs
         assert all(sv.stats["solves"] == i for sv, i in zip(svs, self.solve_ids)), \
             "%s: backward must run before the next %s of the same shape and mode with the same model" % (iv.api, iv.api)
@@ -695,6 +688,7 @@ class _AdjTraj:
     run, a carry row handing z = [y | a_x | a_c] from run to run — and, with parameter gradients, one
     ``nlbac_mlp_bwd_weights`` + ``nlbac_reduce_slabs`` per run over what the launch kept of every stage, the runs'
     flat gradients summed last run first.  Kept buffers are sized by the chunk, not by the horizon."""
+    dx0_total = True
 
     def __init__(self, func, n, iv, method, plan, device):
         self.func, self.n, self.iv, self.method, self.plan, self.device = func, n, iv, method, plan, device
@@ -715,7 +709,7 @@ class _AdjTraj:
                                           (C.c_int * len(begin))(*begin), len(hs))
         return a
 
-    def backward(self, out, dout, need_p):
+    def backward(self, dout, need_p, out):
         n, ns, nc, S, plan, dev = self.n, self.ns, self.nc, self.S, self.plan, self.device
         W = 2 * ns + nc
         z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
@@ -816,22 +810,12 @@ def adj_traj_class(func):
     return AffineAdjTraj if func.affine else ConcatAdjTraj
 
 
-class ChainAdjoint(Chain):
-    """The chained path of ``adjoint=True`` without ``step_size`` (dopri5, shapes the kernels refuse, ``ONE_LAUNCH =
-    False``): ``Chain`` with the continuous adjoint on its solvers — H one-interval ``odeint_adjoint`` solves."""
-
-    def __init__(self, func, n, iv, method, mode, atol, rtol):
-        Chain.__init__(self, func, n, iv, method, mode, atol, rtol, adjoint=True)
-
-    def backward(self, out, dout, need_p):
-        return Chain.backward(self, dout, need_p)
-
-
 class ChainSubAdjoint:
     """The chained path of ``adjoint=True`` with ``step_size``: the forward is the chained forward without gradients;
     the backward solves every output interval backwards on its own fine grid with one ``nlbac_*_adj_step`` launch per
     fine step (``ode_adjoint.AffineAdjoint.adjoint_interval``) on one solver, cached on the model under a key of its
     own.  Its dx0 and controls' gradient are the one-launch path's bit for bit."""
+    dx0_total = True
 
     def __init__(self, func, n, iv, method, plan, atol, rtol):
         self.func, self.n, self.iv, self.method, self.plan, self.tol = func, n, iv, method, plan, (atol, rtol)
@@ -840,7 +824,7 @@ class ChainSubAdjoint:
         self.u = u
         Chain(self.func, self.n, self.iv, self.method, "none", *self.tol).forward(x0, u, xs)
 
-    def backward(self, out, dout, need_p):
+    def backward(self, dout, need_p, out):
         func, plan, ns = self.func, self.plan, self.func.n_s
         sv = func.__dict__.get("_grid_adjoint_solver")
         if sv is None:
@@ -864,7 +848,7 @@ class ChainSubAdjoint:
 
 def solve_adjoint(func, iv, method, mode, one_launch, plan, x0, u, xs, atol=1e-7, rtol=1e-5):
     """``solve`` under ``adjoint=True``: the same forward values, nothing kept for the backward but what the caller
-    holds — returns an object whose ``backward(out, dout, need_p)`` takes the forward's stored outputs
+    holds — returns an object whose ``backward(dout, need_p, out=out)`` takes the forward's stored outputs
     (plan.H + 1, n, >= n_s: the state in the first n_s columns) and gives what ``solve``'s does, or None without
     gradients.  ``one_launch``: the direct path's answer; the adjoint launch must serve the nets as well."""
     n = x0.shape[0]
@@ -875,8 +859,8 @@ def solve_adjoint(func, iv, method, mode, one_launch, plan, x0, u, xs, atol=1e-7
         kept = adj_traj_class(func)(func, n, iv, method, plan, x0.device)
     elif plan.sub:
         kept = ChainSubAdjoint(func, n, iv, method, plan, atol, rtol)
-    else:
-        kept = ChainAdjoint(func, n, iv, method, mode, atol, rtol)
+    else:      # (dopri5, shapes the kernels refuse, ``ONE_LAUNCH = False``: H one-interval ``odeint_adjoint`` solves)
+        kept = Chain(func, n, iv, method, mode, atol, rtol, adjoint=True)
     kept.forward(x0, u, xs)
     return kept
 

@@ -33,6 +33,7 @@ from .ode_adjoint import AffineAdjoint, ConcatAdjoint
 from .ode_consts import CTL_HUSED, DP_BETA, NORM_DEFER_ATTEMPT, TABLEAU, ctl_field_ptr, env_switch
 from .ode_ctl import ControlBlockReader
 from .ode_dopri import DopriDriver
+from .ode_node import PackedSolve, SolveNode, _reduce
 from .ode_workspace import SolverWorkspaces, _ConcatStepWS, _StepWS
 
 
@@ -642,42 +643,35 @@ def _solver_of(func, adjoint=False):
     return sv
 
 
-class _OdeintFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, func, method, dt, atol, rtol, adjoint, y0, *params):
-        sv = _solver_of(func, bool(adjoint))
+class _OdeintSolve(PackedSolve):
+    """``odeint`` / ``odeint_adjoint`` over [t0, t0 + dt] as ``ode_node.SolveNode``'s solve: what is kept is the cached
+    solver, which holds one solve's state.  ``adjoint``: False, or "params" / "no-params" (``adjoint_params=()``)."""
+    api = "odeint"
+
+    def __init__(self, func, method, dt, atol, rtol, adjoint):
+        PackedSolve.__init__(self, func)
+        self.args, self.adjoint, self.with_params = (method, dt, atol, rtol), bool(adjoint), adjoint != "no-params"
+
+    def forward(self, y0):
+        sv = self.kept = _solver_of(self.func, self.adjoint)
         ns, nu = sv.n_s, sv.n_u
         assert y0.dim() == 2 and y0.shape[1] == ns + nu, "y0 must be (batch, %d)" % (ns + nu)
-        y0 = y0.detach().float().contiguous()
-        x0, u = y0[:, :ns].contiguous(), y0[:, ns:].contiguous()
-        x1 = sv.forward(x0, u, 1, y0.shape[0], method, dt, atol, rtol)
-        ctx.func, ctx.sv, ctx.n_params = func, sv, len(params)
-        ctx.solve_id = sv.stats["solves"]
-        ctx.with_params = adjoint != "no-params"
+        y0, x0, u = self.split(y0.float())
+        x1 = sv.forward(x0, u, 1, y0.shape[0], *self.args)
+        self.solve_id = sv.stats["solves"]
         return torch.stack([y0, torch.cat([x1, u], dim=1)])
 
-    @staticmethod
-    def backward(ctx, g):
-        sv, func = ctx.sv, ctx.func
-        assert sv.stats["solves"] == ctx.solve_id, \
+    def backward(self, g, need_in, need_p):
+        sv, ns = self.kept, self.ns
+        assert sv.stats["solves"] == self.solve_id, \
             "odeint: backward must run before the next solve with the same model (the solver keeps one solve's state)"
-        ns = sv.n_s
-        g = g.float()
-        need_p = any(ctx.needs_input_grad[7:]) and ctx.with_params
         du, dy0 = sv.backward(g[1][:, :ns].contiguous(), need_du=True, need_params=need_p, need_dy0=True)
-        gy0 = g[0] + torch.cat([dy0, du + g[1][:, ns:]], dim=1) if ctx.needs_input_grad[6] else None
-        gp = [None] * ctx.n_params
-        if need_p:
-            arena = func.device_handles()[0].arena
-            n_steps = max(1, len(sv.ctx.get("steps") or [None]))
-            used = sv.accumulate_param_grads(arena, max(1, arena.n_slabs // n_steps))
-            flat = torch.empty(arena.n, dtype=torch.float32, device=arena.device)
-            _lib.call("nlbac_reduce_slabs", flat.data_ptr(), arena.grad.data_ptr(), used, arena.n, arena.n, stream_ptr())
-            gp = []
-            for p in func.parameters():
-                off = arena.offset_of[id(p)]
-                gp.append(flat[off:off + p.numel()].view(p.shape))
-        return (None, None, None, None, None, None, gy0, *gp)
+        gy0 = self.grad_y0(g, dy0, du, g[1][:, ns:], self) if need_in[0] else None
+        if not need_p:
+            return gy0, None
+        arena = self.func.device_handles()[0].arena
+        n_steps = max(1, len(sv.ctx.get("steps") or [None]))
+        return gy0, _reduce(arena, sv.accumulate_param_grads(arena, max(1, arena.n_slabs // n_steps)))
 
 
 def _odeint(func, y0, t, method, atol, rtol, adjoint, options):
@@ -713,7 +707,7 @@ def _odeint(func, y0, t, method, atol, rtol, adjoint, options):
                                   % t.numel())
     dt = float(t[1]) - float(t[0])
     func.refresh_device_weights()
-    return _OdeintFunction.apply(func, method, dt, float(atol), float(rtol), adjoint, y0, *func.parameters())
+    return SolveNode.apply(_OdeintSolve(func, method, dt, float(atol), float(rtol), adjoint), 1, y0, *func.parameters())
 
 
 def odeint(func, y0, t, *, method="dopri5", atol=1e-7, rtol=1e-5, **options):

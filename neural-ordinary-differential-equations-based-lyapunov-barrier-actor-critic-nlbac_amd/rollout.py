@@ -24,6 +24,7 @@ import os
 import torch
 
 from . import ode_traj as T
+from .ode_node import SolveNode
 
 ONE_LAUNCH = os.environ.get("NLBAC_ROLLOUT_ONE_LAUNCH", "1") != "0"
 METHODS = ("euler", "rk4", "dopri5")
@@ -202,73 +203,44 @@ def rollout(func, x0, controls, dt, *, method="rk4", atol=1e-7, rtol=1e-5, step_
     params = tuple(func.parameters())
     mode = T.keep_mode(params, x0, controls)
     func.refresh_device_weights()
+    H, plan = controls.shape[0], None
     if slots is not None:
-        iv = T.TileSteps(dt, controls.shape[0], slots, info)
-        return _RolloutFunction.apply(func, method, iv, float(atol), float(rtol), mode, x0, controls, *params)
-    if adjoint:
-        return _RolloutAdjointFunction.apply(func, method, dt if hs is None else hs, float(atol), float(rtol), mode,
-                                             adjoint_chunk, x0, controls, *params)
-    return _RolloutFunction.apply(func, method, dt if hs is None else hs, float(atol), float(rtol), mode, x0, controls,
-                                  *params)
+        iv = T.TileSteps(dt, H, slots, info)
+    else:
+        iv = T.EqualSteps(dt, H) if hs is None else T.HeldSteps(hs, H, x0.device)
+        if adjoint:
+            plan = T.AdjointPlan([(dt,) if hs is None else hs] * H, True, adjoint_chunk, hs is not None)
+    solve = _RolloutSolve(func, method, iv, float(atol), float(rtol), mode, plan)
+    return SolveNode.apply(solve, 2, x0, controls, *params)
 
 
 def _one_launch_ok(func, method):
     return bool(ONE_LAUNCH and method in ("euler", "rk4") and T.traj_class(func).ok(func))
 
 
-class _RolloutFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, func, method, dt, atol, rtol, mode, x0, controls, *params):
-        # (dt: the interval, or with step_size the fine steps of a control interval)
-        H, n, ns = controls.shape[0], x0.shape[0], func.n_s
-        x0 = x0.detach().contiguous()
-        u = controls.detach().contiguous()
-        out = torch.empty(H + 1, n, ns, dtype=torch.float32, device=x0.device)
+class _RolloutSolve:
+    """One rollout as ``ode_node.SolveNode``'s solve, inputs (x0, controls): direct, with an ``AdjointPlan`` the
+    continuous adjoint — what is saved for the backward is then ``out`` (as a saved tensor) and the controls — and with
+    ``TileSteps`` dopri5 under tile-local step control (always one launch)."""
+    api = "rollout"
+
+    def __init__(self, func, method, iv, atol, rtol, mode, plan=None):
+        self.func, self.method, self.iv, self.tol, self.mode, self.plan = func, method, iv, (atol, rtol), mode, plan
+        self.with_params, self.saves_out, self.kept = mode == "params", plan is not None, None
+
+    def forward(self, x0, controls):
+        func, iv, H = self.func, self.iv, controls.shape[0]
+        x0, u = x0.contiguous(), controls.contiguous()
+        out = torch.empty(H + 1, x0.shape[0], func.n_s, dtype=torch.float32, device=x0.device)
         first = out[0].copy_(x0)
-        ctx.func, ctx.mode, ctx.n_params = func, mode, len(params)
-        tile = isinstance(dt, T.TileSteps)      # (the intervals under tile-local step control: always one launch)
-        one = tile or _one_launch_ok(func, method)
+        one = isinstance(iv, T.TileSteps) or _one_launch_ok(func, self.method)
         # (the one launch reads x0 where the caller's tensor is; the chain's first solver keeps a reference, to out[0])
-        iv = dt if tile else (T.HeldSteps(dt, H, x0.device) if isinstance(dt, tuple) else T.EqualSteps(dt, H))
-        ctx.kept = T.solve(func, iv, method, mode, one, x0 if one else first, u, out.narrow(0, 1, H), atol, rtol)
+        args = (x0 if one else first, u, out.narrow(0, 1, H), *self.tol)
+        if self.plan is None:
+            self.kept = T.solve(func, iv, self.method, self.mode, one, *args)
+        else:
+            self.kept = T.solve_adjoint(func, iv, self.method, self.mode, one, self.plan, *args)
         return out
 
-    @staticmethod
-    def backward(ctx, dout):
-        assert ctx.kept is not None, "rollout: nothing was kept for a backward (the forward ran without gradients)"
-        need_p = ctx.mode == "params" and any(ctx.needs_input_grad[8:])
-        dx0, du, flat = ctx.kept.backward(dout.float().contiguous(), need_p)
-        gp = T.param_grads(ctx.func, flat) if need_p else [None] * ctx.n_params
-        return (None, None, None, None, None, None, dx0 if ctx.needs_input_grad[6] else None,
-                du if ctx.needs_input_grad[7] else None, *gp)
-
-
-class _RolloutAdjointFunction(torch.autograd.Function):
-    """``rollout(adjoint=True)``: what is saved for the backward is ``out`` (as a saved tensor) and the controls."""
-
-    @staticmethod
-    def forward(ctx, func, method, dt, atol, rtol, mode, chunk, x0, controls, *params):
-        H, n, ns = controls.shape[0], x0.shape[0], func.n_s
-        x0 = x0.detach().contiguous()
-        u = controls.detach().contiguous()
-        out = torch.empty(H + 1, n, ns, dtype=torch.float32, device=x0.device)
-        first = out[0].copy_(x0)
-        ctx.func, ctx.mode, ctx.n_params = func, mode, len(params)
-        one = _one_launch_ok(func, method)
-        sub = isinstance(dt, tuple)
-        iv = T.HeldSteps(dt, H, x0.device) if sub else T.EqualSteps(dt, H)
-        plan = T.AdjointPlan([dt if sub else (dt,)] * H, True, chunk, sub)
-        ctx.kept = T.solve_adjoint(func, iv, method, mode, one, plan, x0 if one else first, u, out.narrow(0, 1, H), atol, rtol)
-        if ctx.kept is not None:
-            ctx.save_for_backward(out)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        assert ctx.kept is not None, "rollout: nothing was kept for a backward (the forward ran without gradients)"
-        out, = ctx.saved_tensors
-        need_p = ctx.mode == "params" and any(ctx.needs_input_grad[9:])
-        dx0, du, flat = ctx.kept.backward(out, dout.float().contiguous(), need_p)
-        gp = T.param_grads(ctx.func, flat) if need_p else [None] * ctx.n_params
-        return (None, None, None, None, None, None, None, dx0 if ctx.needs_input_grad[7] else None,
-                du if ctx.needs_input_grad[8] else None, *gp)
+    def backward(self, dout, need_in, need_p, out=None):
+        return self.kept.backward(dout.contiguous(), need_p, out=out)

@@ -125,8 +125,9 @@ class Reached(Exception):
 
 
 def test_batch_is_the_call_as_it_was(monkeypatch):
-    """The default call and ``step_control="batch"`` hand ``_DenseFunction.apply`` exactly today's arguments: the model,
-    the cached solver of the keep mode, the output times, the tolerances, the mode, ``y0`` and the parameters."""
+    """The default call and ``step_control="batch"`` hand ``SolveNode.apply`` exactly what they handed
+    ``_DenseFunction.apply``: in the batch solve's object the model, the cached solver of the keep mode, the output times,
+    the tolerances and the mode; then ``y0`` and the parameters."""
     from nlbac_amd import ode_dense as OD
     m = model()
     seen = []
@@ -143,12 +144,12 @@ def test_batch_is_the_call_as_it_was(monkeypatch):
         seen.append(a)
         raise Reached
 
-    monkeypatch.setattr(OD._DenseFunction, "apply", staticmethod(apply))
+    monkeypatch.setattr(OD.SolveNode, "apply", staticmethod(apply))
     monkeypatch.setattr(OD, "solver_of", lambda func, mode: (sv, seen.append(("solver_of", func, mode)))[0])
     monkeypatch.setattr(OD, "_check_device", lambda y0: None)
     monkeypatch.setattr(type(m), "refresh_device_weights", lambda self: seen.append(("refresh", self)))
     monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
-    monkeypatch.setattr(OD._DenseTileFunction, "apply", staticmethod(lambda *a: pytest.fail("the tile path was taken")))
+    monkeypatch.setattr(OD, "_DenseTileSolve", lambda *a: pytest.fail("the tile path was taken"))
     y0 = torch.rand(4, 5, generator=torch.Generator().manual_seed(1)).requires_grad_()
     for kw in ({}, dict(step_control="batch")):
         with pytest.raises(Reached):
@@ -157,9 +158,11 @@ def test_batch_is_the_call_as_it_was(monkeypatch):
     for k in (0, 3):
         assert seen[k] == ("solver_of", m, "params") and seen[k + 1] == ("refresh", m)
         a = seen[k + 2]
-        assert a[0] is m and a[1] is sv and a[2] == OD._taus(GRID) and a[3:6] == (1e-6, 1e-4, "params")
-        assert a[6] is y0 and len(a) == 7 + len(list(m.parameters()))
-        assert all(p is q for p, q in zip(a[7:], m.parameters()))
+        solve = a[0]
+        assert type(solve) is OD._DenseSolve and solve.func is m and solve.sv is sv and solve.taus == OD._taus(GRID)
+        assert (solve.tol, solve.mode) == ((1e-6, 1e-4), "params")
+        assert a[1] == 1 and a[2] is y0 and len(a) == 3 + len(list(m.parameters()))
+        assert all(p is q for p, q in zip(a[3:], m.parameters()))
 
 
 def test_tile_reaches_the_tile_solve_and_leaves_the_cached_solvers_alone(monkeypatch):
@@ -171,7 +174,7 @@ def test_tile_reaches_the_tile_solve_and_leaves_the_cached_solvers_alone(monkeyp
         seen.append(a)
         raise Reached
 
-    monkeypatch.setattr(OD._DenseTileFunction, "apply", staticmethod(apply))
+    monkeypatch.setattr(OD.SolveNode, "apply", staticmethod(apply))
     monkeypatch.setattr(OD, "solver_of", lambda func, mode: pytest.fail("the batch path's solvers were asked for"))
     monkeypatch.setattr(OD, "_check_device", lambda y0: None)
     monkeypatch.setattr(type(m), "refresh_device_weights", lambda self: None)
@@ -182,8 +185,10 @@ def test_tile_reaches_the_tile_solve_and_leaves_the_cached_solvers_alone(monkeyp
         with pytest.raises(Reached):
             OD.odeint_dense(m, y0, GRID, step_control="tile", max_steps=max_steps, info=info)
         a = seen[-1]
-        assert a[0] is m and a[1] == OD._taus(GRID) and a[2:4] == (1e-7, 1e-5) and a[4] == "params"
-        assert a[5] == want and a[6] is info and a[7] is y0
+        solve = a[0]
+        assert type(solve) is OD._DenseTileSolve and solve.func is m and solve.taus == OD._taus(GRID)
+        assert (solve.tol, solve.mode) == ((1e-7, 1e-5), "params")
+        assert solve.slots == want and solve.info is info and a[1] == 1 and a[2] is y0
     assert OD.SOLVERS_KEY not in m.__dict__
 
 

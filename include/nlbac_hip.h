@@ -1088,6 +1088,78 @@ int nlbac_cars_env_step(int n, const double *params /* dt, kp, k_brake, should_k
                         double *obs /*(n,10)*/, double *reward, double *constraint, double *lya_pre /*(n,4)*/,
                         double *lya_next /*(n,4)*/, int *done, double *info, nlbac_stream_t s);
 
+/* ------------------------------------------------------------------------
+ * Backup-controller hand-over of the vectorised driver (train.train_vectorized(handover=...)): lane i is the loop of
+ * train.train for one environment as far as controllers and replays go (U/main.py:39-142, C/main.py:41-112,
+ * P/main.py:40-200; train._UnicycleHandover / _CarsHandover / _PvtolHandover on the host).  Float64 on the simulators'
+ * float64 outputs, the host classes' operations in their order, every product and sum rounded on its own.  (Added
+ * without an ABI bump: new entry points and structs only.)
+ * ---------------------------------------------------------------------- */
+#define NLBAC_HANDOVER_RING 40  /* depth of a lane's position ring: the largest look-back */
+#define NLBAC_HANDOVER_ISTATE 9 /* int32 words of state per lane */
+typedef struct nlbac_handover_params { /* filled from the attributes of the host classes (vector_handover.params_for) */
+    int kind;                   /* 0 Unicycle, 1 SimulatedCars, 2 Pvtol */
+    int first_backup_episode;   /* hand-over is allowed from this episode (finished episodes of the lane) on */
+    int min_check_step;         /* no check before this episode step (50); >= lookback */
+    int lookback;               /* `moved` compares the position with the one lookback - 1 steps earlier (40) */
+    int memory_t_shift;         /* stamps of the controller replay: (k + shift) dt, (k + 1 + shift) dt */
+    int checks;                 /* Unicycle / Pvtol: checks in a row that find the lane stuck / trapped before hand-over (8) */
+    int max_backup;             /* cap on backup steps: Unicycle 30, SimulatedCars 15, Pvtol (trapped) 30 */
+    int min_backup;             /* SimulatedCars: backup steps before open gaps hand back (5) */
+    int run_checks;             /* Pvtol: checks that find it running away before hand-over (1) */
+    int run_max_backup;         /* Pvtol: cap on backup steps of the running-away hand-over (15) */
+    double stuck2;              /* moved^2 at or below which a check counts: Unicycle 0.01, Pvtol 0.015 */
+    double away2;               /* distance^2 from the hand-over point that hands back: Unicycle 0.6, Pvtol 1.0 */
+    double gap;                 /* SimulatedCars: the gap (of 100 obs, metres) 2.5 */
+    double x_mid;               /* Pvtol: the side of the goal, x against 4.5 */
+    double back_frac;           /* Pvtol: hands back within back_frac operator_dist (0.9) */
+    double operator_dist;       /* Pvtol: env.operator_dist */
+} nlbac_handover_params;
+typedef struct nlbac_row_layout { /* columns of a minibatch row (update_plan._Layout), in floats */
+    int obs_dim, act_dim, lya_dim, ld;
+    int obs, act, rew, con, lya, nlya, nobs, mask, t, nt;
+} nlbac_row_layout;
+/* One vector step of n lanes, one lane per thread, 256-thread workgroups.  Per-lane state, flat device arrays the
+ * caller zeroes once (then sets the `allowed` row to first_backup_episode <= 0):
+ *   pos_ring [NLBAC_HANDOVER_RING][2][n] double: (x, y) of next_lya_in, slot (k - 1) mod RING after episode step k
+ *                                                (kinds 0 and 2 only; may be NULL for kind 1);
+ *   istate   [NLBAC_HANDOVER_ISTATE][n] int32:   0 backup (Pvtol: obs_b), 1 Pvtol's y_b, 2 backup_time (obs_time),
+ *                                                3 y_time, 4 violation_time (viol_obs), 5 viol_y, 6 finished episodes,
+ *                                                7 allowed, 8 steps on which the backup controller acted (a tally);
+ *   dstate   [2][n] double:                      x0, y0 (where the hand-over began);
+ *   flags    [n] bytes 0 / 1:                    use_backup for the NEXT step (what the host class would answer).
+ * The flag of THIS step is flags[i] as the last call left it (all 0 before the first).  In order:
+ * (a) with a ring: the transition's row, in the float32 roundings of train_vectorized (mask = 1 at the time limit
+ *     ep_step >= max_steps, else 1 - done; t = float(k) float(dt), nt = (float(k) + 1) float(dt), padding 0), goes to row
+ *     (node_first + i) mod node_cap of node_ring (n <= node_cap);
+ * (b) kept[i] = !flag and counts[workgroup] = kept lanes of the workgroup (64-bit ballots; plain stores), for
+ *     nlbac_ring_append_kept (either may be NULL);
+ * (c) on_backup_action if the flag is set, after_step(k = ep_step[i], ...), and at done[i] the episode count goes up and
+ *     begin_episode resets the lane;  (d) flags[i].
+ * obs_prev / action are float32 (n, obs_dim) / (n, act_dim); every other input float64 / int32 as the simulators leave
+ * them; info0 is column 0 of the simulators' info (rows info_ld doubles apart).  node_ring NULL: the state machine
+ * alone (reward, constraint, obs_prev, action are not read). */
+int nlbac_vector_step_rows(int n, const nlbac_handover_params *p, const nlbac_row_layout *lay, const double *lya_pre,
+                           const double *lya_next, const double *obs_next, const double *reward,
+                           const double *constraint, const double *info0, int info_ld, const int *done,
+                           const int *ep_step, const float *obs_prev, const float *action, double dt, int max_steps,
+                           float *node_ring, long node_first, long node_cap, double *pos_ring, int *istate,
+                           double *dstate, unsigned char *flags, unsigned char *kept, int *counts, nlbac_stream_t s);
+/* Order-preserving compaction: the rows of the lanes with kept[i] != 0, in lane order, from rows (node_first + i) mod
+ * node_cap of node_ring to the controller ring `ring` (cap rows of ld floats) behind its head, t / nt columns rewritten
+ * to float(k + shift) float(dt) and (float(k + shift) + 1) float(dt) when shift != 0 (k = ep_step[i]).  A workgroup's
+ * offset is the sum of counts[] of the workgroups before it (n <= 65536: at most 256 reads; no atomics, no election).
+ * head [2][2] long = {position, length} twice: every workgroup reads half `half`, workgroup 0 writes position + total
+ * (mod cap) and min(cap, length + total) into the other half — the caller alternates `half`.  n <= cap, n <= node_cap. */
+int nlbac_ring_append_kept(int n, const unsigned char *kept, const int *counts, const float *node_ring, long node_first,
+                           long node_cap, float *ring, long cap, int ld, long *head, int half, const int *ep_step,
+                           int shift, double dt, int t_col, int nt_col, nlbac_stream_t s);
+/* nlbac_sample_rows with src_rows read on the device from head[half][1] (clamped to cap) — the same Philox counters:
+ * for an equal length, seed and draw the same rows and noise, bit for bit.  A length of 0 copies nothing and does not
+ * read the ring (the noise is still drawn). */
+int nlbac_sample_rows_head(const float *src, const long *head, int half, long cap, int ld, long n_rows, float *dst,
+                           float *eps, long n_eps, unsigned long long seed, unsigned long long draw, nlbac_stream_t s);
+
 /* small utilities */
 int nlbac_axpby(float a, const float *x, float b, const float *y /*or NULL*/, long n, float *out, nlbac_stream_t s);
 int nlbac_fill(float *p, float v, long n, nlbac_stream_t s);

@@ -129,6 +129,23 @@ class OutMap(C.Structure):
                 ("x", C.c_void_p)]
 
 
+class HandoverParams(C.Structure):
+    """``struct nlbac_handover_params``"""
+    _fields_ = [("kind", C.c_int), ("first_backup_episode", C.c_int), ("min_check_step", C.c_int), ("lookback", C.c_int),
+                ("memory_t_shift", C.c_int), ("checks", C.c_int), ("max_backup", C.c_int), ("min_backup", C.c_int),
+                ("run_checks", C.c_int), ("run_max_backup", C.c_int),
+                ("stuck2", C.c_double), ("away2", C.c_double), ("gap", C.c_double), ("x_mid", C.c_double),
+                ("back_frac", C.c_double), ("operator_dist", C.c_double)]
+
+
+class RowLayout(C.Structure):
+    """``struct nlbac_row_layout``"""
+    _fields_ = [(k, C.c_int) for k in ("obs_dim", "act_dim", "lya_dim", "ld", "obs", "act", "rew", "con", "lya", "nlya",
+                                       "nobs", "mask", "t", "nt")]
+
+
+HANDOVER_RING, HANDOVER_ISTATE = 40, 9      # == NLBAC_HANDOVER_RING / NLBAC_HANDOVER_ISTATE
+
 _P, _I, _F, _D, _L = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_long
 
 # name -> argtypes (return type is always int unless listed in _RESTYPE)
@@ -291,6 +308,11 @@ _PROTOS = {
     "nlbac_unicycle_env_step": [_I, c_double_p, _I] + [_P, _I] + [_P] * 13,
     "nlbac_pvtol_env_step": [_I, c_double_p, _I] + [_P, _I] + [_P] * 11,
     "nlbac_cars_env_step": [_I, c_double_p, _I] + [_P] * 12,
+    # (new entry points of ABI 17: the vectorised driver's backup-controller hand-over, vector_handover.py)
+    "nlbac_vector_step_rows": [_I, C.POINTER(HandoverParams), C.POINTER(RowLayout)] + [_P] * 6 + [_I, _P, _P, _P, _P, _D, _I,
+                                                                                                 _P, _L, _L] + [_P] * 6 + [_P],
+    "nlbac_ring_append_kept": [_I, _P, _P, _P, _L, _L, _P, _L, _I, _P, _I, _P, _I, _D, _I, _I, _P],
+    "nlbac_sample_rows_head": [_P, _P, _I, _L, _I, _L, _P, _P, _L, C.c_uint64, C.c_uint64, _P],
     "nlbac_axpby": [_F, _P, _F, _P, _L, _P, _P],
     "nlbac_fill": [_P, _F, _L, _P],
     "nlbac_sum_partials": [_P, _I, _I, _F, _P, _P],

@@ -152,16 +152,28 @@ class DeviceReplayMemory:
     def push_rows(self, rows):
         """Bulk insert of minibatch-layout rows (host or device tensor, (n, LD))."""
         import torch
-        self.flush()
         rows = torch.as_tensor(rows, dtype=torch.float32)
         n = rows.shape[0]
         assert rows.shape[1] == self.lay.LD and n <= self.capacity
-        first = min(n, self.capacity - self.position)
-        self.rows[self.position:self.position + first].copy_(rows[:first])
+        if n == 0:
+            self.flush()
+            return
+        start = self.reserve_rows(n)
+        first = min(n, self.capacity - start)
+        self.rows[start:start + first].copy_(rows[:first])
         if n > first:
             self.rows[:n - first].copy_(rows[first:])
+
+    def reserve_rows(self, n):
+        """The bookkeeping of ``push_rows`` for ``n`` rows a kernel writes in place: returns the first ring row (row k of
+        the push is ring row ``(first + k) mod capacity``)."""
+        self.flush()
+        n = int(n)
+        assert 0 < n <= self.capacity
+        first = self.position
         self._len = min(self.capacity, max(self._len, self.position + n))
         self.position = (self.position + n) % self.capacity
+        return first
 
     def flush(self):
         if self._n_staged:
@@ -242,6 +254,56 @@ class DeviceReplayMemory:
             c = getattr(lay, name)
             out.append(rows[:, c] if w == 0 else rows[:, c:c + w])
         return tuple(out)
+
+    def __len__(self):
+        return self._len
+
+
+class DeviceKeptReplay:
+    """The controller replay of the vectorised driver with hand-over (``vector_handover.VectorHandover.push``): a ring in
+    HBM that receives, per vector step, the rows of the lanes in which the primary controller acted — how many is decided
+    on the device, so the ring's head ``{position, length}`` lives in device memory (``head``, (2, 2) int64: two copies,
+    ``half`` names the current one; an append reads it and writes the other, the host only alternates ``half``).
+
+    ``sample_rows`` draws on the device through ``nlbac_sample_rows_head``, which reads the length from the head: no
+    index and no length passes through the host.  ``draws_from`` is the NODE replay of the same run: the two share its
+    Philox key and its one draw counter, so a run whose hand-over never fires draws exactly what a single
+    ``DeviceReplayMemory`` serving both purposes draws.  ``len()`` is a cached lower bound (the length never shrinks);
+    ``refresh_len()`` reads the head and is the only host read."""
+    device_rng = True
+
+    def __init__(self, capacity, seed, agent, draws_from):
+        import torch
+        self.capacity, self.agent, self.draws_from = int(capacity), agent, draws_from
+        self.seed = seed           # (kept for the record: the Philox key is draws_from's)
+        self.lay, self.device = agent.lay, agent.device
+        self.rows = torch.zeros(self.capacity, self.lay.LD, dtype=torch.float32, device=self.device)
+        self.head = torch.zeros(2, 2, dtype=torch.int64, device=self.device)
+        self.half = 0
+        self._len = 0
+
+    def refresh_len(self):
+        """Read the current head's length (a host sync); ``len()`` answers with it from then on."""
+        self._len = max(self._len, int(self.head[self.half, 1]))
+        return self._len
+
+    def sample_rows(self, batch_size, out=None, eps_out=None):
+        """``DeviceReplayMemory.sample_rows`` in its ``device_rng`` mode, on the length the device holds."""
+        import torch
+        from .. import _lib
+        from ..arena import stream_ptr
+        if out is None:
+            out = torch.zeros(batch_size, self.lay.LD, dtype=torch.float32, device=self.device)
+        src = self.draws_from
+        src._draws += 1
+        _lib.call("nlbac_sample_rows_head", self.rows.data_ptr(), self.head.data_ptr(), self.half, self.capacity,
+                  self.lay.LD, batch_size, out.data_ptr(), eps_out.data_ptr() if eps_out is not None else None,
+                  eps_out.numel() if eps_out is not None else 0, src._seed, src._draws, stream_ptr())
+        return out
+
+    def sample(self, batch_size):
+        raise NotImplementedError("DeviceKeptReplay.sample: the length of this replay is known on the device only, so "
+                                  "there is no host index draw and no host copy of a minibatch; use sample_rows")
 
     def __len__(self):
         return self._len

@@ -9,6 +9,8 @@ line per episode (the reference's wandb / spinup loggers are host tooling and ou
         --batch_size 128 --seed 0 --start_steps 1000          (the reference README's command line)
 
 ``--device_replay`` keeps both replays in HBM (same index stream, gather on the device).
+``--vector_envs N`` steps N environments on the device (``train_vectorized``); with ``--vector_handover`` each lane
+also follows its copy's hand-over rules on the device (``vector_handover.py``).
 """
 import argparse
 import os
@@ -56,6 +58,10 @@ def get_args(argv=None):
     p.add_argument('--vector_envs', type=int, default=0,
                    help="N > 0: N environments stepping on the device (train_vectorized: no transition touches the host, "
                         "primary controller only); runs --max_steps env steps (default 100000)")
+    p.add_argument('--vector_handover', action="store_true",
+                   help="with --vector_envs: the backup controller acts where the copy's hand-over rules say so, decided "
+                        "per lane on the device; its steps stay out of the controller replay (this command line runs Unicycle "
+                        "and Pvtol vectorised; train_vectorized(handover=...) itself also takes SimulatedCars)")
     return p.parse_args(argv)
 
 
@@ -65,6 +71,7 @@ class _Handover:
     transition is kept out of ``memory``)."""
     first_backup_episode = None        # hand-over is allowed from this episode on (None: this copy has no backup)
     memory_t_shift = 0                 # SimulatedCars stamps the controller replay one step earlier (C/main.py:97-99)
+    MIN_CHECK_STEP, LOOKBACK = 50, 40  # Unicycle / Pvtol: no check before this episode step; `moved` looks this far back
 
     def __init__(self, env):
         self.env = env
@@ -106,9 +113,9 @@ class _UnicycleHandover(_Handover):
 
     def after_step(self, episode_steps, lya_in, next_lya_in, next_obs, info):
         self.positions.append(np.asarray(next_lya_in))
-        if episode_steps < 50:
+        if episode_steps < self.MIN_CHECK_STEP:
             return
-        diff = self.positions[-1] - self.positions[-40]
+        diff = self.positions[-1] - self.positions[-self.LOOKBACK]
         moved = diff[0] * diff[0] + diff[1] * diff[1]
         if self.allowed and not self.backup:
             if moved <= self.STUCK2:
@@ -131,6 +138,7 @@ class _CarsHandover(_Handover):
     -> the backup controller, for at most 15 steps, or from 5 steps on once both gaps exceed 2.5."""
     first_backup_episode = 0
     memory_t_shift = -1
+    GAP, MAX_BACKUP, MIN_BACKUP = 2.5, 15, 5
 
     def begin_episode(self, i_episode):
         super().begin_episode(i_episode)
@@ -147,12 +155,12 @@ class _CarsHandover(_Handover):
         d34 = next_obs[4] * 100.0 - next_obs[6] * 100.0
         d45 = next_obs[6] * 100.0 - next_obs[8] * 100.0
         if self.allowed and not self.backup:
-            if d45 < 2.5 and info.get('reached', 0) != 0:
+            if d45 < self.GAP and info.get('reached', 0) != 0:
                 self.backup = True
         if self.backup and self.allowed:
-            if self.backup_time >= 15:
+            if self.backup_time >= self.MAX_BACKUP:
                 self.backup, self.backup_time = False, 0
-            if self.backup_time >= 5 and d34 > 2.5 and d45 > 2.5:
+            if self.backup_time >= self.MIN_BACKUP and d34 > self.GAP and d45 > self.GAP:
                 self.backup, self.backup_time = False, 0
 
 
@@ -161,6 +169,8 @@ class _PvtolHandover(_Handover):
     8 checks; back after 30 steps or 1.0 away) and running away from the safety operator towards the goal (back after
     15 steps or once within 0.9 operator_dist); allowed from episode 3 on."""
     first_backup_episode = 3
+    STUCK2, CHECKS, MAX_BACKUP, AWAY2 = 0.015, 8, 30, 1.0          # trapped
+    RUN_CHECKS, RUN_MAX_BACKUP, BACK_FRAC, X_MID = 1, 15, 0.9, 4.5   # running away from the safety operator
 
     def begin_episode(self, i_episode):
         super().begin_episode(i_episode)
@@ -184,39 +194,39 @@ class _PvtolHandover(_Handover):
 
     def after_step(self, episode_steps, lya_in, next_lya_in, next_obs, info):
         self.positions.append(np.asarray(next_lya_in))
-        if episode_steps < 50:
+        if episode_steps < self.MIN_CHECK_STEP:
             return
         env, nx, pv = self.env, next_lya_in, lya_in
-        diff = self.positions[-1] - self.positions[-40]
+        diff = self.positions[-1] - self.positions[-self.LOOKBACK]
         moved = diff[0] * diff[0] + diff[1] * diff[1]
         if self.allowed and not self.obs_b:
-            if moved <= 0.015:
+            if moved <= self.STUCK2:
                 self.viol_obs += 1
-                if self.viol_obs >= 8:
+                if self.viol_obs >= self.CHECKS:
                     self.obs_b, self.viol_obs = True, 0
                     self.x0, self.y0 = nx[0], nx[1]
-            if moved > 0.015 and self.viol_obs > 0:
+            if moved > self.STUCK2 and self.viol_obs > 0:
                 self.viol_obs = 0
         if self.obs_b and self.allowed:
-            if self.obs_time >= 30:
+            if self.obs_time >= self.MAX_BACKUP:
                 self.obs_b, self.obs_time = False, 0
             dx, dy = nx[0] - self.x0, nx[1] - self.y0
-            if dx * dx + dy * dy >= 1.0:
+            if dx * dx + dy * dy >= self.AWAY2:
                 self.obs_b, self.obs_time = False, 0
-        running = ((nx[0] <= 4.5 and nx[0] - pv[0] > 0 and nx[0] - nx[7] > env.operator_dist) or
-                   (nx[0] > 4.5 and nx[0] - pv[0] < 0 and nx[7] - nx[0] > env.operator_dist))
+        running = ((nx[0] <= self.X_MID and nx[0] - pv[0] > 0 and nx[0] - nx[7] > env.operator_dist) or
+                   (nx[0] > self.X_MID and nx[0] - pv[0] < 0 and nx[7] - nx[0] > env.operator_dist))
         if self.allowed and not self.y_b:
             if running:
                 self.viol_y += 1
-                if self.viol_y >= 1:
+                if self.viol_y >= self.RUN_CHECKS:
                     self.y_b, self.viol_y = True, 0
             if (not running) and self.viol_y > 0:
                 self.viol_y = 0
         if self.y_b and self.allowed:
-            if self.y_time >= 15:
+            if self.y_time >= self.RUN_MAX_BACKUP:
                 self.y_b, self.y_time = False, 0
-            if ((nx[0] <= 4.5 and nx[0] - nx[7] <= 0.9 * env.operator_dist) or
-                    (nx[0] > 4.5 and nx[7] - nx[0] <= 0.9 * env.operator_dist)):
+            if ((nx[0] <= self.X_MID and nx[0] - nx[7] <= self.BACK_FRAC * env.operator_dist) or
+                    (nx[0] > self.X_MID and nx[7] - nx[0] <= self.BACK_FRAC * env.operator_dist)):
                 self.y_b, self.y_time = False, 0
 
 
@@ -299,7 +309,7 @@ def train(agent, env, dynamics_model, args, memory, node_memory, log=print, trac
     return history
 
 
-def train_vectorized(agent, env, args, n_steps, log=print, memory=None, check=None):
+def train_vectorized(agent, env, args, n_steps, log=print, memory=None, check=None, handover=None):
     """Vectorised rollouts: ``env`` is one of ``nlbac_amd.envs.device`` — N environments stepping in
     lock step on the device — and nothing of a transition touches the host: the policy acts on the (N, obs) device
     tensor (one forward for all lanes), the simulator launch writes the next observations / rewards / constraints /
@@ -310,7 +320,12 @@ def train_vectorized(agent, env, args, n_steps, log=print, memory=None, check=No
     backup-controller hand-over heuristics (which are per-episode host control flow): the primary controller acts in
     every lane.  Time-limit terminations keep mask 1 (U/main.py:150), finished lanes are reset in place.
     ``check``: a callable(step_index, rows) the tests use to look at the rows that were appended.
-    Returns dict(steps, updates, episodes, mean_return)."""
+    Returns dict(steps, updates, episodes, mean_return).
+
+    ``handover``: None / False — the above.  True, or a ``_lib.HandoverParams`` (``vector_handover.params_for``): lane i
+    is ``train``'s loop for one environment as far as controllers and replays go (``_train_vectorized_handover``)."""
+    if handover is not None and handover is not False:
+        return _train_vectorized_handover(agent, env, args, n_steps, log, memory, check, handover)
     import torch
     from .sac_cbf_clf.replay_memory import DeviceReplayMemory
     dev, lay, N = agent.device, agent.lay, env.n
@@ -386,6 +401,97 @@ def train_vectorized(agent, env, args, n_steps, log=print, memory=None, check=No
     return res
 
 
+def _train_vectorized_handover(agent, env, args, n_steps, log, memory, check, handover):
+    """``train_vectorized`` with the backup-controller hand-over decided per lane on the device
+    (``vector_handover.VectorHandover``; DESIGN.md §5 has the definition).  ``memory`` is the NODE replay and receives
+    every transition; a ``DeviceKeptReplay`` of the same capacity is the controller replay — it receives the rows of the
+    lanes in which the primary controller acted and is what ``update_parameters`` draws its minibatch from.  The action
+    of lane i is the backup policy's where ``flags[i]`` is set (the primary policy draws its noise from the global
+    generator as without hand-over, the backup policy from a generator of its own), the uniform draw during
+    ``start_steps`` either way.  Per vector step, on top of the simulator and the two policies: two launches
+    (``nlbac_vector_step_rows``, ``nlbac_ring_append_kept``).  ``check``: callable(step_index, rows, flags) — the rows
+    that went into the NODE replay and the flags that decided the step.
+    Returns dict(steps, updates, episodes, mean_return, backup_steps)."""
+    lay = getattr(agent, "lay", None)
+    if getattr(env, "barrier", False) or getattr(lay, "sig", None) is not None:
+        raise ValueError("train_vectorized(handover=...): the learned-barrier copies have no backup controller")
+    if getattr(agent, "backup_policy", None) is None:
+        raise ValueError("train_vectorized(handover=...): this agent has no backup policy to hand over to")
+    env_name = getattr(env, "dynamics_mode", None)             # (the barrier copies share their base copy's)
+    if env_name not in ("Unicycle", "SimulatedCars", "Pvtol"):
+        raise ValueError("train_vectorized(handover=...): no hand-over rules for %r" % (env_name,))
+    import torch
+    from .sac_cbf_clf.replay_memory import DeviceKeptReplay, DeviceReplayMemory
+    from .vector_handover import VectorHandover, params_for
+    dev, N = agent.device, env.n
+    agent.node_stride = N          # (the NODE replay still holds one row per lane per step)
+    if memory is None:
+        memory = DeviceReplayMemory(args.replay_size, args.seed, agent, device_rng=True)
+    params = params_for(env_name, env) if handover is True else handover
+    ho = VectorHandover(env_name, N, dev, params)
+    kept = DeviceKeptReplay(memory.capacity, args.seed, agent, draws_from=memory)
+    lo = torch.as_tensor(np.asarray(env.action_space.low), dtype=torch.float32, device=dev)
+    hi = torch.as_tensor(np.asarray(env.action_space.high), dtype=torch.float32, device=dev)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(args.seed))
+    gen_backup = torch.Generator(device=dev)                   # (the backup policy's noise: the global stream, which the
+    gen_backup.manual_seed(int(args.seed))                     # primary policy and the updates draw from, does not move)
+    obs = env.reset().to(torch.float32).clone()
+    ep_ret = torch.zeros(N, dtype=torch.float64, device=dev)
+    ret_sum = torch.zeros((), dtype=torch.float64, device=dev)
+    n_done = torch.zeros((), dtype=torch.int64, device=dev)
+    from .sac_cbf_clf.tasks import _Task
+    needs_episode = type(agent.task).fit_due is not _Task.fit_due
+    steps = updates = it = 0
+    gate_open = False
+    log("vectorised: backup-controller hand-over per lane on the device; the controller replay holds the primary "
+        "controller's steps only")
+    while steps < n_steps:
+        if steps < args.start_steps:
+            action = lo + (hi - lo) * torch.rand(N, lay.act_dim, generator=gen, device=dev)
+        else:
+            primary = agent.policy.sample(obs)[0]
+            eps = torch.randn(N, lay.act_dim, generator=gen_backup, device=dev)
+            action = torch.where(ho.flags[:, None], agent.backup_policy.sample(obs, eps=eps)[0], primary)
+        action = action.contiguous()
+        decided = ho.flags.clone() if check is not None else None
+        out = env.step(action)
+        nobs, reward, constraint = out[:3]
+        lya_in, next_lya_in, done, info = out[-4], out[-3], out[-2], out[-1]
+        info0 = info["reached" if env_name == "SimulatedCars" else "goal_met"]
+        first = ho.push(memory, kept, obs, action, reward, constraint, lya_in, next_lya_in, nobs, info0, done, env.ep_step,
+                        float(env.dt), int(env.max_episode_steps))
+        if check is not None:
+            idx = (first + torch.arange(N, device=dev)) % memory.capacity
+            check(it, memory.rows[idx], decided)
+        ep_ret += reward
+        fin = done > 0
+        ret_sum += torch.where(fin, ep_ret, torch.zeros_like(ep_ret)).sum()
+        n_done += fin.sum()
+        ep_ret = torch.where(fin, torch.zeros_like(ep_ret), ep_ret)
+        steps += N
+        it += 1
+        if not gate_open:                                      # (the only host read of the run, until it has passed)
+            gate_open = kept.refresh_len() > args.batch_size
+        if gate_open:
+            i_episode = None                                   # (as without hand-over)
+            if needs_episode and any((updates + k) % args.NODE_model_update_interval == 0 for k in range(args.updates_per_step)):
+                i_episode = 1 + int(n_done) // N
+            for _ in range(args.updates_per_step):
+                agent.update_parameters(kept, args.batch_size, updates, None, memory, args.NODE_model_update_interval,
+                                        i_episode)
+                updates += 1
+        env.reset(fin)
+        obs = env.obs.to(torch.float32).clone()
+    torch.cuda.synchronize()
+    eps_n = int(n_done)
+    res = dict(steps=steps, updates=updates, episodes=eps_n, mean_return=float(ret_sum) / max(eps_n, 1),
+               backup_steps=ho.backup_steps())
+    log("vectorised: %(steps)d env steps in %(episodes)d finished episodes, %(updates)d updates, mean return "
+        "%(mean_return).2f, %(backup_steps)d steps under the backup controller" % res)
+    return res
+
+
 def main(argv=None):
     args = get_args(argv)
     import nlbac_amd  # noqa: F401
@@ -415,7 +521,7 @@ def main(argv=None):
         from .envs import device as device_envs
         args.replay_size = min(args.replay_size, 1 << 20)
         return train_vectorized(agent, device_envs.make(args.env, args.vector_envs, seed=max(args.seed, 0)), args,
-                                args.max_steps or 100000)
+                                args.max_steps or 100000, handover=args.vector_handover or None)
     dynamics_model = DynamicsModel(env, args)
     if args.device_replay:
         cap = min(args.replay_size, 1 << 20)

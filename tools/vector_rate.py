@@ -1,4 +1,11 @@
-"""GPU: throughput of the vectorised driver (train.train_vectorized): N device environments + one update per vector step."""
+"""GPU: throughput of the vectorised driver (train.train_vectorized): N device environments + one update per vector step.
+
+    python tools/vector_rate.py [N [B]] [--handover] [--launches] [--iters=K]
+
+``--handover``: with the backup-controller hand-over decided per lane on the device (two replays, two acting policies).
+``--launches``: after the timed run, a short run that counts the library's launches (``_lib.call``) per vector step.
+``--iters=K``: vector steps of the timed run (300; a kernel trace of two run lengths, differenced, counts the kernels of
+a vector step)."""
 import os, sys, time, types
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -8,14 +15,32 @@ from nlbac_amd.envs import device as denv
 from nlbac_amd.train import train_vectorized
 from test_agent_parity_gpu import make_agent
 
-N, B, iters = int(sys.argv[1]) if len(sys.argv) > 1 else 4096, int(sys.argv[2]) if len(sys.argv) > 2 else 4096, 300
+argv = [a for a in sys.argv[1:] if not a.startswith("--")]
+handover, launches = "--handover" in sys.argv, "--launches" in sys.argv
+N, B, iters = int(argv[0]) if len(argv) > 0 else 4096, int(argv[1]) if len(argv) > 1 else 4096, 300
+iters = next((int(a[8:]) for a in sys.argv[1:] if a.startswith("--iters=")), iters)
 agent, _ = make_agent(B, 256, 0, "dopri5", "Unicycle", 50.0)
 env = denv.make("Unicycle", N, seed=0)
 args = types.SimpleNamespace(replay_size=1 << 20, seed=0, start_steps=2 * N, batch_size=B, updates_per_step=1,
                              NODE_model_update_interval=10)
-train_vectorized(agent, env, args, 20 * N, log=lambda *a: None)        # warm-up (allocations, first launches)
+kw = {"handover": True} if handover else {}
+train_vectorized(agent, env, args, 20 * N, log=lambda *a: None, **kw)        # warm-up (allocations, first launches)
 torch.cuda.synchronize(); t0 = time.perf_counter()
-res = train_vectorized(agent, denv.make("Unicycle", N, seed=1), args, iters * N, log=lambda *a: None)
+res = train_vectorized(agent, denv.make("Unicycle", N, seed=1), args, iters * N, log=lambda *a: None, **kw)
 dt = time.perf_counter() - t0
-print("N=%d lanes, batch %d: %d env steps + %d updates in %.3f s = %.2f M env steps/s, %.2f ms per vector step"
-      % (N, B, res["steps"], res["updates"], dt, res["steps"] / dt / 1e6, 1e3 * dt / iters))
+print("N=%d lanes, batch %d%s: %d env steps + %d updates in %.3f s = %.2f M env steps/s, %.2f ms per vector step"
+      % (N, B, ", hand-over on (%d backup steps)" % res["backup_steps"] if handover else "", res["steps"], res["updates"],
+         dt, res["steps"] / dt / 1e6, 1e3 * dt / iters))
+if launches:
+    from nlbac_amd import _lib
+    names, real, n_it = [], _lib.call, 40
+    _lib.call = lambda name, *a: (names.append(name), real(name, *a))[1]
+    marks = []
+    train_vectorized(agent, denv.make("Unicycle", N, seed=2), args, n_it * N, log=lambda *a: None,
+                     check=lambda it, *a: marks.append(len(names)), **kw)
+    _lib.call = real
+    per_step = [marks[k + 1] - marks[k] for k in range(10, n_it - 1)]         # (past the warm-up and the gate)
+    own = names[marks[20]:marks[21]]
+    driver = [n for n in own if n in ("nlbac_unicycle_env_step", "nlbac_vector_step_rows", "nlbac_ring_append_kept")]
+    print("library launches per vector step (update included): min %d max %d; the driver's own: %s"
+          % (min(per_step), max(per_step), ", ".join(driver)))

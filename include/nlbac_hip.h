@@ -658,6 +658,41 @@ int nlbac_node_dopri_tile_dense_bwd(const nlbac_mlp *f, const nlbac_mlp *g, cons
                                     long acts_f_ls, const float *acts_g, long acts_g_ls, int acts_bits,
                                     const float *dout, float *dx0, float *du, float *dK, float *dG, float *dz_f,
                                     float *dz_g, nlbac_stream_t s);
+/* The four tile launches above with the step slots counted PER TILE (ABI 17, additions): in place of max_slots, page0
+ * [tiles + 1] (DEVICE ints: the exclusive prefix sum of the tiles' slot counts, page0[tiles] == pages) and pages, the
+ * slots of all tiles together.  Tile j owns the pages page0[j] .. page0[j+1] - 1, a page per accepted step, each 7
+ * stages x 32 rows: slot s of the tile is page page0[j] + s, and stage st, tile row m of it sits at stage-row index
+ * (page*7 + st)*32 + m of pages*7*32 — G [pages*7][32][n_s*n_u], Y [pages*7][32][n_s], the acts (and, in the backward,
+ * dK / dG / dz_*) laid out for pages*7 stages of 32 rows, hslots [pages]; ZERO on entry as above (the rows a partial
+ * last tile lacks stay zero).  iv_first / ov_slot count a tile's slots from 0 as before.  A tile that needs more than
+ * its own page0[j+1] - page0[j] slots stops with status 1.  pages >= tiles * (H; 1 for the dense solve) and pages*7*32
+ * < 2^31.  What the kernels read of page0 is clamped to [0, pages], so that no content of it takes an index outside
+ * the buffers.  A forward that keeps nothing (G NULL) takes page0 NULL and pages 0: the same kernel instance as the
+ * kept launch with that acts_bits, hence the same steps — the launch that COUNTS a solve's steps per tile.  All other
+ * arguments, results and refusals are the siblings'. */
+int nlbac_node_dopri_tile_paged_fwd(const nlbac_mlp *f, const nlbac_mlp *g, const float *x0, const float *u, int n, int H,
+                                    const float *beta, const float *c_err, double dt, float rtol, float atol, float *out,
+                                    const int *page0, int pages, float *Y, float *G, float *acts_f, long acts_f_ls,
+                                    float *acts_g, long acts_g_ls, int acts_bits, double *hslots, int *iv_first,
+                                    float *iv_x, int *accepted, int *attempts, int *status, nlbac_stream_t s);
+int nlbac_node_dopri_tile_paged_bwd(const nlbac_mlp *f, const nlbac_mlp *g, const float *u, int n, int H,
+                                    const float *beta, const int *page0, int pages, const double *hslots,
+                                    const int *iv_first, const int *iv_nacc, const float *iv_x, const float *G,
+                                    const float *acts_f, long acts_f_ls, const float *acts_g, long acts_g_ls,
+                                    int acts_bits, const float *dout, float *dx0, float *du, float *dK, float *dG,
+                                    float *dz_f, float *dz_g, nlbac_stream_t s);
+int nlbac_node_dopri_tile_dense_paged_fwd(const nlbac_mlp *f, const nlbac_mlp *g, const float *x0, const float *u, int n,
+                                          const float *beta, const float *c_err, const double *tau, int n_out,
+                                          double t_end, float rtol, float atol, float *out, const int *page0, int pages,
+                                          float *Y, float *G, float *acts_f, long acts_f_ls, float *acts_g,
+                                          long acts_g_ls, int acts_bits, double *hslots, int *ov_slot, float *ov_x,
+                                          int *accepted, int *attempts, int *status, nlbac_stream_t s);
+int nlbac_node_dopri_tile_dense_paged_bwd(const nlbac_mlp *f, const nlbac_mlp *g, const float *u, int n,
+                                          const float *beta, int n_out, const int *page0, int pages,
+                                          const double *hslots, const int *ov_slot, const float *ov_x, const int *nacc,
+                                          const float *G, const float *acts_f, long acts_f_ls, const float *acts_g,
+                                          long acts_g_ls, int acts_bits, const float *dout, float *dx0, float *du,
+                                          float *dK, float *dG, float *dz_f, float *dz_g, nlbac_stream_t s);
 /* One-launch fixed-grid rollout of the single-net NODE dx/dt = net([x | c]) (euler: n_stages 1, rk4: 4, with that
  * method's beta [n_stages][n_stages] and c_out [n_stages]): H intervals of step h, interval k integrating from out[k-1]
  * (x0 for k = 0) with the carried columns c[k] — what H nlbac_concat_rk_fwd launches compute, bit for bit, in one launch

@@ -250,6 +250,15 @@ _PROTOS = {
                                         _F, _P, _I, _P, _P, _P, _L, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P],
     "nlbac_node_dopri_tile_dense_bwd": [C.POINTER(Mlp), C.POINTER(Mlp), _P, _I, c_float_p, _I, _I, _P, _P, _P, _P, _P, _P,
                                         _L, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    # (ABI 17, additions: the four tile launches with the slots counted per tile — (page0, pages) in place of max_slots)
+    "nlbac_node_dopri_tile_paged_fwd": [C.POINTER(Mlp), C.POINTER(Mlp), _P, _P, _I, _I, c_float_p, c_float_p, _D, _F, _F,
+                                        _P, _P, _I, _P, _P, _P, _L, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P],
+    "nlbac_node_dopri_tile_paged_bwd": [C.POINTER(Mlp), C.POINTER(Mlp), _P, _I, _I, c_float_p, _P, _I, _P, _P, _P, _P, _P,
+                                        _P, _L, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "nlbac_node_dopri_tile_dense_paged_fwd": [C.POINTER(Mlp), C.POINTER(Mlp), _P, _P, _I, c_float_p, c_float_p, _P, _I, _D,
+                                              _F, _F, _P, _P, _I, _P, _P, _P, _L, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P],
+    "nlbac_node_dopri_tile_dense_paged_bwd": [C.POINTER(Mlp), C.POINTER(Mlp), _P, _I, c_float_p, _I, _P, _I, _P, _P, _P,
+                                              _P, _P, _P, _L, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "nlbac_concat_rk_traj_ok": [C.POINTER(Mlp)],
     "nlbac_concat_rk_traj_fwd": [C.POINTER(Mlp), _P, _P, _I, _I, _I, c_float_p, c_float_p, _F, _P, _P, _P, _L, _I, _P, _P],
     "nlbac_concat_rk_traj_bwd": [C.POINTER(Mlp), _I, _I, _I, c_float_p, c_float_p, _F, _P, _L, _I, _P, _P, _P, _P, _P, _P,

@@ -848,6 +848,13 @@ __device__ __forceinline__ void rk_traj_bwd_end(const NodeRkBwdLaunch& L, const 
 // first slot, its accepted count and the interpolation abscissa.
 // Every loop has a bound from the launch's arguments: H intervals, NODE_TILE_MAX_ATTEMPTS attempts per interval,
 // max_slots slots.  A tile that hits one stops: status, NaN into its rows of the outputs from that interval on.
+// PAGED (page0 non-null; the *_paged_* entry points): the slots are counted per tile.  Everything kept per (slot, stage,
+// row) lies in pages of S stages x 32 rows, tile j owning the pages page0[j] .. page0[j+1] - 1 (page0 [tiles + 1]: the
+// exclusive prefix sum of the tiles' slot counts, `pages` their total): slot s of the tile is page page0[j] + s, and
+// stage st, tile row m of it sits at stage-row index (page S + st) 32 + m — the index above with 32 in place of n, 0 in
+// place of the tile's first row and the page in place of the slot (NodeTilePlace: the three substitutes, once per
+// workgroup).  hslots is indexed by page; iv_first / ov_slot and the slot arithmetic stay relative to the tile.  What is
+// read of page0 is clamped to the pages, so that no content of it takes an index outside the buffers.
 // ---------------------------------------------------------------------------------------------------------------
 #define NODE_TILE_MAX_ATTEMPTS 1000      /* per interval: the chained solve's own cap (ode_dopri.py) */
 enum { TILE_OK = 0, TILE_NO_SLOT = 1, TILE_MAX_ATTEMPTS = 2 };
@@ -855,8 +862,9 @@ enum { TILE_OK = 0, TILE_NO_SLOT = 1, TILE_MAX_ATTEMPTS = 2 };
 struct NodeTileFwd {
     int H;
     int keep;                         // a backward follows: accepted steps are kept in slots
-    int max_slots;                    // (keep) slots a tile has for the whole horizon
-    double* hslots;                   // (keep) [tile][max_slots] the kept steps' sizes
+    int max_slots;                    // (keep) slots a tile has for the whole horizon; PAGED: the pages of all tiles
+    const int* page0;                 // (keep, PAGED) [tiles + 1] a tile's first page; null: max_slots slots for every tile
+    double* hslots;                   // (keep) [tile][max_slots] the kept steps' sizes; PAGED: [page]
     int* iv_first;                    // (keep) [tile][H] interval k's first slot
     float* iv_x;                      // (keep) [tile][H] the abscissa of out[k+1] in interval k's last step
     int* accepted;                    // [tile][H] accepted steps of interval k
@@ -865,7 +873,8 @@ struct NodeTileFwd {
 };
 
 struct NodeTileBwd {
-    int H, max_slots;
+    int H, max_slots;                 // (max_slots, page0, hslots: as in NodeTileFwd)
+    const int* page0;
     const double* hslots; const int* iv_first; const int* iv_nacc; const float* iv_x;
     const float* dout;                // [H+1][n][n_s]
     float* dx0;                       // [n][n_s]
@@ -888,6 +897,28 @@ struct NodeTileDenseBwd {
     const int* ov_slot; const float* ov_x;
 };
 
+// Where workgroup `tile` keeps its steps: the rows of a kept stage (kn) and the tile's first row there (krow0), its first
+// page (page; 0 when every tile has max_slots slots: the slot is the page), its slots, the stage sets the buffers hold
+// (total: what the layer stride of the BITS-2 words counts) and the index of its slot 0 in hslots.
+struct NodeTilePlace {
+    int kn, krow0, page, slots, total;
+    long hbase;
+};
+__device__ __forceinline__ NodeTilePlace rk_tile_place(const int* page0, int max_slots, int n, int row0, int tile) {
+    NodeTilePlace p;
+    if (page0) {      // (uniform)
+        const int pages = max(max_slots, 1);
+        const int p0 = min(max(page0[tile], 0), pages), p1 = min(max(page0[tile + 1], 0), pages);
+        p.slots = max(p1 - p0, 1);
+        p.page = min(p0, pages - p.slots);
+        p.kn = NLBAC_MLP_TILE; p.krow0 = 0; p.total = pages; p.hbase = p.page;
+    } else {
+        p.kn = n; p.krow0 = row0; p.page = 0; p.slots = max_slots; p.total = max_slots;
+        p.hbase = (long)tile * max_slots;
+    }
+    return p;
+}
+
 // the tile's ints in LDS (TI_OUT: DENSE, the outputs emitted so far)
 enum { TI_SLOT = 0, TI_OUT = 1, TI_COUNT = 4 };
 
@@ -900,7 +931,7 @@ static __device__ __attribute__((noinline)) void rk_tile_controller(double s0, d
 // the first stage's input of a phase (rk_fwd_first_input's arithmetic; probe: the table row is (1, 0, ...)), to sYin
 // and, when the slot keeps its stage inputs, to gY
 __device__ __forceinline__ void rk_tile_first_input(const NodeRkLaunch& L, const RkFwdTile& T, int row0, int st, bool probe,
-                                                    float* gY, float* in, int t, int nthr) {
+                                                    float* gY, int kn, int krow0, float* in, int t, int nthr) {
     const int n = L.n, ns = L.n_s;
     for (int idx = t; idx < NLBAC_MLP_TILE * 8; idx += nthr) {
         const int m = idx >> 3, c = idx & 7;
@@ -912,7 +943,7 @@ __device__ __forceinline__ void rk_tile_first_input(const NodeRkLaunch& L, const
                 const float b = probe ? (j == 0 ? 1.f : 0.f) : L.beta[st][j];
                 if (b != 0.f) a = a + T.sK[(j * NLBAC_MLP_TILE + m) * RK_MAX_NS + c] * (b * h);
             }
-            if (gY && row0 + m < n) gY[((long)st * n + row0 + m) * ns + c] = a;
+            if (gY && row0 + m < n) gY[((long)st * kn + krow0 + m) * ns + c] = a;
         }
         in[m * 8 + c] = a;
     }
@@ -960,11 +991,12 @@ __device__ __forceinline__ void rk_tile_dense_stop(const NodeRkLaunch& L, const 
 // DENSE (H = 1, D the output times): nothing is interpolated at dt; behind an ACCEPTED attempt, before the hand-over,
 // every (row, component) thread writes the pending outputs the step reaches (the walk over tau is uniform), and the
 // interval is done when an accepted step reaches dt = tau[n_out - 1] — by then every output is out.
+// P: where the tile keeps its steps — its own slot count is the limit, its hslots start at P.hbase.
 // Every thread calls it; contains barriers, ends with one.
 template <int NTHR, bool DENSE = false>
-__device__ __forceinline__ int rk_tile_after_phase(const NodeRkLaunch& L, const NodeTileFwd& X, const RkFwdTile& T,
-                                                   const float* sYin, double* sCtl, int* sInt, int row0, int n_rows,
-                                                   int k, int ph, int slot, int tid,
+__device__ __forceinline__ int rk_tile_after_phase(const NodeRkLaunch& L, const NodeTileFwd& X, const NodeTilePlace& P,
+                                                   const RkFwdTile& T, const float* sYin, double* sCtl, int* sInt,
+                                                   int row0, int n_rows, int k, int ph, int slot, int tid,
                                                    const NodeTileDenseFwd* D = nullptr) {
     static_assert(NTHR == NLBAC_MLP_TILE * RK_MAX_NS, "one (row, component) per thread");
     const int n = L.n, ns = L.n_s, nu = L.n_u, tile = row0 / NLBAC_MLP_TILE;
@@ -1051,7 +1083,7 @@ __device__ __forceinline__ int rk_tile_after_phase(const NodeRkLaunch& L, const 
     }
     const bool accept = sCtl[C_ACCEPT] > 0.0, done = sCtl[C_DONE] > 0.0;      // (uniform)
     int ret = done ? 1 : 0;
-    if (accept && tid == 0 && X.keep) X.hslots[(long)tile * X.max_slots + slot] = sCtl[C_HUSED];
+    if (accept && tid == 0 && X.keep) X.hslots[P.hbase + slot] = sCtl[C_HUSED];
     if constexpr (DENSE) {
         if (accept) {      // (uniform) the outputs this step reaches: a0 = y0, a1 = the last stage's input, K_0..6 as the slots hold them
             const double tn = d_t + d_hd;
@@ -1109,7 +1141,7 @@ __device__ __forceinline__ int rk_tile_after_phase(const NodeRkLaunch& L, const 
     }
     if (accept && X.keep) {      // the slot is taken; the next step — of this interval or of the next — needs one more
         const bool need = !done || k + 1 < X.H;
-        if (need && slot + 1 >= X.max_slots) ret = done ? 3 : 2;
+        if (need && slot + 1 >= P.slots) ret = done ? 3 : 2;
         if (tid == 0) sInt[TI_SLOT] = slot + 1;
     }
     __syncthreads();
@@ -1208,14 +1240,15 @@ __device__ __forceinline__ void rk_tile_dense_bwd_begin(const NodeRkBwdLaunch& L
 // FSAL step's stage 0 belongs to the step before: its row stays zero); behind the interval's first step du[k], behind
 // interval 0's dx0 = dout[0] + dy0 (DENSE: dx0 = slot 0's dy0; dout holds no gradient of y0).  No barrier inside.
 template <int NTHR, bool DENSE = false>
-__device__ __forceinline__ void rk_tile_bwd_end(const NodeRkBwdLaunch& L, const NodeTileBwd& X, const RkBwdWhere& w,
-                                                const RkBwdTile& T, int row0, int k, int sj, int tid) {
+__device__ __forceinline__ void rk_tile_bwd_end(const NodeRkBwdLaunch& L, const NodeTileBwd& X, const NodeTilePlace& P,
+                                                const RkBwdWhere& w, const RkBwdTile& T, int row0, int k, int sj, int tid) {
     const int n = L.n, ns = L.n_s, nu = L.n_u;
     if (w.gdK)
         for (int idx = tid; idx < L.st_hi * NLBAC_MLP_TILE * ns; idx += NTHR) {
             const int j = idx / (NLBAC_MLP_TILE * ns), rem = idx - j * NLBAC_MLP_TILE * ns;
             const int m = rem / ns, c = rem - m * ns, row = row0 + m;
-            if (row < n && j >= w.st_lo) w.gdK[((long)j * n + row) * ns + c] = T.sDK[(j * NLBAC_MLP_TILE + m) * RK_MAX_NS + c];
+            if (row < n && j >= w.st_lo)
+                w.gdK[((long)j * P.kn + P.krow0 + m) * ns + c] = T.sDK[(j * NLBAC_MLP_TILE + m) * RK_MAX_NS + c];
         }
     if (sj != 0) return;
     for (int idx = tid; idx < NLBAC_MLP_TILE * nu; idx += NTHR) {

@@ -42,6 +42,15 @@ __device__ __forceinline__ int rr_out_row(int grp, int hu, int ns, int nu) {
 
 #define RR_MAX_W 4        /* layer 0 + up to three hid x hid layers (n_layers <= 5: the reference's f_net) */
 
+// Where a kept stage's rows lie, in both bodies: RR_KN rows per stage, the tile's first at RR_KROW0, a lane's own at
+// RR_KGROW (RR_KGROWC: clamped to the rows there are) — n, row0, grow and growc, except under TILE, where a paged launch
+// (the tile's slots are pages of S stages x 32 rows: NodeTilePlace, node_rk_shared.h) has 32, 0 and the row within the
+// tile.  TILE is a template argument: the instances that are not TILE read n / row0 / grow as they always did.
+#define RR_KN (TILE ? P.kn : n)
+#define RR_KROW0 (TILE ? P.krow0 : row0)
+#define RR_KGROW (TILE ? P.krow0 + m : grow)
+#define RR_KGROWC (TILE ? min(P.krow0 + m, P.kn - 1) : growc)
+
 // dynamic LDS of the forward / backward bodies, in floats (the carve at the top of each); both are even, so the
 // tile-local step control's doubles (TILE: NLBAC_DOPRI_CTL of them and TI_COUNT ints) sit aligned behind them
 __host__ __device__ constexpr int node_rr_fwd_lds_floats() {
@@ -132,6 +141,9 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
     const bool row_ok = grow < n;
     const int KS0 = (ns + 3) >> 2;                       // registers a lane needs for its row's state components (1 or 2)
     const int KL0 = (ns + 4) >> 2;                       // k-steps of layer 0, which contracts [y | 1] with [W_0 | b_0] (1..3)
+    // (TILE) where the tile keeps its steps, uniform per workgroup and read once: RR_KN / RR_KROW0 / RR_KGROW below
+    [[maybe_unused]] NodeTilePlace P{};
+    if constexpr (TILE) P = rk_tile_place(tile->page0, tile->max_slots, n, row0, blockIdx.x);
 
     // ---- what the stage loop reads of the launch descriptor, once
     const float* const params = net.params;
@@ -143,7 +155,7 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
     // the mask words: in place of the rows (BITS 1, layer stride acts_ls), or behind the net's nw layers of rows (BITS 2,
     // [layer][S_total * n][4])
     unsigned* const words = !acts ? nullptr : reinterpret_cast<unsigned*>(BITS == 2 ? acts + (long)nw * acts_ls : acts);
-    const long words_ls = (BITS == 2) ? (long)(TRAJ ? H : (TILE ? tile->max_slots : 1)) * L.S_total * n * 4 : acts_ls;
+    const long words_ls = (BITS == 2) ? (long)(TRAJ ? H : (TILE ? P.total : 1)) * L.S_total * RR_KN * 4 : acts_ls;
     const int stage_end = L.stage_end, S_last = L.S_total - 1;
     // the initial-step probe with its norm fused into this launch (norm_mode 1): nothing it would leave in memory — the
     // probe point, its derivative, g there — is read by anyone (the norm comes from LDS, the step's stage 1 overwrites
@@ -245,7 +257,8 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
     // have to come out of the compiler as they did before there were phases); ph counts them
     int ph = 0;
     [[maybe_unused]] tile_phase:;
-    // (TILE) the phase's stages, and the slot it keeps them in: stage index slot S + st of max_slots S stages
+    // (TILE) the phase's stages, and the slot it keeps them in: stage index slot S + st of max_slots S stages (paged:
+    // the tile's page P.page + slot in place of the slot)
     int slot = 0, tile_b = 0, tile_e = 0;
     bool tile_quiet = false;
     if constexpr (TILE) {
@@ -257,18 +270,18 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
 #define RR_ST_B (TILE ? tile_b : L.stage_begin)
 #define RR_ST_E (TILE ? tile_e : stage_end)
 #define RR_FKEY (TILE ? (int)tile_seq : kS + st + 1)      /* (SPLIT) the stage the hand-over's flag names */
-    const int kS = TILE ? slot * L.S_total : kS_iv;
+    const int kS = TILE ? (P.page + slot) * L.S_total : kS_iv;
     const bool quiet = TILE ? tile_quiet : quiet_launch;
     if constexpr (TILE) {
-        w.gG = L.G ? L.G + (long)kS * n * gout : nullptr;
-        w.gY = (L.Y && !quiet) ? L.Y + (long)kS * n * ns : nullptr;
+        w.gG = L.G ? L.G + (long)kS * RR_KN * gout : nullptr;
+        w.gY = (L.Y && !quiet) ? L.Y + (long)kS * RR_KN * ns : nullptr;
     }
     for (int st = RR_ST_B; st < RR_ST_E; ++st) {
         const int sb = 2 + 8 * (st - RR_ST_B);
         (void)sb;
         if constexpr (TILE) ++tile_seq;
         if (st == RR_ST_B) {
-            if constexpr (TILE) rk_tile_first_input(L, T, row0, st, ph == 1, w.gY, sYin, tid, 256);
+            if constexpr (TILE) rk_tile_first_input(L, T, row0, st, ph == 1, w.gY, RR_KN, RR_KROW0, sYin, tid, 256);
             else rk_fwd_first_input(L, w, T, row0, st, 8, sYin, 8, !quiet, tid, 256);
             __syncthreads();
         }
@@ -281,7 +294,7 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
 #pragma unroll
             for (int j = 0; j < RK_MAX_STAGES; ++j) bn[j] = L.beta[sn][j];
         }
-        const long srow = (long)(kS + st) * n + grow;
+        const long srow = (long)(kS + st) * RR_KN + RR_KGROW;
         float Ha[KS], Hb[KS];             // activations ping-pong between two register sets
         f32x4 acc0[NB], acc[NB], bv[NB], bpre[3];
         unsigned wd = 0u;                 // the mask word being assembled (values arrive in ascending register order)
@@ -413,7 +426,7 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
                 if (grp == 0) T.sF[m * RK_MAX_NS + o_idx[r]] = val;
                 else {
                     T.sG[m * RK_MAX_GOUT + o_idx[r]] = val;
-                    if (row_ok && !quiet) w.gG[((long)st * n + grow) * gout + o_idx[r]] = val;
+                    if (row_ok && !quiet) w.gG[((long)st * RR_KN + RR_KGROW) * gout + o_idx[r]] = val;
                 }
             }
         };
@@ -540,7 +553,7 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
             if (cv) {
                 T.sK[(st * NLBAC_MLP_TILE + mm) * RK_MAX_NS + c] = a;
                 if (rv && !quiet && !TILE) w.gK[((long)st * n + row0 + mm) * ns + c] = a;      // (TILE: K_0..6 stay in LDS)
-                if (more && rv && (!TILE || w.gY)) w.gY[((long)(st + 1) * n + row0 + mm) * ns + c] = y;
+                if (more && rv && (!TILE || w.gY)) w.gY[((long)(st + 1) * RR_KN + RR_KROW0 + mm) * ns + c] = y;
             }
             if (more) sYin[mm * 8 + c] = cv ? y : 0.f;
         }
@@ -556,7 +569,7 @@ __device__ __forceinline__ void node_rr_fwd_body(const NodeRkLaunch& L, int H = 
 #undef RR_ST_E
 #undef RR_FKEY
     if constexpr (TILE) {
-        const int act = rk_tile_after_phase<256, DENSE>(L, *tile, T, sYin, sCtl, sInt, row0, n_rows, k, ph, slot, tid, dense);
+        const int act = rk_tile_after_phase<256, DENSE>(L, *tile, P, T, sYin, sCtl, sInt, row0, n_rows, k, ph, slot, tid, dense);
         if (act >= 2) {
             if constexpr (DENSE) rk_tile_dense_stop<256>(L, *tile, *dense, sCtl, row0, sInt[TI_OUT], TILE_NO_SLOT, tid);
             else rk_tile_stop<256>(L, *tile, row0, act == 3 ? k + 1 : k, TILE_NO_SLOT, tid);
@@ -646,6 +659,9 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
     const int growc = min(grow, n - 1);
     const int KS0 = (ns + 3) >> 2;
     const int KSO = (grp == 0) ? KS0 : KS0 * nu;          // k-steps of the output layer's transposed product (<= 4)
+    // (TILE) where the tile keeps its steps (see the forward)
+    [[maybe_unused]] NodeTilePlace P{};
+    if constexpr (TILE) P = rk_tile_place(tile->page0, tile->max_slots, n, row0, blockIdx.x);
     const bool keep_dz = L.dz[0] != nullptr;
 
     // ---- what the stage loop reads of the launch descriptor, once
@@ -656,8 +672,8 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
     // (WORDS) where the forward left the words: in place of the rows (1), or behind the net's nw layers of rows (2)
     const unsigned* const words = reinterpret_cast<const unsigned*>(BITS == 2 ? acts + (long)nw * acts_ls : acts);
     const int H = TRAJ ? X->H : (TILE ? tile->H : 1);
-    // (the stages the buffers hold: H S of a trajectory, max_slots S under TILE)
-    const long words_ls = (BITS == 2) ? (long)(TILE ? tile->max_slots : H) * L.S_total * n * 4 : acts_ls;
+    // (the stages the buffers hold: H S of a trajectory, max_slots S — paged: pages S — under TILE)
+    const long words_ls = (BITS == 2) ? (long)(TILE ? P.total : H) * L.S_total * RR_KN * 4 : acts_ls;
     const int dx_stage0 = L.dx_stage0;
 
     // ---- weight stream: backward fragments of layers nw-1 .. 1, then nw-1 again (next stage)
@@ -718,7 +734,7 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
         sBeta[tid] = (&L.beta[0][0])[tid];
     auto request_g = [&](int stn) __attribute__((always_inline)) {
         if (!du_thread || stn < w.st_lo) return;
-        const float* gp = w.gG + ((long)stn * n + min(row0 + du_m, n - 1)) * gout + du_c;
+        const float* gp = w.gG + ((long)stn * RR_KN + min(RR_KROW0 + du_m, RR_KN - 1)) * gout + du_c;
 #pragma unroll
         for (int r = 0; r < RK_MAX_NS; ++r) gnext[r] = gp[min(r, ns - 1) * nu];
     };
@@ -730,27 +746,27 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
     float t_x = 0.f;
     if constexpr (TILE && !DENSE) {
         const long ti = (long)blockIdx.x * H + k;
-        t_first = min(max(tile->iv_first[ti], 0), tile->max_slots - 1);
-        t_nacc = min(max(tile->iv_nacc[ti], 1), tile->max_slots - t_first);
+        t_first = min(max(tile->iv_first[ti], 0), P.slots - 1);
+        t_nacc = min(max(tile->iv_nacc[ti], 1), P.slots - t_first);
         t_x = tile->iv_x[ti];
     }
     // (DENSE) the one interval's steps are the slots 0 .. accepted - 1; d_je: the outputs no later step has taken
     [[maybe_unused]] int d_je = 0;
     if constexpr (DENSE) {
-        t_nacc = min(max(tile->iv_nacc[blockIdx.x], 1), tile->max_slots);
+        t_nacc = min(max(tile->iv_nacc[blockIdx.x], 1), P.slots);
         d_je = max(dense->n_out, 0);
     }
     // (TILE) the interval's steps come back to this label, last to first (a jump, not a loop: see the forward)
     int sj = TILE ? t_nacc - 1 : 0;
     [[maybe_unused]] tile_step:;
-    const int kS = TILE ? (t_first + sj) * L.S_total : kS_iv;
+    const int kS = TILE ? (P.page + t_first + sj) * L.S_total : kS_iv;
     if constexpr (TRAJ || TILE) {
-        w.gG = L.G + (long)kS * n * gout;
-        w.gdG = L.dG ? L.dG + (long)kS * n * gout : nullptr;
-        w.gdK = L.dK ? L.dK + (long)kS * n * ns : nullptr;
+        w.gG = L.G + (long)kS * RR_KN * gout;
+        w.gdG = L.dG ? L.dG + (long)kS * RR_KN * gout : nullptr;
+        w.gdK = L.dK ? L.dK + (long)kS * RR_KN * ns : nullptr;
         if constexpr (TILE) {
             w.st_lo = sj == 0 ? 0 : 1;
-            const float h = (float)tile->hslots[(long)blockIdx.x * tile->max_slots + t_first + sj];
+            const float h = (float)tile->hslots[P.hbase + t_first + sj];
             if constexpr (DENSE) rk_tile_dense_bwd_begin<256>(L, *tile, *dense, T, row0, sj, sj == t_nacc - 1, h, d_je, tid);
             else rk_tile_bwd_begin<256>(L, *tile, T, row0, k, kk, sj == t_nacc - 1, h, t_x, tid);
         } else {
@@ -789,7 +805,7 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
                 const bool ok = (grp == 0) ? (e < KS0 && c < ns) : (e < KS0 * nu && c < ns);
                 const float v = (grp == 0) ? dk[e] : dk[e] * uu[e];
                 dy[e] = ok ? v : 0.f;
-                if (grp != 0 && ok && w.gdG && row_ok) w.gdG[((long)st * n + grow) * gout + c * nu + u] = v;
+                if (grp != 0 && ok && w.gdG && row_ok) w.gdG[((long)st * RR_KN + RR_KGROW) * gout + c * nu + u] = v;
             }
             if (du_thread) {        // du += g(Y_st)^T dK_st (rk_bwd_du's sum, same order)
                 float a = 0.f;
@@ -801,7 +817,7 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
         if (!data) continue;              // uniform: nothing below is needed for this stage
         BWSTAMP(sbw + 1)
 
-        const long srow = (long)(kS + st) * n + growc;
+        const long srow = (long)(kS + st) * RR_KN + RR_KGROWC;
         float Za[KS], Zb[KS];              // dz ping-pong between two register sets
         f32x4 acct[NB], acc[NB], zero[NB];
 #pragma unroll
@@ -825,7 +841,7 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
         // like the forward's activations (see there)
         auto save_dz = [&](int l, const float (&Z)[KS]) __attribute__((always_inline)) {
             if (!DZ || !dz || !row_ok) return;
-            float* rowp = dz + (long)l * acts_ls + ((long)(kS + st) * n + grow) * HID;
+            float* rowp = dz + (long)l * acts_ls + ((long)(kS + st) * RR_KN + RR_KGROW) * HID;
 #pragma unroll
             for (int jo = 0; jo < NB; ++jo) {
                 f32x4 zv{0.f, 0.f, 0.f, 0.f};
@@ -972,7 +988,7 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
                 if (WORDS) {
                     const unsigned* const wordsF = reinterpret_cast<const unsigned*>(
                         BITS == 2 ? actsF + (long)(netF.n_layers - 1) * L.acts_ls[0] : actsF);
-                    mwF = wordsF[2 * (BITS == 2 ? (long)(TILE ? tile->max_slots : H) * L.S_total * n * 4 : L.acts_ls[0]) + srow * 4 + q];
+                    mwF = wordsF[2 * (BITS == 2 ? (long)(TILE ? P.total : H) * L.S_total * RR_KN * 4 : L.acts_ls[0]) + srow * 4 + q];
                     mwF = row_ok ? mwF : 0u;
                 } else {
                     const float* arow = actsF + 2 * L.acts_ls[0] + srow * HID;
@@ -1048,13 +1064,18 @@ __device__ __forceinline__ void node_rr_bwd_body(const NodeRkBwdLaunch& L, const
         __syncthreads();
     }
     if constexpr (TILE) {
-        rk_tile_bwd_end<256, DENSE>(L, *tile, w, T, row0, k, sj, tid);
+        rk_tile_bwd_end<256, DENSE>(L, *tile, P, w, T, row0, k, sj, tid);
         __syncthreads();
         if (--sj >= 0) goto tile_step;
     }
     }
     if constexpr (!TRAJ && !TILE) rk_bwd_outputs<256>(L, w, T, row0, tid);
 }
+
+#undef RR_KN
+#undef RR_KROW0
+#undef RR_KGROW
+#undef RR_KGROWC
 
 // ---------------------------------------------------------------------------------------------------------------------
 // host side: which instance of a kernel template serves a launch, and with how much LDS — one definition for the

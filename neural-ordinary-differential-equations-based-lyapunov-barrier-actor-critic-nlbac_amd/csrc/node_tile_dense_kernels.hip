@@ -45,18 +45,19 @@ __global__ __launch_bounds__(256) void node_tile_dense_bwd_kernel(const NodeTile
 // of the outputs it has not emitted.  G non-null: a backward follows — the kept buffers of nlbac_node_dopri_tile_fwd
 // (max_slots slots per tile, zero on entry), and ov_slot / ov_x [tiles][n_out]: the slot that emitted output j and its
 // abscissa.  G null: nothing is kept and no slot runs out.
-extern "C" int nlbac_node_dopri_tile_dense_fwd(const nlbac_mlp* f, const nlbac_mlp* g, const float* x0, const float* u,
-                                               int n, const float* beta, const float* c_err, const double* tau, int n_out,
-                                               double t_end, float rtol, float atol, float* out, int max_slots, float* Y,
-                                               float* G, float* acts_f, long acts_f_ls, float* acts_g, long acts_g_ls,
-                                               int acts_bits, double* hslots, int* ov_slot, float* ov_x, int* accepted,
-                                               int* attempts, int* status, nlbac_stream_t s) {
+// The *_paged_* entry points: the same launches with the slots counted per tile, as node_tile_kernels.hip's — page0
+// [tiles + 1] and `pages` in place of max_slots, the kept buffers pages x 7 stages x 32 rows, hslots [pages]; ov_slot
+// stays relative to the tile.  A forward that keeps nothing takes no page0 (null, pages 0).
+static int tile_dense_fwd(const char* who, const nlbac_mlp* f, const nlbac_mlp* g, const float* x0, const float* u, int n,
+                          const float* beta, const float* c_err, const double* tau, int n_out, double t_end, float rtol,
+                          float atol, float* out, const int* page0, int max_slots, float* Y, float* G, float* acts_f,
+                          long acts_f_ls, float* acts_g, long acts_g_ls, int acts_bits, double* hslots, int* ov_slot,
+                          float* ov_x, int* accepted, int* attempts, int* status, nlbac_stream_t s) {
     static const NodeRrTable<NodeTileDenseFwdLaunch> table = NODE_RR_FWD_TABLE(node_tile_dense_fwd_kernel);
-    const char* who = "nlbac_node_dopri_tile_dense_fwd";
     NodeTileDenseFwdLaunch A;
     memset(&A, 0, sizeof(A));
     if (tile_fill_fwd(A.L, A.X, who, 1, n_out, "output times", "1", f, g, x0, u, n, beta, c_err, t_end, rtol, atol, out,
-                      max_slots, Y, G, acts_f, acts_f_ls, acts_g, acts_g_ls, acts_bits, hslots, accepted, attempts, status))
+                      page0, max_slots, Y, G, acts_f, acts_f_ls, acts_g, acts_g_ls, acts_bits, hslots, accepted, attempts, status))
         return -1;
     NLBAC_REQUIRE(tau, "%s: null pointer", who);
     NLBAC_REQUIRE(!G || (ov_slot && ov_x), "%s: G, the acts and the slot arrays go together", who);
@@ -66,22 +67,44 @@ extern "C" int nlbac_node_dopri_tile_dense_fwd(const nlbac_mlp* f, const nlbac_m
     return 0;
 }
 
+extern "C" int nlbac_node_dopri_tile_dense_fwd(const nlbac_mlp* f, const nlbac_mlp* g, const float* x0, const float* u,
+                                               int n, const float* beta, const float* c_err, const double* tau, int n_out,
+                                               double t_end, float rtol, float atol, float* out, int max_slots, float* Y,
+                                               float* G, float* acts_f, long acts_f_ls, float* acts_g, long acts_g_ls,
+                                               int acts_bits, double* hslots, int* ov_slot, float* ov_x, int* accepted,
+                                               int* attempts, int* status, nlbac_stream_t s) {
+    return tile_dense_fwd("nlbac_node_dopri_tile_dense_fwd", f, g, x0, u, n, beta, c_err, tau, n_out, t_end, rtol, atol, out,
+                          nullptr, max_slots, Y, G, acts_f, acts_f_ls, acts_g, acts_g_ls, acts_bits, hslots, ov_slot, ov_x,
+                          accepted, attempts, status, s);
+}
+
+extern "C" int nlbac_node_dopri_tile_dense_paged_fwd(const nlbac_mlp* f, const nlbac_mlp* g, const float* x0,
+                                                     const float* u, int n, const float* beta, const float* c_err,
+                                                     const double* tau, int n_out, double t_end, float rtol, float atol,
+                                                     float* out, const int* page0, int pages, float* Y, float* G,
+                                                     float* acts_f, long acts_f_ls, float* acts_g, long acts_g_ls,
+                                                     int acts_bits, double* hslots, int* ov_slot, float* ov_x,
+                                                     int* accepted, int* attempts, int* status, nlbac_stream_t s) {
+    const char* who = "nlbac_node_dopri_tile_dense_paged_fwd";
+    NLBAC_REQUIRE(page0 ? pages > 0 : (pages == 0 && !G), "%s: page0 and pages go together, and with G", who);
+    return tile_dense_fwd(who, f, g, x0, u, n, beta, c_err, tau, n_out, t_end, rtol, atol, out, page0, pages, Y, G, acts_f,
+                          acts_f_ls, acts_g, acts_g_ls, acts_bits, hslots, ov_slot, ov_x, accepted, attempts, status, s);
+}
+
 // One launch: the backward of the solve nlbac_node_dopri_tile_dense_fwd kept, every tile's slots last to first.
 // nacc [tiles]: the forward's `accepted`.  dout [n_out][n][n_s]: the gradients of the outputs 1 .. n_out; dx0 [n][n_s]
 // (slot 0's dy0 — the gradient of out[0] is the caller's to add), du [n][n_u]; dK / dG / dz_* (all or none; zero on
 // entry) per (slot, stage, row) for the weight gradients.  Only tiles whose status is TILE_OK have a backward: the
 // caller reads status first.  What is read of nacc / ov_slot is clamped to the slots and the outputs.
-extern "C" int nlbac_node_dopri_tile_dense_bwd(const nlbac_mlp* f, const nlbac_mlp* g, const float* u, int n,
-                                               const float* beta, int n_out, int max_slots, const double* hslots,
-                                               const int* ov_slot, const float* ov_x, const int* nacc, const float* G,
-                                               const float* acts_f, long acts_f_ls, const float* acts_g, long acts_g_ls,
-                                               int acts_bits, const float* dout, float* dx0, float* du, float* dK,
-                                               float* dG, float* dz_f, float* dz_g, nlbac_stream_t s) {
+static int tile_dense_bwd(const char* who, const nlbac_mlp* f, const nlbac_mlp* g, const float* u, int n, const float* beta,
+                          int n_out, const int* page0, int max_slots, const double* hslots, const int* ov_slot,
+                          const float* ov_x, const int* nacc, const float* G, const float* acts_f, long acts_f_ls,
+                          const float* acts_g, long acts_g_ls, int acts_bits, const float* dout, float* dx0, float* du,
+                          float* dK, float* dG, float* dz_f, float* dz_g, nlbac_stream_t s) {
     static const NodeRrTable<NodeTileDenseBwdLaunch> table = NODE_RR_BWD_TABLE(node_tile_dense_bwd_kernel);
-    const char* who = "nlbac_node_dopri_tile_dense_bwd";
     NodeTileDenseBwdLaunch A;
     memset(&A, 0, sizeof(A));
-    if (tile_fill_bwd(A.L, A.X, who, 1, n_out, "output times", "1", f, g, u, n, beta, max_slots, hslots, nacc, G, acts_f,
+    if (tile_fill_bwd(A.L, A.X, who, 1, n_out, "output times", "1", f, g, u, n, beta, page0, max_slots, hslots, nacc, G, acts_f,
                       acts_f_ls, acts_g, acts_g_ls, acts_bits, dout, dx0, du, dK, dG, dz_f, dz_g))
         return -1;
     NLBAC_REQUIRE(ov_slot && ov_x, "%s: null pointer", who);
@@ -89,4 +112,27 @@ extern "C" int nlbac_node_dopri_tile_dense_bwd(const nlbac_mlp* f, const nlbac_m
     node_rr_start(table, A, f->hid, n, acts_bits, node_rr_bwd_lds_floats(), (hipStream_t)s);
     NLBAC_CHECK_LAUNCH(who);
     return 0;
+}
+
+extern "C" int nlbac_node_dopri_tile_dense_bwd(const nlbac_mlp* f, const nlbac_mlp* g, const float* u, int n,
+                                               const float* beta, int n_out, int max_slots, const double* hslots,
+                                               const int* ov_slot, const float* ov_x, const int* nacc, const float* G,
+                                               const float* acts_f, long acts_f_ls, const float* acts_g, long acts_g_ls,
+                                               int acts_bits, const float* dout, float* dx0, float* du, float* dK,
+                                               float* dG, float* dz_f, float* dz_g, nlbac_stream_t s) {
+    return tile_dense_bwd("nlbac_node_dopri_tile_dense_bwd", f, g, u, n, beta, n_out, nullptr, max_slots, hslots, ov_slot,
+                          ov_x, nacc, G, acts_f, acts_f_ls, acts_g, acts_g_ls, acts_bits, dout, dx0, du, dK, dG, dz_f, dz_g, s);
+}
+
+extern "C" int nlbac_node_dopri_tile_dense_paged_bwd(const nlbac_mlp* f, const nlbac_mlp* g, const float* u, int n,
+                                                     const float* beta, int n_out, const int* page0, int pages,
+                                                     const double* hslots, const int* ov_slot, const float* ov_x,
+                                                     const int* nacc, const float* G, const float* acts_f,
+                                                     long acts_f_ls, const float* acts_g, long acts_g_ls, int acts_bits,
+                                                     const float* dout, float* dx0, float* du, float* dK, float* dG,
+                                                     float* dz_f, float* dz_g, nlbac_stream_t s) {
+    const char* who = "nlbac_node_dopri_tile_dense_paged_bwd";
+    NLBAC_REQUIRE(page0, "%s: null page0", who);
+    return tile_dense_bwd(who, f, g, u, n, beta, n_out, page0, pages, hslots, ov_slot, ov_x, nacc, G, acts_f, acts_f_ls,
+                          acts_g, acts_g_ls, acts_bits, dout, dx0, du, dK, dG, dz_f, dz_g, s);
 }

@@ -54,27 +54,34 @@ def _taus(t):
     return tuple(v - times[0] for v in times[1:])
 
 
-def _check_tile(func, n, step_control, max_steps, info):
-    """The checks of ``step_control`` / ``max_steps`` / ``info`` (``func`` is a NeuralODEModel, ``n`` its rows); returns
-    the slots a tile gets (``max_steps``, or 32), None under the batch-wide control."""
+def _check_tile(func, n, step_control, max_steps, info, tile_steps=None):
+    """The checks of ``step_control`` / ``max_steps`` / ``info`` / ``tile_steps`` (``func`` is a NeuralODEModel, ``n`` its
+    rows); returns the slots a tile gets (``max_steps``, or 32), None under the batch-wide control — and, where
+    ``tile_steps`` counts them per tile, ``ode_traj.tile_steps_arg``'s form of it."""
     if step_control not in STEP_CONTROLS:
         raise ValueError("odeint_dense: step_control is one of %s; got %r" % (", ".join(STEP_CONTROLS), step_control))
     if step_control == "batch":
-        if max_steps is not None or info is not None:
-            raise ValueError("odeint_dense: max_steps and info go with step_control='tile' (the batch-wide control keeps "
-                             "its steps in the solver's slot pool and reports through the solver)")
+        if max_steps is not None or info is not None or tile_steps is not None:
+            raise ValueError("odeint_dense: max_steps, tile_steps and info go with step_control='tile' (the batch-wide "
+                             "control keeps its steps in the solver's slot pool and reports through the solver)")
         return None
     if info is not None and not isinstance(info, dict):
         raise ValueError("odeint_dense: info is a dict (it receives the device tensors accepted / attempts / status) or "
                          "None; got %s" % type(info).__name__)
-    if max_steps is None:
-        max_steps = TILE_MAX_STEPS
-    if isinstance(max_steps, bool) or not isinstance(max_steps, int) or max_steps < 1:
-        raise ValueError("odeint_dense: max_steps must be an int >= 1 (the accepted steps a tile may keep) or None (%d); "
-                         "got %r" % (TILE_MAX_STEPS, max_steps))
-    if max_steps * 7 * n >= 2 ** 31:
-        raise ValueError("odeint_dense: max_steps * 7 stages * %d rows is 2^31 or more (the launch's limit: %d * 7 * %d); "
-                         "use a smaller max_steps or fewer rows" % (n, max_steps, n))
+    if tile_steps is not None:
+        if max_steps is not None:
+            raise ValueError("odeint_dense: tile_steps (a slot count per tile) and max_steps (one for all tiles) exclude "
+                             "each other; got both")
+        T.check_tile_steps("odeint_dense", tile_steps, n, 1, "a solve keeps at least one step")
+    else:
+        if max_steps is None:
+            max_steps = TILE_MAX_STEPS
+        if isinstance(max_steps, bool) or not isinstance(max_steps, int) or max_steps < 1:
+            raise ValueError("odeint_dense: max_steps must be an int >= 1 (the accepted steps a tile may keep) or None "
+                             "(%d); got %r" % (TILE_MAX_STEPS, max_steps))
+        if max_steps * 7 * n >= 2 ** 31:
+            raise ValueError("odeint_dense: max_steps * 7 stages * %d rows is 2^31 or more (the launch's limit: %d * 7 * "
+                             "%d); use a smaller max_steps or fewer rows" % (n, max_steps, n))
     if not func.affine:
         raise NotImplementedError("odeint_dense: step_control='tile' serves the control-affine NODE only "
                                   "(nlbac_node_dopri_tile_ok); the single-net form is left open")
@@ -82,7 +89,7 @@ def _check_tile(func, n, step_control, max_steps, info):
         raise NotImplementedError("odeint_dense: step_control='tile' needs nets the register-resident kernels serve "
                                   "(nlbac_node_dopri_tile_ok: both nets 64, 100 or 128 wide, f_net five layers, g_net "
                                   "four); there is no other path under tile-local control")
-    return max_steps
+    return max_steps if tile_steps is None else T.tile_steps_arg(tile_steps)
 
 
 def _check_device(y0):
@@ -133,7 +140,8 @@ def solver_of(func, mode):
     return sv
 
 
-def odeint_dense(func, y0, t, *, atol=1e-7, rtol=1e-5, adjoint=False, step_control="batch", max_steps=None, info=None):
+def odeint_dense(func, y0, t, *, atol=1e-7, rtol=1e-5, adjoint=False, step_control="batch", max_steps=None, info=None,
+                 tile_steps=None):
     """The dopri5 solution of the NODE ``func`` (either form; a model owned by an agent included) at every point of the
     time grid ``t`` (1-D tensor or sequence, T >= 2 finite strictly increasing times): returns ``out`` (T, B, n_s + n_c)
     with ``out[0] = y0``, from ONE adaptive solve over ``[t[0], t[-1]]``.  ``y0`` (B, n_s + n_c) is CUDA float32,
@@ -166,19 +174,37 @@ def odeint_dense(func, y0, t, *, atol=1e-7, rtol=1e-5, adjoint=False, step_contr
     device tensors without a synchronisation: ``accepted`` and ``attempts`` (n_tiles,) int32 and ``status`` (n_tiles,)
     int32 — 0 ok, 1 no slot left, 2 attempt cap.  ``max_steps`` / ``info`` with ``"batch"`` are a ``ValueError``.
 
+    ``tile_steps`` (with ``"tile"`` only, in place of ``max_steps``: both is a ``ValueError``) counts the slots PER TILE,
+    as in ``rollout``: a sequence of ints or a 1-D integer CPU tensor, one entry >= 1 per tile (``ceil(B / 32)``; a CUDA
+    tensor is a ``ValueError`` asking for ``.cpu()``), gives tile j exactly ``tile_steps[j]`` slots.  The kept buffers
+    hold ``sum(tile_steps)`` pages of 7 stages x 32 rows, not ``max_steps * n_tiles`` — per page, with n_g = n_s n_u:
+    input gradients 224 (4 n_g + 112) bytes; parameter gradients 224 (4 n_g + 4 n_s + 28 hid + 112) forward and
+    224 (4 n_g + 4 n_s + 28 hid) more in the backward — and the weight-gradient launch walks ``sum * 7 * 32`` rows
+    (``>= 2**31``: a ``ValueError``).  Values and input gradients are those of a ``max_steps`` call that suffices, bit
+    for bit; parameter gradients to summation order.  A tile that needs more than its own count stops as above, and
+    the backward's ``NlbacError`` names ``tile_steps`` and that tile's count.  ``tile_steps="count"``: the forward launch
+    runs once with nothing kept (the same kernel instance, hence the same steps), the tiles' counts come to the host,
+    and the kept forward runs with exactly those — ONE EXTRA FORWARD LAUNCH AND ONE HOST WAIT per call; under
+    ``torch.no_grad()`` nothing is kept and nothing is counted.  ``info`` also receives ``slots``: the int32 CPU tensor
+    of per-tile counts the buffers were sized with, to pass back in on the next call over similar inputs.
+
     Raises instead of running some other way: decreasing ``t`` (``ValueError``), ``adjoint=True`` (``NotImplementedError``),
     under ``"batch"`` a call inside a hipGraph capture (``RuntimeError``: the solve needs the host's look at the control
     block; the tile-local solve needs no look) and a solver whose device-driven chain is not available — nets the fused
     step kernels refuse, or ``device_loop`` off (``NotImplementedError``); under ``"tile"`` the single-net form and nets
     the register-resident kernels refuse (``NotImplementedError`` naming ``nlbac_node_dopri_tile_ok``)."""
     taus = _check_args(func, y0, t, atol, rtol, adjoint)
-    slots = _check_tile(func, y0.shape[0], step_control, max_steps, info)
+    slots = _check_tile(func, y0.shape[0], step_control, max_steps, info, tile_steps)
     _check_device(y0)
     if slots is not None:
         # the tile-local solve: no solver, no chain — the cached solvers of the batch-wide control are not touched
         params = tuple(func.parameters())
         func.refresh_device_weights()
-        solve = _DenseTileSolve(func, taus, float(atol), float(rtol), T.keep_mode(params, y0), slots, info)
+        mode = T.keep_mode(params, y0)
+        if tile_steps is None:
+            solve = _DenseTileSolve(func, taus, float(atol), float(rtol), mode, slots, info)
+        else:      # (the slots are counted per tile: ``slots`` is tile_steps as the solve takes it)
+            solve = _DenseTileSolve(func, taus, float(atol), float(rtol), mode, None, info, slots)
         return SolveNode.apply(solve, 1, y0, *params)
     if torch.cuda.is_current_stream_capturing():
         raise RuntimeError("odeint_dense: not inside a hipGraph capture — the adaptive solve needs the host's look at the "
@@ -265,13 +291,16 @@ class _DenseTileSolve(PackedSolve):
     packed layout."""
     api = "odeint_dense"
 
-    def __init__(self, func, taus, atol, rtol, mode, slots, info):
+    def __init__(self, func, taus, atol, rtol, mode, slots, info, tile_steps=None):
+        """``slots``: every tile's (``max_steps``), or None with ``tile_steps`` (``ode_traj.tile_steps_arg``'s)."""
         PackedSolve.__init__(self, func)
         self.taus, self.tol, self.mode, self.slots, self.info = taus, (atol, rtol), mode, slots, info
+        self.tile_steps = tile_steps
         self.n_out, self.with_params = len(taus), mode == "params"
 
     def solve(self, x0, c, xs):
-        tile = T.AffineTileDense(self.func, x0.shape[0], self.taus, self.slots, self.info, self.mode, *self.tol, x0.device)
+        tile = T.AffineTileDense(self.func, x0.shape[0], self.taus, self.slots, self.info, self.mode, *self.tol, x0.device,
+                                 self.tile_steps)
         tile.forward(x0, c, xs)
         self.kept = tile if self.mode != "none" else None
 

@@ -19,6 +19,7 @@
     ``Chain(adjoint=True)`` / ``ChainSubAdjoint`` (chained); the same ``backward``, which here needs ``out``.
 """
 import ctypes as C
+import numbers
 
 import torch
 
@@ -247,11 +248,18 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
+def _acts_bits(mode):
+    """The entry points' ``acts_bits`` of keep mode ``mode`` — which also picks the kernel instance of a launch that
+    keeps nothing."""
+    words = mode == "inputs" or (mode == "params" and env_switch("fit_words"))
+    return 0 if mode == "none" else (1 if mode == "inputs" else (2 if words else 0))
+
+
 def _kept_acts(f, g, rows, mode, alloc):
     """What the control-affine form keeps of the hidden layers over ``rows`` stage rows (stages * n), from ``alloc``:
     (acts_bits, the two nets' buffers, their layer strides)."""
-    words = mode == "inputs" or (mode == "params" and env_switch("fit_words"))
-    bits = 0 if mode == "none" else (1 if mode == "inputs" else (2 if words else 0))
+    bits = _acts_bits(mode)
+    words = bits != 0
     acts, ls = [None, None], [0, 0]
     if mode != "none":
         for i, net in enumerate((f, g)):
@@ -392,14 +400,70 @@ class ConcatTraj:
                                              self.ls, dz, HS * n, dev)
 
 
+def tile_steps_arg(tile_steps):
+    """``tile_steps`` as the solve classes take it: None, ``"count"`` or a 1-D int32 CPU tensor (``check_tile_steps`` has
+    checked it)."""
+    if tile_steps is None or isinstance(tile_steps, str):
+        return tile_steps
+    if isinstance(tile_steps, torch.Tensor):
+        return tile_steps.to(torch.int32)
+    return torch.tensor([int(v) for v in tile_steps], dtype=torch.int32)
+
+
+_INT_DTYPES = (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
+
+
+def check_tile_steps(api, tile_steps, n, least, why):
+    """The checks of a ``tile_steps`` that is not None, for ``n`` rows — nothing here touches a device: ``"count"``, or
+    one int >= ``least`` per 32-row tile (``why``: what the least stands for) as a sequence or a 1-D integer CPU tensor,
+    ``sum * 7 * 32`` below 2^31.  (A tensor is checked as a whole: no Python loop over the tiles of a large batch.)"""
+    if isinstance(tile_steps, str):
+        if tile_steps != "count":
+            raise ValueError("%s: tile_steps is None, 'count' or one int per tile; got %r" % (api, tile_steps))
+        return
+    if isinstance(tile_steps, torch.Tensor):
+        if tile_steps.device.type != "cpu":
+            raise ValueError("%s: tile_steps must be a CPU tensor (pass tile_steps.cpu(): the forward does not "
+                             "synchronise behind the caller's back); got one on %s" % (api, tile_steps.device))
+        if tile_steps.dim() != 1 or tile_steps.dtype not in _INT_DTYPES:
+            raise ValueError("%s: a tile_steps tensor is 1-D and of an integer dtype; got %s of %s"
+                             % (api, tuple(tile_steps.shape), tile_steps.dtype))
+        count = tile_steps.numel()
+        low, total = (int(tile_steps.min()), int(tile_steps.sum(dtype=torch.int64))) if count else (least, 0)
+    else:
+        try:
+            vals = list(tile_steps)
+        except TypeError:
+            raise ValueError("%s: tile_steps is None, 'count' or one int per tile (a sequence or a 1-D integer CPU "
+                             "tensor); got %s" % (api, type(tile_steps).__name__)) from None
+        if set(map(type, vals)) - {int}:      # (anything but plain ints: look at each)
+            for v in vals:
+                if isinstance(v, torch.Tensor):
+                    raise ValueError("%s: the entries of tile_steps are Python ints (a tensor goes in whole, as a 1-D "
+                                     "integer CPU tensor); got a sequence of tensors" % api)
+                if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+                    raise ValueError("%s: every entry of tile_steps must be an int; got %r" % (api, v))
+        count = len(vals)
+        low, total = (min(vals), sum(vals)) if count else (least, 0)
+    tiles = (n + _lib.MLP_TILE - 1) // _lib.MLP_TILE
+    if count != tiles:
+        raise ValueError("%s: tile_steps has one entry per 32-row tile, %d for %d rows; got %d" % (api, tiles, n, count))
+    if low < least:
+        raise ValueError("%s: every entry of tile_steps must be >= %d (%s); got %d" % (api, least, why, low))
+    if total * 7 * _lib.MLP_TILE >= 2 ** 31:
+        raise ValueError("%s: sum(tile_steps) * 7 stages * 32 rows is 2^31 or more (the launch's limit: %d * 7 * 32); use "
+                         "fewer slots or fewer rows" % (api, total))
+
+
 class TileSteps(EqualSteps):
     """``EqualSteps`` solved by dopri5 under tile-local step control (``rollout(step_control="tile")``): every 32-row tile
-    an adaptive solve of its own, ``max_steps`` step slots per tile for the whole horizon when a backward follows;
-    ``info`` (a dict or None) receives the solve's device tensors."""
+    an adaptive solve of its own, ``max_steps`` step slots per tile for the whole horizon when a backward follows — or,
+    with ``tile_steps`` (``tile_steps_arg``'s: ``"count"`` or a tensor, ``max_steps`` then None), a count of its own per
+    tile; ``info`` (a dict or None) receives the solve's device tensors."""
 
-    def __init__(self, dt, H, max_steps, info=None):
+    def __init__(self, dt, H, max_steps, info=None, tile_steps=None):
         EqualSteps.__init__(self, dt, H)
-        self.max_steps, self.info = max_steps, info
+        self.max_steps, self.info, self.tile_steps = max_steps, info, tile_steps
 
 
 class AffineTile:
@@ -409,7 +473,15 @@ class AffineTile:
     slot per accepted step of a tile: ``AffineTraj``'s layout with the slot in place of the interval; zero-filled, so
     that a stage nobody evaluated (a slot a tile did not use, stage 0 of a step that took it from the step before) adds
     nothing to the weight gradients.  A leaf has ``api`` and ``words`` (what differs in the stopped-tile message),
-    ``du_shape``, ``_nacc()``, the arrays that say where its outputs lie in the slots, and its launches ``_fwd`` / ``_bwd``."""
+    ``least`` (the slots a tile needs at least), ``du_shape``, ``_nacc()``, the arrays that say where its outputs lie in
+    the slots, and its launches ``_fwd`` / ``_bwd``.
+
+    With ``tile_steps`` (``tile_steps_arg``'s) the slots are counted per tile and the kept buffers are PAGED: tile j owns
+    ``slots[j]`` pages of 7 stages x 32 rows, the buffers hold ``pages = sum(slots)`` of them — [page][stage][32 rows],
+    the layout above with 32 in place of n and the page in place of the slot — and ``page0``, the exclusive prefix sum,
+    goes to the device once; the launches are the ``*_paged_*`` entry points.  ``"count"``: the forward first runs the
+    same entry with nothing kept, brings the tiles' counts of accepted steps to the host (the one wait of such a
+    forward) and sizes the buffers by exactly those."""
     S = 7
 
     @staticmethod
@@ -431,7 +503,7 @@ class AffineTile:
         f, g = func.device_handles()
         return _lib.load().nlbac_node_dopri_tile_ok(C.byref(f.desc), C.byref(g.desc)) == 1
 
-    def __init__(self, func, n, counts, max_steps, info, mode, atol, rtol, device):
+    def __init__(self, func, n, counts, max_steps, info, mode, atol, rtol, device, tile_steps=None):
         """``counts``: the shape of a tile's ``accepted`` / ``attempts`` (a count per interval; one for a dense solve)."""
         if not self.ok(func):
             raise NotImplementedError("%s: step_control='tile' needs nets the register-resident kernels serve "
@@ -441,27 +513,62 @@ class AffineTile:
         self.ns, self.nu, self.n = func.n_s, func.n_u, n
         self.beta, self.c_err = _tableau("dopri5")[1], fptr(*DP_C_ERR)
         self.tiles = (n + _lib.MLP_TILE - 1) // _lib.MLP_TILE
-        z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=device)
-        self.accepted, self.attempts = z(self.tiles, *counts, dtype=torch.int32), z(self.tiles, *counts, dtype=torch.int32)
-        self.status = z(self.tiles, dtype=torch.int32)
-        self.M = max_steps if mode != "none" else 0
-        MS = self.M * self.S
-        self.G = self.Y = self.hslots = None
-        if mode != "none":
-            self.G = z(MS, n, self.ns * self.nu)
-            self.Y = z(MS, n, self.ns) if mode == "params" else None
-            self.hslots = z(self.tiles, self.M, dtype=torch.float64)
-            self._interval_arrays(z)
-        self.bits, self.acts, self.ls = _kept_acts(f, g, MS * n, mode, z)
+        self.device, self.counts, self.paged = device, counts, tile_steps is not None
+        self._counters()
+        self.M = self.pages = 0      # (the slots every tile has; paged: the pages of all tiles)
+        self.G = self.Y = self.hslots = self.slots = self.page0 = None
+        self.bits, self.acts, self.ls = _acts_bits(mode), [None, None], [0, 0]
+        counting = isinstance(tile_steps, str)      # ("count": the buffers wait for the forward's first pass)
+        if self.paged and not counting:
+            self.slots = tile_steps
+        if mode != "none" and not counting:
+            self._keep(tile_steps if self.paged else max_steps)
+
+    def _counters(self):
+        z = lambda *s: torch.zeros(*s, dtype=torch.int32, device=self.device)
+        self.accepted, self.attempts, self.status = z(self.tiles, *self.counts), z(self.tiles, *self.counts), z(self.tiles)
+
+    def _keep(self, slots):
+        """The kept buffers (zero-filled): ``slots`` an int — that many slots for every tile, [slot][stage][n rows] — or
+        an int32 CPU tensor, one count per tile: paged."""
+        z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=self.device)
+        if self.paged:
+            self.slots = slots
+            page0 = torch.zeros(self.tiles + 1, dtype=torch.int32)
+            torch.cumsum(slots, 0, dtype=torch.int32, out=page0[1:])
+            self.pages = int(page0[-1])
+            self.page0 = page0.to(self.device)
+            stages, rows, hs = self.pages * self.S, _lib.MLP_TILE, (self.pages,)
+        else:
+            self.M = slots
+            stages, rows, hs = self.M * self.S, self.n, (self.tiles, self.M)
+        self.G = z(stages, rows, self.ns * self.nu)
+        self.Y = z(stages, rows, self.ns) if self.mode == "params" else None
+        self.hslots = z(*hs, dtype=torch.float64)
+        self._interval_arrays(z)
+        self.bits, self.acts, self.ls = _kept_acts(self.f, self.g, stages * rows, self.mode, z)
 
     def _interval_arrays(self, z):
         """A leaf's kept arrays that come between ``hslots`` and the activations in the order of allocation."""
 
+    def _slot_args(self):
+        """What the entry points take for the slots: ``max_slots``, or (paged) ``page0`` and the pages."""
+        return (_ptr(self.page0), self.pages) if self.paged else (self.M,)
+
     def forward(self, x0, u, xs):
         self.u = u
+        if self.paged and self.G is None and self.mode != "none":
+            # tile_steps="count": the launch as it will be kept (acts_bits picks the same kernel instance, so the steps
+            # are the same), nothing kept; the tiles' counts come to the host, and the buffers hold exactly those
+            self._fwd(x0, u, xs, *self.tol)
+            seen = self._nacc().cpu().clamp_(min=self.least)      # (a tile that stopped at the attempt cap stops again)
+            self._counters()
+            self._keep(seen)
         self._fwd(x0, u, xs, *self.tol)
         if self.info is not None:
             self.info.update(accepted=self.accepted, attempts=self.attempts, status=self.status)
+            if self.paged:
+                self.info.update(slots=self.slots)
 
     def backward(self, dout, need_p, out=None):
         """``dout``: the outputs' gradients as the leaf's launch takes them.  Returns (dx0: the first step's dy0, the
@@ -476,12 +583,21 @@ class AffineTile:
 
     def _look(self):
         """The one look at the solve, long after its launch has finished: every tile's status and count of accepted steps
-        (the leaf's ``_nacc()``) come to the host.  Returns the largest count, the slots in use; raises if a tile stopped."""
+        (the leaf's ``_nacc()``) come to the host.  Returns the largest count, the slots in use; raises if a tile stopped
+        (paged: a tile's count is held against its own slots)."""
         seen = torch.stack((self.status, self._nacc())).cpu()
         used = int(seen[1].max())
         bad = seen[0].nonzero().flatten().tolist()
         if bad:
             why = {1: "ran out of step slots", 2: "took more than 1000 attempts" + self.words[0]}
+            if self.paged:
+                j = bad[0]
+                raise _lib.NlbacError(
+                    "%s(step_control='tile'): tile %d %s (status %d; %d of %d tiles stopped), so the solve has no "
+                    "backward: tile_steps[%d] = %d slots, and the tile had kept %d accepted steps when it stopped — give "
+                    "that tile more (info['accepted'] of a max_steps run has the counts), or pass tile_steps='count'"
+                    % (self.api, j, why.get(int(seen[0][j]), "stopped"), int(seen[0][j]), len(bad), self.tiles, j,
+                       int(self.slots[j]), int(seen[1][j])))
             raise _lib.NlbacError(
                 "%s(step_control='tile'): tile %d %s (status %d; %d of %d tiles stopped), so the solve has no "
                 "backward: max_steps = %d slots per tile, the largest count of accepted steps a tile had kept when it "
@@ -491,17 +607,19 @@ class AffineTile:
         return used
 
     def _weight_rows(self, dev):
-        """dK, dG, dz_f, dz_g per (slot, stage, row) for the weight gradients (zero-filled)."""
-        n, MS = self.n, self.M * self.S
+        """dK, dG, dz_f, dz_g per (slot, stage, row) for the weight gradients (zero-filled; paged: per (page, stage, row))."""
+        n, MS = (_lib.MLP_TILE, self.pages * self.S) if self.paged else (self.n, self.M * self.S)
         zero = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
         return (zero(MS, n, self.ns), zero(MS, n, self.ns * self.nu), zero(self.f.n_layers - 1, MS * n, self.f.hid),
                 zero(self.g.n_layers - 1, MS * n, self.g.hid))
 
     def _weight_grads(self, dK, dG, dz_f, dz_g, used, dev):
         """Every stage of the USED slots as one batch through the weight-gradient launch: the slots are the leading
-        index, so the first used * 7 * n rows of every buffer hold them (the layers' stride stays that of all slots)."""
+        index, so the first used * 7 * n rows of every buffer hold them (the layers' stride stays that of all slots).
+        Paged: all pages * 7 * 32 rows — with exact counts every page is a step somebody took."""
+        rows = self.pages * self.S * _lib.MLP_TILE if self.paged else used * self.S * self.n
         return _affine_weight_grads(self.f, self.g, self.Y.data_ptr(), self.ns, (dK, dG), [_ptr(a) for a in self.acts],
-                                    self.ls, (dz_f, dz_g), used * self.S * self.n, dev)
+                                    self.ls, (dz_f, dz_g), rows, dev)
 
 
 class AffineTileDopri(AffineTile):
@@ -512,9 +630,9 @@ class AffineTileDopri(AffineTile):
     api, words = "rollout", (" in one interval", "8 H")
 
     def __init__(self, func, n, iv, mode, atol, rtol, device):
-        self.iv, self.H, self.du_shape = iv, iv.H, (iv.H, n, func.n_u)
+        self.iv, self.H, self.du_shape, self.least = iv, iv.H, (iv.H, n, func.n_u), iv.H
         self.iv_first = self.iv_x = None
-        AffineTile.__init__(self, func, n, (iv.H,), iv.max_steps, iv.info, mode, atol, rtol, device)
+        AffineTile.__init__(self, func, n, (iv.H,), iv.max_steps, iv.info, mode, atol, rtol, device, iv.tile_steps)
 
     def _interval_arrays(self, z):
         self.iv_first, self.iv_x = z(self.tiles, self.H, dtype=torch.int32), z(self.tiles, self.H)
@@ -523,15 +641,17 @@ class AffineTileDopri(AffineTile):
         return self.accepted.sum(1, dtype=torch.int32)
 
     def _fwd(self, x0, u, xs, rtol, atol):
-        _lib.call("nlbac_node_dopri_tile_fwd", C.byref(self.f.desc), C.byref(self.g.desc), x0.data_ptr(), u.data_ptr(),
-                  self.n, self.H, self.beta, self.c_err, self.iv.dt, rtol, atol, xs.data_ptr(), self.M, _ptr(self.Y),
+        _lib.call("nlbac_node_dopri_tile_paged_fwd" if self.paged else "nlbac_node_dopri_tile_fwd", C.byref(self.f.desc),
+                  C.byref(self.g.desc), x0.data_ptr(), u.data_ptr(), self.n, self.H, self.beta, self.c_err, self.iv.dt,
+                  rtol, atol, xs.data_ptr(), *self._slot_args(), _ptr(self.Y),
                   _ptr(self.G), _ptr(self.acts[0]), self.ls[0], _ptr(self.acts[1]), self.ls[1], self.bits,
                   _ptr(self.hslots), _ptr(self.iv_first), _ptr(self.iv_x), self.accepted.data_ptr(),
                   self.attempts.data_ptr(), self.status.data_ptr(), stream_ptr())
 
     def _bwd(self, dout, dx0, du, dK, dG, dz_f, dz_g):
-        _lib.call("nlbac_node_dopri_tile_bwd", C.byref(self.f.desc), C.byref(self.g.desc), self.u.data_ptr(), self.n,
-                  self.H, self.beta, self.M, self.hslots.data_ptr(), self.iv_first.data_ptr(), self.accepted.data_ptr(),
+        _lib.call("nlbac_node_dopri_tile_paged_bwd" if self.paged else "nlbac_node_dopri_tile_bwd", C.byref(self.f.desc),
+                  C.byref(self.g.desc), self.u.data_ptr(), self.n, self.H, self.beta, *self._slot_args(),
+                  self.hslots.data_ptr(), self.iv_first.data_ptr(), self.accepted.data_ptr(),
                   self.iv_x.data_ptr(), self.G.data_ptr(), _ptr(self.acts[0]), self.ls[0], _ptr(self.acts[1]), self.ls[1],
                   self.bits, dout.data_ptr(), dx0.data_ptr(), du.data_ptr(), dK, dG, dz_f, dz_g, stream_ptr())
 
@@ -543,11 +663,11 @@ class AffineTileDense(AffineTile):
     weight-gradient launch over the used slots).  One count per tile; per tile and output the slot that emitted it and
     its abscissa (``ov_slot`` / ``ov_x``).  ``backward`` takes dxs (T - 1, n, n_s): d loss / d out[1:] on the state
     columns."""
-    api, words = "odeint_dense", ("", "32")
+    api, words, least = "odeint_dense", ("", "32"), 1
     dx0_total = False     # (``backward`` takes dout[1:]: dout[0] is added behind it)
 
-    def __init__(self, func, n, taus, max_steps, info, mode, atol, rtol, device):
-        AffineTile.__init__(self, func, n, (), max_steps, info, mode, atol, rtol, device)
+    def __init__(self, func, n, taus, max_steps, info, mode, atol, rtol, device, tile_steps=None):
+        AffineTile.__init__(self, func, n, (), max_steps, info, mode, atol, rtol, device, tile_steps)
         self.n_out, self.t_end, self.du_shape = len(taus), taus[-1], (n, func.n_u)
         self.tau = torch.tensor(taus, dtype=torch.float64, device=device)
         self.ov_slot = self.ov_x = None
@@ -559,15 +679,17 @@ class AffineTileDense(AffineTile):
         return self.accepted
 
     def _fwd(self, x0, u, xs, rtol, atol):
-        _lib.call("nlbac_node_dopri_tile_dense_fwd", C.byref(self.f.desc), C.byref(self.g.desc), x0.data_ptr(),
+        _lib.call("nlbac_node_dopri_tile_dense_paged_fwd" if self.paged else "nlbac_node_dopri_tile_dense_fwd",
+                  C.byref(self.f.desc), C.byref(self.g.desc), x0.data_ptr(),
                   u.data_ptr(), self.n, self.beta, self.c_err, self.tau.data_ptr(), self.n_out, self.t_end, rtol, atol,
-                  xs.data_ptr(), self.M, _ptr(self.Y), _ptr(self.G), _ptr(self.acts[0]), self.ls[0], _ptr(self.acts[1]),
+                  xs.data_ptr(), *self._slot_args(), _ptr(self.Y), _ptr(self.G), _ptr(self.acts[0]), self.ls[0], _ptr(self.acts[1]),
                   self.ls[1], self.bits, _ptr(self.hslots), _ptr(self.ov_slot), _ptr(self.ov_x),
                   self.accepted.data_ptr(), self.attempts.data_ptr(), self.status.data_ptr(), stream_ptr())
 
     def _bwd(self, dxs, dx0, du, dK, dG, dz_f, dz_g):
-        _lib.call("nlbac_node_dopri_tile_dense_bwd", C.byref(self.f.desc), C.byref(self.g.desc), self.u.data_ptr(),
-                  self.n, self.beta, self.n_out, self.M, self.hslots.data_ptr(), self.ov_slot.data_ptr(),
+        _lib.call("nlbac_node_dopri_tile_dense_paged_bwd" if self.paged else "nlbac_node_dopri_tile_dense_bwd",
+                  C.byref(self.f.desc), C.byref(self.g.desc), self.u.data_ptr(),
+                  self.n, self.beta, self.n_out, *self._slot_args(), self.hslots.data_ptr(), self.ov_slot.data_ptr(),
                   self.ov_x.data_ptr(), self.accepted.data_ptr(), self.G.data_ptr(), _ptr(self.acts[0]), self.ls[0],
                   _ptr(self.acts[1]), self.ls[1], self.bits, dxs.data_ptr(), dx0.data_ptr(), du.data_ptr(), dK, dG, dz_f,
                   dz_g, stream_ptr())

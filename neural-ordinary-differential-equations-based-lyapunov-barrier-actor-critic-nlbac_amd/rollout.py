@@ -37,14 +37,16 @@ def _check_device(x0, controls):
                          % (x0.device, controls.device))
 
 
-def _check_tile(func, H, method, adjoint, step_control, max_steps, info):
-    """The checks of ``step_control`` / ``max_steps`` / ``info``; returns the slots a tile gets (``max_steps``, or 8 H)."""
+def _check_tile(func, H, method, adjoint, step_control, max_steps, info, tile_steps=None, n=None):
+    """The checks of ``step_control`` / ``max_steps`` / ``info`` / ``tile_steps`` (``n``: the rows, which ``tile_steps``
+    is held against); returns the slots every tile gets (``max_steps``, or 8 H) — None under the batch-wide control and
+    where ``tile_steps`` counts them per tile."""
     if step_control not in STEP_CONTROLS:
         raise ValueError("rollout: step_control is one of %s; got %r" % (", ".join(STEP_CONTROLS), step_control))
     if step_control == "batch":
-        if max_steps is not None or info is not None:
-            raise ValueError("rollout: max_steps and info go with step_control='tile' (the batch-wide control keeps its "
-                             "steps per interval and reports through the solvers)")
+        if max_steps is not None or info is not None or tile_steps is not None:
+            raise ValueError("rollout: max_steps, tile_steps and info go with step_control='tile' (the batch-wide control "
+                             "keeps its steps per interval and reports through the solvers)")
         return None
     if method != "dopri5":
         raise ValueError("rollout: step_control='tile' goes with method='dopri5'; %s runs on a fixed grid, which has no "
@@ -55,11 +57,17 @@ def _check_tile(func, H, method, adjoint, step_control, max_steps, info):
     if info is not None and not isinstance(info, dict):
         raise ValueError("rollout: info is a dict (it receives the device tensors accepted / attempts / status) or None; "
                          "got %s" % type(info).__name__)
-    if max_steps is None:
-        max_steps = 8 * H
-    if isinstance(max_steps, bool) or not isinstance(max_steps, int) or max_steps < H:
-        raise ValueError("rollout: max_steps must be an int >= H = %d (every interval keeps at least one step); got %r"
-                         % (H, max_steps))
+    if tile_steps is not None:
+        if max_steps is not None:
+            raise ValueError("rollout: tile_steps (a slot count per tile) and max_steps (one for all tiles) exclude each "
+                             "other; got both")
+        T.check_tile_steps("rollout", tile_steps, n, H, "every interval keeps at least one step: H = %d" % H)
+    else:
+        if max_steps is None:
+            max_steps = 8 * H
+        if isinstance(max_steps, bool) or not isinstance(max_steps, int) or max_steps < H:
+            raise ValueError("rollout: max_steps must be an int >= H = %d (every interval keeps at least one step); got %r"
+                             % (H, max_steps))
     if not func.affine:
         raise NotImplementedError("rollout: step_control='tile' serves the control-affine NODE only "
                                   "(nlbac_node_dopri_tile_ok); the single-net form is left open")
@@ -67,7 +75,7 @@ def _check_tile(func, H, method, adjoint, step_control, max_steps, info):
 
 
 def _check(func, x0, controls, dt, method, step_size=None, *, adjoint=False, step_control="batch", max_steps=None,
-           info=None):
+           info=None, tile_steps=None):
     """Every argument check, before anything touches a device.  Returns ``dt`` rounded to float32 as ``odeint``'s time
     grid rounds it and, with ``step_size``, the fine steps of a control interval (``ode_grid._sub_grid`` over [0, dt])."""
     from .sac_cbf_clf.model import NeuralODEModel
@@ -106,9 +114,9 @@ def _check(func, x0, controls, dt, method, step_size=None, *, adjoint=False, ste
         if H * m * S * x0.shape[0] >= 2 ** 31:
             raise ValueError("rollout: %d intervals x %d fine steps x %d stages x %d rows is 2^31 or more (the launch's "
                              "limit); use a larger step_size, a shorter horizon or fewer rows" % (H, m, S, x0.shape[0]))
-    slots = _check_tile(func, controls.shape[0], method, adjoint, step_control, max_steps, info)
-    if slots is not None:
-        if slots * 7 * x0.shape[0] >= 2 ** 31:
+    slots = _check_tile(func, controls.shape[0], method, adjoint, step_control, max_steps, info, tile_steps, x0.shape[0])
+    if step_control == "tile":
+        if slots is not None and slots * 7 * x0.shape[0] >= 2 ** 31:
             raise ValueError("rollout: max_steps * 7 stages * %d rows is 2^31 or more (the launch's limit: %d * 7 * %d); "
                              "use a smaller max_steps or fewer rows" % (x0.shape[0], slots, x0.shape[0]))
         if not T.AffineTileDopri.shapes_ok(func):
@@ -120,7 +128,7 @@ def _check(func, x0, controls, dt, method, step_size=None, *, adjoint=False, ste
 
 
 def rollout(func, x0, controls, dt, *, method="rk4", atol=1e-7, rtol=1e-5, step_size=None, adjoint=False,
-            adjoint_chunk=None, step_control="batch", max_steps=None, info=None):
+            adjoint_chunk=None, step_control="batch", max_steps=None, info=None, tile_steps=None):
     """Predict H intervals of ``dt`` ahead with the NODE ``func`` (either form; a model owned by an agent included),
     a new control per interval: returns ``out`` (H + 1, B, n_s) with ``out[0] = x0`` and
 
@@ -193,18 +201,42 @@ def rollout(func, x0, controls, dt, *, method="rk4", atol=1e-7, rtol=1e-5, step_
     1 out of step slots, 2 more than 1000 attempts in an interval (the chained solve's own cap).  A tile that stops
     writes NaN into its rows of ``out`` from that interval on; the forward never synchronises, and the backward — which
     reads ``status`` first, one small copy to the host — raises ``NlbacError`` naming ``max_steps`` and the largest
-    count seen."""
+    count seen.
+
+    ``tile_steps`` (with ``"tile"`` only, and in place of ``max_steps``: giving both is a ``ValueError``) counts the
+    slots PER TILE.  ``max_steps`` sizes every tile's slots for the tile that takes the most steps; where the tiles
+    differ, most of what it allocates, zero-fills and hands to the weight-gradient launch holds nothing.  A sequence of
+    ints or a 1-D integer CPU tensor with one entry per tile (``n_tiles = ceil(B / 32)``; every entry an int >= H; a
+    CUDA tensor is a ``ValueError`` — the forward would have to wait for it) gives tile j exactly ``tile_steps[j]``
+    slots for the whole horizon.  The kept buffers then hold ``sum(tile_steps)`` PAGES of 7 stages x 32 rows instead of
+    ``max_steps * n_tiles`` of them — per page 32 x the per-row-and-slot bytes above: input gradients 224 (4 n_g + 112)
+    bytes; parameter gradients 224 (4 n_g + 4 n_s + 28 hid + 112) forward and 224 (4 n_g + 4 n_s + 28 hid) more in
+    the backward (a partial last tile still has whole pages) — and the weight-gradient launch walks ``sum(tile_steps)
+    * 7 * 32`` rows; ``sum(tile_steps) * 7 * 32 >= 2**31`` is a ``ValueError``.  ``out`` and the input gradients are
+    those of a ``max_steps`` call that suffices, bit for bit; the parameter gradients are summed over the rows in
+    another order.  A tile that needs more than its own count stops as above (status 1, NaN rows), and the backward's
+    ``NlbacError`` names ``tile_steps`` and that tile's count.  The forward still never synchronises.
+    ``tile_steps="count"``: the solve counts first — the forward launch runs once with nothing kept (the same kernel
+    instance as the kept launch, hence the same steps: no headroom is needed), the tiles' counts of accepted steps come
+    to the host, and the kept forward runs with exactly those.  That costs ONE EXTRA FORWARD LAUNCH AND ONE HOST WAIT per
+    call; under ``torch.no_grad()`` nothing is kept and nothing is counted.  ``info`` also receives ``slots``: the int32
+    CPU tensor of per-tile counts the buffers were sized with (None where nothing was kept and nothing given) — pass it
+    back in as ``tile_steps`` on the next call over similar inputs to save the counting pass."""
     T.check_adjoint_chunk("rollout", adjoint, adjoint_chunk, chained=method == "dopri5")
     # (the default call is the call as it was; the step-control arguments go along only where one of them is given)
-    tile_args = {} if (step_control == "batch" and max_steps is None and info is None) else dict(
+    tile_args = {} if (step_control == "batch" and max_steps is None and info is None and tile_steps is None) else dict(
         adjoint=adjoint, step_control=step_control, max_steps=max_steps, info=info)
+    if tile_steps is not None:
+        tile_args["tile_steps"] = tile_steps
     dt, hs = _check(func, x0, controls, dt, method, step_size, **tile_args)
     slots = None if step_control == "batch" else (8 * controls.shape[0] if max_steps is None else max_steps)
     params = tuple(func.parameters())
     mode = T.keep_mode(params, x0, controls)
     func.refresh_device_weights()
     H, plan = controls.shape[0], None
-    if slots is not None:
+    if tile_steps is not None:
+        iv = T.TileSteps(dt, H, None, info, T.tile_steps_arg(tile_steps))
+    elif slots is not None:
         iv = T.TileSteps(dt, H, slots, info)
     else:
         iv = T.EqualSteps(dt, H) if hs is None else T.HeldSteps(hs, H, x0.device)

@@ -1195,6 +1195,60 @@ int nlbac_ring_append_kept(int n, const unsigned char *kept, const int *counts, 
 int nlbac_sample_rows_head(const float *src, const long *head, int half, long cap, int ld, long n_rows, float *dst,
                            float *eps, long n_eps, unsigned long long seed, unsigned long long draw, nlbac_stream_t s);
 
+/* ------------------------------------------------------------------------
+ * Per-episode ledger of the vectorised driver (vector_episodes.EpisodeLedger; train.train_vectorized(episodes=...),
+ * train.evaluate_vectorized): per lane the running episode's return, safety cost, number of safety violations, length
+ * and steps under the backup controller, and one record per finished episode in a ring — what the reference's main.py
+ * logs per episode, without a transition or a decision reaching the host.  (Added without an ABI bump: new entry points
+ * and a new struct only.)
+ * ---------------------------------------------------------------------- */
+#define NLBAC_EPISODE_DSTATE 7 /* float64 rows of state per lane */
+#define NLBAC_EPISODE_ISTATE 5 /* int32 rows of state per lane */
+#ifdef __cplusplus
+#define NLBAC_ALIGN16 alignas(16)
+#else
+#define NLBAC_ALIGN16 _Alignas(16)
+#endif
+typedef struct nlbac_episode_record { /* 64 bytes, four 16-byte units */
+    NLBAC_ALIGN16 double ret; /* sum of the episode's rewards, added in step order */
+    double safety_cost;       /* sum of info[2] */
+    double violations;        /* sum of info[1]: integer-valued, exact below 2^53 */
+    double info0;             /* info[0] of the episode's last step (goal_met / reached) */
+    int length;               /* steps of the episode */
+    int lane;
+    int lane_episode;         /* episodes the lane had finished before this one */
+    int vstep;                /* the vector step the episode ended in (the launch argument) */
+    int updates;              /* the driver's update count at that step (the launch argument) */
+    int timeout;              /* 1: ep_step >= max_steps at the last step */
+    int backup_steps;         /* steps of the episode at which the lane's flag was set */
+    int reserved;             /* 0 */
+} nlbac_episode_record;
+/* One vector step of n lanes, one lane per thread, 256-thread workgroups.  Per-lane state, flat device arrays the
+ * caller zeroes once:
+ *   dstate [NLBAC_EPISODE_DSTATE][n] double: 0 return, 1 safety cost, 2 violations of the running episode; 3, 4, 5 the
+ *                                            same summed over the lane's finished episodes; 6 info[0] of the last step;
+ *   istate [NLBAC_EPISODE_ISTATE][n] int32:  0 length, 1 backup steps of the running episode; 2, 3 the same summed over
+ *                                            the lane's finished episodes; 4 finished episodes.
+ * Adds reward[i], info[1], info[2] (acc = acc + x, in call order: the bits of a host loop over the same numbers), 1 to
+ * the length and, where flags[i] != 0, 1 to the backup steps; fin[i] = 0, or 1 | 2 (ep_step[i] >= max_steps) where
+ * done[i] != 0; counts[workgroup] = lanes of the workgroup with done set (64-bit ballots; plain stores).  info0 is
+ * column 0 of the simulators' info block (rows info_ld >= 3 doubles apart; columns 1 and 2 are read behind it); reward
+ * float64, done / ep_step int32 as the simulators leave them; flags bytes 0 / 1 or NULL (no backup controller).
+ * 1 <= n <= 65536. */
+int nlbac_episode_step(int n, const double *reward, const double *info0, int info_ld, const int *done, const int *ep_step,
+                       int max_steps, const unsigned char *flags, double *dstate, int *istate, unsigned char *fin,
+                       int *counts, nlbac_stream_t s);
+/* After nlbac_episode_step of the same vector step: every lane with fin[i] != 0 writes its record into `ring`
+ * (capacity >= n records, aligned to 16 bytes) behind the head, in lane order — rank = finished lanes of the workgroups
+ * before it (a sum over counts[], at most 256 reads) + of the waves before it + of the lower lanes of its wave; no
+ * atomics, the same log in any execution order — then adds the episode to its finished-episode sums, zeroes the running
+ * ones and counts the episode.  head [2][2] long = {write position, records ever written} twice: every workgroup reads
+ * half `half`, workgroup 0 writes (position + total) mod capacity and written + total into the other half — the caller
+ * alternates `half`.  Record k of the log (0-based) lies in slot k mod capacity if the head started at {0, 0}. */
+int nlbac_episode_append(int n, const unsigned char *fin, const int *counts, double *dstate, int *istate,
+                         nlbac_episode_record *ring, long capacity, long *head, int half, int vstep, int updates,
+                         nlbac_stream_t s);
+
 /* small utilities */
 int nlbac_axpby(float a, const float *x, float b, const float *y /*or NULL*/, long n, float *out, nlbac_stream_t s);
 int nlbac_fill(float *p, float v, long n, nlbac_stream_t s);

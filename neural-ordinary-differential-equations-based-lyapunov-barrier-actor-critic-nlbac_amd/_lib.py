@@ -146,6 +146,16 @@ class RowLayout(C.Structure):
 
 HANDOVER_RING, HANDOVER_ISTATE = 40, 9      # == NLBAC_HANDOVER_RING / NLBAC_HANDOVER_ISTATE
 
+
+class EpisodeRecord(C.Structure):
+    """``struct nlbac_episode_record`` (64 bytes; ``vector_episodes.RECORD_DTYPE`` is the same layout for numpy)"""
+    _fields_ = [("ret", C.c_double), ("safety_cost", C.c_double), ("violations", C.c_double), ("info0", C.c_double),
+                ("length", C.c_int), ("lane", C.c_int), ("lane_episode", C.c_int), ("vstep", C.c_int),
+                ("updates", C.c_int), ("timeout", C.c_int), ("backup_steps", C.c_int), ("reserved", C.c_int)]
+
+
+EPISODE_DSTATE, EPISODE_ISTATE = 7, 5       # == NLBAC_EPISODE_DSTATE / NLBAC_EPISODE_ISTATE
+
 _P, _I, _F, _D, _L = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_long
 
 # name -> argtypes (return type is always int unless listed in _RESTYPE)
@@ -322,6 +332,9 @@ _PROTOS = {
                                                                                                  _P, _L, _L] + [_P] * 6 + [_P],
     "nlbac_ring_append_kept": [_I, _P, _P, _P, _L, _L, _P, _L, _I, _P, _I, _P, _I, _D, _I, _I, _P],
     "nlbac_sample_rows_head": [_P, _P, _I, _L, _I, _L, _P, _P, _L, C.c_uint64, C.c_uint64, _P],
+    # (ABI 17, additions: the vectorised driver's per-episode ledger, vector_episodes.py)
+    "nlbac_episode_step": [_I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P],
+    "nlbac_episode_append": [_I, _P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _P],
     "nlbac_axpby": [_F, _P, _F, _P, _L, _P, _P],
     "nlbac_fill": [_P, _F, _L, _P],
     "nlbac_sum_partials": [_P, _I, _I, _F, _P, _P],

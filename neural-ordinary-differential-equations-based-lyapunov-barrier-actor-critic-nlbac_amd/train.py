@@ -10,7 +10,9 @@ line per episode (the reference's wandb / spinup loggers are host tooling and ou
 
 ``--device_replay`` keeps both replays in HBM (same index stream, gather on the device).
 ``--vector_envs N`` steps N environments on the device (``train_vectorized``); with ``--vector_handover`` each lane
-also follows its copy's hand-over rules on the device (``vector_handover.py``).
+also follows its copy's hand-over rules on the device (``vector_handover.py``); with ``--vector_episodes`` the
+per-episode records (reward, length, safety violations, safety cost) are kept on the device (``vector_episodes.py``) and
+``--vector_episode_tsv PATH`` writes them out.  ``evaluate_vectorized`` evaluates the acting policy on the same lanes.
 """
 import argparse
 import os
@@ -62,6 +64,12 @@ def get_args(argv=None):
                    help="with --vector_envs: the backup controller acts where the copy's hand-over rules say so, decided "
                         "per lane on the device; its steps stay out of the controller replay (this command line runs Unicycle "
                         "and Pvtol vectorised; train_vectorized(handover=...) itself also takes SimulatedCars)")
+    p.add_argument('--vector_episodes', nargs='?', type=int, const=True, default=None, metavar="CAP",
+                   help="with --vector_envs: keep the per-episode records (return, length, safety violations, safety cost, "
+                        "goal / time limit, backup steps) on the device, in a ring of CAP records (default max(4 N, 4096))")
+    p.add_argument('--vector_episode_tsv', default=None, metavar="PATH",
+                   help="with --vector_episodes: write one tab-separated line per record, under a header line, at the end of "
+                        "the run")
     return p.parse_args(argv)
 
 
@@ -309,7 +317,31 @@ def train(agent, env, dynamics_model, args, memory, node_memory, log=print, trac
     return history
 
 
-def train_vectorized(agent, env, args, n_steps, log=print, memory=None, check=None, handover=None):
+def _episode_base(ledger):
+    """The ledger's totals when a run begins: zeros for a ledger nothing was pushed to (no host read), else one read —
+    a ledger handed in from an earlier run keeps counting, and the run reports what it added."""
+    if ledger.pushes == 0:
+        return dict(episodes=0, violations=0, safety_cost=0.0)
+    return ledger.totals()
+
+
+def _episode_results(res, ledger, base, log):
+    """What ``episodes=`` adds to a vectorised run's result: THIS run's records that the ring still holds (all of them
+    unless the run finished more episodes than its capacity), this run's totals over its finished episodes (the
+    ledger's totals now less ``base``, those at the run's beginning), the ledger itself."""
+    tot = ledger.totals()
+    first = max(base["episodes"], tot["episodes"] - ledger.capacity)
+    if first > base["episodes"]:
+        log("vectorised: the episode ledger holds the last %d of this run's %d records (capacity)"
+            % (tot["episodes"] - first, tot["episodes"] - base["episodes"]))
+    res["history"] = ledger.records(since=first)[1]
+    res["violations"] = tot["violations"] - base["violations"]
+    res["safety_cost"] = tot["safety_cost"] - base["safety_cost"]
+    res["ledger"] = ledger
+    return res
+
+
+def train_vectorized(agent, env, args, n_steps, log=print, memory=None, check=None, handover=None, episodes=None):
     """Vectorised rollouts: ``env`` is one of ``nlbac_amd.envs.device`` — N environments stepping in
     lock step on the device — and nothing of a transition touches the host: the policy acts on the (N, obs) device
     tensor (one forward for all lanes), the simulator launch writes the next observations / rewards / constraints /
@@ -323,9 +355,25 @@ def train_vectorized(agent, env, args, n_steps, log=print, memory=None, check=No
     Returns dict(steps, updates, episodes, mean_return).
 
     ``handover``: None / False — the above.  True, or a ``_lib.HandoverParams`` (``vector_handover.params_for``): lane i
-    is ``train``'s loop for one environment as far as controllers and replays go (``_train_vectorized_handover``)."""
+    is ``train``'s loop for one environment as far as controllers and replays go (``_train_vectorized_handover``).
+
+    ``episodes``: None / False — the above.  True, a capacity or a ``vector_episodes.EpisodeLedger`` of ``env.n`` lanes:
+    one ``push`` per vector step keeps the reference driver's per-episode records on the device (two small launches, no
+    host read); the dict gains ``history`` (``train``'s list of per-episode dicts, in log order), ``violations`` and
+    ``safety_cost`` (totals over the episodes that finished in this run) and ``ledger``.  Every other key keeps its
+    value.  A ledger handed in from an earlier run keeps counting: its own ``records`` / ``totals`` cover its lifetime,
+    while ``history``, ``violations`` and ``safety_cost`` are this run's alone (one read of the totals before the first
+    step; ``episode`` continues the ledger's numbering, ``total_steps`` and ``updates`` count from this run's start;
+    ``safety_cost`` is the difference of two float64 totals; the ledger does not know that a run has ended, so the
+    steps of an episode the earlier run left open count toward that lane's first record here — hand the environment on
+    with the ledger, or end the earlier run on an episode boundary)."""
+    ledger = ledger_base = None
+    if episodes is not None and episodes is not False:
+        from .vector_episodes import ledger_for
+        ledger = ledger_for(episodes, env.n, agent.device)
+        ledger_base = _episode_base(ledger)
     if handover is not None and handover is not False:
-        return _train_vectorized_handover(agent, env, args, n_steps, log, memory, check, handover)
+        return _train_vectorized_handover(agent, env, args, n_steps, log, memory, check, handover, ledger, ledger_base)
     import torch
     from .sac_cbf_clf.replay_memory import DeviceReplayMemory
     dev, lay, N = agent.device, agent.lay, env.n
@@ -357,6 +405,8 @@ def train_vectorized(agent, env, args, n_steps, log=print, memory=None, check=No
         out = env.step(action)
         nobs, reward, constraint = out[:3]
         lya_in, next_lya_in, done = out[-4], out[-3], out[-2]
+        if ledger is not None:
+            ledger.push(reward, done, out[-1], env.ep_step, int(env.max_episode_steps), vstep=it, updates=updates)
         t = env.ep_step.to(torch.float32)                     # (already advanced by this step)
         timeout = env.ep_step >= int(env.max_episode_steps)
         rows.zero_()
@@ -397,11 +447,16 @@ def train_vectorized(agent, env, args, n_steps, log=print, memory=None, check=No
     torch.cuda.synchronize()
     eps = int(n_done)
     res = dict(steps=steps, updates=updates, episodes=eps, mean_return=float(ret_sum) / max(eps, 1))
-    log("vectorised: %(steps)d env steps in %(episodes)d finished episodes, %(updates)d updates, mean return %(mean_return).2f" % res)
+    if ledger is None:
+        log("vectorised: %(steps)d env steps in %(episodes)d finished episodes, %(updates)d updates, mean return %(mean_return).2f" % res)
+        return res
+    _episode_results(res, ledger, ledger_base, log)
+    log("vectorised: %(steps)d env steps in %(episodes)d finished episodes, %(updates)d updates, mean return "
+        "%(mean_return).2f, %(violations)d safety violations" % res)
     return res
 
 
-def _train_vectorized_handover(agent, env, args, n_steps, log, memory, check, handover):
+def _train_vectorized_handover(agent, env, args, n_steps, log, memory, check, handover, ledger=None, ledger_base=None):
     """``train_vectorized`` with the backup-controller hand-over decided per lane on the device
     (``vector_handover.VectorHandover``; DESIGN.md §5 has the definition).  ``memory`` is the NODE replay and receives
     every transition; a ``DeviceKeptReplay`` of the same capacity is the controller replay — it receives the rows of the
@@ -411,7 +466,8 @@ def _train_vectorized_handover(agent, env, args, n_steps, log, memory, check, ha
     ``start_steps`` either way.  Per vector step, on top of the simulator and the two policies: two launches
     (``nlbac_vector_step_rows``, ``nlbac_ring_append_kept``).  ``check``: callable(step_index, rows, flags) — the rows
     that went into the NODE replay and the flags that decided the step.
-    Returns dict(steps, updates, episodes, mean_return, backup_steps)."""
+    Returns dict(steps, updates, episodes, mean_return, backup_steps).  ``ledger``: the ``episodes=`` ledger; its
+    ``backup_steps`` count the flags that decided each step."""
     lay = getattr(agent, "lay", None)
     if getattr(env, "barrier", False) or getattr(lay, "sig", None) is not None:
         raise ValueError("train_vectorized(handover=...): the learned-barrier copies have no backup controller")
@@ -459,6 +515,9 @@ def _train_vectorized_handover(agent, env, args, n_steps, log, memory, check, ha
         nobs, reward, constraint = out[:3]
         lya_in, next_lya_in, done, info = out[-4], out[-3], out[-2], out[-1]
         info0 = info["reached" if env_name == "SimulatedCars" else "goal_met"]
+        if ledger is not None:                                 # (reads the flags that decided the step: ho.push moves them)
+            ledger.push(reward, done, info, env.ep_step, int(env.max_episode_steps), flags=ho.flags, vstep=it,
+                        updates=updates)
         first = ho.push(memory, kept, obs, action, reward, constraint, lya_in, next_lya_in, nobs, info0, done, env.ep_step,
                         float(env.dt), int(env.max_episode_steps))
         if check is not None:
@@ -487,9 +546,79 @@ def _train_vectorized_handover(agent, env, args, n_steps, log, memory, check, ha
     eps_n = int(n_done)
     res = dict(steps=steps, updates=updates, episodes=eps_n, mean_return=float(ret_sum) / max(eps_n, 1),
                backup_steps=ho.backup_steps())
+    if ledger is None:
+        log("vectorised: %(steps)d env steps in %(episodes)d finished episodes, %(updates)d updates, mean return "
+            "%(mean_return).2f, %(backup_steps)d steps under the backup controller" % res)
+        return res
+    _episode_results(res, ledger, ledger_base, log)
     log("vectorised: %(steps)d env steps in %(episodes)d finished episodes, %(updates)d updates, mean return "
-        "%(mean_return).2f, %(backup_steps)d steps under the backup controller" % res)
+        "%(mean_return).2f, %(backup_steps)d steps under the backup controller, %(violations)d safety violations" % res)
     return res
+
+
+def evaluate_vectorized(agent, env, episodes_per_lane=1, ledger=None):
+    """Evaluation of the acting policy on the device simulators, the reference's ``select_action(evaluate=True)`` for
+    every lane of ``env``: the action is the policy's mean (``policy.sample(obs, eps=zeros)[2]``), there are no updates
+    and no replay, finished lanes are reset in place and a ``vector_episodes.EpisodeLedger`` records every episode.
+    Runs until every lane has finished ``episodes_per_lane`` episodes — at most ``episodes_per_lane *
+    max_episode_steps`` vector steps.
+
+    Host reads.  A lane that has finished is reset and keeps writing records, one per episode, so short episodes fill
+    the ring fast: a vector step writes up to N records.  The new records are therefore read every ``capacity // N``
+    vector steps (and at the time limit), which no run of episodes can overflow, and the same read tells whether every
+    lane has its ``episodes_per_lane`` — the run stops at the first read that finds so, at most ``capacity // N - 1``
+    steps late.  ``lane_episodes`` itself is read once, before the first step.  The default ledger holds ``min(64 N,
+    2^20)`` records (at least ``max(4 N, 4096)``): a read every 64 vector steps up to 16 384 lanes.
+
+    Draws nothing from torch's global generators and changes no agent state: a training run on the Unicycle / Pvtol
+    simulators that evaluates in between continues bit for bit.  (``DeviceSimulatedCarsEnv.reset`` draws its initial
+    velocity noise from numpy's global generator: evaluating on it moves that stream, here as anywhere.)  ``env`` is
+    reset first and left wherever the last step took it.
+
+    Returns dict(history, arrays, episodes, steps, mean_return, std_return, mean_length, std_length,
+    violations_per_episode, safety_cost_per_episode, goal_rate, timeout_rate): the first ``episodes_per_lane`` records of
+    every lane in log order (list of dicts / numpy arrays, ``EpisodeLedger.records``) and their summary."""
+    if isinstance(episodes_per_lane, bool) or not isinstance(episodes_per_lane, (int, np.integer)) or episodes_per_lane < 1:
+        raise ValueError("evaluate_vectorized: episodes_per_lane is an int of at least 1 (got %r)" % (episodes_per_lane,))
+    from .vector_episodes import EpisodeLedger, history_of, ledger_for
+    N, max_steps, per_lane = int(env.n), int(env.max_episode_steps), int(episodes_per_lane)
+    if max_steps < 1:
+        raise ValueError("evaluate_vectorized: the environment's max_episode_steps must be at least 1")
+    if ledger is None:
+        ledger = EpisodeLedger(N, agent.device, capacity=max(4 * N, 4096, min(64 * N, 1 << 20)))
+    else:
+        ledger = ledger_for(ledger, N, agent.device)
+    import torch
+    dev = agent.device
+    obs = env.reset().to(torch.float32).clone()
+    zeros = torch.zeros(N, agent.lay.act_dim, dtype=torch.float32, device=dev)
+    seen = int(ledger.totals()["episodes"]) if ledger.pushes else 0      # (a ledger handed in may hold records already)
+    base = ledger.lane_episodes.cpu().numpy().astype(np.int64)
+    read_every = ledger.capacity // N              # (>= 1; the records of that many steps cannot overflow the ring)
+    parts, have, it, last, limit = [], 0, 0, 0, per_lane * max_steps
+    while it < limit and have < N * per_lane:
+        with torch.no_grad():
+            action = agent.policy.sample(obs, eps=zeros)[2].contiguous()
+        out = env.step(action)
+        ledger.push(out[1], out[-2], out[-1], env.ep_step, max_steps, vstep=it, updates=0)
+        env.reset(out[-2] > 0)
+        obs = env.obs.to(torch.float32).clone()
+        it += 1
+        if it - last >= read_every or it == limit:
+            arrays = ledger.arrays(since=seen)
+            seen, last = arrays.pop("total"), it
+            keep = arrays["lane_episode"] - base[arrays["lane"]] < per_lane     # (a lane's later episodes are dropped)
+            parts.append({k: v[keep] for k, v in arrays.items()})
+            have += int(keep.sum())
+    arrays = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+    assert have == len(arrays["episode"]) == N * per_lane, \
+        "evaluate_vectorized: %d records for %d lanes x %d episodes" % (have, N, per_lane)
+    ret, length = arrays["reward"], arrays["length"].astype(np.float64)
+    return dict(history=history_of(arrays), arrays=arrays, episodes=have, steps=it * N,
+                mean_return=float(ret.mean()), std_return=float(ret.std()), mean_length=float(length.mean()),
+                std_length=float(length.std()), violations_per_episode=float(arrays["violations"].mean()),
+                safety_cost_per_episode=float(arrays["safety_cost"].mean()), goal_rate=float(arrays["goal_met"].mean()),
+                timeout_rate=float(arrays["timeout"].mean()))
 
 
 def main(argv=None):
@@ -520,8 +649,15 @@ def main(argv=None):
         assert args.env != "SimulatedCars", "the vectorised driver covers the envs whose NODE takes no time input"
         from .envs import device as device_envs
         args.replay_size = min(args.replay_size, 1 << 20)
-        return train_vectorized(agent, device_envs.make(args.env, args.vector_envs, seed=max(args.seed, 0)), args,
-                                args.max_steps or 100000, handover=args.vector_handover or None)
+        if args.vector_episode_tsv and args.vector_episodes is None:
+            args.vector_episodes = True
+        res = train_vectorized(agent, device_envs.make(args.env, args.vector_envs, seed=max(args.seed, 0)), args,
+                               args.max_steps or 100000, handover=args.vector_handover or None,
+                               episodes=args.vector_episodes)
+        if args.vector_episode_tsv:
+            from .vector_episodes import write_tsv
+            write_tsv(args.vector_episode_tsv, res["history"])
+        return res
     dynamics_model = DynamicsModel(env, args)
     if args.device_replay:
         cap = min(args.replay_size, 1 << 20)

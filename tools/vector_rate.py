@@ -1,8 +1,9 @@
 """GPU: throughput of the vectorised driver (train.train_vectorized): N device environments + one update per vector step.
 
-    python tools/vector_rate.py [N [B]] [--handover] [--launches] [--iters=K]
+    python tools/vector_rate.py [N [B]] [--handover] [--episodes] [--launches] [--iters=K]
 
 ``--handover``: with the backup-controller hand-over decided per lane on the device (two replays, two acting policies).
+``--episodes``: with the per-episode ledger on the device (``episodes=True``: two more launches per vector step).
 ``--launches``: after the timed run, a short run that counts the library's launches (``_lib.call``) per vector step.
 ``--iters=K``: vector steps of the timed run (300; a kernel trace of two run lengths, differenced, counts the kernels of
 a vector step)."""
@@ -16,7 +17,7 @@ from nlbac_amd.train import train_vectorized
 from test_agent_parity_gpu import make_agent
 
 argv = [a for a in sys.argv[1:] if not a.startswith("--")]
-handover, launches = "--handover" in sys.argv, "--launches" in sys.argv
+handover, launches, episodes = "--handover" in sys.argv, "--launches" in sys.argv, "--episodes" in sys.argv
 N, B, iters = int(argv[0]) if len(argv) > 0 else 4096, int(argv[1]) if len(argv) > 1 else 4096, 300
 iters = next((int(a[8:]) for a in sys.argv[1:] if a.startswith("--iters=")), iters)
 agent, _ = make_agent(B, 256, 0, "dopri5", "Unicycle", 50.0)
@@ -24,13 +25,16 @@ env = denv.make("Unicycle", N, seed=0)
 args = types.SimpleNamespace(replay_size=1 << 20, seed=0, start_steps=2 * N, batch_size=B, updates_per_step=1,
                              NODE_model_update_interval=10)
 kw = {"handover": True} if handover else {}
+if episodes:
+    kw["episodes"] = True
 train_vectorized(agent, env, args, 20 * N, log=lambda *a: None, **kw)        # warm-up (allocations, first launches)
 torch.cuda.synchronize(); t0 = time.perf_counter()
 res = train_vectorized(agent, denv.make("Unicycle", N, seed=1), args, iters * N, log=lambda *a: None, **kw)
 dt = time.perf_counter() - t0
-print("N=%d lanes, batch %d%s: %d env steps + %d updates in %.3f s = %.2f M env steps/s, %.2f ms per vector step"
-      % (N, B, ", hand-over on (%d backup steps)" % res["backup_steps"] if handover else "", res["steps"], res["updates"],
-         dt, res["steps"] / dt / 1e6, 1e3 * dt / iters))
+print("N=%d lanes, batch %d%s%s: %d env steps + %d updates in %.3f s = %.2f M env steps/s, %.2f ms per vector step"
+      % (N, B, ", hand-over on (%d backup steps)" % res["backup_steps"] if handover else "",
+         ", ledger on (%d records, %d safety violations)" % (len(res["history"]), res["violations"]) if episodes else "",
+         res["steps"], res["updates"], dt, res["steps"] / dt / 1e6, 1e3 * dt / iters))
 if launches:
     from nlbac_amd import _lib
     names, real, n_it = [], _lib.call, 40
@@ -41,6 +45,7 @@ if launches:
     _lib.call = real
     per_step = [marks[k + 1] - marks[k] for k in range(10, n_it - 1)]         # (past the warm-up and the gate)
     own = names[marks[20]:marks[21]]
-    driver = [n for n in own if n in ("nlbac_unicycle_env_step", "nlbac_vector_step_rows", "nlbac_ring_append_kept")]
+    driver = [n for n in own if n in ("nlbac_unicycle_env_step", "nlbac_vector_step_rows", "nlbac_ring_append_kept",
+                                      "nlbac_episode_step", "nlbac_episode_append")]
     print("library launches per vector step (update included): min %d max %d; the driver's own: %s"
           % (min(per_step), max(per_step), ", ".join(driver)))

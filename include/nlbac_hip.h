@@ -1123,6 +1123,32 @@ int nlbac_cars_env_step(int n, const double *params /* dt, kp, k_brake, should_k
                         double *obs /*(n,10)*/, double *reward, double *constraint, double *lya_pre /*(n,4)*/,
                         double *lya_next /*(n,4)*/, int *done, double *info, nlbac_stream_t s);
 
+/* Resets of those simulators on the device (envs/device.py, device_resets=True): one launch restarts the flagged lanes
+ * and leaves the float32 observation of every lane.  (Added without an ABI bump: new entry points only.)
+ * done [n] int32 device array, or null = every lane.  Lane i with done[i] > 0 is reset; of every other lane nothing is
+ * written but its obs32 row.  For EVERY lane obs32[i] = (float)obs[i] after the call.  Both refuse n < 1 and a null
+ * required pointer before anything is launched.
+ *
+ * nlbac_env_reset_rows — the fixed-start simulators (Unicycle, Pvtol and their barrier copies).  start_state
+ * [state_dim], start_obs [obs_dim]: float64 device rows (1 <= state_dim, obs_dim <= 64).  A reset lane gets
+ * state[i] = start_state, ep_step[i] = 0, last_dist[i] = start_last_dist (last_dist may be null: Pvtol has none),
+ * obs[i] = start_obs, reset_count[i] += 1.  state (n,state_dim), obs (n,obs_dim) float64, obs32 (n,obs_dim) float32,
+ * ep_step / reset_count [n] int32, all updated in place. */
+int nlbac_env_reset_rows(int n, const int *done, int state_dim, int obs_dim, const double *start_state,
+                         const double *start_obs, double start_last_dist, double *state /*(n,state_dim)*/, int *ep_step,
+                         double *last_dist /*[n] or null*/, double *obs /*(n,obs_dim)*/, float *obs32 /*(n,obs_dim)*/,
+                         int *reset_count, nlbac_stream_t s);
+/* nlbac_cars_env_reset — C/envs/simulated_cars_env.py:128-146.  A reset lane gets positions 42, 34, 26, 18, 10,
+ * velocities 3.0 + off (car 4's stays 3.0), t[i] = 0, ep_step[i] = 0, obs = positions / 100, velocities / 30 (as
+ * products with the rounded reciprocals, which is how torch scales them in the host-mode reset),
+ * reset_noise[i] = off, reset_count[i] += 1.  off = noise[i] where noise [n] (float64) is given; with a null noise it
+ * is the lane's N(0, 0.5) draw at (seed, lane i, reset_count[i] before the increment) — csrc/philox.h has its
+ * definition.  state / obs (n,10) float64, obs32 (n,10) float32, t / reset_noise [n] float64, ep_step / reset_count [n]
+ * int32, all updated in place. */
+int nlbac_cars_env_reset(int n, const int *done, unsigned long long seed, const double *noise, double *state /*(n,10)*/,
+                         double *t, int *ep_step, double *obs /*(n,10)*/, float *obs32 /*(n,10)*/, int *reset_count,
+                         double *reset_noise, nlbac_stream_t s);
+
 /* ------------------------------------------------------------------------
  * Backup-controller hand-over of the vectorised driver (train.train_vectorized(handover=...)): lane i is the loop of
  * train.train for one environment as far as controllers and replays go (U/main.py:39-142, C/main.py:41-112,

@@ -327,6 +327,9 @@ _PROTOS = {
     "nlbac_unicycle_env_step": [_I, c_double_p, _I] + [_P, _I] + [_P] * 13,
     "nlbac_pvtol_env_step": [_I, c_double_p, _I] + [_P, _I] + [_P] * 11,
     "nlbac_cars_env_step": [_I, c_double_p, _I] + [_P] * 12,
+    # (ABI 17, additions: the simulators' resets on the device, envs/device.py device_resets=True)
+    "nlbac_env_reset_rows": [_I, _P, _I, _I, _P, _P, _D, _P, _P, _P, _P, _P, _P, _P],
+    "nlbac_cars_env_reset": [_I, _P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     # (new entry points of ABI 17: the vectorised driver's backup-controller hand-over, vector_handover.py)
     "nlbac_vector_step_rows": [_I, C.POINTER(HandoverParams), C.POINTER(RowLayout)] + [_P] * 6 + [_I, _P, _P, _P, _P, _D, _I,
                                                                                                  _P, _L, _L] + [_P] * 6 + [_P],

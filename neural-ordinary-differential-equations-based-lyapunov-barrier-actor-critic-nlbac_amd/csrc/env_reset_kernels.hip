@@ -1,0 +1,121 @@
+// Resets of the batched device simulators on the device (envs/device.py, device_resets=True): ONE launch per vector
+// step restarts the lanes whose flag is set — state, step counter, clock / last distance, observation, reset counter,
+// and for SimulatedCars the initial-velocity offset, a counter-based draw (philox.h: cars_reset_offset) — and leaves the
+// float32 observation of EVERY lane, which is what the policy reads next.  A lane whose flag is not set keeps every
+// float64 value the step kernel wrote; nothing of it is written but its obs32 row.  One lane per thread, no LDS, no
+// atomics; include/nlbac_hip.h has the contract of every array.
+//
+// The step kernels stay in env_kernels.hip under their own contraction mode, which the reference traces pin.  Here a
+// reset lane must hold what the host-mode reset (torch, numpy: every product and sum rounded on its own) holds, bit for
+// bit, so the pragma below covers every function DEFINED after it and the arithmetic is written with plain * + -
+// (handover_kernels.hip has the reason why the __dmul_rn family does not do).
+#include <cstdint>
+#include "common.h"
+#include "philox.h"
+#pragma clang fp contract(off)
+
+// The N(0, 0.5) initial-velocity offset of lane `lane`'s reset number `count` (0 = the constructor's) under `seed`:
+// philox.h has the definition, tests/test_env_reset_host.py restates it in numpy.
+__device__ __forceinline__ double cars_reset_offset(unsigned long long seed, unsigned lane, unsigned count) {
+    const uint2 key = make_uint2((unsigned)seed, (unsigned)(seed >> 32));
+    const uint4 r = philox4x32_10(make_uint4(lane, count, 0u, PHILOX_TAG_CARS_RESET), key);
+    const unsigned long long m1 = ((unsigned long long)r.x << 20) | (unsigned long long)(r.y >> 12);
+    const unsigned long long m2 = ((unsigned long long)r.z << 20) | (unsigned long long)(r.w >> 12);
+    const double u1 = ((double)m1 + 0.5) * 0x1p-52, u2 = ((double)m2 + 0.5) * 0x1p-52;      // exact, in (0, 1)
+    const double rad = sqrt(-2.0 * log(u1));
+    const double ang = 6.283185307179586 * u2;
+    return 0.5 * (rad * cos(ang));
+}
+
+__global__ __launch_bounds__(256) void env_reset_rows_kernel(int n, const int* __restrict__ done, int state_dim,
+                                                             int obs_dim, const double* __restrict__ start_state,
+                                                             const double* __restrict__ start_obs,
+                                                             double start_last_dist, double* __restrict__ state,
+                                                             int* __restrict__ ep_step, double* __restrict__ last_dist,
+                                                             double* __restrict__ obs, float* __restrict__ obs32,
+                                                             int* __restrict__ reset_count) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double* o = obs + (long)i * obs_dim;
+    float* o32 = obs32 + (long)i * obs_dim;
+    if (!done || done[i] > 0) {
+        double* st = state + (long)i * state_dim;
+        for (int c = 0; c < state_dim; ++c) st[c] = start_state[c];
+        ep_step[i] = 0;
+        if (last_dist) last_dist[i] = start_last_dist;
+        for (int c = 0; c < obs_dim; ++c) {
+            const double v = start_obs[c];
+            o[c] = v;
+            o32[c] = (float)v;
+        }
+        reset_count[i] += 1;
+    } else {
+        for (int c = 0; c < obs_dim; ++c) o32[c] = (float)o[c];
+    }
+}
+
+__global__ __launch_bounds__(256) void cars_env_reset_kernel(int n, const int* __restrict__ done,
+                                                             unsigned long long seed, const double* __restrict__ noise,
+                                                             double* __restrict__ state, double* __restrict__ t,
+                                                             int* __restrict__ ep_step, double* __restrict__ obs,
+                                                             float* __restrict__ obs32, int* __restrict__ reset_count,
+                                                             double* __restrict__ reset_noise) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double* o = obs + (long)i * 10;
+    float* o32 = obs32 + (long)i * 10;
+    if (!done || done[i] > 0) {
+        const int count = reset_count[i];
+        const double off = noise ? noise[i] : cars_reset_offset(seed, (unsigned)i, (unsigned)count);
+        double* st = state + (long)i * 10;
+        // The host-mode reset scales the observation with torch's `tensor /= python scalar`, which the device evaluates
+        // as a product with the scalar's reciprocal (rounded once, on the host): the same two roundings here, so that a
+        // reset lane's observation is the host mode's bit for bit.
+        const double per100 = 1.0 / 100.0, per30 = 1.0 / 30.0;
+        for (int c = 0; c < 5; ++c) {
+            const double pos = 42.0 - 8.0 * (double)c;           // 42, 34, 26, 18, 10
+            const double vel = c == 3 ? 3.0 : 3.0 + off;         // (car 4 keeps 3.0: simulated_cars_env.py:139)
+            const double op = pos * per100, ov = vel * per30;
+            st[2 * c] = pos;
+            st[2 * c + 1] = vel;
+            o[2 * c] = op;
+            o[2 * c + 1] = ov;
+            o32[2 * c] = (float)op;
+            o32[2 * c + 1] = (float)ov;
+        }
+        t[i] = 0.0;
+        ep_step[i] = 0;
+        reset_noise[i] = off;
+        reset_count[i] = count + 1;
+    } else {
+        for (int c = 0; c < 10; ++c) o32[c] = (float)o[c];
+    }
+}
+
+#define RESET_GRID(n) dim3(nlbac_ceil_div((n), 256)), dim3(256), 0, (hipStream_t)s
+
+extern "C" int nlbac_env_reset_rows(int n, const int* done, int state_dim, int obs_dim, const double* start_state,
+                                    const double* start_obs, double start_last_dist, double* state, int* ep_step,
+                                    double* last_dist, double* obs, float* obs32, int* reset_count, nlbac_stream_t s) {
+    NLBAC_REQUIRE(n >= 1, "nlbac_env_reset_rows: n >= 1 lanes (got %d)", n);
+    NLBAC_REQUIRE(state_dim >= 1 && state_dim <= 64 && obs_dim >= 1 && obs_dim <= 64,
+                  "nlbac_env_reset_rows: 1 <= state_dim, obs_dim <= 64 (got %d, %d)", state_dim, obs_dim);
+    NLBAC_REQUIRE(start_state && start_obs && state && ep_step && obs && obs32 && reset_count,
+                  "nlbac_env_reset_rows: null pointer");
+    hipLaunchKernelGGL(env_reset_rows_kernel, RESET_GRID(n), n, done, state_dim, obs_dim, start_state, start_obs,
+                       start_last_dist, state, ep_step, last_dist, obs, obs32, reset_count);
+    NLBAC_CHECK_LAUNCH("nlbac_env_reset_rows");
+    return 0;
+}
+
+extern "C" int nlbac_cars_env_reset(int n, const int* done, unsigned long long seed, const double* noise, double* state,
+                                    double* t, int* ep_step, double* obs, float* obs32, int* reset_count,
+                                    double* reset_noise, nlbac_stream_t s) {
+    NLBAC_REQUIRE(n >= 1, "nlbac_cars_env_reset: n >= 1 lanes (got %d)", n);
+    NLBAC_REQUIRE(state && t && ep_step && obs && obs32 && reset_count && reset_noise,
+                  "nlbac_cars_env_reset: null pointer");
+    hipLaunchKernelGGL(cars_env_reset_kernel, RESET_GRID(n), n, done, seed, noise, state, t, ep_step, obs, obs32,
+                       reset_count, reset_noise);
+    NLBAC_CHECK_LAUNCH("nlbac_cars_env_reset");
+    return 0;
+}

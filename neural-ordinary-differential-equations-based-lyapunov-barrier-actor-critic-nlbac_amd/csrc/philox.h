@@ -17,6 +17,16 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 ctr, uint2 key) {
     return ctr;
 }
 
+// The last counter word tags what a draw is for: 0 and 1 are sample_rows_body's (row indices, policy noise), 2 is the
+// SimulatedCars reset's initial-velocity offset (env_reset_kernels.hip: cars_reset_offset, defined there because it
+// must be compiled with contraction off).  THE definition of that draw, which the tests restate in numpy:
+//   (x, y, z, w) = philox4x32_10(counter (lane, reset_count[lane] before the increment, 0, 2),
+//                                key (seed & 0xffffffff, seed >> 32))
+//   m1 = (x << 20) | (y >> 12),  u1 = (m1 + 0.5) * 2^-52;   m2, u2 likewise from z, w     (52-bit, exact, in (0, 1))
+//   off = 0.5 * (sqrt(-2 * log(u1)) * cos(6.283185307179586 * u2)),   all in float64
+// A lane's k-th offset depends on (seed, lane, k) alone: not on the lane count, nor on when the k-th reset happened.
+#define PHILOX_TAG_CARS_RESET 2u
+
 __device__ __forceinline__ float u01(unsigned x) { return (float)(x >> 8) * 0x1p-24f + 0x1p-25f; }   // (0, 1)
 
 // Thread t of the launch: row indices uniform on [0, src_rows) with replacement, the gather into minibatch layout and

@@ -8,6 +8,13 @@ advanced by ONE launch per step (``csrc/env_kernels.hip``, float64 like the refe
 environments are NOT reset behind the caller's back: ``reset(mask)`` resets those selected (``done`` of the last step
 by default), so the terminal observation is what ``step`` returned — the reference driver's semantics.
 
+``reset_done(done)`` is what a vectorised driver calls after every step: it resets the finished lanes and returns the
+float32 observation the policy reads next.  With ``device_resets=False`` (the default) that is ``reset(done > 0)`` and a
+float32 copy of ``obs``, torch ops with host syncs; with ``device_resets=True`` it is ONE launch
+(``csrc/env_reset_kernels.hip``) and no host read, the lanes that go on keep the observation the step kernel wrote, and
+SimulatedCars draws its initial-velocity offsets on the device from a counter-based generator ("Resets on
+the device") instead of numpy's global one.
+
 Checked against traces recorded from the reference's own env classes (tests/test_device_envs_gpu.py).
 """
 import ctypes as C
@@ -39,6 +46,57 @@ class _DeviceEnv:
         self.info = z(self.n, 3)
         self._all = torch.ones(self.n, dtype=torch.bool, device=self.device)
 
+    def _device_buffers(self):
+        """device mode: the float32 observation every ``reset_done`` leaves and the per-lane reset counter"""
+        self.obs32 = torch.zeros(self.n, self.obs_dim, dtype=torch.float32, device=self.device)
+        self.reset_count = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+
+    def _flags(self, done):
+        """``done`` as the launch reads it: None (every lane), or a contiguous int32 (n,) device tensor"""
+        if done is None:
+            return None
+        d = torch.as_tensor(done, device=self.device)
+        if d.dtype != torch.int32:
+            d = d.to(torch.int32)                  # (a bool mask: one torch op)
+        return d.reshape(self.n).contiguous()
+
+    def _launch_reset(self, flags):
+        """device mode: restart the lanes with ``flags > 0`` (None: every lane), refresh ``obs32``; one launch"""
+        _lib.call("nlbac_env_reset_rows", self.n, None if flags is None else flags.data_ptr(), self.state_dim,
+                  self.obs_dim, self._start_state.data_ptr(), self._start_obs.data_ptr(), float(self._start_last_dist),
+                  self.state.data_ptr(), self.ep_step.data_ptr(),
+                  self.last_dist.data_ptr() if getattr(self, "last_dist", None) is not None else None,
+                  self.obs.data_ptr(), self.obs32.data_ptr(), self.reset_count.data_ptr(), stream_ptr())
+
+    def _capture_start(self):
+        """device mode, once at construction: the start rows, from the host-mode formulas (the torch ``reset`` on every
+        lane), so that a reset lane's observation is the host mode's bit for bit"""
+        self._host_reset(None)
+        self._start_state = self.state[0].clone().contiguous()
+        self._start_obs = self.obs[0].clone().contiguous()
+        last = getattr(self, "last_dist", None)
+        self._start_last_dist = float(last[0]) if last is not None else 0.0
+
+    def reset(self, mask=None):
+        if not self.device_resets:
+            return self._host_reset(mask)
+        self._launch_reset(None if mask is None else self._flags(torch.as_tensor(mask, device=self.device).bool()))
+        return self.obs
+
+    def reset_done(self, done=None):
+        """Reset the lanes with ``done > 0`` (default: ``self.done``, the last step's) and return the float32
+        ``(n, obs_dim)`` observation for the next step.  Host mode: ``reset(done > 0)`` and a fresh float32 copy of
+        ``obs``.  Device mode: one launch and no host read; what is returned is ``self.obs32``, a PERSISTENT buffer that
+        the next ``reset_done`` / ``reset`` overwrites — clone it to keep it.  ``done``: a contiguous int32 (n,) device
+        tensor (the simulator's own ``done``), or a bool tensor, converted by one torch op."""
+        done = self.done if done is None else done
+        if not self.device_resets:
+            d = torch.as_tensor(done, device=self.device)
+            self.reset(d if d.dtype == torch.bool else d > 0)
+            return self.obs.to(torch.float32).clone()
+        self._launch_reset(self._flags(done))
+        return self.obs32
+
     def _action(self, action):
         a = torch.as_tensor(action, device=self.device).to(torch.float64).reshape(self.n, self.act_dim).contiguous()
         return a
@@ -53,15 +111,18 @@ class DeviceUnicycleEnv(UnicycleSpec, _DeviceEnv):
     reward_goal, goal_size, l_p = 500.0, 0.3, 0.03
     little_b, capital_b = 0.0, -20.0
 
-    def __init__(self, n_envs, seed=0, barrier=False, device="cuda"):
+    def __init__(self, n_envs, seed=0, barrier=False, device="cuda", device_resets=False):
         UnicycleSpec.__init__(self, seed)
-        self.barrier = barrier
+        self.barrier, self.device_resets = barrier, bool(device_resets)
         self._common(n_envs, device)
         self.last_dist = torch.zeros(self.n, dtype=torch.float64, device=self.device)
         self._hz = torch.tensor(np.asarray(self.hazards_locations), dtype=torch.float64, device=self.device).contiguous()
+        if self.device_resets:
+            self._device_buffers()
+            self._capture_start()
         self.reset()
 
-    def reset(self, mask=None):
+    def _host_reset(self, mask=None):
         m = self._all if mask is None else torch.as_tensor(mask, device=self.device).bool()
         self.state[m] = torch.tensor([-2.5, -2.5, 0.0], dtype=torch.float64, device=self.device)
         self.ep_step[m] = 0
@@ -98,14 +159,17 @@ class DevicePvtolEnv(PvtolSpec, _DeviceEnv):
     reward_goal, goal_size = 1500.0, 3.5
     little_b, capital_b = 0.0, -0.1
 
-    def __init__(self, n_envs, seed=0, barrier=False, device="cuda", **overrides):
+    def __init__(self, n_envs, seed=0, barrier=False, device="cuda", device_resets=False, **overrides):
         PvtolSpec.__init__(self, seed, **overrides)
-        self.barrier = barrier
+        self.barrier, self.device_resets = barrier, bool(device_resets)
         self._common(n_envs, device)
         self._hz = torch.tensor(np.asarray(self.hazard_locations), dtype=torch.float64, device=self.device).contiguous()
+        if self.device_resets:
+            self._device_buffers()
+            self._capture_start()
         self.reset()
 
-    def reset(self, mask=None):
+    def _host_reset(self, mask=None):
         m = self._all if mask is None else torch.as_tensor(mask, device=self.device).bool()
         self.state[m] = torch.tensor([-4.5, -4.5, 0.0, 0.0, 0.0, 1.0, -4.5], dtype=torch.float64, device=self.device)
         self.ep_step[m] = 0
@@ -132,20 +196,61 @@ class DevicePvtolEnv(PvtolSpec, _DeviceEnv):
 
 class DeviceSimulatedCarsEnv(SimulatedCarsSpec, _DeviceEnv):
     """C/envs/simulated_cars_env.py:66-146 for ``n_envs`` environments; the initial velocity noise of ``reset`` is drawn
-    on the host from numpy's global generator, one draw per environment reset (as the reference does per reset)."""
+    on the host from numpy's global generator, one draw per environment reset (as the reference does per reset).
+
+    ``device_resets=True``: the reset is one launch (``nlbac_cars_env_reset``) and lane i's k-th offset is a
+    counter-based draw at (seed, i, k) made on the device — it depends on neither the lane count nor on when the reset
+    happened, and numpy's global generator is neither seeded nor read.  ``reset_noise`` holds every lane's last offset,
+    ``reset_count`` the number of its resets (the constructor's included)."""
     state_dim, obs_dim, lya_dim, act_dim = 10, 10, 4, 1
     should_keep_thre, reward_goal = 0.5, 2.0
 
-    def __init__(self, n_envs, seed=0, device="cuda"):
+    def __init__(self, n_envs, seed=0, device="cuda", device_resets=False):
         SimulatedCarsSpec.__init__(self, seed)
-        np.random.seed(seed)
+        self.device_resets = bool(device_resets)
+        if not self.device_resets:
+            np.random.seed(seed)
         self._common(n_envs, device)
         self.t = torch.zeros(self.n, dtype=torch.float64, device=self.device)
+        if self.device_resets:
+            self._device_buffers()
+            self.reset_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+            self.reset_noise = torch.zeros(self.n, dtype=torch.float64, device=self.device)
         self.reset()
 
+    def _noise(self, noise):
+        if noise is None:
+            return None
+        return torch.as_tensor(noise, dtype=torch.float64, device=self.device).reshape(self.n).contiguous()
+
+    def _launch_reset(self, flags, noise=None):
+        nz = self._noise(noise)
+        _lib.call("nlbac_cars_env_reset", self.n, None if flags is None else flags.data_ptr(), self.reset_seed,
+                  None if nz is None else nz.data_ptr(), self.state.data_ptr(), self.t.data_ptr(),
+                  self.ep_step.data_ptr(), self.obs.data_ptr(), self.obs32.data_ptr(), self.reset_count.data_ptr(),
+                  self.reset_noise.data_ptr(), stream_ptr())
+
     def reset(self, mask=None, noise=None):
-        """``noise``: the N(0, 0.5) initial-velocity offsets to use, one per environment (default: one draw from numpy's
-        global generator per environment that is reset, in index order)."""
+        """``noise``: the N(0, 0.5) initial-velocity offsets to use, one per environment (default, host mode: one draw
+        from numpy's global generator per environment that is reset, in index order; device mode: the lane's
+        counter-based draw)."""
+        if not self.device_resets:
+            return self._host_reset(mask, noise)
+        self._launch_reset(None if mask is None else self._flags(torch.as_tensor(mask, device=self.device).bool()), noise)
+        return self.obs
+
+    def reset_done(self, done=None, noise=None):
+        """``_DeviceEnv.reset_done``; ``noise``: as for ``reset`` — a float64 (n,) device tensor, or a sequence that is
+        uploaded.  Device mode returns the persistent ``self.obs32``, which the next call overwrites."""
+        done = self.done if done is None else done
+        if not self.device_resets:
+            d = torch.as_tensor(done, device=self.device)
+            self.reset(d if d.dtype == torch.bool else d > 0, noise)
+            return self.obs.to(torch.float32).clone()
+        self._launch_reset(self._flags(done), noise)
+        return self.obs32
+
+    def _host_reset(self, mask=None, noise=None):
         m = (np.ones(self.n, dtype=bool) if mask is None else torch.as_tensor(mask).bool().cpu().numpy())
         for i in np.nonzero(m)[0]:
             st = np.zeros(10)
@@ -172,12 +277,15 @@ class DeviceSimulatedCarsEnv(SimulatedCarsSpec, _DeviceEnv):
         return (self.obs, self.reward, self.constraint, self.lya_pre, self.lya_next, self.done, self._info("reached"))
 
 
-def make(name, n_envs, seed=0, device="cuda", **kw):
-    """``Unicycle`` / ``UnicycleBarrier`` / ``SimulatedCars`` / ``Pvtol`` / ``PvtolBarrier``, batched on the device."""
+def make(name, n_envs, seed=0, device="cuda", device_resets=False, **kw):
+    """``Unicycle`` / ``UnicycleBarrier`` / ``SimulatedCars`` / ``Pvtol`` / ``PvtolBarrier``, batched on the device;
+    ``device_resets=True``: resets on the device (one launch per ``reset_done``).  ``**kw`` goes to the class."""
     if name in ("Unicycle", "UnicycleBarrier"):
-        return DeviceUnicycleEnv(n_envs, seed, barrier=name.endswith("Barrier"), device=device)
+        return DeviceUnicycleEnv(n_envs, seed, barrier=name.endswith("Barrier"), device=device,
+                                 device_resets=device_resets, **kw)
     if name == "SimulatedCars":
-        return DeviceSimulatedCarsEnv(n_envs, seed, device=device)
+        return DeviceSimulatedCarsEnv(n_envs, seed, device=device, device_resets=device_resets, **kw)
     if name in ("Pvtol", "PvtolBarrier"):
-        return DevicePvtolEnv(n_envs, seed, barrier=name.endswith("Barrier"), device=device, **kw)
+        return DevicePvtolEnv(n_envs, seed, barrier=name.endswith("Barrier"), device=device,
+                              device_resets=device_resets, **kw)
     raise Exception("Dynamics mode not supported.")

@@ -12,7 +12,8 @@ line per episode (the reference's wandb / spinup loggers are host tooling and ou
 ``--vector_envs N`` steps N environments on the device (``train_vectorized``); with ``--vector_handover`` each lane
 also follows its copy's hand-over rules on the device (``vector_handover.py``); with ``--vector_episodes`` the
 per-episode records (reward, length, safety violations, safety cost) are kept on the device (``vector_episodes.py``) and
-``--vector_episode_tsv PATH`` writes them out.  ``evaluate_vectorized`` evaluates the acting policy on the same lanes.
+``--vector_episode_tsv PATH`` writes them out; with ``--vector_device_resets`` finished lanes restart by one launch on
+the device (SimulatedCars always does when vectorised).  ``evaluate_vectorized`` evaluates the acting policy on the same lanes.
 """
 import argparse
 import os
@@ -59,11 +60,16 @@ def get_args(argv=None):
     p.add_argument('--max_steps', type=int, default=0, help="stop after this many env steps (0: run all episodes)")
     p.add_argument('--vector_envs', type=int, default=0,
                    help="N > 0: N environments stepping on the device (train_vectorized: no transition touches the host, "
-                        "primary controller only); runs --max_steps env steps (default 100000)")
+                        "primary controller only); runs --max_steps env steps (default 100000).  Every task; SimulatedCars "
+                        "always resets its lanes on the device (see --vector_device_resets)")
+    p.add_argument('--vector_device_resets', action="store_true",
+                   help="with --vector_envs: finished lanes are restarted by one launch per vector step on the device "
+                        "(envs.device.make(device_resets=True)) instead of torch ops with host syncs; SimulatedCars runs so "
+                        "with or without this flag, its initial-velocity draws then come from a counter-based generator on "
+                        "the device")
     p.add_argument('--vector_handover', action="store_true",
                    help="with --vector_envs: the backup controller acts where the copy's hand-over rules say so, decided "
-                        "per lane on the device; its steps stay out of the controller replay (this command line runs Unicycle "
-                        "and Pvtol vectorised; train_vectorized(handover=...) itself also takes SimulatedCars)")
+                        "per lane on the device; its steps stay out of the controller replay")
     p.add_argument('--vector_episodes', nargs='?', type=int, const=True, default=None, metavar="CAP",
                    help="with --vector_envs: keep the per-episode records (return, length, safety violations, safety cost, "
                         "goal / time limit, backup steps) on the device, in a ring of CAP records (default max(4 N, 4096))")
@@ -341,6 +347,18 @@ def _episode_results(res, ledger, base, log):
     return res
 
 
+def _reset_done(env, done):
+    """Finished lanes start over; the float32 observation of every lane for the next step.  The device simulators do
+    both in ``reset_done`` (one launch in their device mode, the two lines below in their host mode); an environment
+    handed in without that method gets the two lines."""
+    reset_done = getattr(env, "reset_done", None)
+    if reset_done is not None:
+        return reset_done(done)
+    import torch
+    env.reset(done > 0)
+    return env.obs.to(torch.float32).clone()
+
+
 def train_vectorized(agent, env, args, n_steps, log=print, memory=None, check=None, handover=None, episodes=None):
     """Vectorised rollouts: ``env`` is one of ``nlbac_amd.envs.device`` — N environments stepping in
     lock step on the device — and nothing of a transition touches the host: the policy acts on the (N, obs) device
@@ -350,7 +368,9 @@ def train_vectorized(agent, env, args, n_steps, log=print, memory=None, check=No
     follow every vector step.  The reference's driver is one host environment at a time (``*/main.py::train``,
     restated by ``train`` above and pinned against it); this is the same data flow widened to N lanes, WITHOUT the
     backup-controller hand-over heuristics (which are per-episode host control flow): the primary controller acts in
-    every lane.  Time-limit terminations keep mask 1 (U/main.py:150), finished lanes are reset in place.
+    every lane.  Time-limit terminations keep mask 1 (U/main.py:150), finished lanes are reset in place by
+    ``env.reset_done(done)``, which also hands back the float32 observation of the next step (one launch on an
+    environment made with ``device_resets=True``, the torch reset and a float32 copy otherwise).
     ``check``: a callable(step_index, rows) the tests use to look at the rows that were appended.
     Returns dict(steps, updates, episodes, mean_return).
 
@@ -442,8 +462,7 @@ def train_vectorized(agent, env, args, n_steps, log=print, memory=None, check=No
                 agent.update_parameters(memory, args.batch_size, updates, None, memory, args.NODE_model_update_interval,
                                         i_episode)
                 updates += 1
-        env.reset(fin)                                         # (finished lanes start over; the others keep their state)
-        obs = env.obs.to(torch.float32).clone()
+        obs = _reset_done(env, done)                           # (finished lanes start over; the others keep their state)
     torch.cuda.synchronize()
     eps = int(n_done)
     res = dict(steps=steps, updates=updates, episodes=eps, mean_return=float(ret_sum) / max(eps, 1))
@@ -540,8 +559,7 @@ def _train_vectorized_handover(agent, env, args, n_steps, log, memory, check, ha
                 agent.update_parameters(kept, args.batch_size, updates, None, memory, args.NODE_model_update_interval,
                                         i_episode)
                 updates += 1
-        env.reset(fin)
-        obs = env.obs.to(torch.float32).clone()
+        obs = _reset_done(env, done)
     torch.cuda.synchronize()
     eps_n = int(n_done)
     res = dict(steps=steps, updates=updates, episodes=eps_n, mean_return=float(ret_sum) / max(eps_n, 1),
@@ -571,9 +589,11 @@ def evaluate_vectorized(agent, env, episodes_per_lane=1, ledger=None):
     2^20)`` records (at least ``max(4 N, 4096)``): a read every 64 vector steps up to 16 384 lanes.
 
     Draws nothing from torch's global generators and changes no agent state: a training run on the Unicycle / Pvtol
-    simulators that evaluates in between continues bit for bit.  (``DeviceSimulatedCarsEnv.reset`` draws its initial
-    velocity noise from numpy's global generator: evaluating on it moves that stream, here as anywhere.)  ``env`` is
-    reset first and left wherever the last step took it.
+    simulators that evaluates in between continues bit for bit.  (A host-mode ``DeviceSimulatedCarsEnv`` draws its
+    initial velocity noise from numpy's global generator: evaluating on it moves that stream, here as anywhere.  One
+    made with ``device_resets=True`` draws on the device from its own counters, and then this call draws nothing from
+    any global generator, numpy's included.)  ``env`` is reset first and left wherever the last step took it; finished
+    lanes are restarted by ``env.reset_done`` (one launch on a device-mode environment).
 
     Returns dict(history, arrays, episodes, steps, mean_return, std_return, mean_length, std_length,
     violations_per_episode, safety_cost_per_episode, goal_rate, timeout_rate): the first ``episodes_per_lane`` records of
@@ -601,8 +621,7 @@ def evaluate_vectorized(agent, env, episodes_per_lane=1, ledger=None):
             action = agent.policy.sample(obs, eps=zeros)[2].contiguous()
         out = env.step(action)
         ledger.push(out[1], out[-2], out[-1], env.ep_step, max_steps, vstep=it, updates=0)
-        env.reset(out[-2] > 0)
-        obs = env.obs.to(torch.float32).clone()
+        obs = _reset_done(env, out[-2])
         it += 1
         if it - last >= read_every or it == limit:
             arrays = ledger.arrays(since=seen)
@@ -646,13 +665,14 @@ def main(argv=None):
     agent.use_graphs = bool(args.hipgraphs)
     agent.solver = args.solver
     if args.vector_envs > 0:
-        assert args.env != "SimulatedCars", "the vectorised driver covers the envs whose NODE takes no time input"
         from .envs import device as device_envs
         args.replay_size = min(args.replay_size, 1 << 20)
         if args.vector_episode_tsv and args.vector_episodes is None:
             args.vector_episodes = True
-        res = train_vectorized(agent, device_envs.make(args.env, args.vector_envs, seed=max(args.seed, 0)), args,
-                               args.max_steps or 100000, handover=args.vector_handover or None,
+        # (SimulatedCars has one vectorised form: its host-mode reset is a per-lane host loop over numpy's global stream)
+        device_resets = bool(args.vector_device_resets) or args.env == "SimulatedCars"
+        venv = device_envs.make(args.env, args.vector_envs, seed=max(args.seed, 0), device_resets=device_resets)
+        res = train_vectorized(agent, venv, args, args.max_steps or 100000, handover=args.vector_handover or None,
                                episodes=args.vector_episodes)
         if args.vector_episode_tsv:
             from .vector_episodes import write_tsv

@@ -1,6 +1,10 @@
 """GPU: throughput of the vectorised driver (train.train_vectorized): N device environments + one update per vector step.
 
-    python tools/vector_rate.py [N [B]] [--handover] [--episodes] [--launches] [--iters=K]
+    python tools/vector_rate.py [N [B]] [--env=NAME] [--device-resets] [--handover] [--episodes] [--launches] [--iters=K]
+
+``--env=NAME``: Unicycle (default), Pvtol or SimulatedCars (which always resets on the device).
+``--device-resets``: environments made with ``device_resets=True`` — finished lanes restart by one launch per vector step
+(``nlbac_env_reset_rows`` / ``nlbac_cars_env_reset``) instead of torch ops with host syncs.
 
 ``--handover``: with the backup-controller hand-over decided per lane on the device (two replays, two acting policies).
 ``--episodes``: with the per-episode ledger on the device (``episodes=True``: two more launches per vector step).
@@ -20,8 +24,13 @@ argv = [a for a in sys.argv[1:] if not a.startswith("--")]
 handover, launches, episodes = "--handover" in sys.argv, "--launches" in sys.argv, "--episodes" in sys.argv
 N, B, iters = int(argv[0]) if len(argv) > 0 else 4096, int(argv[1]) if len(argv) > 1 else 4096, 300
 iters = next((int(a[8:]) for a in sys.argv[1:] if a.startswith("--iters=")), iters)
-agent, _ = make_agent(B, 256, 0, "dopri5", "Unicycle", 50.0)
-env = denv.make("Unicycle", N, seed=0)
+name = next((a[6:] for a in sys.argv[1:] if a.startswith("--env=")), "Unicycle")
+if name not in ("Unicycle", "Pvtol", "SimulatedCars"):
+    sys.exit("--env=NAME: Unicycle, Pvtol or SimulatedCars (got %r)" % name)
+device_resets = "--device-resets" in sys.argv or name == "SimulatedCars"
+make_env = lambda seed: denv.make(name, N, seed=seed, device_resets=device_resets)
+agent, _ = make_agent(B, 256, 0, "dopri5", name, {"Unicycle": 50.0, "Pvtol": 0.8}.get(name))
+env = make_env(0)
 args = types.SimpleNamespace(replay_size=1 << 20, seed=0, start_steps=2 * N, batch_size=B, updates_per_step=1,
                              NODE_model_update_interval=10)
 kw = {"handover": True} if handover else {}
@@ -29,10 +38,10 @@ if episodes:
     kw["episodes"] = True
 train_vectorized(agent, env, args, 20 * N, log=lambda *a: None, **kw)        # warm-up (allocations, first launches)
 torch.cuda.synchronize(); t0 = time.perf_counter()
-res = train_vectorized(agent, denv.make("Unicycle", N, seed=1), args, iters * N, log=lambda *a: None, **kw)
+res = train_vectorized(agent, make_env(1), args, iters * N, log=lambda *a: None, **kw)
 dt = time.perf_counter() - t0
-print("N=%d lanes, batch %d%s%s: %d env steps + %d updates in %.3f s = %.2f M env steps/s, %.2f ms per vector step"
-      % (N, B, ", hand-over on (%d backup steps)" % res["backup_steps"] if handover else "",
+print("%s, N=%d lanes, batch %d, resets on the %s%s%s: %d env steps + %d updates in %.3f s = %.2f M env steps/s, %.2f ms per vector step"
+      % (name, N, B, "device" if device_resets else "host", ", hand-over on (%d backup steps)" % res["backup_steps"] if handover else "",
          ", ledger on (%d records, %d safety violations)" % (len(res["history"]), res["violations"]) if episodes else "",
          res["steps"], res["updates"], dt, res["steps"] / dt / 1e6, 1e3 * dt / iters))
 if launches:
@@ -40,12 +49,13 @@ if launches:
     names, real, n_it = [], _lib.call, 40
     _lib.call = lambda name, *a: (names.append(name), real(name, *a))[1]
     marks = []
-    train_vectorized(agent, denv.make("Unicycle", N, seed=2), args, n_it * N, log=lambda *a: None,
+    train_vectorized(agent, make_env(2), args, n_it * N, log=lambda *a: None,
                      check=lambda it, *a: marks.append(len(names)), **kw)
     _lib.call = real
     per_step = [marks[k + 1] - marks[k] for k in range(10, n_it - 1)]         # (past the warm-up and the gate)
     own = names[marks[20]:marks[21]]
-    driver = [n for n in own if n in ("nlbac_unicycle_env_step", "nlbac_vector_step_rows", "nlbac_ring_append_kept",
-                                      "nlbac_episode_step", "nlbac_episode_append")]
+    driver = [n for n in own if n.endswith("_env_step") or n in (
+        "nlbac_vector_step_rows", "nlbac_ring_append_kept", "nlbac_episode_step", "nlbac_episode_append",
+        "nlbac_env_reset_rows", "nlbac_cars_env_reset")]
     print("library launches per vector step (update included): min %d max %d; the driver's own: %s"
           % (min(per_step), max(per_step), ", ".join(driver)))

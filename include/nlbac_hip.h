@@ -1122,6 +1122,16 @@ int nlbac_cars_env_step(int n, const double *params /* dt, kp, k_brake, should_k
                         int max_steps, const double *action /*(n)*/, double *state /*(n,10)*/, double *t, int *ep_step,
                         double *obs /*(n,10)*/, double *reward, double *constraint, double *lya_pre /*(n,4)*/,
                         double *lya_next /*(n,4)*/, int *done, double *info, nlbac_stream_t s);
+/* nlbac_quadrotor_env_step — the Quadrotor-like task (envspec.QuadrotorLikeSpec has the step; no reference code exists
+ * for it).  obs = state (6) = [x, x', z, z', theta, theta'], the Lyapunov input after the step is obs.  done = goal |
+ * crash | time limit; info[1] = [out of range] + [inside the obstacle].  Refuses n < 1, a null pointer and
+ * max_steps < 1 before anything is launched.  (Added without an ABI bump: a new entry point only.) */
+int nlbac_quadrotor_env_step(int n, const double *params /* [23] dt, MASS, IYY, ARM, G, goal x, goal z, goal size, goal
+                             reward, x range (2), z range (2), obstacle x, z, radius, D1, D2, crash box x (2), z (2),
+                             crash tilt */, int max_steps, const double *action /*(n,2)*/, double *state /*(n,6)*/,
+                             int *ep_step, double *obs /*(n,6)*/, double *reward, double *constraint, double *signal,
+                             double *lya_pre /*(n,6): the observation before the step*/, int *done, double *info,
+                             nlbac_stream_t s);
 
 /* Resets of those simulators on the device (envs/device.py, device_resets=True): one launch restarts the flagged lanes
  * and leaves the float32 observation of every lane.  (Added without an ABI bump: new entry points only.)
@@ -1148,6 +1158,16 @@ int nlbac_env_reset_rows(int n, const int *done, int state_dim, int obs_dim, con
 int nlbac_cars_env_reset(int n, const int *done, unsigned long long seed, const double *noise, double *state /*(n,10)*/,
                          double *t, int *ep_step, double *obs /*(n,10)*/, float *obs32 /*(n,10)*/, int *reset_count,
                          double *reset_noise, nlbac_stream_t s);
+/* nlbac_quadrotor_env_reset — the Quadrotor-like task with a start spread.  params: HOST array [8], the start state (6)
+ * and the spread (sx, sz >= 0).  A reset lane gets state[i] = obs[i] = start with x + dx and z + dz, ep_step[i] = 0,
+ * reset_noise[i] = (dx, dz), reset_count[i] += 1.  (dx, dz) = noise[i] where noise (n,2) float64 is given; with a null
+ * noise they are the lane's draws at (seed, lane i, reset_count[i] before the increment), dx = sx (2 u0 - 1),
+ * dz = sz (2 u1 - 1) — csrc/philox.h has the definition.  state / obs (n,6) float64, obs32 (n,6) float32, reset_noise
+ * (n,2) float64, ep_step / reset_count [n] int32, all updated in place.  (Added without an ABI bump.) */
+int nlbac_quadrotor_env_reset(int n, const int *done, unsigned long long seed, const double *params /*host [8]*/,
+                              const double *noise /*(n,2) or null*/, double *state /*(n,6)*/, int *ep_step,
+                              double *obs /*(n,6)*/, float *obs32 /*(n,6)*/, int *reset_count,
+                              double *reset_noise /*(n,2)*/, nlbac_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Backup-controller hand-over of the vectorised driver (train.train_vectorized(handover=...)): lane i is the loop of

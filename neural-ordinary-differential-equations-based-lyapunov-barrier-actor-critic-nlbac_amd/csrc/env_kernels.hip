@@ -158,6 +158,51 @@ __global__ __launch_bounds__(256) void cars_env_step_kernel(int n, const CarsEnv
     info[3 * i + 2] = fabs(d34 - 2.5) * (d34 < 2.5 ? 1.0 : 0.0) + fabs(d45 - 2.5) * (d45 < 2.5 ? 1.0 : 0.0);
 }
 
+// The Quadrotor-like task (envspec.QuadrotorLikeSpec; no reference code exists, DESIGN.md §5 "The Quadrotor-like
+// simulator"): synth.quadrotor_transitions' Euler step of the planar rigid body, per lane.  obs = state (6) =
+// [x, x', z, z', theta, theta']; the Lyapunov inputs are the observations before / after the step.
+struct QuadEnv {
+    double dt, mass, iyy, arm, g, gx, gz, goal_size, reward_goal, x_lo, x_hi, z_lo, z_hi, ox, oz, obs_r, d1, d2,
+        cx_lo, cx_hi, cz_lo, cz_hi, c_theta;
+    int max_steps;
+};
+#define QUAD_ENV_PARAMS 23
+
+__global__ __launch_bounds__(256) void quadrotor_env_step_kernel(int n, const QuadEnv E, const double* action,
+                                                                 double* state, int* ep_step, double* obs,
+                                                                 double* reward, double* constraint, double* signal,
+                                                                 double* lya_pre, int* done, double* info) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double* st = state + 6 * i;
+    const double a0 = action[2 * i], a1 = action[2 * i + 1];
+    double x[6];
+    for (int k = 0; k < 6; ++k) { x[k] = st[k]; lya_pre[6 * i + k] = x[k]; }
+    const double T = a0 + a1;
+    const double f[6] = {x[1], sin(x[4]) * T / E.mass, x[3], cos(x[4]) * T / E.mass - E.g, x[5],
+                         (a1 - a0) * E.arm / sqrt(2.0) / E.iyy};
+    for (int k = 0; k < 6; ++k) { x[k] = x[k] + E.dt * f[k]; st[k] = x[k]; obs[6 * i + k] = x[k]; }
+    const int step = ep_step[i] + 1;
+    ep_step[i] = step;
+    const double px = x[0], pz = x[2], th = x[4];
+    const double gdx = px - E.gx, gdz = pz - E.gz;
+    const double dist = sqrt(gdx * gdx + gdz * gdz);
+    const bool out = px < E.x_lo || px > E.x_hi || pz < E.z_lo || pz > E.z_hi;
+    const double hx = px - E.ox, hz = pz - E.oz;
+    const double d2 = hx * hx + hz * hz;
+    const bool hit = d2 < E.obs_r * E.obs_r;
+    const bool crash = px < E.cx_lo || px > E.cx_hi || pz < E.cz_lo || pz > E.cz_hi || fabs(th) > E.c_theta;
+    const bool goal = dist <= E.goal_size;
+    double r = -dist, cost = 0.0;
+    if (goal) r += E.reward_goal;
+    if (hit) cost += (E.obs_r - sqrt(d2)) / E.obs_r;
+    if (out) cost += fmax(0.0, E.x_lo - px) + fmax(0.0, px - E.x_hi) + fmax(0.0, E.z_lo - pz) + fmax(0.0, pz - E.z_hi);
+    reward[i] = r; constraint[i] = dist;
+    signal[i] = E.d1 * (out ? 1.0 : 0.0) + E.d2 * (hit ? 1.0 : 0.0);
+    done[i] = (goal || crash || step >= E.max_steps) ? 1 : 0;
+    info[3 * i] = goal ? 1.0 : 0.0; info[3 * i + 1] = (out ? 1.0 : 0.0) + (hit ? 1.0 : 0.0); info[3 * i + 2] = cost;
+}
+
 #define ENV_GRID(n) dim3(nlbac_ceil_div((n), 256)), dim3(256), 0, (hipStream_t)s
 
 extern "C" int nlbac_unicycle_env_step(int n, const double* params /* dt, goal x, goal y, goal size, goal reward,
@@ -199,5 +244,23 @@ extern "C" int nlbac_cars_env_step(int n, const double* params /* dt, kp, k_brak
     hipLaunchKernelGGL(cars_env_step_kernel, ENV_GRID(n), n, E, action, state, t, ep_step, obs, reward, constraint,
                        lya_pre, lya_next, done, info);
     NLBAC_CHECK_LAUNCH("nlbac_cars_env_step");
+    return 0;
+}
+
+extern "C" int nlbac_quadrotor_env_step(int n, const double* params /* dt, MASS, IYY, ARM, G, goal x, goal z, goal size,
+                                        goal reward, x range (2), z range (2), obstacle x, z, radius, D1, D2, crash box
+                                        x (2), z (2), crash tilt */, int max_steps, const double* action, double* state,
+                                        int* ep_step, double* obs, double* reward, double* constraint, double* signal,
+                                        double* lya_pre, int* done, double* info, nlbac_stream_t s) {
+    NLBAC_REQUIRE(n >= 1 && params && action && state && ep_step && obs && reward && constraint && signal && lya_pre &&
+                      done && info, "nlbac_quadrotor_env_step: null pointer");
+    NLBAC_REQUIRE(max_steps >= 1, "nlbac_quadrotor_env_step: max_steps >= 1 (got %d)", max_steps);
+    const double* p = params;
+    QuadEnv E = {p[0],  p[1],  p[2],  p[3],  p[4],  p[5],  p[6],  p[7],  p[8],  p[9],  p[10], p[11],
+                 p[12], p[13], p[14], p[15], p[16], p[17], p[18], p[19], p[20], p[21], p[22], max_steps};
+    static_assert(sizeof(QuadEnv) == (QUAD_ENV_PARAMS + 1) * sizeof(double), "QuadEnv: 23 doubles and max_steps");
+    hipLaunchKernelGGL(quadrotor_env_step_kernel, ENV_GRID(n), n, E, action, state, ep_step, obs, reward, constraint,
+                       signal, lya_pre, done, info);
+    NLBAC_CHECK_LAUNCH("nlbac_quadrotor_env_step");
     return 0;
 }

@@ -1,6 +1,7 @@
 // Resets of the batched device simulators on the device (envs/device.py, device_resets=True): ONE launch per vector
 // step restarts the lanes whose flag is set — state, step counter, clock / last distance, observation, reset counter,
-// and for SimulatedCars the initial-velocity offset, a counter-based draw (philox.h: cars_reset_offset) — and leaves the
+// for SimulatedCars the initial-velocity offset and for the Quadrotor-like task with a start spread the start-position
+// offsets, counter-based draws (philox.h: cars_reset_offset, quadrotor_reset_offsets) — and leaves the
 // float32 observation of EVERY lane, which is what the policy reads next.  A lane whose flag is not set keeps every
 // float64 value the step kernel wrote; nothing of it is written but its obs32 row.  One lane per thread, no LDS, no
 // atomics; include/nlbac_hip.h has the contract of every array.
@@ -92,6 +93,55 @@ __global__ __launch_bounds__(256) void cars_env_reset_kernel(int n, const int* _
     }
 }
 
+// The start-position offsets (dx, dz) of lane `lane`'s reset number `count` of the Quadrotor-like task under `seed`,
+// uniform on [-sx, sx] x [-sz, sz]: philox.h has the definition, tests/test_quadrotor_env_gpu.py restates it in numpy.
+__device__ __forceinline__ void quadrotor_reset_offsets(unsigned long long seed, unsigned lane, unsigned count,
+                                                        double sx, double sz, double* dx, double* dz) {
+    const uint2 key = make_uint2((unsigned)seed, (unsigned)(seed >> 32));
+    const uint4 r = philox4x32_10(make_uint4(lane, count, 0u, PHILOX_TAG_QUADROTOR_RESET), key);
+    const unsigned long long m0 = ((unsigned long long)r.x << 20) | (unsigned long long)(r.y >> 12);
+    const unsigned long long m1 = ((unsigned long long)r.z << 20) | (unsigned long long)(r.w >> 12);
+    const double u0 = ((double)m0 + 0.5) * 0x1p-52, u1 = ((double)m1 + 0.5) * 0x1p-52;      // exact, in (0, 1)
+    *dx = sx * (2.0 * u0 - 1.0);
+    *dz = sz * (2.0 * u1 - 1.0);
+}
+
+struct QuadReset { double start[6], sx, sz; };
+
+__global__ __launch_bounds__(256) void quadrotor_env_reset_kernel(int n, const int* __restrict__ done,
+                                                                  unsigned long long seed, const QuadReset R,
+                                                                  const double* __restrict__ noise,
+                                                                  double* __restrict__ state, int* __restrict__ ep_step,
+                                                                  double* __restrict__ obs, float* __restrict__ obs32,
+                                                                  int* __restrict__ reset_count,
+                                                                  double* __restrict__ reset_noise) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double* o = obs + (long)i * 6;
+    float* o32 = obs32 + (long)i * 6;
+    if (!done || done[i] > 0) {
+        const int count = reset_count[i];
+        double dx, dz;
+        if (noise) { dx = noise[2 * (long)i]; dz = noise[2 * (long)i + 1]; }
+        else quadrotor_reset_offsets(seed, (unsigned)i, (unsigned)count, R.sx, R.sz, &dx, &dz);
+        double* st = state + (long)i * 6;
+        for (int c = 0; c < 6; ++c) {
+            double v = R.start[c];
+            if (c == 0) v = v + dx;                              // (the host simulator's reset(offset): start + offset)
+            if (c == 2) v = v + dz;
+            st[c] = v;
+            o[c] = v;
+            o32[c] = (float)v;
+        }
+        ep_step[i] = 0;
+        reset_noise[2 * (long)i] = dx;
+        reset_noise[2 * (long)i + 1] = dz;
+        reset_count[i] = count + 1;
+    } else {
+        for (int c = 0; c < 6; ++c) o32[c] = (float)o[c];
+    }
+}
+
 #define RESET_GRID(n) dim3(nlbac_ceil_div((n), 256)), dim3(256), 0, (hipStream_t)s
 
 extern "C" int nlbac_env_reset_rows(int n, const int* done, int state_dim, int obs_dim, const double* start_state,
@@ -117,5 +167,21 @@ extern "C" int nlbac_cars_env_reset(int n, const int* done, unsigned long long s
     hipLaunchKernelGGL(cars_env_reset_kernel, RESET_GRID(n), n, done, seed, noise, state, t, ep_step, obs, obs32,
                        reset_count, reset_noise);
     NLBAC_CHECK_LAUNCH("nlbac_cars_env_reset");
+    return 0;
+}
+
+extern "C" int nlbac_quadrotor_env_reset(int n, const int* done, unsigned long long seed,
+                                         const double* params /* host: start state (6), spread in x, in z */,
+                                         const double* noise, double* state, int* ep_step, double* obs, float* obs32,
+                                         int* reset_count, double* reset_noise, nlbac_stream_t s) {
+    NLBAC_REQUIRE(n >= 1, "nlbac_quadrotor_env_reset: n >= 1 lanes (got %d)", n);
+    NLBAC_REQUIRE(params && state && ep_step && obs && obs32 && reset_count && reset_noise,
+                  "nlbac_quadrotor_env_reset: null pointer");
+    NLBAC_REQUIRE(params[6] >= 0.0 && params[7] >= 0.0,
+                  "nlbac_quadrotor_env_reset: the spread is not negative (got %g, %g)", params[6], params[7]);
+    QuadReset R = {{params[0], params[1], params[2], params[3], params[4], params[5]}, params[6], params[7]};
+    hipLaunchKernelGGL(quadrotor_env_reset_kernel, RESET_GRID(n), n, done, seed, R, noise, state, ep_step, obs, obs32,
+                       reset_count, reset_noise);
+    NLBAC_CHECK_LAUNCH("nlbac_quadrotor_env_reset");
     return 0;
 }

@@ -26,6 +26,11 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 ctr, uint2 key) {
 //   off = 0.5 * (sqrt(-2 * log(u1)) * cos(6.283185307179586 * u2)),   all in float64
 // A lane's k-th offset depends on (seed, lane, k) alone: not on the lane count, nor on when the k-th reset happened.
 #define PHILOX_TAG_CARS_RESET 2u
+// 3 is the Quadrotor-like reset's start-position offsets (env_reset_kernels.hip: quadrotor_reset_offsets), the same
+// counter and the same two 52-bit uniforms under a tag of their own:
+//   (x, y, z, w) = philox4x32_10(counter (lane, reset_count[lane] before the increment, 0, 3), the same key)
+//   u0 from (x, y), u1 from (z, w) as u1, u2 above;   dx = sx * (2 * u0 - 1),  dz = sz * (2 * u1 - 1),   all in float64
+#define PHILOX_TAG_QUADROTOR_RESET 3u
 
 __device__ __forceinline__ float u01(unsigned x) { return (float)(x >> 8) * 0x1p-24f + 0x1p-25f; }   // (0, 1)
 

@@ -6,10 +6,11 @@ where ``gym`` is not installed; a real gym env with the same attributes is inter
     UnicycleEnv        U/envs/unicycle_env.py:57-323   (``barrier=True``: NU/envs/unicycle_env.py:105-161)
     SimulatedCarsEnv   C/envs/simulated_cars_env.py:37-180
     PvtolEnv           P/envs/pvtol_env.py:66-406       (``barrier=True``: hazard part of NP/envs/pvtol_env.py:144-220)
+    QuadrotorLikeEnv   no reference code (README prose only): this build's reading, ``envspec.QuadrotorLikeSpec``
 """
 import numpy as np
 
-from ..envspec import PvtolSpec, SimulatedCarsSpec, UnicycleSpec
+from ..envspec import PvtolSpec, QuadrotorLikeSpec, SimulatedCarsSpec, UnicycleSpec
 from ..synth import _pvtol_obs, _unicycle_obs
 
 
@@ -171,8 +172,66 @@ class PvtolEnv(PvtolSpec):
         return obs, reward, dist_goal, lya_pre_term, obs, done, info
 
 
+class QuadrotorLikeEnv(QuadrotorLikeSpec):
+    """The Quadrotor-like task's simulator: ``synth.quadrotor_transitions``' one Euler step of the planar rigid body,
+    run as episodes (``QuadrotorLikeSpec``'s docstring has the step, DESIGN.md §5 the decisions).  Always the barrier
+    copies' 8-tuple: the task has a learned barrier and nothing else."""
+
+    def __init__(self, seed=0):
+        super().__init__(seed)             # (nothing here draws: numpy's global generator is left alone)
+        self.reset()
+
+    def get_obs(self):
+        return self.state.copy()
+
+    def reset(self, offset=None):
+        """``offset``: (dx, dz) added to the start position — what a device environment with an ``init_spread`` draws
+        per reset (``reset_noise``); None: the fixed start."""
+        self.episode_step = 0
+        self.state = np.array(self.start_state, dtype=np.float64)
+        if offset is not None:
+            self.state[0] = self.state[0] + float(offset[0])
+            self.state[2] = self.state[2] + float(offset[1])
+        return self.get_obs()
+
+    def step(self, action):
+        action = np.asarray(action, dtype=np.float64).reshape(-1)
+        lya_pre_term = self.get_obs()
+        st = self.state
+        T = action[0] + action[1]
+        f = np.array([st[1], np.sin(st[4]) * T / self.MASS, st[3], np.cos(st[4]) * T / self.MASS - self.G, st[5],
+                      (action[1] - action[0]) * self.ARM / np.sqrt(2.0) / self.IYY])
+        self.state = st = st + self.dt * f
+        self.episode_step += 1
+        x, z, th = st[0], st[2], st[4]
+        dist_goal = np.sqrt((x - self.goal_pos[0]) ** 2 + (z - self.goal_pos[1]) ** 2)
+        (x_lo, x_hi), (z_lo, z_hi) = self.x_range, self.z_range
+        out = bool(x < x_lo or x > x_hi or z < z_lo or z > z_hi)
+        d2 = (x - self.obstacle[0]) ** 2 + (z - self.obstacle[1]) ** 2
+        hit = bool(d2 < self.obstacle_radius ** 2)
+        crash = bool(x < self.crash_x[0] or x > self.crash_x[1] or z < self.crash_z[0] or z > self.crash_z[1] or
+                     abs(th) > self.crash_theta)
+        reward = -dist_goal
+        info = {}
+        goal = bool(dist_goal <= self.goal_size)
+        if goal:
+            info['goal_met'] = True
+            reward += self.reward_goal
+        cost = 0.0
+        if hit:
+            cost += (self.obstacle_radius - np.sqrt(d2)) / self.obstacle_radius
+        if out:
+            cost += max(0.0, x_lo - x) + max(0.0, x - x_hi) + max(0.0, z_lo - z) + max(0.0, z - z_hi)
+        info['num_safety_violation'] = int(out) + int(hit)
+        info['safety_cost'] = float(cost)
+        barrier_signal = self.D1 * float(out) + self.D2 * float(hit)
+        done = goal or crash or self.episode_step >= self.max_episode_steps
+        obs = self.get_obs()
+        return obs, reward, dist_goal, barrier_signal, lya_pre_term, obs, done, info
+
+
 def make(name, seed=0, **kw):
-    """``Unicycle`` / ``SimulatedCars`` / ``Pvtol`` / ``UnicycleBarrier`` / ``PvtolBarrier``."""
+    """``Unicycle`` / ``SimulatedCars`` / ``Pvtol`` / ``UnicycleBarrier`` / ``PvtolBarrier`` / ``QuadrotorLike``."""
     if name == "Unicycle":
         return UnicycleEnv(seed)
     if name == "UnicycleBarrier":
@@ -183,4 +242,6 @@ def make(name, seed=0, **kw):
         return PvtolEnv(seed, **kw)
     if name == "PvtolBarrier":
         return PvtolEnv(seed, barrier=True, **kw)
+    if name == "QuadrotorLike":
+        return QuadrotorLikeEnv(seed)
     raise Exception("Dynamics mode not supported.")

@@ -13,9 +13,11 @@ float32 observation the policy reads next.  With ``device_resets=False`` (the de
 float32 copy of ``obs``, torch ops with host syncs; with ``device_resets=True`` it is ONE launch
 (``csrc/env_reset_kernels.hip``) and no host read, the lanes that go on keep the observation the step kernel wrote, and
 SimulatedCars draws its initial-velocity offsets on the device from a counter-based generator ("Resets on
-the device") instead of numpy's global one.
+the device") instead of numpy's global one; the Quadrotor-like task draws its start positions the same way where an
+``init_spread`` is asked for.
 
-Checked against traces recorded from the reference's own env classes (tests/test_device_envs_gpu.py).
+Checked against traces recorded from the reference's own env classes (tests/test_device_envs_gpu.py); the Quadrotor-like
+task, for which the reference holds no code, against the host simulator (tests/test_quadrotor_env_gpu.py).
 """
 import ctypes as C
 
@@ -24,7 +26,7 @@ import torch
 
 from .. import _lib
 from ..arena import stream_ptr
-from ..envspec import PvtolSpec, SimulatedCarsSpec, UnicycleSpec
+from ..envspec import PvtolSpec, QuadrotorLikeSpec, SimulatedCarsSpec, UnicycleSpec
 
 
 def _dparams(*v):
@@ -277,9 +279,97 @@ class DeviceSimulatedCarsEnv(SimulatedCarsSpec, _DeviceEnv):
         return (self.obs, self.reward, self.constraint, self.lya_pre, self.lya_next, self.done, self._info("reached"))
 
 
+class DeviceQuadrotorLikeEnv(QuadrotorLikeSpec, _DeviceEnv):
+    """``envs.QuadrotorLikeEnv`` for ``n_envs`` environments (``QuadrotorLikeSpec``'s docstring has the step; no
+    reference code exists for this task).  ``step`` always returns the barrier copies' 8-tuple; the Lyapunov inputs are
+    the observations before / after the step.
+
+    ``init_spread=(sx, sz)``: every reset draws its start position, x = 1.5 + sx (2 u0 - 1), z = 0.3 + sz (2 u1 - 1),
+    so that N lanes are N different episodes.  The draws are made on the device by the reset's own launch
+    (``nlbac_quadrotor_env_reset``) from counters (seed, lane, reset number), as SimulatedCars' are, and need
+    ``device_resets=True``.  ``reset_noise`` (n, 2) holds every lane's last (dx, dz), ``reset_count`` the number of its
+    resets (the constructor's included).  Without a spread the start is the fixed row and device mode is the generic
+    ``nlbac_env_reset_rows``."""
+    state_dim, obs_dim, lya_dim, act_dim = 6, 6, 6, 2
+    barrier = True                             # (the task has a learned barrier and no other form)
+
+    def __init__(self, n_envs, seed=0, device="cuda", device_resets=False, init_spread=(0.0, 0.0)):
+        spread = tuple(float(v) for v in init_spread)
+        if len(spread) != 2 or not all(np.isfinite(v) and v >= 0.0 for v in spread):
+            raise ValueError("DeviceQuadrotorLikeEnv: init_spread is two finite non-negative floats (got %r)" % (init_spread,))
+        if any(spread) and not device_resets:
+            raise ValueError("DeviceQuadrotorLikeEnv: a start spread is drawn by the reset launch on the device: "
+                             "init_spread=%r needs device_resets=True" % (init_spread,))
+        QuadrotorLikeSpec.__init__(self, seed)
+        self.init_spread, self.device_resets = spread, bool(device_resets)
+        self._common(n_envs, device)
+        self._par = _dparams(self.dt, self.MASS, self.IYY, self.ARM, self.G, self.goal_pos[0], self.goal_pos[1],
+                             self.goal_size, self.reward_goal, self.x_range[0], self.x_range[1], self.z_range[0],
+                             self.z_range[1], self.obstacle[0], self.obstacle[1], self.obstacle_radius, self.D1, self.D2,
+                             self.crash_x[0], self.crash_x[1], self.crash_z[0], self.crash_z[1], self.crash_theta)
+        if self.device_resets:
+            self._device_buffers()
+            self._capture_start()
+            self.reset_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+            self.reset_noise = torch.zeros(self.n, 2, dtype=torch.float64, device=self.device)
+            self._reset_par = _dparams(*(tuple(self.start_state) + spread))
+        self.reset()
+
+    def _host_reset(self, mask=None):
+        m = self._all if mask is None else torch.as_tensor(mask, device=self.device).bool()
+        self.state[m] = torch.tensor(self.start_state, dtype=torch.float64, device=self.device)
+        self.ep_step[m] = 0
+        self.obs.copy_(self.state)
+        return self.obs
+
+    def _noise(self, noise):
+        if noise is None:
+            return None
+        return torch.as_tensor(noise, dtype=torch.float64, device=self.device).reshape(self.n, 2).contiguous()
+
+    def _launch_reset(self, flags, noise=None):
+        if noise is None and not any(self.init_spread):
+            return _DeviceEnv._launch_reset(self, flags)           # (the fixed start: the generic row reset)
+        nz = self._noise(noise)
+        _lib.call("nlbac_quadrotor_env_reset", self.n, None if flags is None else flags.data_ptr(), self.reset_seed,
+                  self._reset_par, None if nz is None else nz.data_ptr(), self.state.data_ptr(), self.ep_step.data_ptr(),
+                  self.obs.data_ptr(), self.obs32.data_ptr(), self.reset_count.data_ptr(), self.reset_noise.data_ptr(),
+                  stream_ptr())
+
+    def reset(self, mask=None, noise=None):
+        """``noise``: (n, 2) start-position offsets (dx, dz) to use in place of the lanes' draws (device mode only)."""
+        if not self.device_resets:
+            if noise is not None:
+                raise ValueError("DeviceQuadrotorLikeEnv.reset: start offsets need device_resets=True")
+            return self._host_reset(mask)
+        self._launch_reset(None if mask is None else self._flags(torch.as_tensor(mask, device=self.device).bool()), noise)
+        return self.obs
+
+    def reset_done(self, done=None, noise=None):
+        """``_DeviceEnv.reset_done``; ``noise``: as for ``reset``."""
+        if not self.device_resets:
+            if noise is not None:
+                raise ValueError("DeviceQuadrotorLikeEnv.reset_done: start offsets need device_resets=True")
+            return _DeviceEnv.reset_done(self, done)
+        self._launch_reset(self._flags(self.done if done is None else done), noise)
+        return self.obs32
+
+    def step(self, action):
+        a = self._action(action)
+        _lib.call("nlbac_quadrotor_env_step", self.n, self._par, int(self.max_episode_steps), a.data_ptr(),
+                  self.state.data_ptr(), self.ep_step.data_ptr(), self.obs.data_ptr(), self.reward.data_ptr(),
+                  self.constraint.data_ptr(), self.signal.data_ptr(), self.lya_pre.data_ptr(), self.done.data_ptr(),
+                  self.info.data_ptr(), stream_ptr())
+        return (self.obs, self.reward, self.constraint, self.signal, self.lya_pre, self.obs, self.done,
+                self._info("goal_met"))
+
+
 def make(name, n_envs, seed=0, device="cuda", device_resets=False, **kw):
-    """``Unicycle`` / ``UnicycleBarrier`` / ``SimulatedCars`` / ``Pvtol`` / ``PvtolBarrier``, batched on the device;
-    ``device_resets=True``: resets on the device (one launch per ``reset_done``).  ``**kw`` goes to the class."""
+    """``Unicycle`` / ``UnicycleBarrier`` / ``SimulatedCars`` / ``Pvtol`` / ``PvtolBarrier`` / ``QuadrotorLike``, batched
+    on the device; ``device_resets=True``: resets on the device (one launch per ``reset_done``).  ``**kw`` goes to the
+    class."""
+    if name == "QuadrotorLike":
+        return DeviceQuadrotorLikeEnv(n_envs, seed, device=device, device_resets=device_resets, **kw)
     if name in ("Unicycle", "UnicycleBarrier"):
         return DeviceUnicycleEnv(n_envs, seed, barrier=name.endswith("Barrier"), device=device,
                                  device_resets=device_resets, **kw)

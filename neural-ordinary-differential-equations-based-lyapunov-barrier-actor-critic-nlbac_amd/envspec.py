@@ -117,11 +117,37 @@ class QuadrotorLikeSpec:
     the allowed range and D2 = -10.0 on collision, a NODE on normalised [state (6) | action (2)] -> 6 with
     de-normalised outputs.  This is a SYNTHETIC stand-in of that shape — NO REFERENCE PARITY EXISTS for it: planar
     quadrotor state [x, x', z, z', theta, theta'] (the 2D quadrotor of safe-control-gym's paper), observation = state,
-    two rotor thrusts as the action, dt 0.02; every constant below is this build's choice."""
+    two rotor thrusts as the action, dt 0.02; every constant below is this build's choice.
+
+    The simulator (``envs.QuadrotorLikeEnv`` on the host, ``envs.device.DeviceQuadrotorLikeEnv`` batched on the device;
+    DESIGN.md §5 "The Quadrotor-like simulator") is ``synth.quadrotor_transitions``' arithmetic turned into episodes.
+    One step, float64, in this order (the action ``(a0, a1)`` is not clipped):
+
+        lya_pre = obs;   T = a0 + a1
+        f = [x', sin(theta) T / MASS, z', cos(theta) T / MASS - G, theta', (a1 - a0) ARM / sqrt(2) / IYY]
+        state = state + dt f;   episode_step += 1
+        dist  = sqrt((x - gx)^2 + (z - gz)^2)
+        out   = x, z outside x_range / z_range;   hit = (x - ox)^2 + (z - oz)^2 < obstacle_radius^2
+        crash = x, z outside crash_x / crash_z, or |theta| > crash_theta;   goal = dist <= goal_size
+        reward = -dist (+ reward_goal at the goal);  constraint = dist;  barrier signal = D1 out + D2 hit
+        done   = goal | crash | episode_step >= max_episode_steps
+        info:  goal_met (only when met), num_safety_violation = out + hit,
+               safety_cost = [hit] (r - d) / r + [out] the excess beyond the range, summed over its four sides
+
+    and ``step`` returns the barrier copies' 8-tuple (obs, reward, constraint, signal, lya_pre, obs, done, info).  A
+    crash is a true termination (mask 0), the time limit keeps mask 1, and leaving the allowed range alone ends
+    nothing: the learned barrier has to see D1 rows that go on.  An episode starts at ``start_state``, moved by
+    ``init_spread`` times a uniform draw on [-1, 1] in x and z where a spread is asked for (device resets only)."""
 
     dynamics_mode = "Quadrotor"
     n_s, n_u, obs_dim, lya_in = 6, 2, 6, 6
     MASS, IYY, ARM, G = 0.027, 1.4e-5, 0.0397, 9.8
+    # the simulator's own constants (synth.quadrotor_transitions has the goal's 0.05 and 250).  The straight line from
+    # the start to the goal passes within 0.11 of the obstacle's centre, so the obstacle is in the way.
+    start_state = (1.5, 0.0, 0.3, 0.0, 0.0, 0.0)
+    goal_size, reward_goal = 0.05, 250.0
+    crash_x, crash_z, crash_theta = (-3.0, 3.0), (-1.0, 3.0), np.pi / 2
+    init_spread = (0.0, 0.0)
 
     def __init__(self, seed=0):
         hover = self.MASS * self.G / 2.0

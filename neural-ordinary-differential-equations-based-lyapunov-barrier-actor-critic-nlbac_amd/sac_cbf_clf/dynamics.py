@@ -38,6 +38,8 @@ class DynamicsModel:
                 return (torch.from_numpy(state).type(dtype).to(device),
                         torch.from_numpy(np.ascontiguousarray(dyn)).type(dtype).to(device))
             return state, dyn
+        elif self.env.dynamics_mode == 'Quadrotor':
+            state = o.astype(np.float64).copy()          # the observation is the state (envspec.QuadrotorLikeSpec)
         else:
             raise Exception('Unknown dynamics')
         if single:

@@ -753,7 +753,10 @@ class QuadrotorBarrierTask(_LearnedBarrierTask):
     D2 = -10, CLF (V' - V)/1 + 0.1 V, ratio clamped at 0.002) on a NON-affine single-net NODE
     dx/dt = out_mu + out_sig * net(([x | u] - in_mu) / in_sig)  (8 -> 6, inputs normalised, outputs de-normalised inside
     the fused RK kernels).  The observation is the state, so get_state / get_obs are identities.  Like PvtolBarrier it
-    fits the NODE only in episodes <= 100 and regresses the Lyapunov critic on observations."""
+    fits the NODE only in episodes <= 100 and regresses the Lyapunov critic on observations.  Its transitions come from
+    this build's simulator (envs.QuadrotorLikeEnv / envs.device.DeviceQuadrotorLikeEnv, ``train.py --env
+    QuadrotorLike``) or, in the agent tests and the bench, from ``synth.quadrotor_transitions`` — the same one-step
+    model."""
     name = "QuadrotorBarrier"
     obs_dim, act_dim, lya_dim, n_s = 6, 2, 6, 6
     ratio_mode, gamma_l, lam_hi = 2, 0.1, 400.0

@@ -185,7 +185,8 @@ def quadrotor_transitions(n, seed=1, env=None):
     """Synthetic transitions of the Quadrotor-like task (``envspec.QuadrotorLikeSpec``; no reference code exists):
     random planar-quadrotor states, one Euler step of the rigid-body model, reward / cost = (minus) the distance to
     the goal, barrier signal D1 outside the allowed x / z range and D2 inside the obstacle (README.md:190); the
-    observation is the state and the Lyapunov inputs are the observations (the NP pattern)."""
+    observation is the state and the Lyapunov inputs are the observations (the NP pattern).  ``envs.QuadrotorLikeEnv``
+    is this arithmetic run as episodes and is pinned to these rows (tests/test_quadrotor_env_host.py)."""
     from .envspec import QuadrotorLikeSpec
     env = env or QuadrotorLikeSpec()
     rs = np.random.RandomState(seed)

@@ -7,6 +7,8 @@ line per episode (the reference's wandb / spinup loggers are host tooling and ou
 
     python -m nlbac_amd.train --env Unicycle --gamma_b 50 --max_episodes 200 --cuda --updates_per_step 2 \\
         --batch_size 128 --seed 0 --start_steps 1000          (the reference README's command line)
+    python -m nlbac_amd.train --env QuadrotorLike --gamma_b 1 --cuda ...   (the Quadrotor-like task: this build's
+        simulator, envs.QuadrotorLikeEnv — the reference holds no code for it)
 
 ``--device_replay`` keeps both replays in HBM (same index stream, gather on the device).
 ``--vector_envs N`` steps N environments on the device (``train_vectorized``); with ``--vector_handover`` each lane
@@ -14,6 +16,8 @@ also follows its copy's hand-over rules on the device (``vector_handover.py``); 
 per-episode records (reward, length, safety violations, safety cost) are kept on the device (``vector_episodes.py``) and
 ``--vector_episode_tsv PATH`` writes them out; with ``--vector_device_resets`` finished lanes restart by one launch on
 the device (SimulatedCars always does when vectorised).  ``evaluate_vectorized`` evaluates the acting policy on the same lanes.
+``--env QuadrotorLike`` runs under both drivers like the learned-barrier copies (``has_barrier_signal``): no backup
+controller, so ``--vector_handover`` raises.
 """
 import argparse
 import os
@@ -25,7 +29,7 @@ import numpy as np
 def get_args(argv=None):
     p = argparse.ArgumentParser(description="NLBAC training on MI355X (reference argument names)")
     p.add_argument('--env', default="Unicycle",
-                   choices=["Unicycle", "SimulatedCars", "Pvtol", "UnicycleBarrier", "PvtolBarrier"])
+                   choices=["Unicycle", "SimulatedCars", "Pvtol", "UnicycleBarrier", "PvtolBarrier", "QuadrotorLike"])
     p.add_argument('--policy', default="Gaussian")
     p.add_argument('--gamma', type=float, default=0.99)
     p.add_argument('--tau', type=float, default=0.005)
@@ -77,6 +81,12 @@ def get_args(argv=None):
                    help="with --vector_episodes: write one tab-separated line per record, under a header line, at the end of "
                         "the run")
     return p.parse_args(argv)
+
+
+def has_barrier_signal(env_name):
+    """The tasks whose simulator returns a barrier signal and whose agent learns the barrier from it (the
+    ``neural_barrier_certificate`` package): the two learned-barrier copies and the Quadrotor-like task."""
+    return env_name.endswith("Barrier") or env_name == "QuadrotorLike"
 
 
 class _Handover:
@@ -253,7 +263,7 @@ def make_handover(env_name, env, has_backup):
 def train(agent, env, dynamics_model, args, memory, node_memory, log=print, trace=None):
     """Returns a list of per-episode dicts (reward, length, safety violations, updates).  ``trace``: a list that
     receives one (use_backup, pushed_to_memory) pair per env step (driver tests)."""
-    barrier = args.env.endswith("Barrier")
+    barrier = has_barrier_signal(args.env)
     pvtol = args.env.startswith("Pvtol")
     has_backup = getattr(agent, "backup_policy", None) is not None
     ho = make_handover(args.env, env, has_backup and not barrier)
@@ -644,7 +654,7 @@ def main(argv=None):
     args = get_args(argv)
     import nlbac_amd  # noqa: F401
     from . import envs
-    barrier = args.env.endswith("Barrier")
+    barrier = has_barrier_signal(args.env)
     if barrier:
         from .neural_barrier_certificate.sac_cbf_clf.sac_cbf_clf import SAC_CBF_CLF
         from .neural_barrier_certificate.sac_cbf_clf.replay_memory import DeviceReplayMemory, ReplayMemory

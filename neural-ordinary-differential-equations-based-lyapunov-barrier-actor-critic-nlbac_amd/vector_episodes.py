@@ -7,6 +7,10 @@ running episode — float64, plain adds in step order, the bits a host loop over
 (``nlbac_episode_append``) writes one record per finished lane into a ring, in lane order within the vector step, behind
 a head that lives in device memory.  Nothing of a transition or of a decision reaches the host; the host reads the log
 when it wants it (``records``: one copy) and the sums over all lanes (``totals``: one small copy).
+
+A record's ``goal_met`` is the simulator's ``info[:, 0]`` of the episode's last step and ``timeout`` says that the step
+counter had reached the limit.  An episode that a simulator ends for another reason — the Quadrotor-like task's crash,
+a true termination with mask 0 — is a record with ``goal_met = 0`` and ``timeout = 0``.
 """
 import ctypes as C
 

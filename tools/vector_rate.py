@@ -2,7 +2,7 @@
 
     python tools/vector_rate.py [N [B]] [--env=NAME] [--device-resets] [--handover] [--episodes] [--launches] [--iters=K]
 
-``--env=NAME``: Unicycle (default), Pvtol or SimulatedCars (which always resets on the device).
+``--env=NAME``: Unicycle (default), Pvtol, SimulatedCars (which always resets on the device) or QuadrotorLike.
 ``--device-resets``: environments made with ``device_resets=True`` — finished lanes restart by one launch per vector step
 (``nlbac_env_reset_rows`` / ``nlbac_cars_env_reset``) instead of torch ops with host syncs.
 
@@ -25,11 +25,11 @@ handover, launches, episodes = "--handover" in sys.argv, "--launches" in sys.arg
 N, B, iters = int(argv[0]) if len(argv) > 0 else 4096, int(argv[1]) if len(argv) > 1 else 4096, 300
 iters = next((int(a[8:]) for a in sys.argv[1:] if a.startswith("--iters=")), iters)
 name = next((a[6:] for a in sys.argv[1:] if a.startswith("--env=")), "Unicycle")
-if name not in ("Unicycle", "Pvtol", "SimulatedCars"):
-    sys.exit("--env=NAME: Unicycle, Pvtol or SimulatedCars (got %r)" % name)
+if name not in ("Unicycle", "Pvtol", "SimulatedCars", "QuadrotorLike"):
+    sys.exit("--env=NAME: Unicycle, Pvtol, SimulatedCars or QuadrotorLike (got %r)" % name)
 device_resets = "--device-resets" in sys.argv or name == "SimulatedCars"
 make_env = lambda seed: denv.make(name, N, seed=seed, device_resets=device_resets)
-agent, _ = make_agent(B, 256, 0, "dopri5", name, {"Unicycle": 50.0, "Pvtol": 0.8}.get(name))
+agent, _ = make_agent(B, 256, 0, "dopri5", name, {"Unicycle": 50.0, "Pvtol": 0.8, "QuadrotorLike": 1.0}.get(name))
 env = make_env(0)
 args = types.SimpleNamespace(replay_size=1 << 20, seed=0, start_steps=2 * N, batch_size=B, updates_per_step=1,
                              NODE_model_update_interval=10)
@@ -56,6 +56,6 @@ if launches:
     own = names[marks[20]:marks[21]]
     driver = [n for n in own if n.endswith("_env_step") or n in (
         "nlbac_vector_step_rows", "nlbac_ring_append_kept", "nlbac_episode_step", "nlbac_episode_append",
-        "nlbac_env_reset_rows", "nlbac_cars_env_reset")]
+        "nlbac_env_reset_rows", "nlbac_cars_env_reset", "nlbac_quadrotor_env_reset")]
     print("library launches per vector step (update included): min %d max %d; the driver's own: %s"
           % (min(per_step), max(per_step), ", ".join(driver)))

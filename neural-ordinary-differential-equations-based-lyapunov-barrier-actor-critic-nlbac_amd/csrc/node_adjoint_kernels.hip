@@ -438,11 +438,16 @@ __device__ __forceinline__ void adj_norm_block(const float* a, const float* b, c
     }
 }
 
+// The larger of two norms, NaN if either is: fmax returns the other operand, which would hide a part of the mixed norm
+// that is not a number behind a finite one, and the controller would accept the step.
+__device__ __forceinline__ double max_keep_nan(double a, double b) { return (a != a || b != b) ? a + b : fmax(a, b); }
+__device__ __forceinline__ float max_keep_nan(float a, float b) { return (a != a || b != b) ? a + b : fmaxf(a, b); }
+
 __device__ __forceinline__ void adj_control_one(const double (&s)[4], int p, int mode, int ns, int nu, int rpp,
                                                 double t_end, const float* pnorm, double* ctl) {
     const double cnt = (double)rpp * (double)(ns + nu);
-    double n0 = fmax(sqrt(s[0] / cnt), sqrt(s[2] / cnt)), n1 = fmax(sqrt(s[1] / cnt), sqrt(s[3] / cnt));
-    if (pnorm) { n0 = fmax(n0, (double)pnorm[0]); n1 = fmax(n1, (double)pnorm[1]); }
+    double n0 = max_keep_nan(sqrt(s[0] / cnt), sqrt(s[2] / cnt)), n1 = max_keep_nan(sqrt(s[1] / cnt), sqrt(s[3] / cnt));
+    if (pnorm) { n0 = max_keep_nan(n0, (double)pnorm[0]); n1 = max_keep_nan(n1, (double)pnorm[1]); }
     dopri_control_vals(n0, n1, p, mode, t_end, ctl);
 }
 
@@ -610,8 +615,8 @@ __global__ __launch_bounds__(256) void adj_param_norm_kernel(int mode, const flo
     __threadfence();
     float m0 = 0.f, m1 = 0.f;
     for (int k = 0; k < n_seg; ++k) {
-        m0 = fmaxf(m0, __hip_atomic_load(pseg + 2 * k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        m1 = fmaxf(m1, __hip_atomic_load(pseg + 2 * k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        m0 = max_keep_nan(m0, __hip_atomic_load(pseg + 2 * k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        m1 = max_keep_nan(m1, __hip_atomic_load(pseg + 2 * k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     }
     pnorm[0] = sqrtf(m0); pnorm[1] = sqrtf(m1);
 }

@@ -322,8 +322,10 @@ def run(fn, inputs, dtype):
     return {k: v.detach() for k, v in fn({k: v.to(dtype) for k, v in inputs.items()}).items()}
 
 
-def reference_and_bar(op, fn, inputs, seed=0):
-    """(float64 reference, bar) per output of ``fn`` (dict of tensors -> dict of tensors) at the float32 ``inputs``."""
+def reference_and_bar(op, fn, inputs, seed=0, k=None):
+    """(float64 reference, bar) per output of ``fn`` (dict of tensors -> dict of tensors) at the float32 ``inputs``.
+    ``k``: the bar's factor where the operation is not one of this module's (``ode_control_common``)."""
+    k = K[op] if k is None else k
     base = run(fn, inputs, F64)
     dev = {k: torch.zeros_like(v) for k, v in base.items()}
     g = gen(1000 + seed)
@@ -332,7 +334,7 @@ def reference_and_bar(op, fn, inputs, seed=0):
                for k, v in inputs.items()}
         out = run(fn, nud, F64)
         dev = {k: torch.maximum(dev[k], (out[k] - base[k]).abs()) for k in base}
-    return base, {k: K[op] * (dev[k] + 2.0 ** -24 * base[k].abs()) for k in base}
+    return base, {name: k * (dev[name] + 2.0 ** -24 * base[name].abs()) for name in base}
 
 
 def bar_ratio(x, ref, bar):

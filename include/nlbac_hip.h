@@ -192,7 +192,8 @@ int nlbac_adam_step(float *p, float *m, float *v, const float *grad, int n_slabs
 /* nlbac_adam_prepare + nlbac_adam_step + nlbac_mlp_pack of the stepped nets in one launch.  scatter /
  * scatter_target (or NULL): scatter_slots * n uint64 device addresses, [scatter_slots * i + k] = the k-th
  * MFMA-fragment slot of parameter i inside the nets' `packed` buffers (0 = none; forward / backward pack: 2 slots,
- * with RR packs: 4), for the trained and the target copy. */
+ * with RR packs: 4), for the trained and the target copy.  Both tables are 16-byte aligned (two slots are read per
+ * load); a table that is not is refused. */
 int nlbac_adam_fused(float *p, float *m, float *v, const float *grad, int n_slabs, long slab_stride, long n,
                      void *state, double lr, float *target, float tau, const void *scatter,
                      const void *scatter_target, int scatter_slots /* 2 or 4 */,

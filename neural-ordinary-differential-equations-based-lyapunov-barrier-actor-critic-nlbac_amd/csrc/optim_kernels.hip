@@ -318,7 +318,7 @@ extern "C" int nlbac_adam_fused(float* p, float* m, float* v, const float* grad,
     }
     NLBAC_REQUIRE(n_slabs >= 1 && n >= 1 && lr > 0.0, "nlbac_adam_fused: bad sizes");
     NLBAC_REQUIRE(((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)grad | (uintptr_t)target) % 16 == 0 &&
-                      slab_stride % 4 == 0 && ((uintptr_t)scatter | (uintptr_t)scatter_target) % 8 == 0,
+                      slab_stride % 4 == 0 && ((uintptr_t)scatter | (uintptr_t)scatter_target) % 16 == 0,   // (two slots per load)
                   "nlbac_adam_fused: buffers must be 16-byte aligned");
     NLBAC_REQUIRE(!scatter_target || (target && tau >= 0.f), "nlbac_adam_fused: scatter_target without a target");
     hipLaunchKernelGGL((scatter_slots == 4 ? adam_fused_kernel<4> : adam_fused_kernel<2>), dim3(stream_grid(n, 4)), dim3(256),

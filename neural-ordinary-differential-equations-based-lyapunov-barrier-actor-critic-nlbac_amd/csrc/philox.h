@@ -32,7 +32,7 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 ctr, uint2 key) {
 //   u0 from (x, y), u1 from (z, w) as u1, u2 above;   dx = sx * (2 * u0 - 1),  dz = sz * (2 * u1 - 1),   all in float64
 #define PHILOX_TAG_QUADROTOR_RESET 3u
 
-__device__ __forceinline__ float u01(unsigned x) { return (float)(x >> 8) * 0x1p-24f + 0x1p-25f; }   // (0, 1)
+__device__ __forceinline__ float u01(unsigned x) { return (float)(x >> 8) * 0x1p-24f + 0x1p-25f; }   // (0, 1]
 
 // Thread t of the launch: row indices uniform on [0, src_rows) with replacement, the gather into minibatch layout and
 // the N(0,1) policy noise of the update.  Counter = (draw number, row | lane); Box-Muller.  src_rows == 0: no row is

@@ -1169,6 +1169,29 @@ int nlbac_quadrotor_env_reset(int n, const int *done, unsigned long long seed, c
                               const double *noise /*(n,2) or null*/, double *state /*(n,6)*/, int *ep_step,
                               double *obs /*(n,6)*/, float *obs32 /*(n,6)*/, int *reset_count,
                               double *reset_noise /*(n,2)*/, nlbac_stream_t s);
+/* nlbac_unicycle_env_reset, nlbac_pvtol_env_reset — Unicycle / Pvtol (and their barrier copies) with a start spread:
+ * the contract of nlbac_quadrotor_env_reset, with the reset observation computed from the moved state by the step's
+ * formulas.  (dx, dy) = noise[i] where noise (n,2) float64 is given; with a null noise they are the lane's draws at
+ * (seed, lane i, reset_count[i] before the increment), dx = sx (2 u0 - 1), dy = sy (2 u1 - 1), Philox tag 4 —
+ * csrc/philox.h has the definition.  A reset lane gets ep_step[i] = 0, reset_noise[i] = (dx, dy), reset_count[i] += 1 and
+ *   Unicycle  params: HOST array [9], start state (3: x, y, heading), start centre (2), goal (2), spread (sx, sy >= 0).
+ *             state[i] = (x + dx, y + dy, heading);  last_dist[i] = |goal - (centre + (dx, dy))|, the distance the first
+ *             step's reward starts from;  obs[i] (7) = [x, y, cos, sin, compass (2), exp(-|goal - (x, y)|)].
+ *   Pvtol     params: HOST array [11], start state (7), goal (2), spread (sx, sy >= 0).
+ *             state[i] = start with x + dx, y + dy and the safety operator's x (component 6) + dx;
+ *             obs[i] (11) = [x, y, cos, sin, vx, vy, thrust, operator x, compass (2), exp(-|goal - (x, y)|)].
+ * state (n,3 | n,7) / obs (n,7 | n,11) float64, obs32 (n,7 | n,11) float32, last_dist [n] float64, reset_noise (n,2)
+ * float64, ep_step / reset_count [n] int32, all updated in place; of a lane that is not reset nothing is written but its
+ * obs32 row.  Both refuse n < 1, a null required pointer and a negative spread before anything is launched.  (Added
+ * without an ABI bump: new entry points only.) */
+int nlbac_unicycle_env_reset(int n, const int *done, unsigned long long seed, const double *params /*host [9]*/,
+                             const double *noise /*(n,2) or null*/, double *state /*(n,3)*/, int *ep_step,
+                             double *last_dist, double *obs /*(n,7)*/, float *obs32 /*(n,7)*/, int *reset_count,
+                             double *reset_noise /*(n,2)*/, nlbac_stream_t s);
+int nlbac_pvtol_env_reset(int n, const int *done, unsigned long long seed, const double *params /*host [11]*/,
+                          const double *noise /*(n,2) or null*/, double *state /*(n,7)*/, int *ep_step,
+                          double *obs /*(n,11)*/, float *obs32 /*(n,11)*/, int *reset_count,
+                          double *reset_noise /*(n,2)*/, nlbac_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Backup-controller hand-over of the vectorised driver (train.train_vectorized(handover=...)): lane i is the loop of

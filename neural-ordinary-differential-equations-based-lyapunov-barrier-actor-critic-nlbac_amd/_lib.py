@@ -333,6 +333,9 @@ _PROTOS = {
     # (ABI 17, additions: the Quadrotor-like task's simulator, envs/device.py DeviceQuadrotorLikeEnv)
     "nlbac_quadrotor_env_step": [_I, c_double_p, _I] + [_P] * 11,
     "nlbac_quadrotor_env_reset": [_I, _P, C.c_uint64, c_double_p] + [_P] * 8,
+    # (ABI 17, additions: start positions drawn per reset for Unicycle / Pvtol, envs/device.py init_spread=)
+    "nlbac_unicycle_env_reset": [_I, _P, C.c_uint64, c_double_p] + [_P] * 9,
+    "nlbac_pvtol_env_reset": [_I, _P, C.c_uint64, c_double_p] + [_P] * 8,
     # (new entry points of ABI 17: the vectorised driver's backup-controller hand-over, vector_handover.py)
     "nlbac_vector_step_rows": [_I, C.POINTER(HandoverParams), C.POINTER(RowLayout)] + [_P] * 6 + [_I, _P, _P, _P, _P, _D, _I,
                                                                                                  _P, _L, _L] + [_P] * 6 + [_P],

@@ -31,6 +31,12 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 ctr, uint2 key) {
 //   (x, y, z, w) = philox4x32_10(counter (lane, reset_count[lane] before the increment, 0, 3), the same key)
 //   u0 from (x, y), u1 from (z, w) as u1, u2 above;   dx = sx * (2 * u0 - 1),  dz = sz * (2 * u1 - 1),   all in float64
 #define PHILOX_TAG_QUADROTOR_RESET 3u
+// 4 is the start-position offsets of the Unicycle and Pvtol resets and their barrier copies' (env_reset_kernels.hip:
+// start_reset_offsets), one tag for both tasks, again the same counter and the same two 52-bit uniforms:
+//   (x, y, z, w) = philox4x32_10(counter (lane, reset_count[lane] before the increment, 0, 4), the same key)
+//   u0 from (x, y), u1 from (z, w) as u1, u2 above;   dx = sx * (2 * u0 - 1),  dy = sy * (2 * u1 - 1),   all in float64
+// (tests/test_start_spread_host.py restates it in numpy).
+#define PHILOX_TAG_START_RESET 4u
 
 __device__ __forceinline__ float u01(unsigned x) { return (float)(x >> 8) * 0x1p-24f + 0x1p-25f; }   // (0, 1]
 

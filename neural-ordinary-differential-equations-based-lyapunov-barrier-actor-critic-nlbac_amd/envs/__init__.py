@@ -30,11 +30,20 @@ class UnicycleEnv(UnicycleSpec):
     def get_obs(self):
         return _unicycle_obs(self.state[None], self.goal_pos)[0]
 
-    def reset(self):
+    def reset(self, offset=None):
+        """``offset``: (dx, dy) added to the start position — what a device environment with an ``init_spread`` draws
+        per reset (``reset_noise``); None: the fixed start.  The position (state 0, 1) and the centre ``l_p`` ahead of
+        it move, and with the centre the distance to the goal that the first step's reward starts from; the heading
+        stays 0."""
         self.episode_step = 0
         self.state = np.array([-2.5, -2.5, 0.0])
         self.center = np.array([-2.47, -2.5])
         self.next_center = np.array([-2.47, -2.5])
+        if offset is not None:
+            d = np.array([float(offset[0]), float(offset[1])])
+            self.state[:2] = self.state[:2] + d
+            self.center = self.center + d
+            self.next_center = self.next_center + d
         self.last_goal_dist = np.linalg.norm(self.goal_pos - self.next_center)
         return self.get_obs()
 
@@ -134,9 +143,17 @@ class PvtolEnv(PvtolSpec):
     def get_obs(self):
         return _pvtol_obs(self.state[None], self.goal_pos)[0]
 
-    def reset(self):
+    def reset(self, offset=None):
+        """``offset``: (dx, dy) added to the start position — what a device environment with an ``init_spread`` draws
+        per reset (``reset_noise``); None: the fixed start.  x, y (state 0, 1) move, and with x the safety operator
+        (state 6), which the reference places at the vehicle's x; the tilt, the velocities and the thrust (state 2 - 5)
+        stay."""
         self.episode_step = 0
         self.state = np.array([-4.5, -4.5, 0.0, 0.0, 0.0, 1.0, -4.5])
+        if offset is not None:
+            self.state[0] = self.state[0] + float(offset[0])
+            self.state[1] = self.state[1] + float(offset[1])
+            self.state[6] = self.state[6] + float(offset[0])
         self.last_goal_dist = np.linalg.norm(self.goal_pos - self.state[:2])
         return self.get_obs()
 

@@ -15,7 +15,9 @@ line per episode (the reference's wandb / spinup loggers are host tooling and ou
 also follows its copy's hand-over rules on the device (``vector_handover.py``); with ``--vector_episodes`` the
 per-episode records (reward, length, safety violations, safety cost) are kept on the device (``vector_episodes.py``) and
 ``--vector_episode_tsv PATH`` writes them out; with ``--vector_device_resets`` finished lanes restart by one launch on
-the device (SimulatedCars always does when vectorised).  ``evaluate_vectorized`` evaluates the acting policy on the same lanes.
+the device (SimulatedCars always does when vectorised), and with ``--vector_init_spread SX SY`` every restart draws its
+start position there, so that the lanes are different episodes.  ``evaluate_vectorized`` evaluates the acting policy on
+the same lanes.
 ``--env QuadrotorLike`` runs under both drivers like the learned-barrier copies (``has_barrier_signal``): no backup
 controller, so ``--vector_handover`` raises.
 """
@@ -71,6 +73,11 @@ def get_args(argv=None):
                         "(envs.device.make(device_resets=True)) instead of torch ops with host syncs; SimulatedCars runs so "
                         "with or without this flag, its initial-velocity draws then come from a counter-based generator on "
                         "the device")
+    p.add_argument('--vector_init_spread', nargs=2, type=float, default=None, metavar=("SX", "SY"),
+                   help="with --vector_envs: every reset draws its start position on the device, uniform within SX, SY of "
+                        "the task's start (envs.device.make(init_spread=(SX, SY))), so that the lanes are different "
+                        "episodes; implies --vector_device_resets.  Unicycle, Pvtol, their barrier copies and QuadrotorLike "
+                        "(SX, SZ); an error for SimulatedCars, whose initial-velocity draw is its own")
     p.add_argument('--vector_handover', action="store_true",
                    help="with --vector_envs: the backup controller acts where the copy's hand-over rules say so, decided "
                         "per lane on the device; its steps stay out of the controller replay")
@@ -81,6 +88,16 @@ def get_args(argv=None):
                    help="with --vector_episodes: write one tab-separated line per record, under a header line, at the end of "
                         "the run")
     return p.parse_args(argv)
+
+
+def vector_env_options(env_name, device_resets, init_spread=None):
+    """The keywords ``envs.device.make`` gets from the command line: ``--vector_init_spread SX SY`` is drawn by the reset
+    launch, so it implies resets on the device; SimulatedCars has a draw of its own and takes none."""
+    if init_spread is None:
+        return dict(device_resets=bool(device_resets))
+    if env_name == "SimulatedCars":
+        raise ValueError("--vector_init_spread: SimulatedCars draws its initial velocities itself and has no start spread")
+    return dict(device_resets=True, init_spread=tuple(float(v) for v in init_spread))
 
 
 def has_barrier_signal(env_name):
@@ -681,7 +698,8 @@ def main(argv=None):
             args.vector_episodes = True
         # (SimulatedCars has one vectorised form: its host-mode reset is a per-lane host loop over numpy's global stream)
         device_resets = bool(args.vector_device_resets) or args.env == "SimulatedCars"
-        venv = device_envs.make(args.env, args.vector_envs, seed=max(args.seed, 0), device_resets=device_resets)
+        venv = device_envs.make(args.env, args.vector_envs, seed=max(args.seed, 0),
+                                **vector_env_options(args.env, device_resets, args.vector_init_spread))
         res = train_vectorized(agent, venv, args, args.max_steps or 100000, handover=args.vector_handover or None,
                                episodes=args.vector_episodes)
         if args.vector_episode_tsv:

@@ -1,10 +1,13 @@
 """GPU: throughput of the vectorised driver (train.train_vectorized): N device environments + one update per vector step.
 
-    python tools/vector_rate.py [N [B]] [--env=NAME] [--device-resets] [--handover] [--episodes] [--launches] [--iters=K]
+    python tools/vector_rate.py [N [B]] [--env=NAME] [--device-resets] [--init-spread=SX,SY] [--handover] [--episodes]
+                                [--launches] [--iters=K]
 
 ``--env=NAME``: Unicycle (default), Pvtol, SimulatedCars (which always resets on the device) or QuadrotorLike.
 ``--device-resets``: environments made with ``device_resets=True`` — finished lanes restart by one launch per vector step
 (``nlbac_env_reset_rows`` / ``nlbac_cars_env_reset``) instead of torch ops with host syncs.
+``--init-spread=SX,SY``: environments made with ``init_spread=(SX, SY)`` — every restart draws its start position in that
+launch (``nlbac_unicycle_env_reset`` / ``nlbac_pvtol_env_reset`` / ``nlbac_quadrotor_env_reset``); implies ``--device-resets``.
 
 ``--handover``: with the backup-controller hand-over decided per lane on the device (two replays, two acting policies).
 ``--episodes``: with the per-episode ledger on the device (``episodes=True``: two more launches per vector step).
@@ -27,8 +30,10 @@ iters = next((int(a[8:]) for a in sys.argv[1:] if a.startswith("--iters=")), ite
 name = next((a[6:] for a in sys.argv[1:] if a.startswith("--env=")), "Unicycle")
 if name not in ("Unicycle", "Pvtol", "SimulatedCars", "QuadrotorLike"):
     sys.exit("--env=NAME: Unicycle, Pvtol, SimulatedCars or QuadrotorLike (got %r)" % name)
-device_resets = "--device-resets" in sys.argv or name == "SimulatedCars"
-make_env = lambda seed: denv.make(name, N, seed=seed, device_resets=device_resets)
+spread = next((tuple(float(v) for v in a[14:].split(",")) for a in sys.argv[1:] if a.startswith("--init-spread=")), None)
+device_resets = "--device-resets" in sys.argv or name == "SimulatedCars" or spread is not None
+env_kw = {"init_spread": spread} if spread is not None else {}
+make_env = lambda seed: denv.make(name, N, seed=seed, device_resets=device_resets, **env_kw)
 agent, _ = make_agent(B, 256, 0, "dopri5", name, {"Unicycle": 50.0, "Pvtol": 0.8, "QuadrotorLike": 1.0}.get(name))
 env = make_env(0)
 args = types.SimpleNamespace(replay_size=1 << 20, seed=0, start_steps=2 * N, batch_size=B, updates_per_step=1,
@@ -40,8 +45,9 @@ train_vectorized(agent, env, args, 20 * N, log=lambda *a: None, **kw)        # w
 torch.cuda.synchronize(); t0 = time.perf_counter()
 res = train_vectorized(agent, make_env(1), args, iters * N, log=lambda *a: None, **kw)
 dt = time.perf_counter() - t0
-print("%s, N=%d lanes, batch %d, resets on the %s%s%s: %d env steps + %d updates in %.3f s = %.2f M env steps/s, %.2f ms per vector step"
-      % (name, N, B, "device" if device_resets else "host", ", hand-over on (%d backup steps)" % res["backup_steps"] if handover else "",
+print("%s, N=%d lanes, batch %d, resets on the %s%s%s%s: %d env steps + %d updates in %.3f s = %.2f M env steps/s, %.2f ms per vector step"
+      % (name, N, B, "device" if device_resets else "host", ", start spread %g, %g" % spread if spread is not None else "",
+         ", hand-over on (%d backup steps)" % res["backup_steps"] if handover else "",
          ", ledger on (%d records, %d safety violations)" % (len(res["history"]), res["violations"]) if episodes else "",
          res["steps"], res["updates"], dt, res["steps"] / dt / 1e6, 1e3 * dt / iters))
 if launches:
@@ -56,6 +62,7 @@ if launches:
     own = names[marks[20]:marks[21]]
     driver = [n for n in own if n.endswith("_env_step") or n in (
         "nlbac_vector_step_rows", "nlbac_ring_append_kept", "nlbac_episode_step", "nlbac_episode_append",
-        "nlbac_env_reset_rows", "nlbac_cars_env_reset", "nlbac_quadrotor_env_reset")]
+        "nlbac_env_reset_rows", "nlbac_cars_env_reset", "nlbac_quadrotor_env_reset", "nlbac_unicycle_env_reset",
+        "nlbac_pvtol_env_reset")]
     print("library launches per vector step (update included): min %d max %d; the driver's own: %s"
           % (min(per_step), max(per_step), ", ".join(driver)))

@@ -62,17 +62,22 @@ __device__ __forceinline__ void gauss_bwd_one(const float* heads, int heads_ld, 
                                               int n_u, long i, int c, const float* da0, int da0_ld, const float* da1,
                                               int da1_ld, const float* da2, int da2_ld, float dlp, float& dmean,
                                               float& dls) {
+    // Every rounding is written out (no contraction by the compiler; the three fused products by name): which of these
+    // products the compiler fuses depends on the kernel this is inlined into — nlbac_gauss_sample_bwd's kernel took
+    // fma(scale, 1 - y^2, eps) and fma(da, s1, .), the dy heads neither, 1 ulp apart in d heads — and nlbac_dy_head
+    // promises the per-row entry point's outputs bit for bit.  The form is the one the dy heads compiled to.
+#pragma clang fp contract(off)
     const float mean = heads[i * heads_ld + c];
     const float ls_raw = heads[i * heads_ld + n_u + c];
     const float ls = fminf(fmaxf(ls_raw, LOG_SIG_MIN), LOG_SIG_MAX);
     const float std = expf(ls);
     const float e = eps[i * n_u + c];
-    const float y = tanhf(mean + e * std);
+    const float y = tanhf(__builtin_fmaf(e, std, mean));
     float da = 0.f;
     if (da0) da += da0[i * da0_ld + c];
     if (da1) da += da1[i * da1_ld + c];
     if (da2) da += da2[i * da2_ld + c];
-    const float one_m = 1.0f - y * y;
+    const float one_m = __builtin_fmaf(-y, y, 1.0f);
     const float s1 = scale[c] * one_m;
     // dx through a = scale*tanh(x)+bias and through -log(scale(1-y^2)+eps)
     const float gx = da * s1 + dlp * (2.0f * y * s1 / (s1 + SAMPLE_EPS));
@@ -80,7 +85,7 @@ __device__ __forceinline__ void gauss_bwd_one(const float* heads, int heads_ld, 
     dmean = gx;
     const float dstd = gx * e;
     const bool in_range = (ls_raw >= LOG_SIG_MIN) && (ls_raw <= LOG_SIG_MAX);
-    dls = in_range ? (dstd * std - dlp) : 0.f;
+    dls = in_range ? __builtin_fmaf(std, dstd, -dlp) : 0.f;
 }
 
 // Sum of n_tiles partials (stride floats apart) read past the non-coherent caches: thread t takes tiles t, t + 256, ...

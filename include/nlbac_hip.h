@@ -1098,6 +1098,18 @@ int nlbac_sample_windows(const float *src, long src_rows, long cap, long head, i
  * partials, that many, 1, 1.0f, out) finishes the scalar.  H = 1 with every window valid is nn.MSELoss('mean'). */
 int nlbac_traj_mse_fwd_bwd(const float *pred, const float *target, const float *valid, const int *counts, int n_counts,
                            long n, int H, int n_s, float *dpred, float *partials, nlbac_stream_t s);
+/* Prediction-error statistics over trajectory windows, by look-ahead step k and state component c (NODE validation):
+ * pred / target [H][n][n_s] and x0 [n][n_s] contiguous float32, valid [n] (1.0f / 0.0f; NULL: every window),
+ * 1 <= H <= 65535, 1 <= n < 2^31, 1 <= n_s <= 16.  With e = (double)pred - (double)target, over the valid windows:
+ *   stats [5][H][n_s] (double):  0 sum e^2,  1 sum |e|,  2 max |e| (0 without a valid window),
+ *                                3 sum ((double)x0 - (double)target)^2 (the state does not move),  4 sum target^2;
+ *   nvalid (one long): the valid windows.
+ * Float64 from the load on; a NaN / Inf error in a valid window makes that (k, c)'s planes 0 - 2 non-finite, an invalid
+ * window's values are never looked at.  No atomics and no election: min(128, ceil(n n_s / 2048)) workgroups per step
+ * leave 5 n_s + 1 doubles each in `scratch` (scratch_doubles >= H * that many * (5 n_s + 1)), a second launch adds them
+ * in block order — the same bits on every call.  (Added without an ABI bump: a new entry point only.) */
+int nlbac_traj_err_stats(const float *pred, const float *target, const float *x0, const float *valid, long n, int H,
+                         int n_s, double *scratch, long scratch_doubles, double *stats, long *nvalid, nlbac_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Batched device simulators (row f3): n independent environments advanced by one launch, one lane each, float64 like

@@ -234,6 +234,8 @@ _PROTOS = {
     "nlbac_gather_windows": [_P, _L, _L, _L, _I, _P, _L, _I, _L, _I, _I, _I, _P, _P, _P, _P],
     "nlbac_sample_windows": [_P, _L, _L, _L, _I, _L, _I, _L, _I, _I, _I, _P, _P, _P, C.c_uint64, C.c_uint64, _P],
     "nlbac_traj_mse_fwd_bwd": [_P, _P, _P, _P, _I, _L, _I, _I, _P, _P, _P],
+    # (ABI 17, addition: prediction-error statistics over trajectory windows, node_fit.traj_error_stats)
+    "nlbac_traj_err_stats": [_P, _P, _P, _P, _L, _I, _I, _P, _L, _P, _P, _P],
     "nlbac_td_value": [_P, _P, _I, _P, _I, _P, _F, _I, _I, _P, _P, _P, _P, _F, _P, _P],
     "nlbac_unicycle_obs_fwd": [_P, _I, _F, _F, _P, _I, _P],
     "nlbac_unicycle_obs_bwd": [_P, _P, _I, _I, _F, _F, _P, _I, _P],

@@ -75,9 +75,10 @@ def _check_tile(func, H, method, adjoint, step_control, max_steps, info, tile_st
 
 
 def _check(func, x0, controls, dt, method, step_size=None, *, adjoint=False, step_control="batch", max_steps=None,
-           info=None, tile_steps=None):
+           info=None, tile_steps=None, on_device=True):
     """Every argument check, before anything touches a device.  Returns ``dt`` rounded to float32 as ``odeint``'s time
-    grid rounds it and, with ``step_size``, the fine steps of a control interval (``ode_grid._sub_grid`` over [0, dt])."""
+    grid rounds it and, with ``step_size``, the fine steps of a control interval (``ode_grid._sub_grid`` over [0, dt]).
+    ``on_device=False``: everything but where the tensors are (a caller that moves them itself, afterwards)."""
     from .sac_cbf_clf.model import NeuralODEModel
     if not isinstance(func, NeuralODEModel):
         raise TypeError("nlbac_amd.rollout integrates this build's NeuralODEModel (its field runs as HIP kernels); "
@@ -123,7 +124,8 @@ def _check(func, x0, controls, dt, method, step_size=None, *, adjoint=False, ste
             raise NotImplementedError("rollout: step_control='tile' needs nets the register-resident kernels serve "
                                       "(nlbac_node_dopri_tile_ok: both nets 64, 100 or 128 wide, f_net five layers, "
                                       "g_net four); there is no chained fallback")
-    _check_device(x0, controls)
+    if on_device:
+        _check_device(x0, controls)
     return dt, hs
 
 

@@ -64,6 +64,16 @@ class ReplayMemory:
                                   self._cols[0], self._cols[nstate])
         return tuple(c[rows] for c in self._cols), valid
 
+    def windows_at(self, idx, horizon, stride=1):
+        """``sample_windows``'s ``(fields, valid)`` for the caller's start rows ``idx`` (int64, in [0, len)): nothing is
+        drawn, no generator moves (``SAC_CBF_CLF.validate_node``)."""
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        check_windows(max(1, len(idx)), horizon, stride, self._len, host_draw=False)
+        nstate = len(self._cols) - 4
+        rows, valid = window_rows(idx, horizon, stride, self._len, self.capacity, self.position,
+                                  self._cols[0], self._cols[nstate])
+        return tuple(c[rows] for c in self._cols), valid
+
     def __len__(self):
         return self._len
 

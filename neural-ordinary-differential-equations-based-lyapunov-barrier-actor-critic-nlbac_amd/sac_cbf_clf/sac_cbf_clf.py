@@ -196,6 +196,8 @@ class SAC_CBF_CLF(object):
         self._noise = None
         self._fit_ws = {}
         self._fit_win_ws = {}                 # fit_node_windows' buffers per (rows, horizon)
+        self._val_ws = {}                     # validate_node_windows' own, per (rows, horizon)
+        self._val_seed, self._val_gen = int(args.seed), None      # validate_node's private CPU generator (made when needed)
         self._fill = collections.deque()      # pieces of part 1 not yet queued (see _upd_part1)
         self._fill_first = True               # the next solver wait is the first of its update
         self._readback = ScalarsReadback(self.sc)
@@ -575,6 +577,118 @@ class SAC_CBF_CLF(object):
             self._fit_win_ws[(N, H)] = dict(x0=z(N, ns), target=z(H, N, ns), u=z(H, N, nc), xs=z(H, N, ns),
                                             dout=z(H + 1, N, ns), part=z(loss_blocks(H, N, ns)))
         return self._fit_win_ws[(N, H)]
+
+    # -- NODE validation over trajectory windows ---------------------------------------------
+    def validate_node_windows(self, rows, valid=None, counts=None):
+        """The NODE's prediction error over trajectory windows, by look-ahead step and state component:
+        ``fit_node_windows`` up to the loss — the same ``rows`` (H, N, LD) / ``valid`` / ``counts`` contract (``counts``
+        is accepted and not needed), ``fit_inputs``, ``state_rows`` for x_0 and the targets, the carried columns, ``dt``
+        on the float32 grid, ONE ``ode_traj.solve`` over the H intervals that keeps nothing — then
+        ``nlbac_traj_err_stats`` instead of the loss.  Returns ``(stats (5, H, n_s) float64, nvalid () int64)`` on the
+        device without a synchronisation (``node_fit.error_report`` reads them).
+
+        Measures only: the scalars block (``SC_NODE_LOSS`` keeps the last fit's value), the arenas, Adam's state, every
+        generator, the fit's workspaces and the update's queued pieces stay as they are; its buffers are its own, two
+        shapes at most.  Angles are not wrapped (``node_fit.validate_rollout``)."""
+        from .. import ode_traj as T
+        from ..node_fit import traj_error_stats_launch
+        from ..rollout import _one_launch_ok
+        if self.world > 1:
+            raise RuntimeError("validate_node_windows: trajectory windows are not sharded over GPUs; use node_horizon = 1 "
+                               "under enable_data_parallel")
+        if not isinstance(rows, torch.Tensor) or rows.dim() != 3 or rows.shape[2] != self.lay.LD \
+                or rows.dtype != torch.float32 or not rows.is_cuda:
+            raise ValueError("validate_node_windows: rows must be a float32 device tensor (H, N, %d); got %s"
+                             % (self.lay.LD, tuple(rows.shape) if isinstance(rows, torch.Tensor) else type(rows).__name__))
+        rows = rows.contiguous()
+        H, N, LD = rows.shape
+        task, model, ns = self.task, self.neural_ode_model, self.task.n_s
+        if valid is not None:
+            valid = (torch.as_tensor(valid).to(self.device).reshape(-1) != 0).to(torch.float32).contiguous()
+            if valid.numel() != N:
+                raise ValueError("validate_node_windows: valid must hold one entry per window (%d); got %d"
+                                 % (N, valid.numel()))
+        w = self._validate_ws(N, H)
+        flat = rows.view(H * N, LD)
+        p_obs, obs_ld, ctl, p_nobs, nobs_ld, _ = task.fit_inputs(flat)
+        task.state_rows(p_obs, obs_ld, N, w["x0"])                      # step 0's observation
+        task.state_rows(p_nobs, nobs_ld, H * N, w["target"])            # every step's next observation
+        w["u"].view(H * N, -1).copy_(ctl)                               # every step's carried columns
+        dt = float(torch.tensor([0.0, float(self.env.dt)], dtype=torch.float32)[1])      # (as odeint's time grid rounds it)
+        T.solve(model, T.EqualSteps(dt, H), self.solver, "none", _one_launch_ok(model, self.solver),
+                w["x0"], w["u"], w["xs"], self.atol, self.rtol)
+        stats = torch.empty(5, H, ns, dtype=torch.float64, device=self.device)      # (the caller's: a driver keeps a list)
+        nvalid = torch.empty((), dtype=torch.int64, device=self.device)
+        traj_error_stats_launch(w["xs"], w["target"], w["x0"], valid, H, N, ns, w["scratch"], stats, nvalid)
+        return stats, nvalid
+
+    def _validate_ws(self, N, H):
+        ws = self._val_ws
+        if (N, H) not in ws:
+            from ..node_fit import stats_scratch_doubles
+            while len(ws) >= 2:                    # as _fit_win_ws
+                ws.pop(next(iter(ws)))
+            z, ns = self.task.z, self.task.n_s
+            nc = self.neural_ode_model.n_u if self.neural_ode_model.affine else self.neural_ode_model.n_carry
+            ws[(N, H)] = dict(x0=z(N, ns), target=z(H, N, ns), u=z(H, N, nc), xs=z(H, N, ns),
+                              scratch=torch.empty(stats_scratch_doubles(H, N, ns), dtype=torch.float64, device=self.device))
+        return ws[(N, H)]
+
+    VALIDATE_SEED_TAG = 0x6E6F64655F76616C      # the private generator of validate_node: args.seed and this tag
+
+    def validate_node(self, memory, n_windows, horizon=None, stride=None, idx=None, generator=None):
+        """``validate_node_windows`` on ``n_windows`` windows of ``horizon`` steps ``stride`` rows apart out of the replay
+        ``memory`` (defaults: the agent's ``node_horizon`` / ``node_stride``).  Start rows: ``idx`` (int64, one per
+        window), else ``torch.randint(0, len(memory), (n_windows,), generator=g)`` with ``g`` = ``generator`` or a CPU
+        generator of the agent's own, seeded from ``args.seed`` and a fixed tag when first needed; the replay's gather
+        launch decides which windows are unbroken trajectories (``nlbac_gather_windows``; a host ``ReplayMemory`` applies
+        the same rule and is packed step by step).  Returns ``(stats, nvalid)`` on the device, or None while
+        ``(horizon - 1) * stride >= len(memory)`` — nothing to validate on yet.
+
+        Leaves as found: the replay's draw counter and ``window_counts``, Python's ``random``, numpy's global generator,
+        torch's global CPU and CUDA generators — a training run that validates in between continues bit for bit."""
+        H = self.node_horizon if horizon is None else horizon
+        stride = self.node_stride if stride is None else stride
+        for name, v in (("n_windows", n_windows), ("horizon", H), ("stride", stride)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError("validate_node: %s must be an integer >= 1; got %r" % (name, v))
+        if generator is not None and (not isinstance(generator, torch.Generator) or generator.device.type != "cpu"):
+            raise ValueError("validate_node: generator must be a CPU torch.Generator")
+        if idx is not None:
+            idx = torch.as_tensor(idx)
+            if idx.dtype != torch.int64 or idx.dim() != 1 or idx.numel() != n_windows:
+                raise ValueError("validate_node: idx must be %d int64 start rows" % n_windows)
+        if self.world > 1:
+            raise RuntimeError("validate_node: trajectory windows are not sharded over GPUs; use node_horizon = 1 "
+                               "under enable_data_parallel")
+        H, stride, n_windows = int(H), int(stride), int(n_windows)
+        if (H - 1) * stride >= len(memory):
+            return None
+        if idx is None:
+            g = generator
+            if g is None:
+                g = self._val_gen
+                if g is None:
+                    g = self._val_gen = torch.Generator()
+                    g.manual_seed((self._val_seed * 0x9E3779B97F4A7C15 + self.VALIDATE_SEED_TAG) & 0x7FFFFFFFFFFFFFFF)
+            idx = torch.randint(0, len(memory), (n_windows,), generator=g, dtype=torch.int64)
+        if hasattr(memory, "sample_rows") and hasattr(memory, "sample_windows"):
+            had, counts = hasattr(memory, "window_counts"), getattr(memory, "window_counts", None)
+            draws = getattr(memory, "_draws", None)      # (a replay without a draw counter has none to put back)
+            try:
+                rows, valid = memory.sample_windows(n_windows, H, stride, idx=idx)
+            finally:
+                if draws is not None:
+                    memory._draws = draws
+                if had:
+                    memory.window_counts = counts
+                elif hasattr(memory, "window_counts"):
+                    del memory.window_counts
+        else:                                        # host replay: its own rule, packed step by step
+            fields, valid = memory.windows_at(idx.numpy(), H, stride)
+            rows = torch.stack([self._rows_from_host(tuple(f[k] for f in fields)) for k in range(H)]).to(self.device)
+            valid = torch.from_numpy(valid.astype(np.float32))
+        return self.validate_node_windows(rows, valid)
 
     # -- the update proper --------------------------------------------------------
     def _plan(self, ws, NP=None):

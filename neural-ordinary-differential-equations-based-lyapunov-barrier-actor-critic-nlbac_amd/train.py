@@ -87,7 +87,93 @@ def get_args(argv=None):
     p.add_argument('--vector_episode_tsv', default=None, metavar="PATH",
                    help="with --vector_episodes: write one tab-separated line per record, under a header line, at the end of "
                         "the run")
+    p.add_argument('--node_validate_every', type=int, default=0, metavar="K",
+                   help="K > 0: before every update whose index is a multiple of K, measure the NODE's prediction error by "
+                        "look-ahead step and state component over trajectory windows of the NODE replay "
+                        "(SAC_CBF_CLF.validate_node; changes no bit of training; read and logged at the end of the run); "
+                        "0: off")
+    p.add_argument('--node_validate_windows', type=int, default=4096, metavar="W",
+                   help="with --node_validate_every: start rows drawn per validation")
+    p.add_argument('--node_validate_horizon', type=int, default=None, metavar="H",
+                   help="with --node_validate_every: steps ahead (default max(node_horizon, 3))")
+    p.add_argument('--node_validate_tsv', default=None, metavar="PATH",
+                   help="with --node_validate_every: write one tab-separated line per (validation, step, state component), "
+                        "under a header line, at the end of the run")
     return p.parse_args(argv)
+
+
+class NodeValidation:
+    """``--node_validate_every K`` for both drivers: ``due(updates)`` before an update, ``run`` queues one
+    ``SAC_CBF_CLF.validate_node`` on the NODE replay and keeps its device tensors — no host read inside the loop —
+    ``finish`` reads them all in one copy at the end of the run, turns them into ``node_fit.error_report`` dicts tagged
+    with ``updates``, env ``steps``, ``horizon``, ``stride``, ``windows`` and ``solver``, logs one line per record and
+    writes ``--node_validate_tsv``.  ``make`` returns None with the option off: the drivers then do nothing they did not
+    do before."""
+    TSV_COLUMNS = ("updates", "steps", "horizon", "stride", "windows", "windows_valid", "solver", "k", "c", "rmse", "mae",
+                   "max_abs", "skill", "nrmse")
+
+    @classmethod
+    def make(cls, agent, args):
+        every = int(getattr(args, "node_validate_every", 0) or 0)
+        if every < 0:
+            raise ValueError("--node_validate_every must be >= 0; got %d" % every)
+        return cls(agent, args, every) if every > 0 else None
+
+    def __init__(self, agent, args, every):
+        self.agent, self.every = agent, every
+        self.windows = int(getattr(args, "node_validate_windows", 4096))
+        horizon = getattr(args, "node_validate_horizon", None)
+        self.horizon = int(horizon) if horizon is not None else max(int(getattr(args, "node_horizon", 1)), 3)
+        if self.windows < 1 or self.horizon < 1:
+            raise ValueError("--node_validate_windows and --node_validate_horizon must be >= 1; got %d and %d"
+                             % (self.windows, self.horizon))
+        self.tsv = getattr(args, "node_validate_tsv", None)
+        self.pending = []                    # (tags, stats, nvalid): device tensors
+
+    def due(self, updates):
+        return updates % self.every == 0
+
+    def run(self, node_memory, updates, steps):
+        agent = self.agent
+        out = agent.validate_node(node_memory, self.windows, horizon=self.horizon)
+        if out is not None:                  # (None: the replay does not hold one window yet)
+            tags = dict(updates=updates, steps=steps, horizon=self.horizon, stride=int(agent.node_stride),
+                        windows=self.windows, solver=agent.solver)
+            self.pending.append((tags,) + tuple(out))
+
+    def finish(self, log=print):
+        """The records, read in one device-to-host copy."""
+        if not self.pending:
+            return []
+        import torch
+        from .node_fit import error_report
+        # (one float64 row per record: the statistics, then the window count — an integer below 2^53 is exact there)
+        host = torch.stack([torch.cat((st.reshape(-1), nv.reshape(1).to(torch.float64))) for _, st, nv in self.pending]).cpu()
+        records = []
+        for (tags, st, _), row in zip(self.pending, host):
+            records.append(error_report(row[:-1].reshape(st.shape), int(row[-1]), **tags))
+        self.pending = []
+        for r in records:
+            last = r["skill"][-1]
+            worst = float(last[~last.isnan()].min()) if bool((~last.isnan()).any()) else float("nan")
+            log("node validation: updates %d  steps %d  %d / %d windows  rmse by step %s  worst skill at step %d %.4f"
+                % (r["updates"], r["steps"], r["windows_valid"], r["windows"],
+                   " ".join("%.4g" % float(v) for v in r["rmse_step"]), r["horizon"], worst))
+        if self.tsv:
+            write_validation_tsv(self.tsv, records)
+        return records
+
+
+def write_validation_tsv(path, records):
+    """One tab-separated line per (record, look-ahead step k = 1 .. H, state component c), under a header line."""
+    with open(path, "w") as f:
+        f.write("\t".join(NodeValidation.TSV_COLUMNS) + "\n")
+        for r in records:
+            H, n_s = r["rmse"].shape
+            for k in range(H):
+                for c in range(n_s):
+                    f.write("\t".join([str(r[key]) for key in NodeValidation.TSV_COLUMNS[:7]] + [str(k + 1), str(c)] +
+                                      ["%.17g" % float(r[key][k, c]) for key in NodeValidation.TSV_COLUMNS[9:]]) + "\n")
 
 
 def vector_env_options(env_name, device_resets, init_spread=None):
@@ -277,9 +363,11 @@ def make_handover(env_name, env, has_backup):
     return {"Unicycle": _UnicycleHandover, "SimulatedCars": _CarsHandover, "Pvtol": _PvtolHandover}[env_name](env)
 
 
-def train(agent, env, dynamics_model, args, memory, node_memory, log=print, trace=None):
+def train(agent, env, dynamics_model, args, memory, node_memory, log=print, trace=None, validation=None):
     """Returns a list of per-episode dicts (reward, length, safety violations, updates).  ``trace``: a list that
-    receives one (use_backup, pushed_to_memory) pair per env step (driver tests)."""
+    receives one (use_backup, pushed_to_memory) pair per env step (driver tests).  ``validation``: a list that receives
+    the records of ``--node_validate_every`` (``NodeValidation``) at the end of the run."""
+    val = NodeValidation.make(agent, args)
     barrier = has_barrier_signal(args.env)
     pvtol = args.env.startswith("Pvtol")
     has_backup = getattr(agent, "backup_policy", None) is not None
@@ -296,6 +384,8 @@ def train(agent, env, dynamics_model, args, memory, node_memory, log=print, trac
             if len(memory) > args.batch_size:
                 for _ in range(args.updates_per_step):
                     extra = (i_episode,) if pvtol else ()
+                    if val is not None and val.due(updates):
+                        val.run(node_memory, updates, total_numsteps)
                     agent.update_parameters(memory, args.batch_size, updates, dynamics_model, node_memory,
                                             args.NODE_model_update_interval, *extra)
                     updates += 1
@@ -347,6 +437,10 @@ def train(agent, env, dynamics_model, args, memory, node_memory, log=print, trac
             log("  checksum " + " ".join("%.17g" % float(a.theta.double().sum()) for a in agent.arenas))
         if args.max_steps and total_numsteps >= args.max_steps:
             break
+    if val is not None:
+        records = val.finish(log)
+        if validation is not None:
+            validation.extend(records)
     return history
 
 
@@ -399,7 +493,8 @@ def train_vectorized(agent, env, args, n_steps, log=print, memory=None, check=No
     ``env.reset_done(done)``, which also hands back the float32 observation of the next step (one launch on an
     environment made with ``device_resets=True``, the torch reset and a float32 copy otherwise).
     ``check``: a callable(step_index, rows) the tests use to look at the rows that were appended.
-    Returns dict(steps, updates, episodes, mean_return).
+    Returns dict(steps, updates, episodes, mean_return) — and ``node_validation``, the list of ``NodeValidation``
+    records, when ``args.node_validate_every`` is on (every other key keeps its value).
 
     ``handover``: None / False — the above.  True, or a ``_lib.HandoverParams`` (``vector_handover.params_for``): lane i
     is ``train``'s loop for one environment as far as controllers and replays go (``_train_vectorized_handover``).
@@ -441,6 +536,7 @@ def train_vectorized(agent, env, args, n_steps, log=print, memory=None, check=No
     from .sac_cbf_clf.tasks import _Task
     needs_episode = type(agent.task).fit_due is not _Task.fit_due
     steps = updates = it = 0
+    val = NodeValidation.make(agent, args)
     if getattr(agent, "backup_policy", None) is not None:
         log("vectorised: the backup controller is trained by every update but never acts (the hand-over heuristics are "
             "per-episode host control flow): its replay distribution is the primary controller's, unlike the reference's")
@@ -486,6 +582,8 @@ def train_vectorized(agent, env, args, n_steps, log=print, memory=None, check=No
             if needs_episode and any((updates + k) % args.NODE_model_update_interval == 0 for k in range(args.updates_per_step)):
                 i_episode = 1 + int(n_done) // N
             for _ in range(args.updates_per_step):
+                if val is not None and val.due(updates):
+                    val.run(memory, updates, steps)
                 agent.update_parameters(memory, args.batch_size, updates, None, memory, args.NODE_model_update_interval,
                                         i_episode)
                 updates += 1
@@ -493,6 +591,8 @@ def train_vectorized(agent, env, args, n_steps, log=print, memory=None, check=No
     torch.cuda.synchronize()
     eps = int(n_done)
     res = dict(steps=steps, updates=updates, episodes=eps, mean_return=float(ret_sum) / max(eps, 1))
+    if val is not None:
+        res["node_validation"] = val.finish(log)
     if ledger is None:
         log("vectorised: %(steps)d env steps in %(episodes)d finished episodes, %(updates)d updates, mean return %(mean_return).2f" % res)
         return res
@@ -545,6 +645,7 @@ def _train_vectorized_handover(agent, env, args, n_steps, log, memory, check, ha
     from .sac_cbf_clf.tasks import _Task
     needs_episode = type(agent.task).fit_due is not _Task.fit_due
     steps = updates = it = 0
+    val = NodeValidation.make(agent, args)
     gate_open = False
     log("vectorised: backup-controller hand-over per lane on the device; the controller replay holds the primary "
         "controller's steps only")
@@ -583,6 +684,8 @@ def _train_vectorized_handover(agent, env, args, n_steps, log, memory, check, ha
             if needs_episode and any((updates + k) % args.NODE_model_update_interval == 0 for k in range(args.updates_per_step)):
                 i_episode = 1 + int(n_done) // N
             for _ in range(args.updates_per_step):
+                if val is not None and val.due(updates):
+                    val.run(memory, updates, steps)
                 agent.update_parameters(kept, args.batch_size, updates, None, memory, args.NODE_model_update_interval,
                                         i_episode)
                 updates += 1
@@ -591,6 +694,8 @@ def _train_vectorized_handover(agent, env, args, n_steps, log, memory, check, ha
     eps_n = int(n_done)
     res = dict(steps=steps, updates=updates, episodes=eps_n, mean_return=float(ret_sum) / max(eps_n, 1),
                backup_steps=ho.backup_steps())
+    if val is not None:
+        res["node_validation"] = val.finish(log)
     if ledger is None:
         log("vectorised: %(steps)d env steps in %(episodes)d finished episodes, %(updates)d updates, mean return "
             "%(mean_return).2f, %(backup_steps)d steps under the backup controller" % res)

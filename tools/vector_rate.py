@@ -1,7 +1,7 @@
 """GPU: throughput of the vectorised driver (train.train_vectorized): N device environments + one update per vector step.
 
     python tools/vector_rate.py [N [B]] [--env=NAME] [--device-resets] [--init-spread=SX,SY] [--handover] [--episodes]
-                                [--launches] [--iters=K]
+                                [--launches] [--iters=K] [--node-validate-every=K]
 
 ``--env=NAME``: Unicycle (default), Pvtol, SimulatedCars (which always resets on the device) or QuadrotorLike.
 ``--device-resets``: environments made with ``device_resets=True`` — finished lanes restart by one launch per vector step
@@ -12,6 +12,8 @@ launch (``nlbac_unicycle_env_reset`` / ``nlbac_pvtol_env_reset`` / ``nlbac_quadr
 ``--handover``: with the backup-controller hand-over decided per lane on the device (two replays, two acting policies).
 ``--episodes``: with the per-episode ledger on the device (``episodes=True``: two more launches per vector step).
 ``--launches``: after the timed run, a short run that counts the library's launches (``_lib.call``) per vector step.
+``--node-validate-every=K``: with the NODE validated on 4096 windows of 3 steps before every K-th update
+(``args.node_validate_every``; read at the end of the run).
 ``--iters=K``: vector steps of the timed run (300; a kernel trace of two run lengths, differenced, counts the kernels of
 a vector step)."""
 import os, sys, time, types
@@ -38,6 +40,9 @@ agent, _ = make_agent(B, 256, 0, "dopri5", name, {"Unicycle": 50.0, "Pvtol": 0.8
 env = make_env(0)
 args = types.SimpleNamespace(replay_size=1 << 20, seed=0, start_steps=2 * N, batch_size=B, updates_per_step=1,
                              NODE_model_update_interval=10)
+validate = next((int(a[22:]) for a in sys.argv[1:] if a.startswith("--node-validate-every=")), 0)
+if validate:
+    args.node_validate_every = validate
 kw = {"handover": True} if handover else {}
 if episodes:
     kw["episodes"] = True
@@ -45,10 +50,11 @@ train_vectorized(agent, env, args, 20 * N, log=lambda *a: None, **kw)        # w
 torch.cuda.synchronize(); t0 = time.perf_counter()
 res = train_vectorized(agent, make_env(1), args, iters * N, log=lambda *a: None, **kw)
 dt = time.perf_counter() - t0
-print("%s, N=%d lanes, batch %d, resets on the %s%s%s%s: %d env steps + %d updates in %.3f s = %.2f M env steps/s, %.2f ms per vector step"
+print("%s, N=%d lanes, batch %d, resets on the %s%s%s%s%s: %d env steps + %d updates in %.3f s = %.2f M env steps/s, %.2f ms per vector step"
       % (name, N, B, "device" if device_resets else "host", ", start spread %g, %g" % spread if spread is not None else "",
          ", hand-over on (%d backup steps)" % res["backup_steps"] if handover else "",
          ", ledger on (%d records, %d safety violations)" % (len(res["history"]), res["violations"]) if episodes else "",
+         ", NODE validated every %d updates (%d records)" % (validate, len(res["node_validation"])) if validate else "",
          res["steps"], res["updates"], dt, res["steps"] / dt / 1e6, 1e3 * dt / iters))
 if launches:
     from nlbac_amd import _lib
